@@ -1,7 +1,13 @@
 """Headline benchmark: fused-attention fwd+bwd at (B,H,S,D) = (4,32,4096,128), int8 vs bf16.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3|4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3|4] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (multi-GPU)
+
+A plain run sets up, warms up, times K int8 steps, writes the last step's outputs when
+``--dump-outputs DIR`` is given (DIR/O.npy, lse.npy, dq.npy, dk.npy, dv.npy, float32) and prints the
+result line.  ``--full`` adds every other measurement to that line: the bf16 step, each int8 kernel
+alone and the roofline, the inference and MX-FP4 forwards, the other configs, the CPU baseline and,
+at N > 1, the step without the all-gather.
 
 ``--gpus N`` without a torchrun environment starts the N ranks itself (one process per GPU, RCCL),
 before this process touches the GPU, and exits with their status.
@@ -9,7 +15,7 @@ before this process touches the GPU, and exits with their status.
 A step = one training pass of the attention operator over one synthetic batch:
   int8 (the reported `value`): sage_attention_3_int8 forward (k-mean + q/k/v quantisation +
   int8 attention) and its backward (dO quantisation + D + dK/dV + dQ kernels);
-  bf16 (reported beside it at N = 1): flash_atten_2_bf16 forward + backward.
+  bf16 (reported beside it at N = 1 with --full): flash_atten_2_bf16 forward + backward.
 Workloads (BASELINE.json):
   --config 3 (default at N = 1): each rank owns its own (4,32,4096,128) shard of a (4N,32,4096,128)
       batch (weak scaling);
@@ -71,10 +77,22 @@ def parse():
     p.add_argument("--skip-bf16", action="store_true")
     p.add_argument("--no-configs", action="store_true",
                    help="skip the other-config timings (a profiled run whose kernels are all config 3)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="after the headline steps also measure the bf16 step, each int8 kernel alone, "
+                        "the roofline, the inference / MX-FP4 forwards, the other configs, the CPU "
+                        "baseline and (N > 1) the step without the all-gather")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (O, lse, dq, dk, dv of rank 0) as "
+                        "DIR/<name>.npy in float32")
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
-def timed(fn, steps, warmup, world):
+def timed(fn, steps, warmup, world, last=None):
+    """Seconds per call of fn() over `steps` calls after `warmup` calls; the last timed call is
+    last() when given (the same step, keeping its outputs)."""
     for _ in range(warmup):
         fn()
     torch.cuda.synchronize()
@@ -82,8 +100,9 @@ def timed(fn, steps, warmup, world):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(steps - 1):
         fn()
+    (last or fn)()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -427,64 +446,11 @@ def make_inputs(cfg, shape_arg, world, rank, dev):
     return [q, k, v, dO], world * 14.0 * B * H * S * S * D
 
 
-def main():
-    a = parse()
-    env_world = os.environ.get("WORLD_SIZE")
-    if env_world is None and a.gpus > 1:
-        sys.exit(spawn_ranks(a.gpus))
-    world = int(env_world or "1")
-    if world != a.gpus:
-        raise SystemExit(f"bench.py: --gpus {a.gpus} but WORLD_SIZE={world}")
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    torch.cuda.set_device(local)          # before the process group: RCCL binds this device
-    dev = torch.device("cuda", local)
-    if world > 1:
-        dist.init_process_group("nccl", device_id=dev)
-        assert dist.get_world_size() == a.gpus
-    cfg = a.config or (3 if world == 1 else 4)
-    (q, k, v, dO), flop_step = make_inputs(cfg, a.shape, world, rank, dev)
+def full_report(a, q, k, v, dO, world, extras, res_bf, t_i8, t_ng, flop_step):
+    """The --full part of the result line (rank 0): each int8 kernel alone, the roofline of the
+    dominant one, the inference and MX-FP4 forwards, the other configs and the CPU baseline, beside
+    the bf16 step and the step without the all-gather that main() timed on every rank."""
     B, H, S, D = q.shape
-    gather = world > 1 and not a.no_gather
-    O_full = torch.empty((world * B * H, S, D), dtype=torch.float16, device=dev) if gather else None
-    comm = torch.cuda.Stream(device=dev) if gather else None
-
-    def step_int8(with_gather=True):
-        # the autograd path of sage_attention_3_int8: quantiser passes also write the bf16 images
-        O, lse, qi, kiT, vi, sq, sk, sv, km, qb_, kb_ = _int8_forward(q, k, v, smooth=True, images=True)
-        work = None
-        if gather and with_gather:
-            comm.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(comm):
-                work = dist.all_gather_into_tensor(O_full, O.view(B * H, S, D), async_op=True)
-        _int8_backward(dO, qi, sq, kiT, sk, vi, sv, O, lse, qb_, kb_)
-        if work is not None:
-            work.wait()
-            torch.cuda.current_stream().wait_stream(comm)
-
-    flop_fb = 14.0 * B * H * S * S * D     # this rank's work per step
-    t_i8 = timed(step_int8, a.steps, a.warmup, world)
-    # N > 1 (SURVEY §8e "with and without the all-gather"): the same step without the O gather
-    t_ng = timed(lambda: step_int8(False), a.steps, a.warmup, world) if gather else None
-    extras = world == 1 and not a.skip_bf16
-    res_bf = None
-    if extras:
-        qb, kb, vb = q, k, v.bfloat16()
-        dOf = dO.float()
-
-        def step_bf16():
-            O, lse = helion_atten_bf16_fwd_training(qb, kb, vb, False)
-            helion_flash_atten_2_algo_4_bwd(qb, kb, vb, O, lse, False, dOf)
-
-        t_bf = timed(step_bf16, max(3, a.steps // 2), a.warmup, world)
-        res_bf = {"value": flop_fb / t_bf / 1e12, "unit": "TFLOP/s", "ms_per_step": t_bf * 1e3,
-                  "frac_of_bf16_peak": flop_fb / t_bf / PEAK_BF16}
-        del qb, kb, vb, dOf
-
-    if rank != 0:
-        if world > 1:
-            dist.destroy_process_group()
-        return
     kt = int8_kernel_times(q, k, v, dO, max(3, a.steps // 2))
     chunk = ws_chunk_heads(B * H, S)
     launches = {"int8_attn_fwd_kernel": 1, "int8_bwd_dkdv_kernel<dK+dV, dS out>": -(-B * H // chunk),
@@ -500,28 +466,7 @@ def main():
     # (k-mean + q/k/v quantisation + attention, no bf16 images), one HIP-event-timed call
     fwd_ms = event_time(lambda: _int8_forward(q, k, v, smooth=True, images=False), max(3, a.steps // 2))
     fwd_flop = 4.0 * B * H * S * S * D
-    shape_txt = "(8,32,8192,128) split over %d GPU(s), (%d,%d,%d,%d) per rank" % (world, B, H, S, D) \
-        if cfg == 4 else "(%d,%d,%d,%d) per rank" % (B, H, S, D)
     out = {
-        "metric": "fused-attn fwd+bwd TFLOP/s & us/call at (B,H,S,D)=(4,32,4096,128), int8 vs bf16",
-        "value": flop_step / t_i8 / 1e12,
-        "unit": "TFLOP/s",
-        "n_gpus": world,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "ms_per_step": t_i8 * 1e3,
-        "us_per_call": t_i8 * 1e6,
-        "higher_is_better": True,
-        "scaling": "strong" if cfg == 4 else "weak",
-        "vs_baseline": None,
-        "dtype": "int8",
-        "data": "synthetic (seeded randn q,k,v fp16; dO = 1e-3*randn fp16)",
-        "config": {"workload": f"config {cfg}: int8 SageAttention-3 fwd+bwd {shape_txt}, non-causal",
-                   "shape_per_rank": [B, H, S, D],
-                   "global_shape": [8, 32, 8192, 128] if cfg == 4 else [B * world, H, S, D],
-                   "global_batch": 8 if cfg == 4 else B * world,
-                   "parallelism": f"batch x head shard over {world} GPU(s)"
-                                  + (" + async RCCL all-gather of O" if gather else "")},
         "bf16": res_bf,
         "int8_fwd": {"ms": fwd_ms, "TOPS": fwd_flop / (fwd_ms * 1e-3) / 1e12,
                      "frac_of_int8_peak": fwd_flop / (fwd_ms * 1e-3) / PEAK_I8,
@@ -531,7 +476,6 @@ def main():
         "kernel_ms": kt,
         "mxfp4_fwd": mxfp4_fwd_times(q, k, v, max(3, a.steps // 2)) if extras and D == 128 else None,
         "configs": other_configs(max(3, a.steps // 2)) if extras and not a.no_configs else None,
-        "per_gpu": {"TOPS": flop_fb / t_i8 / 1e12, "frac_of_int8_peak": flop_fb / t_i8 / PEAK_I8},
         "without_gather": None if t_ng is None else {
             "value": flop_step / t_ng / 1e12, "ms_per_step": t_ng * 1e3,
             "gather_cost_ms": (t_i8 - t_ng) * 1e3},
@@ -580,6 +524,124 @@ def main():
         out["cpu_baseline"] = cpu_baseline(S, D, a.cpu_seconds)
     else:
         out["cpu_baseline"] = None
+    return out
+
+
+DUMP_MAX_ELEMS = 2_500_000   # per array: five float32 arrays stay under 64 MB together
+DUMP_SEED = 20240
+
+
+def dump_outputs(path, arrays):
+    """Write each named tensor as <path>/<name>.npy in float32.  An array of more than
+    DUMP_MAX_ELEMS elements is stored as its values at DUMP_MAX_ELEMS flat indices drawn once from a
+    fixed seed (sorted; the same indices for every array of that size and for every run), so two
+    builds run with the same arguments can be compared value for value."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    picks = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        if n > DUMP_MAX_ELEMS:
+            if n not in picks:
+                idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_MAX_ELEMS))
+                picks[n] = torch.from_numpy(idx).to(flat.device)
+            x = flat[picks[n]].float().cpu().numpy()
+        else:
+            x = t.detach().float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), x)
+
+
+def main():
+    a = parse()
+    env_world = os.environ.get("WORLD_SIZE")
+    if env_world is None and a.gpus > 1:
+        sys.exit(spawn_ranks(a.gpus))
+    world = int(env_world or "1")
+    if world != a.gpus:
+        raise SystemExit(f"bench.py: --gpus {a.gpus} but WORLD_SIZE={world}")
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    torch.cuda.set_device(local)          # before the process group: RCCL binds this device
+    dev = torch.device("cuda", local)
+    if world > 1:
+        dist.init_process_group("nccl", device_id=dev)
+        assert dist.get_world_size() == a.gpus
+    cfg = a.config or (3 if world == 1 else 4)
+    (q, k, v, dO), flop_step = make_inputs(cfg, a.shape, world, rank, dev)
+    B, H, S, D = q.shape
+    gather = world > 1 and not a.no_gather
+    O_full = torch.empty((world * B * H, S, D), dtype=torch.float16, device=dev) if gather else None
+    comm = torch.cuda.Stream(device=dev) if gather else None
+
+    def step_int8(with_gather=True):
+        # the autograd path of sage_attention_3_int8: quantiser passes also write the bf16 images
+        O, lse, qi, kiT, vi, sq, sk, sv, km, qb_, kb_ = _int8_forward(q, k, v, smooth=True, images=True)
+        work = None
+        if gather and with_gather:
+            comm.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(comm):
+                work = dist.all_gather_into_tensor(O_full, O.view(B * H, S, D), async_op=True)
+        dq, dk, dv = _int8_backward(dO, qi, sq, kiT, sk, vi, sv, O, lse, qb_, kb_)
+        if work is not None:
+            work.wait()
+            torch.cuda.current_stream().wait_stream(comm)
+        return {"O": O, "lse": lse, "dq": dq, "dk": dk, "dv": dv}
+
+    kept = {}   # what the last timed step returned (its tensors live on only for --dump-outputs)
+    keep_last = (lambda: kept.update(step_int8())) if a.dump_outputs else None
+    flop_fb = 14.0 * B * H * S * S * D     # this rank's work per step
+    t_i8 = timed(step_int8, a.steps, a.warmup, world, last=keep_last)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, kept)
+    kept.clear()
+    # N > 1 (SURVEY §8e "with and without the all-gather"): the same step without the O gather
+    t_ng = timed(lambda: step_int8(False), a.steps, a.warmup, world) if gather and a.full else None
+    extras = a.full and world == 1 and not a.skip_bf16
+    res_bf = None
+    if extras:
+        qb, kb, vb = q, k, v.bfloat16()
+        dOf = dO.float()
+
+        def step_bf16():
+            O, lse = helion_atten_bf16_fwd_training(qb, kb, vb, False)
+            helion_flash_atten_2_algo_4_bwd(qb, kb, vb, O, lse, False, dOf)
+
+        t_bf = timed(step_bf16, max(3, a.steps // 2), a.warmup, world)
+        res_bf = {"value": flop_fb / t_bf / 1e12, "unit": "TFLOP/s", "ms_per_step": t_bf * 1e3,
+                  "frac_of_bf16_peak": flop_fb / t_bf / PEAK_BF16}
+        del qb, kb, vb, dOf
+
+    if rank != 0:
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    shape_txt = "(8,32,8192,128) split over %d GPU(s), (%d,%d,%d,%d) per rank" % (world, B, H, S, D) \
+        if cfg == 4 else "(%d,%d,%d,%d) per rank" % (B, H, S, D)
+    out = {
+        "metric": "fused-attn fwd+bwd TFLOP/s & us/call at (B,H,S,D)=(4,32,4096,128), int8 vs bf16",
+        "value": flop_step / t_i8 / 1e12,
+        "unit": "TFLOP/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": t_i8 * 1e3,
+        "us_per_call": t_i8 * 1e6,
+        "higher_is_better": True,
+        "scaling": "strong" if cfg == 4 else "weak",
+        "vs_baseline": None,
+        "dtype": "int8",
+        "data": "synthetic (seeded randn q,k,v fp16; dO = 1e-3*randn fp16)",
+        "config": {"workload": f"config {cfg}: int8 SageAttention-3 fwd+bwd {shape_txt}, non-causal",
+                   "shape_per_rank": [B, H, S, D],
+                   "global_shape": [8, 32, 8192, 128] if cfg == 4 else [B * world, H, S, D],
+                   "global_batch": 8 if cfg == 4 else B * world,
+                   "parallelism": f"batch x head shard over {world} GPU(s)"
+                                  + (" + async RCCL all-gather of O" if gather else "")},
+        "per_gpu": {"TOPS": flop_fb / t_i8 / 1e12, "frac_of_int8_peak": flop_fb / t_i8 / PEAK_I8},
+    }
+    if a.full:
+        out.update(full_report(a, q, k, v, dO, world, extras, res_bf, t_i8, t_ng, flop_step))
     print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

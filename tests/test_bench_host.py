@@ -66,6 +66,47 @@ def test_chunk_heads_match_the_step():
     assert bench.ws_chunk_heads(4, 256) == 4        # small problems: one launch over all heads
 
 
+def test_plain_run_is_the_default_and_steps_are_checked(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "0"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 0
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_timed_runs_warmup_then_exactly_steps_calls(monkeypatch):
+    monkeypatch.setattr(bench.torch.cuda, "synchronize", lambda: None)
+    calls = []
+    t = bench.timed(lambda: calls.append("step"), 5, 2, 1, last=lambda: calls.append("last"))
+    assert calls == ["step"] * 6 + ["last"] and t >= 0
+    calls.clear()
+    bench.timed(lambda: calls.append("step"), 1, 0, 1)
+    assert calls == ["step"]
+
+
+def test_dump_samples_large_outputs_at_fixed_indices(tmp_path):
+    """An output above bench.DUMP_MAX_ELEMS elements is stored as a fixed seeded sample: the same
+    sorted flat indices on every call, the values at them in float32; five such arrays (O, lse, dq,
+    dk, dv) stay under 64 MB."""
+    import numpy as np
+    n = bench.DUMP_MAX_ELEMS + 12345
+    x = torch.arange(n, dtype=torch.float32).view(-1, 5)
+    bench.dump_outputs(str(tmp_path / "a"), {"x": x.half().float(), "small": x[:7].double()})
+    bench.dump_outputs(str(tmp_path / "b"), {"x": x})
+    a, b = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert b.dtype == np.float32 and b.shape == (bench.DUMP_MAX_ELEMS,)
+    # drawn with replacement from barely more indices than the sample holds: ~1 - 1/e of them distinct
+    assert (np.diff(b) >= 0).all() and 0 <= b[0] and b[-1] < n and len(np.unique(b)) > 0.6 * len(b)
+    assert np.array_equal(a, x.half().float().view(-1).numpy()[b.astype(np.int64)])   # same indices
+    small = np.load(tmp_path / "a" / "small.npy")
+    assert small.dtype == np.float32 and np.array_equal(small, x[:7].numpy())
+    assert 5 * 4 * bench.DUMP_MAX_ELEMS <= 64e6
+
+
 def test_profile_tools_tell_grids_apart(tmp_path):
     """tools/profile_summary.key_of separates the chunk-sized and one-pass launches of the same
     kernel by their grids, and tools/trace_summary.py groups a kernel trace per (kernel, grid)."""

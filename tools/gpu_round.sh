@@ -1,6 +1,6 @@
 #!/bin/bash
 # One GPU round (runs on the GPU box from the repo root):  tools/gpu_round.sh <tag>
-#   GPU test suite, smoke(), then tools/profile_round.sh <tag> (PMC passes, traced bench, plain bench).
+#   GPU test suite, smoke(), then tools/profile_round.sh <tag> (PMC passes, traced bench, bench --full).
 # Stops at the first failing step (no GPU step runs after a failure or a time-out).
 set -o pipefail
 TAG=${1:?tag}

@@ -9,7 +9,7 @@
 #   3. rocprofv3 --kernel-trace --stats of the bench command without the other-config leg (every
 #      launch config 3), and tools/trace_summary.py: per (kernel, grid, LDS) rows
 #      (<tag>_kernel_shapes.csv) beside rocprof's per-name --stats table
-#   4. the plain `python bench.py` line (roofline with traffic, cpu_baseline)
+#   4. the `python bench.py --full` line (roofline with traffic, cpu_baseline)
 # Everything lands in gpurun_out/prof_<tag>/ (merged back by gpurun); copy profiles/ from there.
 set -e
 set -o pipefail
@@ -39,10 +39,10 @@ cp $OUT/profiles/traffic_latest.json profiles/traffic_latest.json
 echo "pmc summary done"
 cd /tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o run -- \
-  python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-configs > $OUT/bench_traced.json 2> $OUT/bench_traced.err
+  python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-configs > $OUT/bench_traced.json 2> $OUT/bench_traced.err
 cd $R
 cp $(find $OUT/bench -name '*kernel_stats.csv' | head -n 1) $OUT/profiles/${TAG}_kernel_stats.csv
 python3 tools/trace_summary.py $OUT/bench $OUT/profiles/${TAG}_kernel_shapes.csv
 echo "trace done"
-timeout -k 10 400 python3 bench.py > $OUT/profiles/${TAG}_bench.json 2> $OUT/bench.err
+timeout -k 10 400 python3 bench.py --full > $OUT/profiles/${TAG}_bench.json 2> $OUT/bench.err
 tail -c 400 $OUT/profiles/${TAG}_bench.json
