@@ -362,6 +362,15 @@ int qattn_mxfp4_attn_fwd(const void* q4, const void* qscale, const void* k4, con
                          const void* vt, const void* vscale, void* out, void* lse, long bh, long sq,
                          long sk, int group, int head_dim, float qks, void* stream);
 
+/* qattn_mxfp4_attn_fwd with a causal mask, causal as in qattn_int8_attn_fwd_ex: 0 none (the call
+ * above), 1 top-left (query row i sees keys j <= i; any sq, sk), 2 bottom-right (j <= i + sk - sq,
+ * the last sq rows of a square problem: a query chunk against a cache; sk >= sq).  A masked key's P
+ * is exactly 0 before its fp4 quantisation and takes no part in the row max; tiles past a row
+ * block's diagonal are not read.  Returns 1 for any other causal and for causal == 2 with sk < sq. */
+int qattn_mxfp4_attn_fwd_ex(const void* q4, const void* qscale, const void* k4, const void* kscale,
+                            const void* vt, const void* vscale, void* out, void* lse, long bh, long sq,
+                            long sk, int group, int causal, int head_dim, float qks, void* stream);
+
 /* Fragment-layout probes and other diagnostics live in a separate development library
  * (libqattn_dev.so, include/qattn_dev.h); this library exports the product API only. */
 

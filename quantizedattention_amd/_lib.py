@@ -82,6 +82,8 @@ SIGNATURES = {
     "qattn_mxfp4_quant_rows": [_vp, _vp, _vp, _vp, _c_long, _c_long, _c_int, _vp],
     "qattn_mxfp4_quant_vt": [_vp, _vp, _vp, _c_long, _c_long, _c_int, _vp],
     "qattn_mxfp4_attn_fwd": [_vp] * 8 + [_c_long, _c_long, _c_long, _c_int, _c_int, _c_float, _vp],
+    "qattn_mxfp4_attn_fwd_ex": [_vp] * 8 + [_c_long, _c_long, _c_long, _c_int, _c_int, _c_int, _c_float,
+                                            _vp],
 }
 
 # libqattn_dev.so (include/qattn_dev.h): fragment-layout probes for tests/test_gpu_layout.py

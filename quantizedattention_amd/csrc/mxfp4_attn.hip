@@ -18,6 +18,14 @@
 // P = exp2(fma(S, qks, -m)) in fp32 (so P <= 2^8); P_fp4 = MX(P); l += sum(deq P_fp4);
 // O += (deq P_fp4)(deq V).  Out: O / l (fp16), lse = m + log2(l) (fp32, base 2).  Because every
 // rescale is a power of two, the fp4 codes of P do not depend on when m was raised.
+// Causal (CAUSAL, key offset qoff): query row i sees key j iff j <= i + qoff (qoff = 0 top-left,
+// Sk - Sq bottom-right).  Masked scores take no part in the row max (a lane whose 32 keys are all
+// masked contributes -inf, which never raises m) and a masked key's P is exactly 0 before the MX
+// quantisation -- a select, since exp2 of a masked score may be inf -- so the block's scale comes
+// from the visible keys alone and a fully masked block is scale byte 0 with all-zero codes.  Key 0
+// is visible to every row, so m is finite after tile 0.  A tile no row of a wave sees is the same
+// as one with mx = -inf and P = 0: it is skipped (the workgroup's loop ends at its last row's
+// diagonal tile), which changes no bit of O or lse.
 #include "common.h"
 
 namespace qattn {
@@ -137,16 +145,21 @@ struct MxCfg {
 #ifndef QA_MX_OCC
 #define QA_MX_OCC 2   // min waves per SIMD the register budget is sized for
 #endif
-template <int D>
-__global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_fwd_kernel(
+#ifndef QA_MX_OCC_CAUSAL
+#define QA_MX_OCC_CAUSAL QA_MX_OCC   // the same budget for the causal instantiation
+#endif
+template <int D, bool CAUSAL>
+__global__ __launch_bounds__(256, CAUSAL ? QA_MX_OCC_CAUSAL : QA_MX_OCC) void mxfp4_attn_fwd_kernel(
     const uint8_t* __restrict__ q4, const uint8_t* __restrict__ qs, const uint8_t* __restrict__ k4,
     const uint8_t* __restrict__ ks, const uint8_t* __restrict__ vt, const uint8_t* __restrict__ vs,
-    _Float16* __restrict__ out, float* __restrict__ lse, int BH, int Sq, int Sk, int G, float qks) {
+    _Float16* __restrict__ out, float* __restrict__ lse, int BH, int Sq, int Sk, int G, float qks,
+    int qoff) {
   using C = MxCfg<D>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int nq = (Sq + C::QROWS - 1) / C::QROWS;
   int bh, qt;
-  xcd_remap(blockIdx.x, nq, BH, bh, qt);
+  if constexpr (CAUSAL) xcd_remap_lpt(blockIdx.x, nq, BH, true, bh, qt);   // longest workgroups first
+  else xcd_remap(blockIdx.x, nq, BH, bh, qt);
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63, h = lane >> 5, c32 = lane & 31;
@@ -155,6 +168,11 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_fwd_kernel(
   const int qi = min(q0 + c32, Sq - 1);
   const long kvh = bh / G;
   const int nt = Sk / C::KT;
+  // tiles this workgroup runs: up to the diagonal tile of its last real row (padding rows of a
+  // partial workgroup do not extend it)
+  int ntw = nt;
+  if constexpr (CAUSAL) ntw = min(nt, (min(qt * C::QROWS + C::QROWS, Sq) - 1 + qoff) / C::KT + 1);
+  const int wlast = q0 + 31 + qoff;   // last key any row of this wave sees
 
   // ---- LDS-DMA plan: pieces 0..P16-1 of (K | V^T) and one dma4 each for the two scale blocks
   const char* kbase = reinterpret_cast<const char*>(k4 + kvh * Sk * C::KROWB);
@@ -183,7 +201,7 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_fwd_kernel(
     dma4_buf(vs_rs, 4 * lane, (unsigned)t * C::VS_BYTES, slot + C::VSOFF);
   };
 #pragma unroll
-  for (int i = 0; i < C::NSLOT - 1; ++i) issue(smem_lds + i * C::SLOT, min(i, nt - 1));
+  for (int i = 0; i < C::NSLOT - 1; ++i) issue(smem_lds + i * C::SLOT, min(i, ntw - 1));
 
   // ---- own query fragments (B operand of S^T): lane holds Q[qi][64s + 32h .. +32] and its scales
   v4i qf[C::NKS];
@@ -204,10 +222,19 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_fwd_kernel(
 
   vmem_drain();
   __syncthreads();
-  for (int t = 0; t < nt; ++t) {
+  for (int t = 0; t < ntw; ++t) {
     ring_wait_barrier<2 * C::IPW>();   // tile t landed (t+1, t+2 may be in flight); slot (t+3)&3 is free
-    issue(smem_lds + ((t + 3) & 3) * C::SLOT, min(t + 3, nt - 1));
+    issue(smem_lds + ((t + 3) & 3) * C::SLOT, min(t + 3, ntw - 1));
     const char* sl = smem + (t & 3) * C::SLOT;
+    // causal: a wave past its own diagonal (or without rows) keeps its share of the DMA and the
+    // barrier and skips the tile; `diag` (wave-uniform) marks the tiles that cross the diagonal
+    bool diag = false;
+    int lim = 0;   // the lane sees element r of half u iff 32u + 8(r>>2) + (r&3) <= lim
+    if constexpr (CAUSAL) {
+      if (!active || C::KT * t > wlast) continue;
+      diag = C::KT * t + C::KT - 1 > q0 + qoff;
+      lim = q0 + c32 + qoff - C::KT * t - 4 * h;
+    }
     // S^T for the two 32-key halves u: A = K rows 32u + c32, k = 64s + 32h .. +32
     v16f acc[2];
 #pragma unroll
@@ -228,11 +255,21 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_fwd_kernel(
     // online softmax over the tile (fp32); the lane holds 32 keys of its query row.  m is an
     // integer (log2 units) raised only when the row max exceeds it by more than MSLACK, so every
     // rescale is an exact power of two and, between raises, P <= 2^MSLACK needs no rescale at all.
-    float amx = acc[0][0];
+    float amx;
+    if (CAUSAL && diag) {
+      amx = -INFINITY;
 #pragma unroll
-    for (int u = 0; u < 2; ++u)
+      for (int u = 0; u < 2; ++u)
 #pragma unroll
-      for (int r = (u == 0 ? 1 : 0); r < 16; ++r) amx = fmaxf(amx, acc[u][r]);
+        for (int r = 0; r < 16; ++r)
+          amx = 32 * u + 8 * (r >> 2) + (r & 3) <= lim ? fmaxf(amx, acc[u][r]) : amx;
+    } else {
+      amx = acc[0][0];
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int r = (u == 0 ? 1 : 0); r < 16; ++r) amx = fmaxf(amx, acc[u][r]);
+    }
     const float lmx = amx * qks;                                  // this lane's max of S * qks
     const float mx = fmaxf(lmx, xor32_swap(lmx, lane));
     if (__ballot(mx > m + C::MSLACK)) {
@@ -251,7 +288,15 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_fwd_kernel(
     for (int u = 0; u < 2; ++u)
 #pragma unroll
       for (int r = 0; r < 16; ++r) x[16 * u + r] = exp2_f32(__builtin_fmaf(acc[u][r], qks, nm));
-    // the block max is exp2 of the lane's max argument (exp2 and the fma are monotonic)
+    if (CAUSAL && diag) {   // masked P is exactly 0 (a select: exp2 of a masked score may be inf)
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          x[16 * u + r] = 32 * u + 8 * (r >> 2) + (r & 3) <= lim ? x[16 * u + r] : 0.f;
+    }
+    // the block max is exp2 of the lane's max argument (exp2 and the fma are monotonic); with every
+    // key of the lane masked amx = -inf and pmax = 0
     const float pmax = exp2_f32(__builtin_fmaf(amx, qks, nm));
     // P block of this lane half: its 32 values, nibble j = 16u + r
     const unsigned pe = e8m0_of(pmax);
@@ -318,20 +363,41 @@ extern "C" int qattn_mxfp4_quant_vt(const void* v, void* vt, void* vscale, long 
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
+template <bool CAUSAL>
+static int mxfp4_attn_launch(const void* q4, const void* qscale, const void* k4, const void* kscale,
+                             const void* vt, const void* vscale, void* out, void* lse, long bh, long sq,
+                             long sk, int group, float qks, int qoff, void* stream) {
+  using C = MxCfg<128>;
+  const int nq = (int)((sq + C::QROWS - 1) / C::QROWS);
+  const int lds = C::NSLOT * C::SLOT;
+  { static LdsGrant granted_; lds_grant((const void*)mxfp4_attn_fwd_kernel<128, CAUSAL>, lds, granted_); }
+  hipLaunchKernelGGL((mxfp4_attn_fwd_kernel<128, CAUSAL>), dim3((unsigned)(nq * bh)), dim3(256), lds,
+                     (hipStream_t)stream, (const uint8_t*)q4, (const uint8_t*)qscale, (const uint8_t*)k4,
+                     (const uint8_t*)kscale, (const uint8_t*)vt, (const uint8_t*)vscale, (_Float16*)out,
+                     (float*)lse, (int)bh, (int)sq, (int)sk, group, qks, qoff);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// causal: 0 none, 1 top-left (row i sees keys <= i), 2 bottom-right (keys <= i + sk - sq; sk >= sq)
+extern "C" int qattn_mxfp4_attn_fwd_ex(const void* q4, const void* qscale, const void* k4,
+                                       const void* kscale, const void* vt, const void* vscale, void* out,
+                                       void* lse, long bh, long sq, long sk, int group, int causal,
+                                       int head_dim, float qks, void* stream) {
+  if (sq % 32 != 0 || sk % 64 != 0 || group < 1 || bh % group != 0 || head_dim != 128) return 1;
+  if (causal < 0 || causal > 2 || (causal == 2 && sk < sq)) return 1;
+  if (bh == 0 || sq == 0) return 0;
+  if (sk == 0) return 1;
+  if (causal)
+    return mxfp4_attn_launch<true>(q4, qscale, k4, kscale, vt, vscale, out, lse, bh, sq, sk, group, qks,
+                                   causal == 2 ? (int)(sk - sq) : 0, stream);
+  return mxfp4_attn_launch<false>(q4, qscale, k4, kscale, vt, vscale, out, lse, bh, sq, sk, group, qks, 0,
+                                  stream);
+}
+
 extern "C" int qattn_mxfp4_attn_fwd(const void* q4, const void* qscale, const void* k4,
                                     const void* kscale, const void* vt, const void* vscale, void* out,
                                     void* lse, long bh, long sq, long sk, int group, int head_dim,
                                     float qks, void* stream) {
-  if (sq % 32 != 0 || sk % 64 != 0 || group < 1 || bh % group != 0 || head_dim != 128) return 1;
-  if (bh == 0 || sq == 0) return 0;
-  if (sk == 0) return 1;
-  using C = MxCfg<128>;
-  const int nq = (int)((sq + C::QROWS - 1) / C::QROWS);
-  const int lds = C::NSLOT * C::SLOT;
-  { static LdsGrant granted_; lds_grant((const void*)mxfp4_attn_fwd_kernel<128>, lds, granted_); }
-  hipLaunchKernelGGL((mxfp4_attn_fwd_kernel<128>), dim3((unsigned)(nq * bh)), dim3(256), lds,
-                     (hipStream_t)stream, (const uint8_t*)q4, (const uint8_t*)qscale, (const uint8_t*)k4,
-                     (const uint8_t*)kscale, (const uint8_t*)vt, (const uint8_t*)vscale, (_Float16*)out,
-                     (float*)lse, (int)bh, (int)sq, (int)sk, group, qks);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+  return qattn_mxfp4_attn_fwd_ex(q4, qscale, k4, kscale, vt, vscale, out, lse, bh, sq, sk, group, 0,
+                                 head_dim, qks, stream);
 }

@@ -20,6 +20,7 @@
 //   bf16_bwd(q, k, v, O, lse, bool causal, dO) -> (dq, dk, dv)           attention_bf16.py:299-448
 //   jvp_fwd(q, k, v, tq, tk, tv) -> (O, tO, lse)                         attention_jvp.py:24-195
 //   mxfp4_fwd(q, k, v) -> O                                  (README.md:49-55)
+//   mxfp4_fwd_ex(q, k, v, causal) -> O                       (the same with a mask: 0 / 1 / 2)
 // Errors: TORCH_CHECK (c10::Error, RuntimeError in Python) with the drop-ins' messages; int8_quant's
 // argument checks raise ValueError (TORCH_CHECK_VALUE) as its Python predecessor did.
 #include <ATen/ATen.h>
@@ -367,8 +368,9 @@ T3 jvp_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& tq, 
 }
 
 // ----------------------------------------------------------------------------------- mxfp4
-// attention_mxfp4.mxfp4_attn_fwd with k smoothing (sage_attention_3_fp4)
-Tensor mxfp4_fwd(const Tensor& q_in, const Tensor& k_in, const Tensor& v_in) {
+// attention_mxfp4.mxfp4_attn_fwd with k smoothing (sage_attention_3_fp4); causal 0 none, 1 top-left,
+// 2 bottom-right (Sk >= Sq)
+Tensor mxfp4_fwd_ex(const Tensor& q_in, const Tensor& k_in, const Tensor& v_in, int64_t causal) {
   TORCH_CHECK(q_in.dim() == 4 && k_in.sizes() == v_in.sizes() && q_in.size(0) == k_in.size(0) &&
                   q_in.size(-1) == k_in.size(-1),
               "qattn mxfp4: q [B,H,Sq,D], k = v [B,Hkv,Sk,D] expected");
@@ -376,6 +378,8 @@ Tensor mxfp4_fwd(const Tensor& q_in, const Tensor& k_in, const Tensor& v_in) {
   TORCH_CHECK(q_in.size(-1) == 128, "qattn mxfp4: head_dim must be 128");
   TORCH_CHECK(q_in.size(2) % 32 == 0 && k_in.size(2) % 64 == 0,
               "qattn mxfp4: q tokens must be a multiple of 32, k tokens of 64");
+  TORCH_CHECK(causal >= 0 && causal <= 2, "qattn mxfp4: causal must be 0, 1 (top-left) or 2 (bottom-right)");
+  TORCH_CHECK(causal != 2 || q_in.size(2) <= k_in.size(2), "qattn mxfp4: causal=2 (bottom-right) needs Sk >= Sq");
   require_gpu({&q_in, &k_in, &v_in});
   Ctx c(q_in);
   const Tensor q = q_in.to(at::kHalf).contiguous(), k = k_in.to(at::kHalf).contiguous(),
@@ -393,11 +397,13 @@ Tensor mxfp4_fwd(const Tensor& q_in, const Tensor& k_in, const Tensor& v_in) {
   Tensor vt = empty({B * Hkv, Sk / 64, D, 32}, at::kByte, q), vs = empty({B * Hkv, Sk / 64, D, 2}, at::kByte, q);
   call(qattn_mxfp4_quant_vt(P(v), P(vt), P(vs), B * Hkv, Sk, (int)D, c.stream), "quantise v");
   Tensor out = empty({B, H, Sq, D}, at::kHalf, q), lse = empty({B * H, Sq}, at::kFloat, q);
-  call(qattn_mxfp4_attn_fwd(P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(out), P(lse), B * H, Sq, Sk,
-                            (int)(H / Hkv), (int)D, qk_scale(D), c.stream),
+  call(qattn_mxfp4_attn_fwd_ex(P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(out), P(lse), B * H, Sq, Sk,
+                               (int)(H / Hkv), (int)causal, (int)D, qk_scale(D), c.stream),
        "mxfp4 forward");
   return out;
 }
+
+Tensor mxfp4_fwd(const Tensor& q, const Tensor& k, const Tensor& v) { return mxfp4_fwd_ex(q, k, v, 0); }
 
 }  // namespace
 
@@ -412,6 +418,7 @@ TORCH_LIBRARY(qattn, m) {
         "(Tensor, Tensor, Tensor)");
   m.def("jvp_fwd(Tensor q, Tensor k, Tensor v, Tensor tq, Tensor tk, Tensor tv) -> (Tensor, Tensor, Tensor)");
   m.def("mxfp4_fwd(Tensor q, Tensor k, Tensor v) -> Tensor");
+  m.def("mxfp4_fwd_ex(Tensor q, Tensor k, Tensor v, int causal) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
@@ -422,4 +429,5 @@ TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
   m.impl("bf16_bwd", &bf16_bwd);
   m.impl("jvp_fwd", &jvp_fwd);
   m.impl("mxfp4_fwd", &mxfp4_fwd);
+  m.impl("mxfp4_fwd_ex", &mxfp4_fwd_ex);
 }

@@ -15,6 +15,7 @@ the autograd rules of ``int8_fwd`` and ``bf16_fwd`` (their backward operators).
     torch.ops.qattn.bf16_bwd(q, k, v, O, lse, causal, dO) -> (dq, dk, dv)
     torch.ops.qattn.jvp_fwd(q, k, v, tq, tk, tv) -> (O, tO, lse)
     torch.ops.qattn.mxfp4_fwd(q, k, v) -> O
+    torch.ops.qattn.mxfp4_fwd_ex(q, k, v, causal) -> O      (causal 0 / 1 top-left / 2 bottom-right)
 
 Shapes follow the drop-in functions (attention_int8.py:259-262 for the int8 outputs) except that
 k_i8 is returned row-major [B*Hkv*Sk, D] (the drop-in's k_i8T is its transposed view: an operator
@@ -28,7 +29,8 @@ import torch
 
 from . import _lib
 
-__all__ = ["int8_quant", "int8_fwd", "int8_bwd", "bf16_fwd", "bf16_bwd", "jvp_fwd", "mxfp4_fwd"]
+__all__ = ["int8_quant", "int8_fwd", "int8_bwd", "bf16_fwd", "bf16_bwd", "jvp_fwd", "mxfp4_fwd",
+           "mxfp4_fwd_ex"]
 
 _lib.load_ops()
 _ops = torch.ops.qattn
@@ -83,6 +85,11 @@ def _(q, k, v, tq, tk, tv):
 
 @torch.library.register_fake("qattn::mxfp4_fwd")
 def _(q, k, v):
+    return q.new_empty(q.shape, dtype=torch.float16)
+
+
+@torch.library.register_fake("qattn::mxfp4_fwd_ex")
+def _(q, k, v, causal):
     return q.new_empty(q.shape, dtype=torch.float16)
 
 
@@ -171,3 +178,9 @@ def jvp_fwd(q, k, v, tq, tk, tv):
 def mxfp4_fwd(q, k, v):
     """MX-FP4 inference forward, k smoothed: O fp16."""
     return _ops.mxfp4_fwd(q, k, v)
+
+
+def mxfp4_fwd_ex(q, k, v, causal):
+    """``mxfp4_fwd`` with a causal mask: 0 none, 1 top-left, 2 bottom-right (Sk >= Sq); the same
+    kernels as ``sage_attention_3_fp4(q, k, v, causal=causal)``."""
+    return _ops.mxfp4_fwd_ex(q, k, v, int(causal))
