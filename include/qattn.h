@@ -371,6 +371,28 @@ int qattn_mxfp4_attn_fwd_ex(const void* q4, const void* qscale, const void* k4, 
                             const void* vt, const void* vscale, void* out, void* lse, long bh, long sq,
                             long sk, int group, int causal, int head_dim, float qks, void* stream);
 
+/* The forward in the decoding layout, split over the keys (an MX-FP4 key/value cache,
+ * kv_cache_mxfp4.py).  bhv = batch x key/value heads; each key/value head is attended by ONE virtual
+ * head of rows = G * sq_head query rows, the G query heads of its group as consecutive [sq_head, 128]
+ * blocks of q4 / qscale (q4 u8 [bhv*rows, 64], qscale u8 [bhv*rows, 4]).  rows is any value >= 1.
+ * Split y of nsplit = ceil(sk / keys_per_split) runs the keys [y*kps, min(sk, y*kps + kps)) from
+ * m = -inf and writes the unnormalised state: opart f32 [nsplit][bhv*rows][128] = O_s, ml f32 x 2
+ * [nsplit][bhv*rows] = {m_s, l_s} (m_s an integer or, for a row that sees no key of the split, -inf
+ * with l_s = 0 and O_s = 0).  causal: 0 none, 2 bottom-right over the cache (row r is query position
+ * r % sq_head and sees key j iff j <= r % sq_head + sk - sq_head).  Returns 1 for head_dim != 128,
+ * sk % 64, sk == 0 with rows > 0, keys_per_split < 64 or % 64, sq_head < 1, rows % sq_head, any other
+ * causal, causal == 2 with sk < sq_head; 0 without a launch for bhv == 0 or rows == 0. */
+int qattn_mxfp4_attn_fwd_split(const void* q4, const void* qscale, const void* k4, const void* kscale,
+                               const void* vt, const void* vscale, void* opart, void* ml, long bhv,
+                               long rows, long sq_head, long sk, int causal, int keys_per_split,
+                               int head_dim, float qks, void* stream);
+
+/* Merge of the splits, per row of rows_total = bhv*rows: M = max_s m_s, w_s = 2^(m_s - M) (exact; 0
+ * for m_s = -inf), L = sum_s w_s l_s, out f16 [rows_total, 128] = (sum_s w_s O_s) * (1 / L), lse f32
+ * [rows_total] = M + log2(L).  With nsplit == 1 this is the one-pass forward's epilogue bit for bit. */
+int qattn_mxfp4_split_combine(const void* opart, const void* ml, void* out, void* lse, long rows_total,
+                              int nsplit, int head_dim, void* stream);
+
 /* Fragment-layout probes and other diagnostics live in a separate development library
  * (libqattn_dev.so, include/qattn_dev.h); this library exports the product API only. */
 

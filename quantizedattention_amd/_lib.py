@@ -84,6 +84,9 @@ SIGNATURES = {
     "qattn_mxfp4_attn_fwd": [_vp] * 8 + [_c_long, _c_long, _c_long, _c_int, _c_int, _c_float, _vp],
     "qattn_mxfp4_attn_fwd_ex": [_vp] * 8 + [_c_long, _c_long, _c_long, _c_int, _c_int, _c_int, _c_float,
                                             _vp],
+    "qattn_mxfp4_attn_fwd_split": [_vp] * 8 + [_c_long, _c_long, _c_long, _c_long, _c_int, _c_int, _c_int,
+                                               _c_float, _vp],
+    "qattn_mxfp4_split_combine": [_vp] * 4 + [_c_long, _c_int, _c_int, _vp],
 }
 
 # libqattn_dev.so (include/qattn_dev.h): fragment-layout probes for tests/test_gpu_layout.py

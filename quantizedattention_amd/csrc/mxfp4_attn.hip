@@ -26,6 +26,10 @@
 // is visible to every row, so m is finite after tile 0.  A tile no row of a wave sees is the same
 // as one with mx = -inf and P = 0: it is skipped (the workgroup's loop ends at its last row's
 // diagonal tile), which changes no bit of O or lse.
+// Key split (mxfp4_attn_split_kernel, the decoding forward of kv_cache_mxfp4.py): the same tile body
+// over a range of the keys, from m = -inf, writing the unnormalised (O_s, m_s, l_s); the merge
+// weighs the splits by 2^(m_s - max_s m_s), exact because every m_s is an integer, and applies the
+// epilogue above.  tests/mxfp4_split_ref.py restates it; tests/test_gpu_mxfp4_cache.py checks it.
 #include "common.h"
 
 namespace qattn {
@@ -328,6 +332,272 @@ __global__ __launch_bounds__(256, CAUSAL ? QA_MX_OCC_CAUSAL : QA_MX_OCC) void mx
   store_rows<D, _Float16>(o, 1.0f / l, smem + wave * RowTile<D, _Float16>::BYTES, out + row0 * D, lane);
 }
 
+// ------------------------------------------------------------------------------ key-split forward
+// The decoding layout of the forward above (kv_cache_mxfp4.py): the G query heads of a key/value
+// head are consecutive [sq_head, D] blocks of q and run as ONE virtual head of rows = G * sq_head
+// query rows against that key/value head, so a key/value tile is read once per group; and the keys
+// are split over blockIdx.y, workgroup (x, y) running the tiles of keys [y * kps, min(Sk, y * kps +
+// kps)) from m = -inf with a ring of its own.  The tile body is the one-pass kernel's, statement for
+// statement.  Written: the unnormalised state, opart f32 [nsplit][BHV * rows][D] = O_s and ml f32 x 2
+// [nsplit][BHV * rows] = {m_s, l_s}; mxfp4_split_combine_kernel merges them.  Every m_s is an integer,
+// so the merge's weights 2^(m_s - M) are exact and one split reproduces the one-pass result bit for bit.
+// rows is any value >= 1: the lanes past the last row of a partial wave read a clamped row (as qi
+// above) and store nothing.
+// CAUSAL (bottom-right over the cache, qoff = Sk - sq_head): row r is query position r % sq_head and
+// sees key j iff j <= r % sq_head + qoff.  A row that sees no key of a split keeps m = -inf, l = 0,
+// O = 0: its scores never raise m, its P is selected to 0 before the quantisation (exp2 of a masked
+// score is inf there) and the P block is scale byte 0 with zero codes; the merge gives it weight 0.
+template <int D, typename T>
+QA_DEVICE void store_rows_upto(const v16f* acc, char* lds, T* dst_row0, int lane, int nrows) {
+  // store_rows<D, T, 2> without a scale, rows >= nrows left unwritten
+  using RT = RowTile<D, T, 2>;
+  constexpr int NBP = D / 32 / 2;
+  const int h = lane >> 5, c32 = lane & 31;
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+#pragma unroll
+    for (int bb = 0; bb < NBP; ++bb) {
+      const int b = pass * NBP + bb;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        char* p = lds + c32 * RT::PITCH + (32 * bb + 8 * g + 4 * h) * (int)sizeof(T);
+        v4f w;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[j] = acc[b][4 * g + j];
+        *reinterpret_cast<v4f*>(p) = w;
+      }
+    }
+    constexpr int CPR = RT::DC * (int)sizeof(T) / 16;   // 16-B chunks per staged row
+    constexpr int RPI = 64 / CPR;                       // rows per instruction
+    const int r = lane / CPR, c = lane % CPR;
+#pragma unroll
+    for (int i = 0; i < 32 / RPI; ++i) {
+      const int row = i * RPI + r;
+      const v4u v = *reinterpret_cast<const v4u*>(lds + row * RT::PITCH + 16 * c);
+      if (row < nrows)
+        *reinterpret_cast<v4u*>(reinterpret_cast<char*>(dst_row0) + (long)row * D * (long)sizeof(T) +
+                                pass * RT::DC * (int)sizeof(T) + 16 * c) = v;
+    }
+  }
+}
+
+template <int D, bool CAUSAL>
+__global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
+    const uint8_t* __restrict__ q4, const uint8_t* __restrict__ qs, const uint8_t* __restrict__ k4,
+    const uint8_t* __restrict__ ks, const uint8_t* __restrict__ vt, const uint8_t* __restrict__ vs,
+    float* __restrict__ opart, float2* __restrict__ ml, int BHV, int rows, int sq_head, int Sk,
+    int kps, float qks, int qoff) {
+  using C = MxCfg<D>;
+  static_assert(sizeof(float) == 4 && D == 128, "fp32 staging in two passes fills the ring exactly");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int nrb = (rows + C::QROWS - 1) / C::QROWS;
+  int bh, qt;
+  xcd_remap(blockIdx.x, nrb, BHV, bh, qt);
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = tid & 63, h = lane >> 5, c32 = lane & 31;
+  const int q0 = qt * C::QROWS + wave * 32;
+  const bool active = q0 < rows;
+  const int qi = min(q0 + c32, rows - 1);
+  const int nt = Sk / C::KT;
+  // this workgroup's tiles [t0, t0 + ntw) of the key/value head: ntw >= 1 (nsplit = ceil(Sk / kps))
+  const int t0 = (int)blockIdx.y * (kps / C::KT);
+  const int ntw = min(nt - t0, kps / C::KT);
+  // causal: query positions of the wave's rows (a wave that crosses a head boundary holds both ends)
+  int wmin = 0, wmax = 0, pos = 0;
+  if constexpr (CAUSAL) {
+    const int nr = min(32, rows - q0), p0 = q0 % sq_head;
+    const bool wraps = p0 + nr > sq_head;
+    wmin = wraps ? 0 : p0;
+    wmax = wraps ? sq_head - 1 : p0 + nr - 1;
+    pos = qi % sq_head;
+  }
+
+  // ---- LDS-DMA plan as above, over the split's own byte range (the buffer bounds end at its last tile)
+  const long kvh = bh;
+  const char* kbase = reinterpret_cast<const char*>(k4 + (kvh * Sk + (long)t0 * C::KT) * C::KROWB);
+  const char* vbase = reinterpret_cast<const char*>(vt + (kvh * nt + t0) * C::V_BYTES);
+  const char* ksbase = reinterpret_cast<const char*>(ks + (kvh * Sk + (long)t0 * C::KT) * (D / 32));
+  const char* vsbase = reinterpret_cast<const char*>(vs + (kvh * nt + t0) * C::VS_BYTES);
+  unsigned voff[C::IPW16], loff[C::IPW16], stride[C::IPW16];
+  v4u rs[C::IPW16];
+#pragma unroll
+  for (int i = 0; i < C::IPW16; ++i) {
+    const int p = wave + C::WAVES * i;
+    const bool isv = p >= C::K_BYTES / 1024;
+    const int piece = isv ? p - C::K_BYTES / 1024 : p;
+    voff[i] = piece * 1024 + 16 * lane;
+    loff[i] = (isv ? C::VOFF : C::KOFF) + piece * 1024;
+    stride[i] = isv ? C::V_BYTES : C::K_BYTES;
+    rs[i] = make_rsrc(isv ? vbase : kbase, (unsigned)(ntw * (isv ? C::V_BYTES : C::K_BYTES)));
+  }
+  const v4u ks_rs = make_rsrc(ksbase, (unsigned)(ntw * C::KS_BYTES));
+  const v4u vs_rs = make_rsrc(vsbase, (unsigned)(ntw * C::VS_BYTES));
+  const unsigned smem_lds = lds_addr(smem);
+  auto issue = [&](unsigned slot, int t) {
+#pragma unroll
+    for (int i = 0; i < C::IPW16; ++i) dma16_buf(rs[i], voff[i], (unsigned)t * stride[i], slot + loff[i]);
+    dma4_buf(ks_rs, 4 * lane, (unsigned)t * C::KS_BYTES, slot + C::KSOFF);
+    dma4_buf(vs_rs, 4 * lane, (unsigned)t * C::VS_BYTES, slot + C::VSOFF);
+  };
+#pragma unroll
+  for (int i = 0; i < C::NSLOT - 1; ++i) issue(smem_lds + i * C::SLOT, min(i, ntw - 1));
+
+  v4i qf[C::NKS];
+  unsigned qsw;
+  {
+    const long r = (long)bh * rows + qi;
+#pragma unroll
+    for (int s = 0; s < C::NKS; ++s) qf[s] = *reinterpret_cast<const v4i*>(q4 + r * C::KROWB + 32 * s + 16 * h);
+    qsw = 0;
+#pragma unroll
+    for (int b = 0; b < D / 32; ++b) qsw |= (unsigned)qs[r * (D / 32) + b] << (8 * b);
+  }
+
+  v16f o[C::NDB];
+#pragma unroll
+  for (int b = 0; b < C::NDB; ++b) o[b] = v16f{};
+  float m = -INFINITY, l = 0.f;
+
+  vmem_drain();
+  __syncthreads();
+  for (int t = 0; t < ntw; ++t) {
+    ring_wait_barrier<2 * C::IPW>();
+    issue(smem_lds + ((t + 3) & 3) * C::SLOT, min(t + 3, ntw - 1));
+    const char* sl = smem + (t & 3) * C::SLOT;
+    if (!active) continue;   // a wave without rows keeps its share of the DMA and the barrier
+    bool diag = false;
+    int lim = 0;   // the lane sees element r of half u iff 32u + 8(r>>2) + (r&3) <= lim
+    if constexpr (CAUSAL) {
+      const int k0 = C::KT * (t0 + t);
+      if (k0 > wmax + qoff) continue;           // no row of the wave sees the tile: m, l, O unchanged
+      diag = k0 + C::KT - 1 > wmin + qoff;
+      lim = pos + qoff - k0 - 4 * h;
+    }
+    v16f acc[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      acc[u] = v16f{};
+      const int key = 32 * u + c32;
+      const unsigned ksw = *reinterpret_cast<const unsigned*>(sl + C::KSOFF + key * (D / 32));
+#pragma unroll
+      for (int s = 0; s < C::NKS; ++s) {
+        const v4i ka = *reinterpret_cast<const v4i*>(sl + C::KOFF + key * C::KROWB + 32 * s + 16 * h);
+        const v8i_t a = {ka[0], ka[1], ka[2], ka[3], 0, 0, 0, 0};
+        const v8i_t b = {qf[s][0], qf[s][1], qf[s][2], qf[s][3], 0, 0, 0, 0};
+        const int sa = (int)((ksw >> (8 * (2 * s + h))) & 0xff);
+        const int sb = (int)((qsw >> (8 * (2 * s + h))) & 0xff);
+        acc[u] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc[u], 4, 4, 0, sa, 0, sb);
+      }
+    }
+    float amx;
+    if (CAUSAL && diag) {
+      amx = -INFINITY;
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          amx = 32 * u + 8 * (r >> 2) + (r & 3) <= lim ? fmaxf(amx, acc[u][r]) : amx;
+    } else {
+      amx = acc[0][0];
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int r = (u == 0 ? 1 : 0); r < 16; ++r) amx = fmaxf(amx, acc[u][r]);
+    }
+    const float lmx = amx * qks;
+    const float mx = fmaxf(lmx, xor32_swap(lmx, lane));
+    if (__ballot(mx > m + C::MSLACK)) {
+      const float nm = mx > m + C::MSLACK ? ceilf(mx) : m;
+      const float rsc = m == -INFINITY ? 0.f : __builtin_ldexpf(1.f, (int)(m - nm));
+      m = nm;
+      l *= rsc;
+#pragma unroll
+      for (int b = 0; b < C::NDB; ++b)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[b][i] = o[b][i] * rsc;
+    }
+    const float nm = -m;
+    float x[32];
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) x[16 * u + r] = exp2_f32(__builtin_fmaf(acc[u][r], qks, nm));
+    if (CAUSAL && diag) {
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          x[16 * u + r] = 32 * u + 8 * (r >> 2) + (r & 3) <= lim ? x[16 * u + r] : 0.f;
+    }
+    // a row still at m = -inf with every key of the lane masked: the argument is -inf + inf = NaN,
+    // which e8m0_of maps to scale byte 0 like pmax = 0 (its P is all zero)
+    const float pmax = exp2_f32(__builtin_fmaf(amx, qks, nm));
+    const unsigned pe = e8m0_of(pmax);
+    const v4i pk = pack_fp4x32(x, e8m0_value(pe));
+    const v8i_t pb = {pk[0], pk[1], pk[2], pk[3], 0, 0, 0, 0};
+    {
+      const v8i_t ones = {0x22222222, 0x22222222, 0x22222222, 0x22222222, 0, 0, 0, 0};   // e2m1 1.0
+      const v16f ts = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ones, pb, v16f{}, 4, 4, 0, 127, 0,
+                                                                      (int)pe);
+      l += ts[0];
+    }
+#pragma unroll
+    for (int b = 0; b < C::NDB; ++b) {
+      const int d = 32 * b + c32;
+      const v4i va = *reinterpret_cast<const v4i*>(sl + C::VOFF + d * 32 + 16 * h);
+      const v8i_t a = {va[0], va[1], va[2], va[3], 0, 0, 0, 0};
+      const int sa = (int)*reinterpret_cast<const uint8_t*>(sl + C::VSOFF + 2 * d + h);
+      o[b] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, pb, o[b], 4, 4, 0, sa, 0, (int)pe);
+    }
+  }
+  vmcnt_wait_all();
+  __syncthreads();
+  if (!active) return;
+  const long row0 = ((long)blockIdx.y * BHV + bh) * rows + q0;
+  const int nr = min(32, rows - q0);
+  if (h == 0 && c32 < nr) ml[row0 + c32] = make_float2(m, l);
+  static_assert(C::WAVES * RowTile<D, float, 2>::BYTES <= C::NSLOT * C::SLOT, "staging fits the ring");
+  store_rows_upto<D, float>(o, smem + wave * RowTile<D, float, 2>::BYTES, opart + row0 * D, lane, nr);
+}
+
+// Merge of the key splits: per row M = max_s m_s, w_s = 2^(m_s - M) (exact: every m_s is an integer
+// or -inf, which weighs 0), L = sum_s w_s l_s, out = f16((sum_s w_s O_s) * (1 / L)), lse = M + log2(L):
+// the one-pass epilogue on the merged state.  One thread per 8 columns of a row.
+template <int D>
+__global__ __launch_bounds__(256) void mxfp4_split_combine_kernel(const float* __restrict__ opart,
+                                                                  const float2* __restrict__ ml,
+                                                                  _Float16* __restrict__ out,
+                                                                  float* __restrict__ lse, long rows,
+                                                                  int nsplit) {
+  constexpr int TPR = D / 8;
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+  const long row = gid / TPR;
+  const int c = (int)(gid % TPR);
+  if (row >= rows) return;
+  float M = -INFINITY;
+  for (int s = 0; s < nsplit; ++s) M = fmaxf(M, ml[s * rows + row].x);
+  float L = 0.f, acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int s = 0; s < nsplit; ++s) {
+    const float2 v = ml[s * rows + row];
+    const float w = v.x == -INFINITY ? 0.f : __builtin_ldexpf(1.f, (int)(v.x - M));
+    L = fmaf(w, v.y, L);
+    const v4f* a = reinterpret_cast<const v4f*>(opart + ((long)s * rows + row) * D + 8 * c);
+    const v4f a0 = a[0], a1 = a[1];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      acc[i] = fmaf(w, a0[i], acc[i]);
+      acc[4 + i] = fmaf(w, a1[i], acc[4 + i]);
+    }
+  }
+  const float inv = 1.0f / L;
+  v8h o;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) o[i] = (_Float16)(acc[i] * inv);
+  *reinterpret_cast<v8h*>(out + row * D + 8 * c) = o;
+  if (c == 0) lse[row] = M + log2_f32(L);
+}
+
 }  // namespace qattn
 
 using namespace qattn;
@@ -400,4 +670,55 @@ extern "C" int qattn_mxfp4_attn_fwd(const void* q4, const void* qscale, const vo
                                     float qks, void* stream) {
   return qattn_mxfp4_attn_fwd_ex(q4, qscale, k4, kscale, vt, vscale, out, lse, bh, sq, sk, group, 0,
                                  head_dim, qks, stream);
+}
+
+template <bool CAUSAL>
+static int mxfp4_split_launch(const void* q4, const void* qscale, const void* k4, const void* kscale,
+                              const void* vt, const void* vscale, void* opart, void* ml, long bhv,
+                              long rows, long sq_head, long sk, int kps, float qks, void* stream) {
+  using C = MxCfg<128>;
+  const long nrb = (rows + C::QROWS - 1) / C::QROWS;
+  const long nsplit = (sk + kps - 1) / kps;
+  if (nrb * bhv > 0x7fffffffL || nsplit > 65535) return 1;
+  const int lds = C::NSLOT * C::SLOT;
+  { static LdsGrant granted_; if (!lds_grant((const void*)mxfp4_attn_split_kernel<128, CAUSAL>, lds, granted_)) return 1; }
+  hipLaunchKernelGGL((mxfp4_attn_split_kernel<128, CAUSAL>), dim3((unsigned)(nrb * bhv), (unsigned)nsplit),
+                     dim3(256), lds, (hipStream_t)stream, (const uint8_t*)q4, (const uint8_t*)qscale,
+                     (const uint8_t*)k4, (const uint8_t*)kscale, (const uint8_t*)vt,
+                     (const uint8_t*)vscale, (float*)opart, (float2*)ml, (int)bhv, (int)rows,
+                     (int)sq_head, (int)sk, kps, qks, (int)(sk - sq_head));
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// the decoding layout: bhv key/value heads, each attended by one virtual head of rows = G * sq_head
+// query rows; causal 0 or 2 (bottom-right over the cache: row r sees keys <= r % sq_head + sk - sq_head)
+extern "C" int qattn_mxfp4_attn_fwd_split(const void* q4, const void* qscale, const void* k4,
+                                          const void* kscale, const void* vt, const void* vscale,
+                                          void* opart, void* ml, long bhv, long rows, long sq_head, long sk,
+                                          int causal, int keys_per_split, int head_dim, float qks,
+                                          void* stream) {
+  if (head_dim != 128 || bhv < 0 || rows < 0 || sk < 0 || sk % 64 != 0) return 1;
+  if (keys_per_split < 64 || keys_per_split % 64 != 0) return 1;
+  if (sq_head < 1 || rows % sq_head != 0) return 1;
+  if ((causal != 0 && causal != 2) || (causal == 2 && sk < sq_head)) return 1;
+  if (bhv == 0 || rows == 0) return 0;
+  // 32-bit row indices inside a virtual head and 32-bit byte ranges of a key/value head
+  if (sk == 0 || sk > (1L << 25) || rows > (1L << 30) || bhv > 0x7fffffffL) return 1;
+  if (causal)
+    return mxfp4_split_launch<true>(q4, qscale, k4, kscale, vt, vscale, opart, ml, bhv, rows, sq_head, sk,
+                                    keys_per_split, qks, stream);
+  return mxfp4_split_launch<false>(q4, qscale, k4, kscale, vt, vscale, opart, ml, bhv, rows, sq_head, sk,
+                                   keys_per_split, qks, stream);
+}
+
+extern "C" int qattn_mxfp4_split_combine(const void* opart, const void* ml, void* out, void* lse,
+                                         long rows_total, int nsplit, int head_dim, void* stream) {
+  if (head_dim != 128 || rows_total < 0 || nsplit < 1) return 1;
+  if (rows_total == 0) return 0;
+  const long nthr = rows_total * (128 / 8);
+  if ((nthr + 255) / 256 > 0x7fffffffL) return 1;
+  hipLaunchKernelGGL(mxfp4_split_combine_kernel<128>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)opart, (const float2*)ml, (_Float16*)out,
+                     (float*)lse, rows_total, nsplit);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
 }

@@ -21,6 +21,9 @@
 //   jvp_fwd(q, k, v, tq, tk, tv) -> (O, tO, lse)                         attention_jvp.py:24-195
 //   mxfp4_fwd(q, k, v) -> O                                  (README.md:49-55)
 //   mxfp4_fwd_ex(q, k, v, causal) -> O                       (the same with a mask: 0 / 1 / 2)
+//   mxfp4_cached(q, k4, ks, vt, vs, causal, keys_per_split) -> (O, lse)
+//       kv_cache_mxfp4.attention_mxfp4_cached on the cache's four operands (causal 0 / 1 bottom-right
+//       over the cache; keys_per_split 0: the plan of _split_plan_fp4)
 // Errors: TORCH_CHECK (c10::Error, RuntimeError in Python) with the drop-ins' messages; int8_quant's
 // argument checks raise ValueError (TORCH_CHECK_VALUE) as its Python predecessor did.
 #include <ATen/ATen.h>
@@ -405,6 +408,56 @@ Tensor mxfp4_fwd_ex(const Tensor& q_in, const Tensor& k_in, const Tensor& v_in, 
 
 Tensor mxfp4_fwd(const Tensor& q, const Tensor& k, const Tensor& v) { return mxfp4_fwd_ex(q, k, v, 0); }
 
+// kv_cache_mxfp4._split_plan_fp4: 512 workgroups, no split under 1024 keys, multiples of 64
+int64_t split_plan_fp4(int64_t bhv, int64_t rows, int64_t sk) {
+  const int64_t wgs = bhv * ((rows + 127) / 128);
+  const int64_t nsplit = std::max<int64_t>(1, std::min(sk / 1024, (512 + wgs - 1) / wgs));
+  return (sk / 64 + nsplit - 1) / nsplit * 64;
+}
+
+// kv_cache_mxfp4.attention_mxfp4_cached: q of any Sq >= 1 against an MX-FP4 cache in the decoding
+// layout (split over the keys, then merged)
+std::tuple<Tensor, Tensor> mxfp4_cached(const Tensor& q_in, const Tensor& k4, const Tensor& ks,
+                                        const Tensor& vt, const Tensor& vs, int64_t causal,
+                                        int64_t keys_per_split) {
+  require_gpu({&q_in, &k4, &ks, &vt, &vs});
+  TORCH_CHECK(q_in.dim() == 4 && k4.dim() == 4 && q_in.size(3) == 128 && k4.size(3) == 64,
+              "qattn mxfp4 kv cache: head_dim must be 128 in q and in the cache");
+  const int64_t B = k4.size(0), Hkv = k4.size(1), Sk = k4.size(2), D = 128;
+  TORCH_CHECK(q_in.size(0) == B && Hkv > 0 && q_in.size(1) % Hkv == 0,
+              "qattn mxfp4 kv cache: q must be [B, G*Hkv, Sq, D] for the cache's B, Hkv");
+  const int64_t Hq = q_in.size(1), Sq = q_in.size(2);
+  TORCH_CHECK(Sq >= 1 && Sk >= 64 && Sk % 64 == 0,
+              "qattn mxfp4 kv cache: Sq >= 1 and a cache of 64*n tokens expected");
+  TORCH_CHECK(causal == 0 || causal == 1, "qattn mxfp4 kv cache: causal must be 0 or 1");
+  TORCH_CHECK(!causal || Sq <= Sk, "qattn mxfp4 kv cache: causal attention needs Sq <= the cached tokens");
+  for (const Tensor* t : {&k4, &ks, &vt, &vs})
+    TORCH_CHECK(t->scalar_type() == at::kByte && t->is_contiguous(),
+                "qattn mxfp4 kv cache: the quantised operands must be contiguous uint8");
+  TORCH_CHECK(ks.sizes() == at::IntArrayRef({B, Hkv, Sk, D / 32}) &&
+                  vt.sizes() == at::IntArrayRef({B * Hkv, Sk / 64, D, 32}) &&
+                  vs.sizes() == at::IntArrayRef({B * Hkv, Sk / 64, D, 2}),
+              "qattn mxfp4 kv cache: ks / vt / vs do not match k4");
+  const int64_t bhv = B * Hkv, rows = (Hq / Hkv) * Sq;
+  int64_t kps = keys_per_split == 0 ? split_plan_fp4(bhv, rows, Sk) : keys_per_split;
+  TORCH_CHECK(kps >= 64 && kps % 64 == 0, "qattn mxfp4 kv cache: keys_per_split must be a multiple of 64");
+  kps = std::min(kps, Sk);
+  const int64_t nsplit = (Sk + kps - 1) / kps;
+  Ctx c(q_in);
+  const Tensor q = q_in.to(at::kHalf).contiguous();
+  Tensor q4 = empty({B * Hq * Sq, D / 2}, at::kByte, q), qs = empty({B * Hq * Sq, D / 32}, at::kByte, q);
+  Tensor out = empty({B, Hq, Sq, D}, at::kHalf, q), lse = empty({B * Hq, Sq}, at::kFloat, q);
+  if (out.numel() == 0) return {out, lse};
+  call(qattn_mxfp4_quant_rows(P(q), nullptr, P(q4), P(qs), B * Hq * Sq, Sq, (int)D, c.stream), "quantise q");
+  Tensor opart = empty({nsplit, bhv * rows, D}, at::kFloat, q), ml = empty({nsplit, bhv * rows, 2}, at::kFloat, q);
+  call(qattn_mxfp4_attn_fwd_split(P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), bhv, rows, Sq,
+                                  Sk, causal ? 2 : 0, (int)kps, (int)D, qk_scale(D), c.stream),
+       "mxfp4 split forward");
+  call(qattn_mxfp4_split_combine(P(opart), P(ml), P(out), P(lse), bhv * rows, (int)nsplit, (int)D, c.stream),
+       "mxfp4 split merge");
+  return {out, lse};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(qattn, m) {
@@ -419,6 +472,8 @@ TORCH_LIBRARY(qattn, m) {
   m.def("jvp_fwd(Tensor q, Tensor k, Tensor v, Tensor tq, Tensor tk, Tensor tv) -> (Tensor, Tensor, Tensor)");
   m.def("mxfp4_fwd(Tensor q, Tensor k, Tensor v) -> Tensor");
   m.def("mxfp4_fwd_ex(Tensor q, Tensor k, Tensor v, int causal) -> Tensor");
+  m.def("mxfp4_cached(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, int causal, int keys_per_split) -> "
+        "(Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
@@ -430,4 +485,5 @@ TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
   m.impl("jvp_fwd", &jvp_fwd);
   m.impl("mxfp4_fwd", &mxfp4_fwd);
   m.impl("mxfp4_fwd_ex", &mxfp4_fwd_ex);
+  m.impl("mxfp4_cached", &mxfp4_cached);
 }

@@ -16,6 +16,7 @@ the autograd rules of ``int8_fwd`` and ``bf16_fwd`` (their backward operators).
     torch.ops.qattn.jvp_fwd(q, k, v, tq, tk, tv) -> (O, tO, lse)
     torch.ops.qattn.mxfp4_fwd(q, k, v) -> O
     torch.ops.qattn.mxfp4_fwd_ex(q, k, v, causal) -> O      (causal 0 / 1 top-left / 2 bottom-right)
+    torch.ops.qattn.mxfp4_cached(q, k4, ks, vt, vs, causal, keys_per_split) -> (O, lse)
 
 Shapes follow the drop-in functions (attention_int8.py:259-262 for the int8 outputs) except that
 k_i8 is returned row-major [B*Hkv*Sk, D] (the drop-in's k_i8T is its transposed view: an operator
@@ -30,7 +31,7 @@ import torch
 from . import _lib
 
 __all__ = ["int8_quant", "int8_fwd", "int8_bwd", "bf16_fwd", "bf16_bwd", "jvp_fwd", "mxfp4_fwd",
-           "mxfp4_fwd_ex"]
+           "mxfp4_fwd_ex", "mxfp4_cached"]
 
 _lib.load_ops()
 _ops = torch.ops.qattn
@@ -91,6 +92,13 @@ def _(q, k, v):
 @torch.library.register_fake("qattn::mxfp4_fwd_ex")
 def _(q, k, v, causal):
     return q.new_empty(q.shape, dtype=torch.float16)
+
+
+@torch.library.register_fake("qattn::mxfp4_cached")
+def _(q, k4, ks, vt, vs, causal, keys_per_split):
+    B, H, S, D = q.shape
+    return (q.new_empty((B, H, S, D), dtype=torch.float16),
+            q.new_empty((B * H, S), dtype=torch.float32))
 
 
 # ---------------------------------------------------------------------------- autograd rules
@@ -184,3 +192,10 @@ def mxfp4_fwd_ex(q, k, v, causal):
     """``mxfp4_fwd`` with a causal mask: 0 none, 1 top-left, 2 bottom-right (Sk >= Sq); the same
     kernels as ``sage_attention_3_fp4(q, k, v, causal=causal)``."""
     return _ops.mxfp4_fwd_ex(q, k, v, int(causal))
+
+
+def mxfp4_cached(q, kv, causal=False, keys_per_split=None):
+    """``kv_cache_mxfp4.attention_mxfp4_cached`` as one operator: q [B, Hq, Sq, 128] (any Sq >= 1)
+    against a ``QuantizedKVFP4`` -> (O fp16, lse fp32 [B*Hq, Sq]); ``keys_per_split`` None: the plan."""
+    return _ops.mxfp4_cached(q, kv.k4, kv.ks, kv.vt, kv.vs, int(bool(causal)),
+                             0 if keys_per_split is None else int(keys_per_split))
