@@ -577,10 +577,11 @@ struct RowTile {
   static constexpr int PITCH = DC * (int)sizeof(T) + 16;
   static constexpr int BYTES = 32 * PITCH;
 };
-// Element value written: acc * sc, or fma(acc, sc, add) when AFFINE.
-template <int D, typename T, int NPASS = 1, bool AFFINE = false>
+// Element value written: acc * sc, or fma(acc, sc, add) when AFFINE.  BOUNDED: rows >= nrows of the
+// tile are staged like the others and not stored.
+template <int D, typename T, int NPASS = 1, bool AFFINE = false, bool BOUNDED = false>
 QA_DEVICE void store_rows(const v16f* acc, float sc, char* lds, T* dst_row0, int lane,
-                          float add = 0.f) {
+                          float add = 0.f, int nrows = 32) {
   using RT = RowTile<D, T, NPASS>;
   constexpr int NBP = D / 32 / NPASS;                        // 32-wide d blocks per pass
   const int h = lane >> 5, c32 = lane & 31;
@@ -614,8 +615,9 @@ QA_DEVICE void store_rows(const v16f* acc, float sc, char* lds, T* dst_row0, int
     for (int i = 0; i < 32 / RPI; ++i) {
       const int row = i * RPI + r;
       const v4u v = *reinterpret_cast<const v4u*>(lds + row * RT::PITCH + 16 * c);
-      *reinterpret_cast<v4u*>(reinterpret_cast<char*>(dst_row0) + (long)row * D * (long)sizeof(T) +
-                              pass * RT::DC * (int)sizeof(T) + 16 * c) = v;
+      if (!BOUNDED || row < nrows)
+        *reinterpret_cast<v4u*>(reinterpret_cast<char*>(dst_row0) + (long)row * D * (long)sizeof(T) +
+                                pass * RT::DC * (int)sizeof(T) + 16 * c) = v;
     }
   }
 }

@@ -26,10 +26,11 @@
 // is visible to every row, so m is finite after tile 0.  A tile no row of a wave sees is the same
 // as one with mx = -inf and P = 0: it is skipped (the workgroup's loop ends at its last row's
 // diagonal tile), which changes no bit of O or lse.
-// Key split (mxfp4_attn_split_kernel, the decoding forward of kv_cache_mxfp4.py): the same tile body
-// over a range of the keys, from m = -inf, writing the unnormalised (O_s, m_s, l_s); the merge
-// weighs the splits by 2^(m_s - max_s m_s), exact because every m_s is an integer, and applies the
-// epilogue above.  tests/mxfp4_split_ref.py restates it; tests/test_gpu_mxfp4_cache.py checks it.
+// Key split (mxfp4_attn_split_kernel, the decoding forward of kv_cache_mxfp4.py): mx_tile, the tile
+// body both kernels share, over a range of the keys, from m = -inf, writing the unnormalised (O_s, m_s,
+// l_s); the merge weighs the splits by 2^(m_s - max_s m_s), exact because every m_s is an integer, and
+// applies the epilogue above.  tests/mxfp4_split_ref.py restates it; tests/test_gpu_mxfp4_cache.py
+// checks it.
 #include "common.h"
 
 namespace qattn {
@@ -152,6 +153,156 @@ struct MxCfg {
 #ifndef QA_MX_OCC_CAUSAL
 #define QA_MX_OCC_CAUSAL QA_MX_OCC   // the same budget for the causal instantiation
 #endif
+
+// ---- what the one-pass and the key-split kernel share: the ring plan, the Q load and the tile body
+// LDS-DMA plan of one wave: pieces 0..P16-1 of (K | V^T) and one dma4 each for the two scale blocks.
+// The bases point at tile 0 of the ring; the buffer resources cover `tiles` tiles from there.
+template <int D>
+struct MxRing {
+  using C = MxCfg<D>;
+  unsigned voff[C::IPW16], loff[C::IPW16], stride[C::IPW16];
+  v4u rs[C::IPW16], ks_rs, vs_rs;
+  unsigned smem_lds;
+  int lane;
+  QA_DEVICE MxRing(const void* kbase, const void* ksbase, const void* vbase, const void* vsbase, int tiles,
+                   const char* smem, int wave, int lane_)
+      : lane(lane_) {
+#pragma unroll
+    for (int i = 0; i < C::IPW16; ++i) {
+      const int p = wave + C::WAVES * i;
+      const bool isv = p >= C::K_BYTES / 1024;
+      const int piece = isv ? p - C::K_BYTES / 1024 : p;
+      voff[i] = piece * 1024 + 16 * lane;
+      loff[i] = (isv ? C::VOFF : C::KOFF) + piece * 1024;
+      stride[i] = isv ? C::V_BYTES : C::K_BYTES;
+      rs[i] = make_rsrc(isv ? vbase : kbase, (unsigned)(tiles * (isv ? C::V_BYTES : C::K_BYTES)));
+    }
+    ks_rs = make_rsrc(ksbase, (unsigned)(tiles * C::KS_BYTES));
+    vs_rs = make_rsrc(vsbase, (unsigned)(tiles * C::VS_BYTES));
+    smem_lds = lds_addr(smem);
+  }
+  // tile min(t, ntw - 1) into slot t & 3 (past the last tile the wave keeps its DMA count)
+  QA_DEVICE void issue(int t, int ntw) const {
+    const unsigned slot = smem_lds + (t & 3) * C::SLOT;
+    t = min(t, ntw - 1);
+#pragma unroll
+    for (int i = 0; i < C::IPW16; ++i) dma16_buf(rs[i], voff[i], (unsigned)t * stride[i], slot + loff[i]);
+    dma4_buf(ks_rs, 4 * lane, (unsigned)t * C::KS_BYTES, slot + C::KSOFF);
+    dma4_buf(vs_rs, 4 * lane, (unsigned)t * C::VS_BYTES, slot + C::VSOFF);
+  }
+  QA_DEVICE void prologue(int ntw) const {
+#pragma unroll
+    for (int i = 0; i < C::NSLOT - 1; ++i) issue(i, ntw);
+  }
+};
+
+// Query fragments of row r (B operand of S^T): the lane holds Q[r][64s + 32h .. +32] and the row's
+// D / 32 scale bytes packed into one word, which is returned.
+template <int D>
+QA_DEVICE unsigned mx_load_q(const uint8_t* q4, const uint8_t* qs, long r, int h, v4i (&qf)[MxCfg<D>::NKS]) {
+  using C = MxCfg<D>;
+#pragma unroll
+  for (int s = 0; s < C::NKS; ++s) qf[s] = *reinterpret_cast<const v4i*>(q4 + r * C::KROWB + 32 * s + 16 * h);
+  unsigned qsw = 0;   // byte b = the scale of block b, in one (unaligned) load
+  __builtin_memcpy(&qsw, qs + r * (D / 32), D / 32);
+  return qsw;
+}
+
+// One 64-key tile, landed in ring slot sl, into the running state (o, m, l) of the lane's query row.
+// CAUSAL and diag (wave-uniform): the tile crosses the diagonal and the lane sees element r of half u
+// iff 32u + 8(r>>2) + (r&3) <= lim; otherwise every key of the tile is visible.
+template <int D, bool CAUSAL>
+QA_DEVICE void mx_tile(const char* sl, const v4i (&qf)[MxCfg<D>::NKS], unsigned qsw,
+                       v16f (&o)[MxCfg<D>::NDB], float& m, float& l, bool diag, int lim, float qks, int lane,
+                       int h, int c32) {
+  using C = MxCfg<D>;
+  // S^T for the two 32-key halves u: A = K rows 32u + c32, k = 64s + 32h .. +32
+  v16f acc[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    acc[u] = v16f{};
+    const int key = 32 * u + c32;
+    const unsigned ksw = *reinterpret_cast<const unsigned*>(sl + C::KSOFF + key * (D / 32));
+#pragma unroll
+    for (int s = 0; s < C::NKS; ++s) {
+      const v4i ka = *reinterpret_cast<const v4i*>(sl + C::KOFF + key * C::KROWB + 32 * s + 16 * h);
+      const v8i_t a = {ka[0], ka[1], ka[2], ka[3], 0, 0, 0, 0};
+      const v8i_t b = {qf[s][0], qf[s][1], qf[s][2], qf[s][3], 0, 0, 0, 0};
+      const int sa = (int)((ksw >> (8 * (2 * s + h))) & 0xff);
+      const int sb = (int)((qsw >> (8 * (2 * s + h))) & 0xff);
+      acc[u] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc[u], 4, 4, 0, sa, 0, sb);
+    }
+  }
+  // online softmax over the tile (fp32); the lane holds 32 keys of its query row.  m is an
+  // integer (log2 units) raised only when the row max exceeds it by more than MSLACK, so every
+  // rescale is an exact power of two and, between raises, P <= 2^MSLACK needs no rescale at all.
+  float amx;
+  if (CAUSAL && diag) {
+    amx = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        amx = 32 * u + 8 * (r >> 2) + (r & 3) <= lim ? fmaxf(amx, acc[u][r]) : amx;
+  } else {
+    amx = acc[0][0];
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int r = (u == 0 ? 1 : 0); r < 16; ++r) amx = fmaxf(amx, acc[u][r]);
+  }
+  const float lmx = amx * qks;                                  // this lane's max of S * qks
+  const float mx = fmaxf(lmx, xor32_swap(lmx, lane));
+  if (__ballot(mx > m + C::MSLACK)) {
+    const float nm = mx > m + C::MSLACK ? ceilf(mx) : m;
+    const float rsc = m == -INFINITY ? 0.f : __builtin_ldexpf(1.f, (int)(m - nm));
+    m = nm;
+    l *= rsc;
+#pragma unroll
+    for (int b = 0; b < C::NDB; ++b)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) o[b][i] = o[b][i] * rsc;
+  }
+  const float nm = -m;
+  float x[32];
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) x[16 * u + r] = exp2_f32(__builtin_fmaf(acc[u][r], qks, nm));
+  if (CAUSAL && diag) {   // masked P is exactly 0 (a select: exp2 of a masked score may be inf)
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        x[16 * u + r] = 32 * u + 8 * (r >> 2) + (r & 3) <= lim ? x[16 * u + r] : 0.f;
+  }
+  // the block max is exp2 of the lane's max argument (exp2 and the fma are monotonic); with every
+  // key of the lane masked amx = -inf and pmax = 0.  In a row still at m = -inf (a key split none of
+  // whose keys the row sees) the argument is then -inf + inf = NaN, which e8m0_of maps to scale byte
+  // 0 like pmax = 0 (its P is all zero)
+  const float pmax = exp2_f32(__builtin_fmaf(amx, qks, nm));
+  // P block of this lane half: its 32 values, nibble j = 16u + r
+  const unsigned pe = e8m0_of(pmax);
+  const v4i pk = pack_fp4x32(x, e8m0_value(pe));
+  const v8i_t pb = {pk[0], pk[1], pk[2], pk[3], 0, 0, 0, 0};
+  // row sum of the quantised P on the matrix core: every row of ONES . P^T is the column sum
+  {
+    const v8i_t ones = {0x22222222, 0x22222222, 0x22222222, 0x22222222, 0, 0, 0, 0};   // e2m1 1.0
+    const v16f ts = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ones, pb, v16f{}, 4, 4, 0, 127, 0,
+                                                                    (int)pe);
+    l += ts[0];
+  }
+  // O^T[d][q] += V^T[d][keys] P^T[keys][q], A = V^T rows d = 32b + c32, k = the half-h key set
+#pragma unroll
+  for (int b = 0; b < C::NDB; ++b) {
+    const int d = 32 * b + c32;
+    const v4i va = *reinterpret_cast<const v4i*>(sl + C::VOFF + d * 32 + 16 * h);
+    const v8i_t a = {va[0], va[1], va[2], va[3], 0, 0, 0, 0};
+    const int sa = (int)*reinterpret_cast<const uint8_t*>(sl + C::VSOFF + 2 * d + h);
+    o[b] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, pb, o[b], 4, 4, 0, sa, 0, (int)pe);
+  }
+}
+
 template <int D, bool CAUSAL>
 __global__ __launch_bounds__(256, CAUSAL ? QA_MX_OCC_CAUSAL : QA_MX_OCC) void mxfp4_attn_fwd_kernel(
     const uint8_t* __restrict__ q4, const uint8_t* __restrict__ qs, const uint8_t* __restrict__ k4,
@@ -178,46 +329,12 @@ __global__ __launch_bounds__(256, CAUSAL ? QA_MX_OCC_CAUSAL : QA_MX_OCC) void mx
   if constexpr (CAUSAL) ntw = min(nt, (min(qt * C::QROWS + C::QROWS, Sq) - 1 + qoff) / C::KT + 1);
   const int wlast = q0 + 31 + qoff;   // last key any row of this wave sees
 
-  // ---- LDS-DMA plan: pieces 0..P16-1 of (K | V^T) and one dma4 each for the two scale blocks
-  const char* kbase = reinterpret_cast<const char*>(k4 + kvh * Sk * C::KROWB);
-  const char* vbase = reinterpret_cast<const char*>(vt + kvh * (long)nt * C::V_BYTES);
-  const char* ksbase = reinterpret_cast<const char*>(ks + kvh * Sk * (D / 32));
-  const char* vsbase = reinterpret_cast<const char*>(vs + kvh * (long)nt * C::VS_BYTES);
-  unsigned voff[C::IPW16], loff[C::IPW16], stride[C::IPW16];
-  v4u rs[C::IPW16];
-#pragma unroll
-  for (int i = 0; i < C::IPW16; ++i) {
-    const int p = wave + C::WAVES * i;
-    const bool isv = p >= C::K_BYTES / 1024;
-    const int piece = isv ? p - C::K_BYTES / 1024 : p;
-    voff[i] = piece * 1024 + 16 * lane;
-    loff[i] = (isv ? C::VOFF : C::KOFF) + piece * 1024;
-    stride[i] = isv ? C::V_BYTES : C::K_BYTES;
-    rs[i] = make_rsrc(isv ? vbase : kbase, (unsigned)(nt * (isv ? C::V_BYTES : C::K_BYTES)));
-  }
-  const v4u ks_rs = make_rsrc(ksbase, (unsigned)(nt * C::KS_BYTES));
-  const v4u vs_rs = make_rsrc(vsbase, (unsigned)(nt * C::VS_BYTES));
-  const unsigned smem_lds = lds_addr(smem);
-  auto issue = [&](unsigned slot, int t) {
-#pragma unroll
-    for (int i = 0; i < C::IPW16; ++i) dma16_buf(rs[i], voff[i], (unsigned)t * stride[i], slot + loff[i]);
-    dma4_buf(ks_rs, 4 * lane, (unsigned)t * C::KS_BYTES, slot + C::KSOFF);
-    dma4_buf(vs_rs, 4 * lane, (unsigned)t * C::VS_BYTES, slot + C::VSOFF);
-  };
-#pragma unroll
-  for (int i = 0; i < C::NSLOT - 1; ++i) issue(smem_lds + i * C::SLOT, min(i, ntw - 1));
+  const MxRing<D> ring(k4 + kvh * Sk * C::KROWB, ks + kvh * Sk * (D / 32), vt + kvh * (long)nt * C::V_BYTES,
+                       vs + kvh * (long)nt * C::VS_BYTES, nt, smem, wave, lane);
+  ring.prologue(ntw);
 
-  // ---- own query fragments (B operand of S^T): lane holds Q[qi][64s + 32h .. +32] and its scales
   v4i qf[C::NKS];
-  unsigned qsw;
-  {
-    const long r = (long)bh * Sq + qi;
-#pragma unroll
-    for (int s = 0; s < C::NKS; ++s) qf[s] = *reinterpret_cast<const v4i*>(q4 + r * C::KROWB + 32 * s + 16 * h);
-    qsw = 0;
-#pragma unroll
-    for (int b = 0; b < D / 32; ++b) qsw |= (unsigned)qs[r * (D / 32) + b] << (8 * b);
-  }
+  const unsigned qsw = mx_load_q<D>(q4, qs, (long)bh * Sq + qi, h, qf);
 
   v16f o[C::NDB];
 #pragma unroll
@@ -228,100 +345,17 @@ __global__ __launch_bounds__(256, CAUSAL ? QA_MX_OCC_CAUSAL : QA_MX_OCC) void mx
   __syncthreads();
   for (int t = 0; t < ntw; ++t) {
     ring_wait_barrier<2 * C::IPW>();   // tile t landed (t+1, t+2 may be in flight); slot (t+3)&3 is free
-    issue(smem_lds + ((t + 3) & 3) * C::SLOT, min(t + 3, ntw - 1));
-    const char* sl = smem + (t & 3) * C::SLOT;
+    ring.issue(t + 3, ntw);
     // causal: a wave past its own diagonal (or without rows) keeps its share of the DMA and the
     // barrier and skips the tile; `diag` (wave-uniform) marks the tiles that cross the diagonal
     bool diag = false;
-    int lim = 0;   // the lane sees element r of half u iff 32u + 8(r>>2) + (r&3) <= lim
+    int lim = 0;
     if constexpr (CAUSAL) {
       if (!active || C::KT * t > wlast) continue;
       diag = C::KT * t + C::KT - 1 > q0 + qoff;
       lim = q0 + c32 + qoff - C::KT * t - 4 * h;
     }
-    // S^T for the two 32-key halves u: A = K rows 32u + c32, k = 64s + 32h .. +32
-    v16f acc[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      acc[u] = v16f{};
-      const int key = 32 * u + c32;
-      const unsigned ksw = *reinterpret_cast<const unsigned*>(sl + C::KSOFF + key * (D / 32));
-#pragma unroll
-      for (int s = 0; s < C::NKS; ++s) {
-        const v4i ka = *reinterpret_cast<const v4i*>(sl + C::KOFF + key * C::KROWB + 32 * s + 16 * h);
-        const v8i_t a = {ka[0], ka[1], ka[2], ka[3], 0, 0, 0, 0};
-        const v8i_t b = {qf[s][0], qf[s][1], qf[s][2], qf[s][3], 0, 0, 0, 0};
-        const int sa = (int)((ksw >> (8 * (2 * s + h))) & 0xff);
-        const int sb = (int)((qsw >> (8 * (2 * s + h))) & 0xff);
-        acc[u] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc[u], 4, 4, 0, sa, 0, sb);
-      }
-    }
-    // online softmax over the tile (fp32); the lane holds 32 keys of its query row.  m is an
-    // integer (log2 units) raised only when the row max exceeds it by more than MSLACK, so every
-    // rescale is an exact power of two and, between raises, P <= 2^MSLACK needs no rescale at all.
-    float amx;
-    if (CAUSAL && diag) {
-      amx = -INFINITY;
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          amx = 32 * u + 8 * (r >> 2) + (r & 3) <= lim ? fmaxf(amx, acc[u][r]) : amx;
-    } else {
-      amx = acc[0][0];
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = (u == 0 ? 1 : 0); r < 16; ++r) amx = fmaxf(amx, acc[u][r]);
-    }
-    const float lmx = amx * qks;                                  // this lane's max of S * qks
-    const float mx = fmaxf(lmx, xor32_swap(lmx, lane));
-    if (__ballot(mx > m + C::MSLACK)) {
-      const float nm = mx > m + C::MSLACK ? ceilf(mx) : m;
-      const float rsc = m == -INFINITY ? 0.f : __builtin_ldexpf(1.f, (int)(m - nm));
-      m = nm;
-      l *= rsc;
-#pragma unroll
-      for (int b = 0; b < C::NDB; ++b)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) o[b][i] = o[b][i] * rsc;
-    }
-    const float nm = -m;
-    float x[32];
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) x[16 * u + r] = exp2_f32(__builtin_fmaf(acc[u][r], qks, nm));
-    if (CAUSAL && diag) {   // masked P is exactly 0 (a select: exp2 of a masked score may be inf)
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          x[16 * u + r] = 32 * u + 8 * (r >> 2) + (r & 3) <= lim ? x[16 * u + r] : 0.f;
-    }
-    // the block max is exp2 of the lane's max argument (exp2 and the fma are monotonic); with every
-    // key of the lane masked amx = -inf and pmax = 0
-    const float pmax = exp2_f32(__builtin_fmaf(amx, qks, nm));
-    // P block of this lane half: its 32 values, nibble j = 16u + r
-    const unsigned pe = e8m0_of(pmax);
-    const v4i pk = pack_fp4x32(x, e8m0_value(pe));
-    const v8i_t pb = {pk[0], pk[1], pk[2], pk[3], 0, 0, 0, 0};
-    // row sum of the quantised P on the matrix core: every row of ONES . P^T is the column sum
-    {
-      const v8i_t ones = {0x22222222, 0x22222222, 0x22222222, 0x22222222, 0, 0, 0, 0};   // e2m1 1.0
-      const v16f ts = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ones, pb, v16f{}, 4, 4, 0, 127, 0,
-                                                                      (int)pe);
-      l += ts[0];
-    }
-    // O^T[d][q] += V^T[d][keys] P^T[keys][q], A = V^T rows d = 32b + c32, k = the half-h key set
-#pragma unroll
-    for (int b = 0; b < C::NDB; ++b) {
-      const int d = 32 * b + c32;
-      const v4i va = *reinterpret_cast<const v4i*>(sl + C::VOFF + d * 32 + 16 * h);
-      const v8i_t a = {va[0], va[1], va[2], va[3], 0, 0, 0, 0};
-      const int sa = (int)*reinterpret_cast<const uint8_t*>(sl + C::VSOFF + 2 * d + h);
-      o[b] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, pb, o[b], 4, 4, 0, sa, 0, (int)pe);
-    }
+    mx_tile<D, CAUSAL>(smem + (t & 3) * C::SLOT, qf, qsw, o, m, l, diag, lim, qks, lane, h, c32);
   }
   vmcnt_wait_all();
   __syncthreads();
@@ -337,50 +371,17 @@ __global__ __launch_bounds__(256, CAUSAL ? QA_MX_OCC_CAUSAL : QA_MX_OCC) void mx
 // head are consecutive [sq_head, D] blocks of q and run as ONE virtual head of rows = G * sq_head
 // query rows against that key/value head, so a key/value tile is read once per group; and the keys
 // are split over blockIdx.y, workgroup (x, y) running the tiles of keys [y * kps, min(Sk, y * kps +
-// kps)) from m = -inf with a ring of its own.  The tile body is the one-pass kernel's, statement for
-// statement.  Written: the unnormalised state, opart f32 [nsplit][BHV * rows][D] = O_s and ml f32 x 2
-// [nsplit][BHV * rows] = {m_s, l_s}; mxfp4_split_combine_kernel merges them.  Every m_s is an integer,
-// so the merge's weights 2^(m_s - M) are exact and one split reproduces the one-pass result bit for bit.
+// kps)) from m = -inf with a ring of its own.  Shared with the one-pass kernel: MxRing, mx_load_q and
+// mx_tile; its own: the row mapping, the tile range, the causal prelude and the epilogue.  Written: the
+// unnormalised state, opart f32 [nsplit][BHV * rows][D] = O_s and ml f32 x 2 [nsplit][BHV * rows] =
+// {m_s, l_s}; mxfp4_split_combine_kernel merges them.  Every m_s is an integer, so the merge's weights
+// 2^(m_s - M) are exact and one split reproduces the one-pass result bit for bit.
 // rows is any value >= 1: the lanes past the last row of a partial wave read a clamped row (as qi
 // above) and store nothing.
 // CAUSAL (bottom-right over the cache, qoff = Sk - sq_head): row r is query position r % sq_head and
 // sees key j iff j <= r % sq_head + qoff.  A row that sees no key of a split keeps m = -inf, l = 0,
 // O = 0: its scores never raise m, its P is selected to 0 before the quantisation (exp2 of a masked
 // score is inf there) and the P block is scale byte 0 with zero codes; the merge gives it weight 0.
-template <int D, typename T>
-QA_DEVICE void store_rows_upto(const v16f* acc, char* lds, T* dst_row0, int lane, int nrows) {
-  // store_rows<D, T, 2> without a scale, rows >= nrows left unwritten
-  using RT = RowTile<D, T, 2>;
-  constexpr int NBP = D / 32 / 2;
-  const int h = lane >> 5, c32 = lane & 31;
-#pragma unroll
-  for (int pass = 0; pass < 2; ++pass) {
-#pragma unroll
-    for (int bb = 0; bb < NBP; ++bb) {
-      const int b = pass * NBP + bb;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        char* p = lds + c32 * RT::PITCH + (32 * bb + 8 * g + 4 * h) * (int)sizeof(T);
-        v4f w;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = acc[b][4 * g + j];
-        *reinterpret_cast<v4f*>(p) = w;
-      }
-    }
-    constexpr int CPR = RT::DC * (int)sizeof(T) / 16;   // 16-B chunks per staged row
-    constexpr int RPI = 64 / CPR;                       // rows per instruction
-    const int r = lane / CPR, c = lane % CPR;
-#pragma unroll
-    for (int i = 0; i < 32 / RPI; ++i) {
-      const int row = i * RPI + r;
-      const v4u v = *reinterpret_cast<const v4u*>(lds + row * RT::PITCH + 16 * c);
-      if (row < nrows)
-        *reinterpret_cast<v4u*>(reinterpret_cast<char*>(dst_row0) + (long)row * D * (long)sizeof(T) +
-                                pass * RT::DC * (int)sizeof(T) + 16 * c) = v;
-    }
-  }
-}
-
 template <int D, bool CAUSAL>
 __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
     const uint8_t* __restrict__ q4, const uint8_t* __restrict__ qs, const uint8_t* __restrict__ k4,
@@ -413,46 +414,15 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
     pos = qi % sq_head;
   }
 
-  // ---- LDS-DMA plan as above, over the split's own byte range (the buffer bounds end at its last tile)
+  // the ring over the split's own byte range: the buffer bounds end at its last tile
   const long kvh = bh;
-  const char* kbase = reinterpret_cast<const char*>(k4 + (kvh * Sk + (long)t0 * C::KT) * C::KROWB);
-  const char* vbase = reinterpret_cast<const char*>(vt + (kvh * nt + t0) * C::V_BYTES);
-  const char* ksbase = reinterpret_cast<const char*>(ks + (kvh * Sk + (long)t0 * C::KT) * (D / 32));
-  const char* vsbase = reinterpret_cast<const char*>(vs + (kvh * nt + t0) * C::VS_BYTES);
-  unsigned voff[C::IPW16], loff[C::IPW16], stride[C::IPW16];
-  v4u rs[C::IPW16];
-#pragma unroll
-  for (int i = 0; i < C::IPW16; ++i) {
-    const int p = wave + C::WAVES * i;
-    const bool isv = p >= C::K_BYTES / 1024;
-    const int piece = isv ? p - C::K_BYTES / 1024 : p;
-    voff[i] = piece * 1024 + 16 * lane;
-    loff[i] = (isv ? C::VOFF : C::KOFF) + piece * 1024;
-    stride[i] = isv ? C::V_BYTES : C::K_BYTES;
-    rs[i] = make_rsrc(isv ? vbase : kbase, (unsigned)(ntw * (isv ? C::V_BYTES : C::K_BYTES)));
-  }
-  const v4u ks_rs = make_rsrc(ksbase, (unsigned)(ntw * C::KS_BYTES));
-  const v4u vs_rs = make_rsrc(vsbase, (unsigned)(ntw * C::VS_BYTES));
-  const unsigned smem_lds = lds_addr(smem);
-  auto issue = [&](unsigned slot, int t) {
-#pragma unroll
-    for (int i = 0; i < C::IPW16; ++i) dma16_buf(rs[i], voff[i], (unsigned)t * stride[i], slot + loff[i]);
-    dma4_buf(ks_rs, 4 * lane, (unsigned)t * C::KS_BYTES, slot + C::KSOFF);
-    dma4_buf(vs_rs, 4 * lane, (unsigned)t * C::VS_BYTES, slot + C::VSOFF);
-  };
-#pragma unroll
-  for (int i = 0; i < C::NSLOT - 1; ++i) issue(smem_lds + i * C::SLOT, min(i, ntw - 1));
+  const MxRing<D> ring(k4 + (kvh * Sk + (long)t0 * C::KT) * C::KROWB,
+                       ks + (kvh * Sk + (long)t0 * C::KT) * (D / 32), vt + (kvh * nt + t0) * C::V_BYTES,
+                       vs + (kvh * nt + t0) * C::VS_BYTES, ntw, smem, wave, lane);
+  ring.prologue(ntw);
 
   v4i qf[C::NKS];
-  unsigned qsw;
-  {
-    const long r = (long)bh * rows + qi;
-#pragma unroll
-    for (int s = 0; s < C::NKS; ++s) qf[s] = *reinterpret_cast<const v4i*>(q4 + r * C::KROWB + 32 * s + 16 * h);
-    qsw = 0;
-#pragma unroll
-    for (int b = 0; b < D / 32; ++b) qsw |= (unsigned)qs[r * (D / 32) + b] << (8 * b);
-  }
+  const unsigned qsw = mx_load_q<D>(q4, qs, (long)bh * rows + qi, h, qf);
 
   v16f o[C::NDB];
 #pragma unroll
@@ -463,93 +433,17 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
   __syncthreads();
   for (int t = 0; t < ntw; ++t) {
     ring_wait_barrier<2 * C::IPW>();
-    issue(smem_lds + ((t + 3) & 3) * C::SLOT, min(t + 3, ntw - 1));
-    const char* sl = smem + (t & 3) * C::SLOT;
+    ring.issue(t + 3, ntw);
     if (!active) continue;   // a wave without rows keeps its share of the DMA and the barrier
     bool diag = false;
-    int lim = 0;   // the lane sees element r of half u iff 32u + 8(r>>2) + (r&3) <= lim
+    int lim = 0;
     if constexpr (CAUSAL) {
       const int k0 = C::KT * (t0 + t);
       if (k0 > wmax + qoff) continue;           // no row of the wave sees the tile: m, l, O unchanged
       diag = k0 + C::KT - 1 > wmin + qoff;
       lim = pos + qoff - k0 - 4 * h;
     }
-    v16f acc[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      acc[u] = v16f{};
-      const int key = 32 * u + c32;
-      const unsigned ksw = *reinterpret_cast<const unsigned*>(sl + C::KSOFF + key * (D / 32));
-#pragma unroll
-      for (int s = 0; s < C::NKS; ++s) {
-        const v4i ka = *reinterpret_cast<const v4i*>(sl + C::KOFF + key * C::KROWB + 32 * s + 16 * h);
-        const v8i_t a = {ka[0], ka[1], ka[2], ka[3], 0, 0, 0, 0};
-        const v8i_t b = {qf[s][0], qf[s][1], qf[s][2], qf[s][3], 0, 0, 0, 0};
-        const int sa = (int)((ksw >> (8 * (2 * s + h))) & 0xff);
-        const int sb = (int)((qsw >> (8 * (2 * s + h))) & 0xff);
-        acc[u] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc[u], 4, 4, 0, sa, 0, sb);
-      }
-    }
-    float amx;
-    if (CAUSAL && diag) {
-      amx = -INFINITY;
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          amx = 32 * u + 8 * (r >> 2) + (r & 3) <= lim ? fmaxf(amx, acc[u][r]) : amx;
-    } else {
-      amx = acc[0][0];
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = (u == 0 ? 1 : 0); r < 16; ++r) amx = fmaxf(amx, acc[u][r]);
-    }
-    const float lmx = amx * qks;
-    const float mx = fmaxf(lmx, xor32_swap(lmx, lane));
-    if (__ballot(mx > m + C::MSLACK)) {
-      const float nm = mx > m + C::MSLACK ? ceilf(mx) : m;
-      const float rsc = m == -INFINITY ? 0.f : __builtin_ldexpf(1.f, (int)(m - nm));
-      m = nm;
-      l *= rsc;
-#pragma unroll
-      for (int b = 0; b < C::NDB; ++b)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) o[b][i] = o[b][i] * rsc;
-    }
-    const float nm = -m;
-    float x[32];
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) x[16 * u + r] = exp2_f32(__builtin_fmaf(acc[u][r], qks, nm));
-    if (CAUSAL && diag) {
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          x[16 * u + r] = 32 * u + 8 * (r >> 2) + (r & 3) <= lim ? x[16 * u + r] : 0.f;
-    }
-    // a row still at m = -inf with every key of the lane masked: the argument is -inf + inf = NaN,
-    // which e8m0_of maps to scale byte 0 like pmax = 0 (its P is all zero)
-    const float pmax = exp2_f32(__builtin_fmaf(amx, qks, nm));
-    const unsigned pe = e8m0_of(pmax);
-    const v4i pk = pack_fp4x32(x, e8m0_value(pe));
-    const v8i_t pb = {pk[0], pk[1], pk[2], pk[3], 0, 0, 0, 0};
-    {
-      const v8i_t ones = {0x22222222, 0x22222222, 0x22222222, 0x22222222, 0, 0, 0, 0};   // e2m1 1.0
-      const v16f ts = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ones, pb, v16f{}, 4, 4, 0, 127, 0,
-                                                                      (int)pe);
-      l += ts[0];
-    }
-#pragma unroll
-    for (int b = 0; b < C::NDB; ++b) {
-      const int d = 32 * b + c32;
-      const v4i va = *reinterpret_cast<const v4i*>(sl + C::VOFF + d * 32 + 16 * h);
-      const v8i_t a = {va[0], va[1], va[2], va[3], 0, 0, 0, 0};
-      const int sa = (int)*reinterpret_cast<const uint8_t*>(sl + C::VSOFF + 2 * d + h);
-      o[b] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, pb, o[b], 4, 4, 0, sa, 0, (int)pe);
-    }
+    mx_tile<D, CAUSAL>(smem + (t & 3) * C::SLOT, qf, qsw, o, m, l, diag, lim, qks, lane, h, c32);
   }
   vmcnt_wait_all();
   __syncthreads();
@@ -558,7 +452,8 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
   const int nr = min(32, rows - q0);
   if (h == 0 && c32 < nr) ml[row0 + c32] = make_float2(m, l);
   static_assert(C::WAVES * RowTile<D, float, 2>::BYTES <= C::NSLOT * C::SLOT, "staging fits the ring");
-  store_rows_upto<D, float>(o, smem + wave * RowTile<D, float, 2>::BYTES, opart + row0 * D, lane, nr);
+  store_rows<D, float, 2, false, true>(o, 1.0f, smem + wave * RowTile<D, float, 2>::BYTES, opart + row0 * D,
+                                       lane, 0.f, nr);
 }
 
 // Merge of the key splits: per row M = max_s m_s, w_s = 2^(m_s - M) (exact: every m_s is an integer
