@@ -14,6 +14,8 @@ powers of two; with one split the result is the one-pass forward's bit for bit.
 
 Granularity: a cache grows by 64 tokens.  A caller with a shorter tail keeps it in fp16, attends to
 it separately and merges the two results by their ``lse`` (base 2), which is why ``lse`` is returned.
+With a smoothed cache that ``lse`` is the one of the scores q . (k - k_mean), so the tail keys must
+have the cache's ``k_mean`` subtracted before they are attended.
 
 Wire format (little-endian), the container of kv_cache.py with a magic of its own::
 
