@@ -36,7 +36,7 @@ extern "C" {
  * qattn_source_hash() is the sha256 (hex) of the kernel sources and compile flags the library was
  * built from (quantizedattention_amd/_srchash.py); the Python binding refuses a library whose hash
  * differs from the sources beside it (a stale prebuilt library). */
-#define QATTN_ABI_VERSION 6
+#define QATTN_ABI_VERSION 7
 int qattn_abi_version(void);
 const char* qattn_source_hash(void);
 
@@ -392,6 +392,32 @@ int qattn_mxfp4_attn_fwd_split(const void* q4, const void* qscale, const void* k
  * [rows_total] = M + log2(L).  With nsplit == 1 this is the one-pass forward's epilogue bit for bit. */
 int qattn_mxfp4_split_combine(const void* opart, const void* ml, void* out, void* lse, long rows_total,
                               int nsplit, int head_dim, void* stream);
+
+/* ---------------------------------------------------------------- launch plans (csrc/plan.hip)
+ * Host-only: no device, no stream, nothing launched.  Each answers a choice a host makes before it
+ * calls an entry above; every answer gives bit-identical outputs and differs only in time and memory.
+ * The Python drop-ins and the TORCH_LIBRARY operators take their plans from these functions, so a
+ * host that does the same allocates and launches what they do.  The environment variables are read
+ * on every call. */
+
+/* keys per split of a decoding forward, a multiple of tile (32 int8, 64 MX-FP4); sk when one split
+ * suffices or when there is no work (bhv * rows == 0); -1 for a bad tile / sk */
+long qattn_split_keys(long bhv, long rows, long sk, int tile);
+
+/* int8 record backward over bkv key/value heads of `group` query heads each.
+ * chunk_req: key/value heads per chunk; < 0 = auto (QATTN_BWD_WS_CHUNK if set and >= 0, else the
+ * measured rule), 0 = all heads.  cap: byte limit, < 0 = qattn_bwd_ws_cap().
+ * Writes the chunk (1..bkv) to *kv_chunk; returns the workspace bytes of one chunk, 0 when the dQ
+ * pass must recompute (region >= 2 GiB per key/value head, or over the cap), -1 for bad shapes.
+ * With bytes > 0: qattn_int8_attn_bwd_wsc(..., ws, *kv_chunk, ...); with 0: qattn_int8_attn_bwd_ex. */
+long qattn_int8_bwd_plan(long bkv, int group, long sq_tok, long sk_tok, int causal,
+                         long chunk_req, long cap, long* kv_chunk);
+
+/* bf16 backward: bytes of the dS-record workspace (qattn_bf16_bwd_ws_ex), 0 = the recomputing entry
+ * (qattn_bf16_bwd_ex), -1 for bad shapes.
+ * force: < 0 auto (QATTN_BF16_BWD_WS = 1 / 0 if set, else records when causal), 0 off, 1 on.
+ * cap as above. */
+long qattn_bf16_bwd_plan(long bh, long sq_tok, long sk_tok, int causal, int force, long cap);
 
 /* Fragment-layout probes and other diagnostics live in a separate development library
  * (libqattn_dev.so, include/qattn_dev.h); this library exports the product API only. */

@@ -7,6 +7,7 @@ There is no fallback: if the library is missing or a call fails, an exception is
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from pathlib import Path
 
@@ -87,6 +88,9 @@ SIGNATURES = {
     "qattn_mxfp4_attn_fwd_split": [_vp] * 8 + [_c_long, _c_long, _c_long, _c_long, _c_int, _c_int, _c_int,
                                                _c_float, _vp],
     "qattn_mxfp4_split_combine": [_vp] * 4 + [_c_long, _c_int, _c_int, _vp],
+    "qattn_split_keys": [_c_long, _c_long, _c_long, _c_int],
+    "qattn_int8_bwd_plan": [_c_long, _c_int, _c_long, _c_long, _c_int, _c_long, _c_long, _vp],
+    "qattn_bf16_bwd_plan": [_c_long, _c_long, _c_long, _c_int, _c_int, _c_long],
 }
 
 # libqattn_dev.so (include/qattn_dev.h): fragment-layout probes for tests/test_gpu_layout.py
@@ -107,10 +111,11 @@ DEV_SIGNATURES = {
 RESTYPES = {"qattn_abi_version": ctypes.c_int, "qattn_source_hash": ctypes.c_char_p,
             "qattn_int8_bwd_ws_bytes": ctypes.c_long, "qattn_bf16_bwd_ws_bytes": ctypes.c_long,
             "qattn_bf16_fwd_ws_bytes": ctypes.c_long,
-            "qattn_bwd_ws_cap": ctypes.c_long}
+            "qattn_bwd_ws_cap": ctypes.c_long, "qattn_split_keys": ctypes.c_long,
+            "qattn_int8_bwd_plan": ctypes.c_long, "qattn_bf16_bwd_plan": ctypes.c_long}
 
 # include/qattn.h QATTN_ABI_VERSION: the argument lists SIGNATURES describes
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 _lib = None
 _dev = None
@@ -222,6 +227,31 @@ def call(name: str, *args) -> None:
         raise QAttnError(f"{name}: unsupported shape/argument (status 1)")
     if rc != 0:
         raise QAttnError(f"{name}: kernel launch failed (status {rc})")
+
+
+def qk_scale(head_dim: int) -> float:
+    """qks of include/qattn.h: 1/sqrt(D) * log2(e), the double rounded once to fp32."""
+    return float(torch.tensor(1.0 / math.sqrt(head_dim) * 1.44269504, dtype=torch.float32))
+
+
+def sm_scale(head_dim: int) -> float:
+    """sms of include/qattn.h: 1/sqrt(D), the double rounded once to fp32."""
+    return float(torch.tensor(1.0 / math.sqrt(head_dim), dtype=torch.float32))
+
+
+UNBOUNDED = 2 ** 63 - 1   # a `cap` argument of the plan functions that no workspace exceeds
+
+
+def int8_bwd_plan(bkv: int, group: int, sq_tok: int, sk_tok: int, causal, chunk_req=None, cap=None):
+    """qattn_int8_bwd_plan -> (workspace bytes of one chunk, 0 = recompute; key/value heads per
+    chunk).  chunk_req / cap None: the library's own (environment, else the measured rule / cap)."""
+    chunk = ctypes.c_long(0)
+    nbytes = load().qattn_int8_bwd_plan(bkv, group, sq_tok, sk_tok, int(bool(causal)),
+                                        -1 if chunk_req is None else max(0, int(chunk_req)),
+                                        -1 if cap is None else max(0, int(cap)), ctypes.byref(chunk))
+    if nbytes < 0:
+        raise QAttnError("qattn_int8_bwd_plan: unsupported shape/argument")
+    return nbytes, chunk.value
 
 
 def plain(t):

@@ -14,8 +14,6 @@ attention, query head h reads key/value head h // (Hq / Hkv)); dk, dv then sum o
 """
 from __future__ import annotations
 
-import math
-import os
 from typing import Tuple
 
 import torch
@@ -31,10 +29,6 @@ __all__ = [
 ]
 
 KT = 16  # k-tile of the beta rule (reference tuned config, bf16:736)
-
-
-def _f32(x: float) -> float:
-    return float(torch.tensor(x, dtype=torch.float32))
 
 
 def _check(q, k, v):
@@ -68,7 +62,7 @@ def helion_atten_bf16_fwd_training(
     Sk = k.shape[2]
     O = torch.empty((B, H, S, D), dtype=torch.float32, device=q.device)
     lse = torch.empty((B * H, S), dtype=torch.float32, device=q.device)
-    qks = _f32(1.0 / math.sqrt(D) * 1.44269504)
+    qks = _lib.qk_scale(D)
     # grouped-query attention (SURVEY §8f N2 extension): query head h reads k/v head h // (H / Hkv);
     # causal: the per-head V suffix sums stand in for the fully masked key tiles (include/qattn.h);
     # without room for them the kernel runs the whole masked tile loop (same results)
@@ -114,35 +108,32 @@ def helion_flash_atten_2_algo_4_bwd(
     Hkv = k.shape[1]
     dk = torch.empty((B, Hkv, Sk, D), dtype=torch.float32, device=dev)
     dv = torch.empty((B, Hkv, Sk, D), dtype=torch.float32, device=dev)
-    qks = _f32(1.0 / math.sqrt(D) * 1.44269504)
-    sms = _f32(1.0 / math.sqrt(D))
     args = (_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(dO_bf), _lib.ptr(LD), _lib.ptr(q_bf),
             _lib.ptr(k_bf), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv),
-            B * H, S, Sk, H // Hkv, int(bool(causal)), D, qks, sms)
-    entry = _BWD_ENTRY
-    if entry == "auto":
-        entry = "ws" if causal else "qattn_bf16_bwd_ex"
+            B * H, S, Sk, H // Hkv, int(bool(causal)), D, _lib.qk_scale(D), _lib.sm_scale(D))
+    force = {"auto": -1, "ws": 1}.get(_BWD_ENTRY)   # (None: an entry by name, no records)
     ws = None
-    if entry == "ws":
-        ws_bytes = _lib.load().qattn_bf16_bwd_ws_bytes(B * H, S, Sk)
-        cap = _lib.load().qattn_bwd_ws_cap() if WS_MAX_BYTES is None else WS_MAX_BYTES
-        if 0 < ws_bytes <= cap:
+    if force is not None:
+        ws_bytes = _lib.load().qattn_bf16_bwd_plan(B * H, S, Sk, int(bool(causal)), force,
+                                                   -1 if WS_MAX_BYTES is None else max(0, WS_MAX_BYTES))
+        if ws_bytes > 0:
             # (None when there is no room for the dS records: recompute dS in the dQ pass, same
             # results)
             ws = _lib.try_workspace(ws_bytes, dev)
     if ws is not None:
         _lib.call("qattn_bf16_bwd_ws_ex", *args, _lib.ptr(ws), st)
     else:
-        _lib.call("qattn_bf16_bwd_ex" if entry == "ws" else entry, *args, st)
+        _lib.call("qattn_bf16_bwd_ex" if force is not None else _BWD_ENTRY, *args, st)
     return dq, dk, dv
 
 
-# "auto" (default): causal -> "ws", else "qattn_bf16_bwd_ex".  "qattn_bf16_bwd_ex": fused dK+dV, dQ
-# recomputing S and dP; "ws": the fused kernel also stores bf16 dS records (2 B per score, up to
-# QATTN_BWD_WS_MAX bytes) and dQ reads them -- non-causal at config 3 the record traffic costs what
-# the dQ pass saves, causal it is 7 % faster; "qattn_bf16_bwd_split_ex": separate dV
-# and dK kernels.  All give bit-identical gradients.  QATTN_BF16_BWD_WS=1 / 0 forces ws on / off.
-_BWD_ENTRY = {"1": "ws", "0": "qattn_bf16_bwd_ex"}.get(os.environ.get("QATTN_BF16_BWD_WS", ""), "auto")
+# "auto" (default): the library's plan (qattn_bf16_bwd_plan: records when causal; QATTN_BF16_BWD_WS=1
+# / 0 forces them on / off).  "qattn_bf16_bwd_ex": fused dK+dV, dQ recomputing S and dP; "ws": the
+# fused kernel also stores bf16 dS records (2 B per score, up to QATTN_BWD_WS_MAX bytes) and dQ reads
+# them -- non-causal at config 3 the record traffic costs what the dQ pass saves, causal it is 7 %
+# faster; "qattn_bf16_bwd_split_ex": separate dV and dK kernels.  All give
+# bit-identical gradients.
+_BWD_ENTRY = "auto"
 # None: the library's shared cap (qattn_bwd_ws_cap), as the int8 backward and the C++ operators
 WS_MAX_BYTES = None
 

@@ -20,7 +20,6 @@ the reference-shaped one.
 from __future__ import annotations
 
 import math
-import os
 import weakref
 from typing import Tuple
 
@@ -98,7 +97,7 @@ def _int8_forward(q, k, v, smooth: bool, images: bool = False, causal: bool = Fa
         q_bf = torch.empty((N, D), dtype=torch.bfloat16, device=dev)
         k_bf = torch.empty((Nkv, D), dtype=torch.bfloat16, device=dev)
     k_mean = None
-    qks = float(torch.tensor(_qk_scale(D), dtype=torch.float32))
+    qks = _lib.qk_scale(D)
     # k (smoothed, with the backward's bf16 image when asked), then v with its P.V operand image
     # (two launches: one launch alternating k and v workgroups measured 105 against 31 + 45 us at
     # config 3, HISTORY.md round 5)
@@ -125,25 +124,18 @@ def _int8_forward(q, k, v, smooth: bool, images: bool = False, causal: bool = Fa
 
 
 # Largest dS workspace (bytes) the backward allocates to skip the dQ pass's recomputation of S,
-# dP, P and dS (qattn_int8_attn_bwd_ws); larger problems recompute (qattn_int8_attn_bwd_ex).  The
+# dP, P and dS (qattn_int8_attn_bwd_wsc); larger problems recompute (qattn_int8_attn_bwd_ex).  The
 # results are bit-identical either way.  1 B per score + 4 B per 32x32 tile: 2.2 GB at (4,32,4096).
 # None: the library's shared cap (qattn_bwd_ws_cap: QATTN_BWD_WS_MAX, else 16 GiB; an allocation that
-# fails falls back to recomputation), the same rule as the bf16 backward and the C++ operators.
+# fails falls back to recomputation).  The plan itself -- the cap, the key/value heads per chunk
+# (QATTN_BWD_WS_CHUNK, else the measured rule) and the 2 GiB region check -- is the library's
+# qattn_int8_bwd_plan (csrc/plan.hip), which the C++ operators and the C host ask too.
 WS_MAX_BYTES = None
-# Key/value heads per chunk of the record backward (qattn_int8_attn_bwd_wsc): dK+dV then dQ per
-# chunk, one chunk-sized workspace re-used by every chunk; 0: one pass over all heads; unset: auto
-# (non-causal: chunks of >= 512 dK+dV workgroups, two per CU, measured 2-4 % faster than one pass
-# at config 3 with a quarter of the workspace; causal: one pass, since a causal chunk's uneven
-# workgroups leave a longer tail per launch, measured 10-170 % slower in chunks).
-WS_CHUNK = os.environ.get("QATTN_BWD_WS_CHUNK")
 
 
 def _ws_chunk(chunk, causal, bkv, sk):
-    if chunk is None and WS_CHUNK is not None:
-        chunk = int(WS_CHUNK)
-    if chunk is None:
-        chunk = 0 if causal else -(-512 // max(1, sk // 256))
-    return bkv if chunk <= 0 else min(int(chunk), bkv)
+    """Key/value heads per chunk of the record backward (chunk None: the library's choice, 0: all)."""
+    return _lib.int8_bwd_plan(bkv, 1, 32, sk, causal, chunk)[1]
 
 
 def _int8_backward(dO, q_i8, sq, k_i8T, sk, v_i8, sv, O, lse, q_bf=None, k_bf=None, causal=False,
@@ -152,7 +144,7 @@ def _int8_backward(dO, q_i8, sq, k_i8T, sk, v_i8, sv, O, lse, q_bf=None, k_bf=No
 
     kv_heads: key/value heads (default: those of O); their token count follows from k_i8T.
     use_ws: dQ from the dS workspace (True), by recomputation (False), or by size (None).
-    ws_chunk: key/value heads per workspace chunk (None: WS_CHUNK / auto; 0 = all heads at once).
+    ws_chunk: key/value heads per workspace chunk (None: QATTN_BWD_WS_CHUNK / auto; 0 = all heads).
     kv_len: key/value tokens, needed only to shape the (empty) gradients of an empty batch.
     ws_poison: a byte to fill the dS workspace with before the launch (protocol checks: every record
     the dQ pass reads must have been written by the dK+dV pass, so results cannot depend on it)."""
@@ -194,34 +186,28 @@ def _int8_backward(dO, q_i8, sq, k_i8T, sk, v_i8, sv, O, lse, q_bf=None, k_bf=No
     dq = torch.empty((B, H, S, D), dtype=torch.float16, device=dev)
     dk = torch.empty((B, Hkv, Sk, D), dtype=torch.float16, device=dev)
     dv = torch.empty((B, Hkv, Sk, D), dtype=torch.float16, device=dev)
-    qks = float(torch.tensor(_qk_scale(D), dtype=torch.float32))
-    sms = float(torch.tensor(1.0 / math.sqrt(D), dtype=torch.float32))
+    qks, sms = _lib.qk_scale(D), _lib.sm_scale(D)
     # (contiguous copies bound to names: they must outlive the launches that read them)
     sq, sk, sv = sq.contiguous(), sk.contiguous(), sv.contiguous()
     common = (_lib.ptr(dO_i8), _lib.ptr(sdO), _lib.ptr(q_i8), _lib.ptr(sq), _lib.ptr(k_i8),
               _lib.ptr(sk), _lib.ptr(v_i8), _lib.ptr(sv), _lib.ptr(LD),
               _lib.ptr(q_bf), _lib.ptr(k_bf), _lib.ptr(dO_bf), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv))
     shape = (B * H, S, Sk, H // Hkv, int(bool(causal)), D, qks, sms, st)
-    chunk = _ws_chunk(ws_chunk, causal, B * Hkv, Sk)
-    ws_bytes = _lib.load().qattn_int8_bwd_ws_bytes(chunk * (H // Hkv), S, Sk)
-    # the records of one key/value head (its H / Hkv query heads) are addressed with 32-bit offsets
-    region_ok = (H // Hkv) * (S // 32) * (Sk // 32) * 1024 < (1 << 31)
-    if use_ws is None:
-        cap = _lib.load().qattn_bwd_ws_cap() if WS_MAX_BYTES is None else WS_MAX_BYTES
-        use_ws = 0 <= ws_bytes <= cap and region_ok
-    elif use_ws and not (region_ok and ws_bytes >= 0):
-        raise _lib.QAttnError("qattn int8 backward: dS workspace region exceeds 2 GiB per key/value "
-                              "head; use the recomputing backward (use_ws=False)")
     ws = None
-    if use_ws and ws_bytes > 0:
-        # (None when there is no room: recompute dS in the dQ pass, same results)
-        ws = _lib.try_workspace(ws_bytes, dev)
-        if ws is not None and ws_poison is not None:
-            ws.fill_(int(ws_poison) & 0xFF)
-    if ws is not None and chunk < B * Hkv:
+    if use_ws is None or use_ws:
+        ws_bytes, chunk = _lib.int8_bwd_plan(B * Hkv, H // Hkv, S, Sk, causal, ws_chunk,
+                                             _lib.UNBOUNDED if use_ws else WS_MAX_BYTES)
+        if use_ws and ws_bytes == 0:
+            raise _lib.QAttnError("qattn int8 backward: dS workspace region exceeds 2 GiB per key/value "
+                                  "head; use the recomputing backward (use_ws=False)")
+        if ws_bytes > 0:
+            # (None when there is no room: recompute dS in the dQ pass, same results)
+            ws = _lib.try_workspace(ws_bytes, dev)
+            if ws is not None and ws_poison is not None:
+                ws.fill_(int(ws_poison) & 0xFF)
+    if ws is not None:
+        # (a chunk of all the heads is one pass: qattn_int8_attn_bwd_ws's launches exactly)
         _lib.call("qattn_int8_attn_bwd_wsc", *common, _lib.ptr(ws), chunk, *shape)
-    elif ws is not None:
-        _lib.call("qattn_int8_attn_bwd_ws", *common, _lib.ptr(ws), *shape)
     else:
         _lib.call("qattn_int8_attn_bwd_ex", *common, *shape)
     return dq, dk, dv

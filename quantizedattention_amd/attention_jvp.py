@@ -16,7 +16,6 @@ Other dtypes are cast to fp32 first.
 """
 from __future__ import annotations
 
-import math
 import threading
 
 import torch
@@ -78,8 +77,7 @@ def _jvp(q_fp32_input, k_fp32_input, v_fp32_input, tangents, out_O=None):
     LAUNCHES["primal" if tangents is None else "tangent"] += 1
     tO = torch.empty_like(O) if tangents is not None else None
     lse = torch.empty((B * H, S), dtype=torch.float32, device=dev)
-    qks = float(torch.tensor(1.0 / math.sqrt(D) * 1.44269504, dtype=torch.float32))
-    sm = float(torch.tensor(1.0 / math.sqrt(D), dtype=torch.float32))
+    qks, sm = _lib.qk_scale(D), _lib.sm_scale(D)
     st = _lib.stream_of(q_fp32_input)
     shape = (B * H, S, k_tokens, group, D, qks, sm, st)
     if all(t.dtype == torch.bfloat16 for t in ins):

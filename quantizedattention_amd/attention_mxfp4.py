@@ -21,8 +21,6 @@ outputs carry no autograd graph.
 """
 from __future__ import annotations
 
-import math
-
 import torch
 
 from . import _lib
@@ -31,8 +29,7 @@ __all__ = ["mxfp4_quantize_rows", "mxfp4_quantize_v", "mxfp4_attn_fwd", "mxfp4_a
            "sage_attention_3_fp4"]
 
 
-def _qk_scale(head_dim: int) -> float:
-    return float(torch.tensor(1.0 / math.sqrt(head_dim) * 1.44269504, dtype=torch.float32))
+_qk_scale = _lib.qk_scale
 
 
 def mxfp4_quantize_rows(x: torch.Tensor, mean: torch.Tensor | None = None):

@@ -1138,107 +1138,90 @@ extern "C" int qattn_i8_to_bf16(const void* x, void* y, long n, void* stream) {
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
+// The arguments of an int8 backward launch as the extern "C" entries fill them, in the entries'
+// order: operands (an entry that runs some of the kernels leaves what they do not read null), shapes
+// (bh = batch * query heads of sqt rows; the key/value side has bh / group heads of skt rows), scales,
+// stream, dS workspace.
+struct BwdArgs {
+  const void *dO_i8, *sdO, *q_i8, *sq, *k_i8, *sk, *v_i8, *sv, *LD, *q_bf, *k_bf, *dO_bf;
+  void *dq, *dk, *dv;
+  long bh, sqt, skt;
+  int group, causal, head_dim;
+  float qks, sms;
+  void* stream;
+  void* ws = nullptr;   // the records dS_i8 (1 KiB per 32x32 tile), then their fp32 scales
+  char* ds8() const { return (char*)ws; }
+  char* sds() const { return (char*)ws + bh * (sqt / 32) * (skt / 32) * 1024; }
+};
+
 template <int D, int ROLE, bool CAUSAL, bool WS>
-static void launch_bwd_c(const void* x8a, const void* x8b, const void* sxa, const void* sxb,
-                         const void* y8a, const void* y8b, const void* ytr, const void* ytr2,
-                         const void* yld, const void* sya, const void* syb, const void* xld, void* out,
-                         void* out2, long bhx, long sx, long ny, int ydiv, long smod, float qks,
-                         float sms, void* ds8, void* sds, hipStream_t st) {
+static void launch_bwd_c(const BwdArgs& a) {
   using G = BwdCfg<D, ROLE>;
+  // The kernel's own side X and streamed side Y (the role table above int8_bwd_kernel).  dQ: own Q, dO
+  // (+ their LD row stats) / streamed K8, V8, k image of the query head's key/value head; scales
+  // sq|sdO own, sk|sv streamed.  dV, dK, dK+dV: own K (and V) / streamed Q8 (and dO8), q and / or dO
+  // image, LD of the key/value head's group of query heads; scales sk|sv own, sq|sdO streamed.
+  constexpr bool DQ = ROLE == ROLE_DQ, DV = ROLE == ROLE_DV, DKV = ROLE == ROLE_DKV;
+  const long bhx = DQ ? a.bh : a.bh / a.group, sx = DQ ? a.sqt : a.skt;
+  const long ny = DQ ? a.skt : a.group * a.sqt, smod = DQ ? a.skt : a.sqt;
   const int lds = G::NSLOT * G::SLOT + (int)((2 * (ny / 32) * 2 + 15) / 16 * 16) +
                   (WS ? G::WAVES * (int)(ny / 32) * 4 : 0);
   { static LdsGrant granted_; lds_grant((const void*)int8_bwd_kernel<D, ROLE, CAUSAL, WS>, lds, granted_); }
   const int nb = (int)((sx + G::XROWS - 1) / G::XROWS);
-  hipLaunchKernelGGL((int8_bwd_kernel<D, ROLE, CAUSAL, WS>), dim3((unsigned)(nb * bhx)),
-                     dim3(64 * G::WAVES), lds, st, (const int8_t*)x8a, (const int8_t*)x8b,
-                     (const _Float16*)sxa, (const _Float16*)sxb, (const int8_t*)y8a,
-                     (const int8_t*)y8b, (const __bf16*)ytr, (const __bf16*)ytr2, (const float2*)yld,
-                     (const _Float16*)sya, (const _Float16*)syb, (const float2*)xld, (_Float16*)out,
-                     (_Float16*)out2, (int)bhx, (int)sx, (int)ny, ydiv, (int)smod, qks, sms,
-                     (int8_t*)ds8, (float*)sds);
+  hipLaunchKernelGGL(
+      (int8_bwd_kernel<D, ROLE, CAUSAL, WS>), dim3((unsigned)(nb * bhx)), dim3(64 * G::WAVES), lds,
+      (hipStream_t)a.stream,
+      (const int8_t*)(DQ ? a.q_i8 : a.k_i8), (const int8_t*)(DQ ? a.dO_i8 : DV ? nullptr : a.v_i8),
+      (const _Float16*)(DQ ? a.sq : a.sk), (const _Float16*)(DQ ? a.sdO : a.sv),
+      (const int8_t*)(DQ ? a.k_i8 : a.q_i8), (const int8_t*)(DQ ? a.v_i8 : DV ? nullptr : a.dO_i8),
+      (const __bf16*)(DQ ? a.k_bf : DV ? a.dO_bf : a.q_bf), (const __bf16*)(DKV ? a.dO_bf : nullptr),
+      (const float2*)(DQ ? nullptr : a.LD), (const _Float16*)(DQ ? a.sk : a.sq),
+      (const _Float16*)(DQ ? a.sv : a.sdO), (const float2*)(DQ ? a.LD : nullptr),
+      (_Float16*)(DQ ? a.dq : DV ? a.dv : a.dk), (_Float16*)(DKV ? a.dv : nullptr), (int)bhx, (int)sx,
+      (int)ny, DQ ? a.group : 1, (int)smod, a.qks, a.sms, (int8_t*)(WS ? a.ds8() : nullptr),
+      (float*)(WS ? a.sds() : nullptr));
 }
 template <int D, int ROLE, bool WS = false>
-static void launch_bwd(int causal, const void* x8a, const void* x8b, const void* sxa, const void* sxb,
-                       const void* y8a, const void* y8b, const void* ytr, const void* ytr2,
-                       const void* yld, const void* sya, const void* syb, const void* xld, void* out,
-                       void* out2, long bhx, long sx, long ny, int ydiv, long smod, float qks,
-                       float sms, hipStream_t st, void* ds8 = nullptr, void* sds = nullptr) {
-  if (causal)
-    launch_bwd_c<D, ROLE, true, WS>(x8a, x8b, sxa, sxb, y8a, y8b, ytr, ytr2, yld, sya, syb, xld, out,
-                                    out2, bhx, sx, ny, ydiv, smod, qks, sms, ds8, sds, st);
-  else
-    launch_bwd_c<D, ROLE, false, WS>(x8a, x8b, sxa, sxb, y8a, y8b, ytr, ytr2, yld, sya, syb, xld, out,
-                                     out2, bhx, sx, ny, ydiv, smod, qks, sms, ds8, sds, st);
+static void launch_bwd(const BwdArgs& a) {
+  if (a.causal) launch_bwd_c<D, ROLE, true, WS>(a);
+  else launch_bwd_c<D, ROLE, false, WS>(a);
 }
 
 template <int D, bool CAUSAL>
-static void launch_dqw_c(const void* ds8, const void* sds, const void* k_bf, const void* sk, void* dq,
-                         long bh, long sqt, long skt, int group, float sms, hipStream_t st) {
+static void launch_dqw_c(const BwdArgs& a) {
   using G = DqwCfg<D>;
-  const int nkt = (int)(skt / 32);
+  const int nkt = (int)(a.skt / 32);
   const int lds = G::RBASE + G::RSLOT * G::REC + G::WAVES * nkt * 4 + 16;
   { static LdsGrant granted_; lds_grant((const void*)int8_bwd_dqw_kernel<D, CAUSAL>, lds, granted_); }
-  const int nb = (int)((sqt + 32 * G::WAVES - 1) / (32 * G::WAVES));
-  hipLaunchKernelGGL((int8_bwd_dqw_kernel<D, CAUSAL>), dim3((unsigned)(nb * bh)), dim3(64 * G::WAVES),
-                     lds, st, (const int8_t*)ds8, (const float*)sds, (const __bf16*)k_bf,
-                     (const _Float16*)sk, (_Float16*)dq, (int)bh, (int)sqt, (int)skt, group, sms);
+  const int nb = (int)((a.sqt + 32 * G::WAVES - 1) / (32 * G::WAVES));
+  hipLaunchKernelGGL((int8_bwd_dqw_kernel<D, CAUSAL>), dim3((unsigned)(nb * a.bh)),
+                     dim3(64 * G::WAVES), lds, (hipStream_t)a.stream, (const int8_t*)a.ds8(),
+                     (const float*)a.sds(), (const __bf16*)a.k_bf, (const _Float16*)a.sk,
+                     (_Float16*)a.dq, (int)a.bh, (int)a.sqt, (int)a.skt, a.group, a.sms);
 }
 
 // which: bit mask 1 = dV kernel, 4 = dK kernel, 8 = fused dK+dV kernel, 2 = dQ kernel,
-// 16 = fused dK+dV kernel writing the dS workspace ws, 32 = dQ from the dS workspace.
-// bh = batch * query heads; the key/value side has bh / group heads of skt rows.
+// 16 = fused dK+dV kernel writing the dS workspace a.ws, 32 = dQ from the dS workspace.
 template <int D>
-static void bwd_launch_d(int which, const void* dO_i8, const void* sdO, const void* q_i8,
-                         const void* sq, const void* k_i8, const void* sk, const void* v_i8,
-                         const void* sv, const void* LD, const void* q_bf, const void* k_bf,
-                         const void* dO_bf, void* dq, void* dk, void* dv, long bh, long sqt, long skt,
-                         int group, int causal, float qks, float sms, hipStream_t st,
-                         void* ws = nullptr) {
-  const long bkv = bh / group, ny = group * sqt;
-  char* ds8 = (char*)ws;
-  char* sds = ws ? ds8 + bh * (sqt / 32) * (skt / 32) * 1024 : nullptr;
-  if (which & 16)
-    launch_bwd<D, ROLE_DKV, true>(causal, k_i8, v_i8, sk, sv, q_i8, dO_i8, q_bf, dO_bf, LD, sq, sdO,
-                                  nullptr, dk, dv, bkv, skt, ny, 1, sqt, qks, sms, st, ds8, sds);
+static void bwd_launch_d(int which, const BwdArgs& a) {
+  if (which & 16) launch_bwd<D, ROLE_DKV, true>(a);
   if (which & 32) {
-    if (causal) launch_dqw_c<D, true>(ds8, sds, k_bf, sk, dq, bh, sqt, skt, group, sms, st);
-    else launch_dqw_c<D, false>(ds8, sds, k_bf, sk, dq, bh, sqt, skt, group, sms, st);
+    if (a.causal) launch_dqw_c<D, true>(a);
+    else launch_dqw_c<D, false>(a);
   }
-  // dV: own K (x8a) / streamed Q8 (y8a), dO image (ytr), LD; scales: sk|sv own, sq|sdO streamed
-  if (which & 1)
-    launch_bwd<D, ROLE_DV>(causal, k_i8, nullptr, sk, sv, q_i8, nullptr, dO_bf, nullptr, LD, sq, sdO,
-                           nullptr, dv, nullptr, bkv, skt, ny, 1, sqt, qks, sms, st);
-  // dK: own K, V / streamed Q8, dO8, q image, LD
-  if (which & 4)
-    launch_bwd<D, ROLE_DK>(causal, k_i8, v_i8, sk, sv, q_i8, dO_i8, q_bf, nullptr, LD, sq, sdO, nullptr,
-                           dk, nullptr, bkv, skt, ny, 1, sqt, qks, sms, st);
-  // dK and dV in one pass: + dO image
-  if (which & 8)
-    launch_bwd<D, ROLE_DKV>(causal, k_i8, v_i8, sk, sv, q_i8, dO_i8, q_bf, dO_bf, LD, sq, sdO, nullptr,
-                            dk, dv, bkv, skt, ny, 1, sqt, qks, sms, st);
-  // dQ: own Q, dO (+ their LD row stats) / streamed K8, V8, k image; scales: sq|sdO own, sk|sv
-  if (which & 2)
-    launch_bwd<D, ROLE_DQ>(causal, q_i8, dO_i8, sq, sdO, k_i8, v_i8, k_bf, nullptr, nullptr, sk, sv, LD,
-                           dq, nullptr, bh, sqt, skt, group, skt, qks, sms, st);
+  if (which & 1) launch_bwd<D, ROLE_DV>(a);
+  if (which & 4) launch_bwd<D, ROLE_DK>(a);
+  if (which & 8) launch_bwd<D, ROLE_DKV>(a);
+  if (which & 2) launch_bwd<D, ROLE_DQ>(a);
 }
 
-static int int8_bwd_launch(int which, const void* dO_i8, const void* sdO, const void* q_i8,
-                           const void* sq, const void* k_i8, const void* sk, const void* v_i8,
-                           const void* sv, const void* LD, const void* q_bf, const void* k_bf,
-                           const void* dO_bf, void* dq, void* dk, void* dv, long bh, long sqt,
-                           long skt, int group, int causal, int head_dim, float qks, float sms,
-                           void* stream, void* ws = nullptr) {
-  if (sqt % 32 != 0 || skt % 32 != 0 || group < 1 || bh % group != 0 ||
-      (head_dim != 64 && head_dim != 128))
+static int int8_bwd_launch(int which, const BwdArgs& a) {
+  if (a.sqt % 32 != 0 || a.skt % 32 != 0 || a.group < 1 || a.bh % a.group != 0 ||
+      (a.head_dim != 64 && a.head_dim != 128))
     return 1;
-  if (bh == 0 || sqt == 0 || skt == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (head_dim == 128)
-    bwd_launch_d<128>(which, dO_i8, sdO, q_i8, sq, k_i8, sk, v_i8, sv, LD, q_bf, k_bf, dO_bf, dq, dk,
-                      dv, bh, sqt, skt, group, causal, qks, sms, st, ws);
-  else
-    bwd_launch_d<64>(which, dO_i8, sdO, q_i8, sq, k_i8, sk, v_i8, sv, LD, q_bf, k_bf, dO_bf, dq, dk,
-                     dv, bh, sqt, skt, group, causal, qks, sms, st, ws);
+  if (a.bh == 0 || a.sqt == 0 || a.skt == 0) return 0;
+  if (a.head_dim == 128) bwd_launch_d<128>(which, a);
+  else bwd_launch_d<64>(which, a);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -1248,8 +1231,8 @@ extern "C" int qattn_int8_attn_bwd_ex(const void* dO_i8, const void* sdO, const 
                                       const void* q_bf, const void* k_bf, const void* dO_bf, void* dq,
                                       void* dk, void* dv, long bh, long sq_tok, long sk_tok, int group,
                                       int causal, int head_dim, float qks, float sms, void* stream) {
-  return int8_bwd_launch(8 | 2, dO_i8, sdO, q_i8, sq, k_i8, sk, v_i8, sv, LD, q_bf, k_bf, dO_bf, dq, dk,
-                         dv, bh, sq_tok, sk_tok, group, causal, head_dim, qks, sms, stream);
+  return int8_bwd_launch(8 | 2, {dO_i8, sdO, q_i8, sq, k_i8, sk, v_i8, sv, LD, q_bf, k_bf, dO_bf, dq, dk,
+                                 dv, bh, sq_tok, sk_tok, group, causal, head_dim, qks, sms, stream});
 }
 
 extern "C" int qattn_int8_attn_bwd(const void* dO_i8, const void* sdO, const void* q_i8,
@@ -1257,63 +1240,44 @@ extern "C" int qattn_int8_attn_bwd(const void* dO_i8, const void* sdO, const voi
                                    const void* sv, const void* LD, const void* q_bf, const void* k_bf,
                                    const void* dO_bf, void* dq, void* dk, void* dv, long bh, long seq,
                                    int head_dim, float qks, float sms, void* stream) {
-  return int8_bwd_launch(8 | 2, dO_i8, sdO, q_i8, sq, k_i8, sk, v_i8, sv, LD, q_bf, k_bf, dO_bf, dq, dk,
-                         dv, bh, seq, seq, 1, 0, head_dim, qks, sms, stream);
+  return int8_bwd_launch(8 | 2, {dO_i8, sdO, q_i8, sq, k_i8, sk, v_i8, sv, LD, q_bf, k_bf, dO_bf, dq, dk,
+                                 dv, bh, seq, seq, 1, 0, head_dim, qks, sms, stream});
 }
 extern "C" int qattn_int8_bwd_dkdv(const void* dO_i8, const void* sdO, const void* q_i8,
                                    const void* sq, const void* k_i8, const void* sk, const void* v_i8,
                                    const void* sv, const void* LD, const void* q_bf, const void* dO_bf,
                                    void* dk, void* dv, long bh, long seq, int head_dim, float qks,
                                    float sms, void* stream) {
-  return int8_bwd_launch(8, dO_i8, sdO, q_i8, sq, k_i8, sk, v_i8, sv, LD, q_bf, nullptr, dO_bf,
-                         nullptr, dk, dv, bh, seq, seq, 1, 0, head_dim, qks, sms, stream);
+  return int8_bwd_launch(8, {dO_i8, sdO, q_i8, sq, k_i8, sk, v_i8, sv, LD, q_bf, nullptr, dO_bf,
+                             nullptr, dk, dv, bh, seq, seq, 1, 0, head_dim, qks, sms, stream});
 }
 extern "C" int qattn_int8_bwd_dv(const void* dO_i8, const void* sdO, const void* q_i8,
                                    const void* sq, const void* k_i8, const void* sk, const void* v_i8,
                                    const void* sv, const void* LD, const void* q_bf, const void* dO_bf,
                                    void* dk, void* dv, long bh, long seq, int head_dim, float qks,
                                    float sms, void* stream) {
-  return int8_bwd_launch(1, dO_i8, sdO, q_i8, sq, k_i8, sk, v_i8, sv, LD, q_bf, nullptr, dO_bf,
-                         nullptr, dk, dv, bh, seq, seq, 1, 0, head_dim, qks, sms, stream);
+  return int8_bwd_launch(1, {dO_i8, sdO, q_i8, sq, k_i8, sk, v_i8, sv, LD, q_bf, nullptr, dO_bf,
+                             nullptr, dk, dv, bh, seq, seq, 1, 0, head_dim, qks, sms, stream});
 }
 extern "C" int qattn_int8_bwd_dk(const void* dO_i8, const void* sdO, const void* q_i8,
                                    const void* sq, const void* k_i8, const void* sk, const void* v_i8,
                                    const void* sv, const void* LD, const void* q_bf, const void* dO_bf,
                                    void* dk, void* dv, long bh, long seq, int head_dim, float qks,
                                    float sms, void* stream) {
-  return int8_bwd_launch(4, dO_i8, sdO, q_i8, sq, k_i8, sk, v_i8, sv, LD, q_bf, nullptr, dO_bf,
-                         nullptr, dk, dv, bh, seq, seq, 1, 0, head_dim, qks, sms, stream);
+  return int8_bwd_launch(4, {dO_i8, sdO, q_i8, sq, k_i8, sk, v_i8, sv, LD, q_bf, nullptr, dO_bf,
+                             nullptr, dk, dv, bh, seq, seq, 1, 0, head_dim, qks, sms, stream});
 }
 extern "C" int qattn_int8_bwd_dq(const void* dO_i8, const void* sdO, const void* q_i8,
                                  const void* sq, const void* k_i8, const void* sk, const void* v_i8,
                                  const void* sv, const void* LD, const void* k_bf, void* dq, long bh,
                                  long seq, int head_dim, float qks, float sms, void* stream) {
-  return int8_bwd_launch(2, dO_i8, sdO, q_i8, sq, k_i8, sk, v_i8, sv, LD, nullptr, k_bf, nullptr, dq,
-                         nullptr, nullptr, bh, seq, seq, 1, 0, head_dim, qks, sms, stream);
+  return int8_bwd_launch(2, {dO_i8, sdO, q_i8, sq, k_i8, sk, v_i8, sv, LD, nullptr, k_bf, nullptr, dq,
+                             nullptr, nullptr, bh, seq, seq, 1, 0, head_dim, qks, sms, stream});
 }
 
-// The dK+dV kernel addresses the records of one key/value head (its G query heads) with 32-bit
-// buffer offsets: that region, G * (sq/32) * (sk/32) KiB, must stay below 2^31 bytes.
-static bool ws_region_fits(long group, long sq_tok, long sk_tok) {
-  return group * (sq_tok / 32) * (sk_tok / 32) * 1024 < (1L << 31);
-}
-
-// Largest dS-record workspace either backward (int8 or bf16) allocates before it falls back to
-// recomputation: QATTN_BWD_WS_MAX bytes if set, else 16 GiB.  A fixed figure, not the device's free
-// memory: hipMemGetInfo does not see what the caller's caching allocator holds reserved, so a free-
-// memory cap would depend on allocator history; an allocation that fails falls back to the
-// recomputing backward instead (same results).
-extern "C" long qattn_bwd_ws_cap(void) {
-  const char* s = getenv("QATTN_BWD_WS_MAX");
-  if (s != nullptr && *s != 0) return strtol(s, nullptr, 10);
-  return 16L << 30;
-}
-
-extern "C" long qattn_int8_bwd_ws_bytes(long bh, long sq_tok, long sk_tok) {
-  if (sq_tok % 32 != 0 || sk_tok % 32 != 0 || bh < 0) return -1;
-  if (!ws_region_fits(1, sq_tok, sk_tok)) return -1;   // too large even ungrouped: recompute instead
-  return bh * (sq_tok / 32) * (sk_tok / 32) * (1024 + 4);
-}
+// (plan.hip, with the size and cap functions of the dS workspace: the records of one key/value head
+// must stay below 2^31 bytes)
+namespace qattn { bool ws_region_fits(long group, long sq_tok, long sk_tok); }
 
 extern "C" int qattn_int8_attn_bwd_ws(const void* dO_i8, const void* sdO, const void* q_i8,
                                       const void* sq, const void* k_i8, const void* sk,
@@ -1323,20 +1287,20 @@ extern "C" int qattn_int8_attn_bwd_ws(const void* dO_i8, const void* sdO, const 
                                       int group, int causal, int head_dim, float qks, float sms,
                                       void* stream) {
   if (ws == nullptr || group < 1 || !ws_region_fits(group, sq_tok, sk_tok)) return 1;
-  return int8_bwd_launch(16 | 32, dO_i8, sdO, q_i8, sq, k_i8, sk, v_i8, sv, LD,
-                         q_bf, k_bf, dO_bf, dq, dk, dv, bh, sq_tok, sk_tok, group, causal, head_dim, qks,
-                         sms, stream, ws);
+  return int8_bwd_launch(16 | 32, {dO_i8, sdO, q_i8, sq, k_i8, sk, v_i8, sv, LD, q_bf, k_bf, dO_bf, dq,
+                                   dk, dv, bh, sq_tok, sk_tok, group, causal, head_dim, qks, sms, stream,
+                                   ws});
 }
 
 // qattn_int8_attn_bwd_ws over chunks of kv_chunk key/value heads (with their group query heads):
 // dK+dV of a chunk writes its records into ws, the dQ pass of the same chunk reads them, and the next
 // chunk re-uses the same ws bytes.  Every tensor is head-major and contiguous, so a chunk is a plain
 // pointer offset; results are bit-identical to the one-shot call (each head's arithmetic is
-// unchanged).  The chunk size is the caller's: a chunk's records stay in the 256 MB Infinity Cache
-// between their write and their read only if the chunk's records plus the other bytes both passes
-// move stay under ~256 MB (MI355X_MICROARCH "Infinity Cache"); the default chunk at config 3 (32
-// heads, 539 MB of records) does not, so there the records go through HBM.  What chunking buys
-// there is a quarter of the workspace and a measured 2-4 % (attention_int8.WS_CHUNK).
+// unchanged).  The chunk size is the caller's (qattn_int8_bwd_plan, plan.hip): a chunk's records
+// stay in the 256 MB Infinity Cache between their write and their read only if the chunk's records
+// plus the other bytes both passes move stay under ~256 MB (MI355X_MICROARCH "Infinity Cache"); the
+// planned chunk at config 3 (32 heads, 539 MB of records) does not, so there the records go through
+// HBM.  What chunking buys there is a quarter of the workspace and a measured 2-4 %.
 extern "C" int qattn_int8_attn_bwd_wsc(const void* dO_i8, const void* sdO, const void* q_i8,
                                        const void* sq, const void* k_i8, const void* sk,
                                        const void* v_i8, const void* sv, const void* LD,
@@ -1353,11 +1317,12 @@ extern "C" int qattn_int8_attn_bwd_wsc(const void* dO_i8, const void* sdO, const
     const long nkv = std::min(kv_chunk, bkv - k0);
     const long qr = k0 * group * sq_tok, kr = k0 * sk_tok;   // first query / key row of the chunk
     const int rc = int8_bwd_launch(
-        16 | 32, at(dO_i8, qr * D), at(sdO, qr / 32 * 2), at(q_i8, qr * D), at(sq, qr / 32 * 2),
-        at(k_i8, kr * D), at(sk, kr / 32 * 2), at(v_i8, kr * D), at(sv, kr / 32 * 2), at(LD, qr * 8),
-        at(q_bf, qr * D * 2), at(k_bf, kr * D * 2), at(dO_bf, qr * D * 2), at(dq, qr * D * 2),
-        at(dk, kr * D * 2), at(dv, kr * D * 2), nkv * group, sq_tok, sk_tok, group, causal, head_dim,
-        qks, sms, stream, ws);
+        16 | 32,
+        {at(dO_i8, qr * D), at(sdO, qr / 32 * 2), at(q_i8, qr * D), at(sq, qr / 32 * 2),
+         at(k_i8, kr * D), at(sk, kr / 32 * 2), at(v_i8, kr * D), at(sv, kr / 32 * 2), at(LD, qr * 8),
+         at(q_bf, qr * D * 2), at(k_bf, kr * D * 2), at(dO_bf, qr * D * 2), at(dq, qr * D * 2),
+         at(dk, kr * D * 2), at(dv, kr * D * 2), nkv * group, sq_tok, sk_tok, group, causal, head_dim,
+         qks, sms, stream, ws});
     if (rc != 0) return rc;
   }
   return 0;
@@ -1377,14 +1342,13 @@ extern "C" int qattn_int8_bwd_dkdv_ws(const void* dO_i8, const void* sdO, const 
                                       long bh, long seq, int head_dim, float qks, float sms,
                                       void* stream) {
   if (ws == nullptr || !ws_region_fits(1, seq, seq)) return 1;
-  return int8_bwd_launch(16, dO_i8, sdO, q_i8, sq, k_i8, sk, v_i8, sv, LD, q_bf,
-                         nullptr, dO_bf, nullptr, dk, dv, bh, seq, seq, 1, 0, head_dim, qks, sms, stream,
-                         ws);
+  return int8_bwd_launch(16, {dO_i8, sdO, q_i8, sq, k_i8, sk, v_i8, sv, LD, q_bf, nullptr, dO_bf,
+                              nullptr, dk, dv, bh, seq, seq, 1, 0, head_dim, qks, sms, stream, ws});
 }
 extern "C" int qattn_int8_bwd_dq_ws(const void* k_bf, const void* sk, void* dq, void* ws, long bh,
                                     long seq, int head_dim, float sms, void* stream) {
   if (ws == nullptr) return 1;
-  return int8_bwd_launch(32, nullptr, nullptr, nullptr, nullptr, nullptr, sk, nullptr, nullptr,
-                         nullptr, nullptr, k_bf, nullptr, dq, nullptr, nullptr, bh, seq, seq, 1, 0,
-                         head_dim, 0.f, sms, stream, ws);
+  return int8_bwd_launch(32, {nullptr, nullptr, nullptr, nullptr, nullptr, sk, nullptr, nullptr,
+                              nullptr, nullptr, k_bf, nullptr, dq, nullptr, nullptr, bh, seq, seq, 1, 0,
+                              head_dim, 0.f, sms, stream, ws});
 }

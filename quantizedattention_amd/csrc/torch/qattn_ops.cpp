@@ -23,7 +23,8 @@
 //   mxfp4_fwd_ex(q, k, v, causal) -> O                       (the same with a mask: 0 / 1 / 2)
 //   mxfp4_cached(q, k4, ks, vt, vs, causal, keys_per_split) -> (O, lse)
 //       kv_cache_mxfp4.attention_mxfp4_cached on the cache's four operands (causal 0 / 1 bottom-right
-//       over the cache; keys_per_split 0: the plan of _split_plan_fp4)
+//       over the cache; keys_per_split 0: the plan of qattn_split_keys)
+// Workspaces, head chunks and key splits are planned by the library (csrc/plan.hip), as in the drop-ins.
 // Errors: TORCH_CHECK (c10::Error, RuntimeError in Python) with the drop-ins' messages; int8_quant's
 // argument checks raise ValueError (TORCH_CHECK_VALUE) as its Python predecessor did.
 #include <ATen/ATen.h>
@@ -34,7 +35,6 @@
 #include <c10/hip/HIPCachingAllocator.h>
 
 #include <cmath>
-#include <cstdlib>
 #include <map>
 #include <mutex>
 #include <string>
@@ -70,11 +70,6 @@ void require_gpu(std::initializer_list<const Tensor*> ts) {
 // fp32(1/sqrt(D) * log2(e)) and fp32(1/sqrt(D)): the Python double rounded once to fp32
 float qk_scale(int64_t D) { return (float)(1.0 / std::sqrt((double)D) * 1.44269504); }
 float sm_scale(int64_t D) { return (float)(1.0 / std::sqrt((double)D)); }
-
-int64_t env_i64(const char* name, int64_t dflt) {
-  const char* s = std::getenv(name);
-  return (s && *s) ? std::strtoll(s, nullptr, 10) : dflt;
-}
 
 Tensor empty(at::IntArrayRef shape, at::ScalarType dt, const Tensor& like) {
   return at::empty(shape, like.options().dtype(dt));
@@ -216,25 +211,14 @@ T3 int8_bwd(const Tensor& dO_in, const Tensor& q_i8_in, const Tensor& sq, const 
   Tensor dq = empty({B, H, S, D}, at::kHalf, O), dk = empty({B, Hkv, Sk, D}, at::kHalf, O),
          dv = empty({B, Hkv, Sk, D}, at::kHalf, O);
   const float qks = qk_scale(D), sms = sm_scale(D);
-  // workspace chunking (attention_int8._ws_chunk): non-causal >= 512 dK+dV workgroups per chunk
-  const int64_t bkv = B * Hkv;
-  int64_t chunk = env_i64("QATTN_BWD_WS_CHUNK", -1);
-  if (chunk < 0) chunk = causal ? 0 : (512 + std::max<int64_t>(1, Sk / 256) - 1) / std::max<int64_t>(1, Sk / 256);
-  chunk = chunk <= 0 ? bkv : std::min(chunk, bkv);
-  const int64_t ws_bytes = qattn_int8_bwd_ws_bytes(chunk * G, S, Sk);
-  const bool region_ok = G * (S / 32) * (Sk / 32) * 1024 < (int64_t(1) << 31);
+  long chunk = 0;
+  const long ws_bytes = qattn_int8_bwd_plan(B * Hkv, (int)G, S, Sk, causal ? 1 : 0, -1, -1, &chunk);
   Tensor ws;
-  if (ws_bytes > 0 && region_ok && ws_bytes <= qattn_bwd_ws_cap())
-    ws = try_empty(ws_bytes, O);
-  if (ws.defined() && chunk < bkv) {
+  if (ws_bytes > 0) ws = try_empty(ws_bytes, O);
+  if (ws.defined()) {
     call(qattn_int8_attn_bwd_wsc(P(dO_i8), P(sdO), P(q_i8), P(sqc), P(k_i8), P(skc), P(v_i8), P(svc),
                                  P(LD), P(q_bf), P(k_bf), P(dO_bf), P(dq), P(dk), P(dv), P(ws), chunk,
                                  B * H, S, Sk, (int)G, causal ? 1 : 0, (int)D, qks, sms, c.stream),
-         "int8 backward");
-  } else if (ws.defined()) {
-    call(qattn_int8_attn_bwd_ws(P(dO_i8), P(sdO), P(q_i8), P(sqc), P(k_i8), P(skc), P(v_i8), P(svc),
-                                P(LD), P(q_bf), P(k_bf), P(dO_bf), P(dq), P(dk), P(dv), P(ws), B * H, S,
-                                Sk, (int)G, causal ? 1 : 0, (int)D, qks, sms, c.stream),
          "int8 backward");
   } else {
     call(qattn_int8_attn_bwd_ex(P(dO_i8), P(sdO), P(q_i8), P(sqc), P(k_i8), P(skc), P(v_i8), P(svc),
@@ -302,13 +286,9 @@ T3 bf16_bwd(const Tensor& q_in, const Tensor& k_in, const Tensor& v_in, const Te
   Tensor dq = empty({B, H, S, D}, at::kFloat, q), dk = empty({B, Hkv, Sk, D}, at::kFloat, q),
          dv = empty({B, Hkv, Sk, D}, at::kFloat, q);
   const float qks = qk_scale(D), sms = sm_scale(D);
-  const int64_t forced = env_i64("QATTN_BF16_BWD_WS", -1);   // 1 / 0 force the records on / off
-  const bool want_ws = forced < 0 ? causal : forced == 1;
+  const long ws_bytes = qattn_bf16_bwd_plan(B * H, S, Sk, causal ? 1 : 0, -1, -1);
   Tensor ws;
-  if (want_ws) {
-    const int64_t ws_bytes = qattn_bf16_bwd_ws_bytes(B * H, S, Sk);
-    if (ws_bytes > 0 && ws_bytes <= qattn_bwd_ws_cap()) ws = try_empty(ws_bytes, q);
-  }
+  if (ws_bytes > 0) ws = try_empty(ws_bytes, q);
   if (ws.defined())
     call(qattn_bf16_bwd_ws_ex(P(q), P(k), P(v), P(dO_bf), P(LD), P(q_bf), P(k_bf), P(dq), P(dk), P(dv),
                               B * H, S, Sk, (int)(H / Hkv), causal ? 1 : 0, (int)D, qks, sms, P(ws),
@@ -408,13 +388,6 @@ Tensor mxfp4_fwd_ex(const Tensor& q_in, const Tensor& k_in, const Tensor& v_in, 
 
 Tensor mxfp4_fwd(const Tensor& q, const Tensor& k, const Tensor& v) { return mxfp4_fwd_ex(q, k, v, 0); }
 
-// kv_cache_mxfp4._split_plan_fp4: 512 workgroups, no split under 1024 keys, multiples of 64
-int64_t split_plan_fp4(int64_t bhv, int64_t rows, int64_t sk) {
-  const int64_t wgs = bhv * ((rows + 127) / 128);
-  const int64_t nsplit = std::max<int64_t>(1, std::min(sk / 1024, (512 + wgs - 1) / wgs));
-  return (sk / 64 + nsplit - 1) / nsplit * 64;
-}
-
 // kv_cache_mxfp4.attention_mxfp4_cached: q of any Sq >= 1 against an MX-FP4 cache in the decoding
 // layout (split over the keys, then merged)
 std::tuple<Tensor, Tensor> mxfp4_cached(const Tensor& q_in, const Tensor& k4, const Tensor& ks,
@@ -439,7 +412,7 @@ std::tuple<Tensor, Tensor> mxfp4_cached(const Tensor& q_in, const Tensor& k4, co
                   vs.sizes() == at::IntArrayRef({B * Hkv, Sk / 64, D, 2}),
               "qattn mxfp4 kv cache: ks / vt / vs do not match k4");
   const int64_t bhv = B * Hkv, rows = (Hq / Hkv) * Sq;
-  int64_t kps = keys_per_split == 0 ? split_plan_fp4(bhv, rows, Sk) : keys_per_split;
+  int64_t kps = keys_per_split == 0 ? qattn_split_keys(bhv, rows, Sk, 64) : keys_per_split;
   TORCH_CHECK(kps >= 64 && kps % 64 == 0, "qattn mxfp4 kv cache: keys_per_split must be a multiple of 64");
   kps = std::min(kps, Sk);
   const int64_t nsplit = (Sk + kps - 1) / kps;

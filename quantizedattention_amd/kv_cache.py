@@ -31,7 +31,6 @@ qattn_int8_attn_fwd_ex), so a decode step sees the whole prefix.
 from __future__ import annotations
 
 import json
-import math
 from dataclasses import dataclass
 from typing import Optional
 
@@ -233,7 +232,7 @@ def attention_int8_cached(q: torch.Tensor, kv: QuantizedKV, causal: bool = False
     O = torch.empty((B, Hq, Sq, D), dtype=torch.float16, device=dev)
     lse = torch.empty((N,), dtype=torch.float16, device=dev)
     _lib.call("qattn_int8_quant", _lib.ptr(q), _lib.ptr(q_i8), _lib.ptr(sq), None, None, N, Sq, D, st)
-    qks = float(torch.tensor(1.0 / math.sqrt(D) * 1.44269504, dtype=torch.float32))
+    qks = _lib.qk_scale(D)
     mode = 2 if causal else 0          # bottom-right aligned causal mask
     if not causal and D == 128:
         _decode_split(q_i8, sq, kv, O, lse, B, Hq, Sq, qks, st)
@@ -250,10 +249,8 @@ def _split_plan(bhv: int, rows: int, sk: int) -> int:
     tiles); sk (a multiple of 32) when one split suffices.  Measured on MI355X (tools/sweep_decode.py,
     D = 128): (B, Hq, Hkv, Sk) = (8, 32, 8, 8192) 1024 keys 56 us (512: 72, 2048: 60, one pass
     154); (8, 32, 32, 8192) 4096 keys 110 us (1024: 127, one pass 142); (1, 32, 8, 32768) 1024 keys
-    49 us (512: 65, 2048: 56, one pass 578)."""
-    wgs = bhv * -(-rows // 128)
-    nsplit = max(1, min(sk // 1024, -(-512 // wgs)))
-    return -(-(sk // 32) // nsplit) * 32
+    49 us (512: 65, 2048: 56, one pass 578).  The rule itself is the library's (qattn_split_keys)."""
+    return _lib.load().qattn_split_keys(bhv, rows, sk, BLOCK)
 
 
 def _decode_split(q_i8, sq, kv, O, lse, B, Hq, Sq, qks, st):

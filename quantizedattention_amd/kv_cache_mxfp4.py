@@ -165,7 +165,7 @@ def quantize_kv_fp4(k: torch.Tensor, v: torch.Tensor, smooth: bool = True,
     return QuantizedKVFP4(k4.view(B, H, S, D // 2), ks.view(B, H, S, D // 32), vt, vs, km)
 
 
-MIN_SPLIT_KEYS = 1024
+MIN_SPLIT_KEYS = 1024   # (qattn_split_keys' constant, restated: the tests hold the plan to it)
 
 
 def _split_plan_fp4(bhv: int, rows: int, sk: int) -> int:
@@ -178,10 +178,8 @@ def _split_plan_fp4(bhv: int, rows: int, sk: int) -> int:
     512: 106, one pass 160); (1, 32, 8, 32, 32768) 1024 keys 46 us (512: 59, 2048: 51, one pass
     481); (4, 32, 32, 128, 8192) 2048 keys 61 us (1024: 68, 4096: 77, one pass 130); (8, 32, 8, 1,
     8192) 1024 keys 47 us (256 to 2048: 47 to 48, 4096: 72).  Splits under 1024 keys lose at every
-    shape with 32 or more query rows per head."""
-    wgs = bhv * -(-rows // 128)
-    nsplit = max(1, min(sk // MIN_SPLIT_KEYS, -(-512 // wgs)))
-    return -(-(sk // BLOCK) // nsplit) * BLOCK
+    shape with 32 or more query rows per head.  The rule itself is the library's (qattn_split_keys)."""
+    return _lib.load().qattn_split_keys(bhv, rows, sk, BLOCK)
 
 
 @torch.no_grad()

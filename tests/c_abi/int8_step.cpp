@@ -79,21 +79,29 @@ int main(int argc, char** argv) {
   CHECK_QA(qattn_int8_quant_img(k, k_i8, sk, nullptr, k_bf, k_mean, N, (int)S, D, st));
   CHECK_QA(qattn_int8_quant_vt(v, v_i8, sv, vt, N, D, st));
   CHECK_QA(qattn_int8_attn_fwd_ex(q_i8, sq, k_i8, sk, vt, sv, O, lse, B * H, S, S, 1, 0, D, qks, st));
-  // backward (attention_int8._int8_backward: prologue, then the one-pass dS-record backward)
+  // backward (attention_int8._int8_backward: prologue, then the dS-record backward in head chunks)
   void *dO_i8 = dalloc(i8b), *sdO = dalloc(sb), *LD = dalloc((size_t)N * 8), *dO_bf = dalloc(f16b);
   void *dq = dalloc(f16b), *dk = dalloc(f16b), *dv = dalloc(f16b);
   CHECK_QA(qattn_int8_bwd_prep(dO, O, lse, dO_i8, sdO, LD, dO_bf, B * H, S, D, st));
-  const long ws_bytes = qattn_int8_bwd_ws_bytes(B * H, S, S);
-  void* ws = dalloc((size_t)ws_bytes);
-  CHECK_QA(qattn_int8_attn_bwd_ws(dO_i8, sdO, q_i8, sq, k_i8, sk, v_i8, sv, LD, q_bf, k_bf, dO_bf, dq, dk,
-                                  dv, ws, B * H, S, S, 1, 0, D, qks, sms, st));
+  // the library's plan, as the drop-in takes it: heads per chunk and the bytes of one chunk's records
+  // (0: no records, the dQ pass recomputes)
+  long kv_chunk = 0;
+  const long ws_bytes = qattn_int8_bwd_plan(B * H, 1, S, S, 0, -1, -1, &kv_chunk);
+  if (ws_bytes < 0) { std::fprintf(stderr, "qattn_int8_bwd_plan refused the shape\n"); return 4; }
+  void* ws = ws_bytes > 0 ? dalloc((size_t)ws_bytes) : nullptr;
+  if (ws != nullptr)
+    CHECK_QA(qattn_int8_attn_bwd_wsc(dO_i8, sdO, q_i8, sq, k_i8, sk, v_i8, sv, LD, q_bf, k_bf, dO_bf, dq,
+                                     dk, dv, ws, kv_chunk, B * H, S, S, 1, 0, D, qks, sms, st));
+  else
+    CHECK_QA(qattn_int8_attn_bwd_ex(dO_i8, sdO, q_i8, sq, k_i8, sk, v_i8, sv, LD, q_bf, k_bf, dO_bf, dq,
+                                    dk, dv, B * H, S, S, 1, 0, D, qks, sms, st));
   CHECK_HIP(hipStreamSynchronize(st));
   write_file(dir + "/O.f16", O, f16b);
   write_file(dir + "/lse.f16", lse, (size_t)N * 2);
   write_file(dir + "/dq.f16", dq, f16b);
   write_file(dir + "/dk.f16", dk, f16b);
   write_file(dir + "/dv.f16", dv, f16b);
-  std::printf("int8_step ok: %ld x %d, workspace %ld B\n", N, D, ws_bytes);
+  std::printf("int8_step ok: %ld x %d, workspace %ld B, %ld heads per chunk\n", N, D, ws_bytes, kv_chunk);
   for (void* p : {q, k, v, dO, q_i8, k_i8, v_i8, vt, sq, sk, sv, k_mean, q_bf, k_bf, O, lse, dO_i8, sdO, LD,
                   dO_bf, dq, dk, dv, ws})
     CHECK_HIP(hipFree(p));
