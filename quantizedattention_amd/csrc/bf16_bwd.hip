@@ -16,7 +16,7 @@
 // exp2(-128 - lse) < 2^-120 per element and are skipped.
 #include <type_traits>
 
-#include "common.h"
+#include "tile_image.h"
 
 namespace qattn {
 
@@ -92,14 +92,14 @@ enum B16Role { B16_DV = 0, B16_DK = 1, B16_DQ = 2, B16_DKV = 3 };
 
 template <int D, int ROLE>
 struct B16Cfg {
-  static constexpr int ROWB = 2 * D;
-  static constexpr int NCH = ROWB / 16;
-  static constexpr int T16 = 32 * ROWB;                     // one 32-row 16-bit tile
+  using Rows = B16Rows<D>;                                  // row-read regions (tile_image.h)
+  using Tr = B16Tr<D>;                                      // transposed-read regions
+  static constexpr int T16 = Tr::TILE;                      // one 32-row 16-bit tile
   static constexpr bool TWO = ROLE != B16_DV;               // S and dP
   static constexpr bool HAS_LD = ROLE != B16_DQ;            // {lse, D} per row of the streamed side
   static constexpr bool FUSED = ROLE == B16_DKV;
   // FUSED at D=128: one dO image serves both the row reads (dP) and the tr reads (dV), under the
-  // swizzle b16_csw that is conflict-free for both; D=64 keeps a separate dO tr image
+  // swizzle B16Csw that is conflict-free for both; D=64 keeps a separate dO tr image
   static constexpr bool MERGE = FUSED && D == 128;
   static constexpr int NREG = FUSED ? (MERGE ? 3 : 4) : TWO ? 3 : 2;   // 16-bit regions per slot
   static constexpr int NROW = FUSED ? 2 : NREG - 1;         // row-read regions come first
@@ -108,7 +108,7 @@ struct B16Cfg {
   static constexpr int NSLOT = (ROLE == B16_DV) ? QA_B16_DV_NSLOT : 3;
   static constexpr int WAVES = FUSED ? 8 : (ROLE == B16_DQ && D == 128) ? QA_B16_DQ_WAVES : 4;
   static constexpr int XROWS = 32 * (FUSED ? 4 : WAVES);    // own rows per workgroup
-  static constexpr int NP = T16 / 1024;                     // 1-KiB LDS-DMA pieces per region
+  static constexpr int NP = Tr::NP;                         // 1-KiB LDS-DMA pieces per region
   static constexpr int INST = NREG * NP;
   static constexpr int DMA_WAVES = (FUSED && QA_B16_DMA_P) ? 4 : WAVES;   // waves issuing the DMA
   static constexpr int IPW16 = INST / DMA_WAVES;
@@ -122,14 +122,17 @@ struct B16Cfg {
   static constexpr int LDS = (RING > STAGE) ? RING : STAGE;
   static_assert(INST % DMA_WAVES == 0, "DMA pieces split evenly over the waves");
 };
+// The merged dO image (D = 128), read both ways: ds_read_b128 row reads see 16 distinct chunks per
+// 16-lane group, and ds_read_b64_tr_b16 reads of 4 rows x 4 chunks per 32-lane group see 16 distinct
+// chunks.  Unlike B16Tr's its swizzle changes under row + 8, so tr reads keep one offset per 8-row
+// half (the per-half tr_load).
+struct B16Csw {
+  static QA_IMG int sw(int row) { return (row & 15) ^ ((row & 3) << 2); }
+};
 template <int D>
-QA_DEVICE int b16_rsw(int row) { return (D == 128) ? (row & 15) : ((row >> 1) & 7); }   // row reads
-template <int D>
-QA_DEVICE int b16_tsw(int row) { return (row & 3) << ((D == 128) ? 2 : 1); }            // tr reads
-// both (D = 128): ds_read_b128 row reads see 16 distinct chunks per 16-lane group, and
-// ds_read_b64_tr_b16 reads of 4 rows x 4 chunks per 32-lane group see 16 distinct chunks; unlike
-// b16_tsw it is not invariant under row += 8, so tr reads keep one offset per 8-row half
-QA_DEVICE int b16_csw(int row) { return (row & 15) ^ ((row & 3) << 2); }
+using B16Merged = TileImage<2 * D, B16Csw>;
+static_assert(row_reads_agree<B16Merged<128>>() && tr_reads_agree<B16Merged<128>>() && !B16Merged<128>::period(8),
+              "the merged dO image's DMA plan and its two readers disagree");
 
 template <int D, int ROLE>
 struct B16Dma {
@@ -139,20 +142,19 @@ struct B16Dma {
   v4u rsrc[G::IPW16];
   v4u ld_rsrc;
   bool ld_on;
-  // region r of a slot is filled from src[r] (row-swizzled for r < NROW, tr-swizzled after; the
-  // merged dO region with b16_csw)
+  // region r of a slot is filled from src[r] (a Rows image for r < NROW, a Tr image after; the
+  // merged dO region a B16Merged image)
   QA_DEVICE void init(int wave, int lane, int Sy, const char* const* src, const char* ld) {
-    constexpr int RPI = 64 / G::NCH;
 #pragma unroll
     for (int i = 0; i < G::IPW16; ++i) {
       const int p = wave % G::DMA_WAVES + G::DMA_WAVES * i;
       const int r = p / G::NP, q = p % G::NP;
       const bool is_tr = r >= G::NROW;
-      const int row = q * RPI + lane / G::NCH, c = lane % G::NCH;
-      const int sw = (G::MERGE && r == 1) ? b16_csw(row) : is_tr ? b16_tsw<D>(row) : b16_rsw<D>(row);
-      voff[i] = row * G::ROWB + 16 * (c ^ sw);
+      const int row = G::Tr::piece_row(q, lane), c = lane % G::Tr::NCH;
+      const int sw = (G::MERGE && r == 1) ? B16Csw::sw(row) : is_tr ? G::Tr::sw(row) : G::Rows::sw(row);
+      voff[i] = G::Tr::chunk_at(row, c, sw);
       lds_off[i] = r * G::T16 + q * 1024;
-      rsrc[i] = make_rsrc(src[r], (unsigned)Sy * G::ROWB);
+      rsrc[i] = make_rsrc(src[r], (unsigned)Sy * G::Tr::ROWB);
     }
     if constexpr (G::HAS_LD) ld_rsrc = make_rsrc(ld, (unsigned)Sy * 8);
     ld_on = !G::FUSED || wave == G::DMA_WAVES - 1;   // FUSED: one wave brings the {lse, D} rows
@@ -239,16 +241,10 @@ bf16_bwd_kernel(const _Float16* __restrict__ xa, const __bf16* __restrict__ xb,
   // lane-constant LDS offsets: row-read A operand chunk (2s+h) of row c32; tr A operand per d block
   int roff[G::NKS], troff[G::NDB];
 #pragma unroll
-  for (int s = 0; s < G::NKS; ++s) roff[s] = c32 * G::ROWB + 16 * ((2 * s + h) ^ b16_rsw<D>(c32));
-  {
-    const int gg = (lane >> 4) & 1, i16 = lane & 15;
-    const int row = 4 * h + (i16 >> 2);
+  for (int s = 0; s < G::NKS; ++s) roff[s] = G::Rows::row_off(c32, 2 * s + h);
+  const auto trl = G::Tr::tr_lane(lane, h);
 #pragma unroll
-    for (int b = 0; b < G::NDB; ++b) {
-      const int d = 32 * b + 16 * gg + 4 * (i16 & 3);
-      troff[b] = G::TR + row * G::ROWB + 16 * ((d / 8) ^ b16_tsw<D>(row)) + (d % 8) * 2;
-    }
-  }
+  for (int b = 0; b < G::NDB; ++b) troff[b] = G::TR + G::Tr::tr_off(trl, b);
   v16f acc[G::NDB];
 #pragma unroll
   for (int b = 0; b < G::NDB; ++b) acc[b] = v16f{};
@@ -307,16 +303,7 @@ bf16_bwd_kernel(const _Float16* __restrict__ xa, const __bf16* __restrict__ xb,
       op[s] = __builtin_bit_cast(v8bf, w);
     }
   };
-  auto tr_load = [&](auto SLc, v8bf* ta) {
-    const char* base = slot(SLc);
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int b = 0; b < G::NDB; ++b) {
-        const char* a = base + troff[b] + 16 * s * G::ROWB;
-        ta[s * G::NDB + b] = __builtin_bit_cast(v8bf, ds_read_tr16_x2(a, a + 8 * G::ROWB));
-      }
-  };
+  auto tr_load = [&](auto SLc, v8bf* ta) { G::Tr::tr_load(slot(SLc), troff, ta); };
 
   vmem_drain();
   __syncthreads();
@@ -422,23 +409,18 @@ __global__ __launch_bounds__(512, 2) void bf16_bwd_dkv_kernel(
   int roff[G::NKS], troff[2][2][G::NDB];
 #pragma unroll
   for (int s = 0; s < G::NKS; ++s)
-    roff[s] = c32 * G::ROWB + 16 * ((2 * s + h) ^ (csw_rows ? b16_csw(c32) : b16_rsw<D>(c32)));
-  {
-    const int gg = (lane >> 4) & 1, i16 = lane & 15;
-    const int treg = pwave ? G::TR2 : G::TR;
+    roff[s] = G::Tr::chunk_at(c32, 2 * s + h, csw_rows ? B16Csw::sw(c32) : G::Rows::sw(c32));
+  const auto trl = G::Tr::tr_lane(lane, h);
+  const int treg = pwave ? G::TR2 : G::TR;
 #pragma unroll
-    for (int s = 0; s < 2; ++s)
+  for (int s = 0; s < 2; ++s)
 #pragma unroll
-      for (int hf = 0; hf < 2; ++hf) {
-        const int row = 16 * s + 8 * hf + 4 * h + (i16 >> 2);
-        const int sw = csw_tr ? b16_csw(row) : b16_tsw<D>(row);
+    for (int hf = 0; hf < 2; ++hf) {
+      const int row = 16 * s + 8 * hf + trl.row;
+      const int sw = csw_tr ? B16Csw::sw(row) : G::Tr::sw(row);
 #pragma unroll
-        for (int b = 0; b < G::NDB; ++b) {
-          const int d = 32 * b + 16 * gg + 4 * (i16 & 3);
-          troff[s][hf][b] = treg + row * G::ROWB + 16 * ((d / 8) ^ sw) + (d % 8) * 2;
-        }
-      }
-  }
+      for (int b = 0; b < G::NDB; ++b) troff[s][hf][b] = treg + G::Tr::elem_at(row, G::Tr::tr_d(trl, b), sw);
+    }
   v16f acc[G::NDB];
 #pragma unroll
   for (int b = 0; b < G::NDB; ++b) acc[b] = v16f{};
@@ -457,14 +439,8 @@ __global__ __launch_bounds__(512, 2) void bf16_bwd_dkv_kernel(
     }
   };
   auto accumulate = [&](auto SLc, const v8bf* op) {
-    const char* base = slot(SLc);
     v8bf ta[2 * G::NDB];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int b = 0; b < G::NDB; ++b)
-        ta[s * G::NDB + b] =
-            __builtin_bit_cast(v8bf, ds_read_tr16_x2(base + troff[s][0][b], base + troff[s][1][b]));
+    G::Tr::tr_load(slot(SLc), troff, ta);
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -622,13 +598,17 @@ __global__ __launch_bounds__(512, 2) void bf16_bwd_dkv_kernel(
 template <int D>
 struct B16DqwCfg {
   static constexpr int WAVES = 8;
-  static constexpr int ROWB = 2 * D;
-  static constexpr int T16 = 32 * ROWB;
+  using Tr = B16Tr<D>;                   // the k image
+  struct Plain {
+    static QA_IMG int sw(int) { return 0; }
+  };
+  using Rec = TileImage<64, Plain>;      // a dS record: 32 keys x 32 bf16 queries, unswizzled
+  static_assert(Rec::NDB == 1, "a record is one d block: its tr_load takes the one offset");
+  static constexpr int T16 = Tr::TILE;
   static constexpr int NSLOT = 4, RSLOT = 5;
-  static constexpr int REC = WAVES * 2048;
+  static constexpr int REC = WAVES * Rec::TILE;
   static constexpr int RBASE = NSLOT * T16;
-  static constexpr int NP16 = T16 / 1024;
-  static constexpr int IPK = (NP16 + WAVES - 1) / WAVES;
+  static constexpr int IPK = TrImageDma<D, WAVES>::IPK;
   static constexpr int NDB = D / 32;
   static constexpr int RING = RBASE + RSLOT * REC;
   static constexpr int STAGE = WAVES * RowTile<D, float, 2>::BYTES;
@@ -657,29 +637,16 @@ __global__ __launch_bounds__(512, 2) void bf16_bwd_dqw_kernel(const __bf16* __re
   const int ntw = CAUSAL ? min(nkt, (q0 / 128) * 4 + 4) : nkt;             // this wave's tiles
   const long rec0 = ((long)bh * nqt + (active ? q0 / 32 : 0)) * nkt;
 
-  unsigned kvoff[W::IPK], klds[W::IPK];
-  v4u krsrc[W::IPK];
-#pragma unroll
-  for (int i = 0; i < W::IPK; ++i) {
-    int pc = wave + W::WAVES * i;
-    if (pc >= W::NP16) pc = wave % W::NP16;
-    constexpr int NCH = W::ROWB / 16, RPI = 64 / NCH;
-    const int row = pc * RPI + lane / NCH, c = lane % NCH;
-    kvoff[i] = row * W::ROWB + 16 * (c ^ b16_tsw<D>(row));
-    klds[i] = pc * 1024;
-    krsrc[i] = make_rsrc(kbf + kv_row0 * D, (unsigned)Sk * W::ROWB);
-  }
-  const v4u rrsrc = make_rsrc(ws + rec0 * 1024, active ? (unsigned)nkt * 2048u : 0u);
+  TrImageDma<D, W::WAVES> kdma;
+  kdma.init(wave, lane, kbf + kv_row0 * D, (unsigned)Sk);
+  const v4u rrsrc = make_rsrc(ws + rec0 * 1024, active ? (unsigned)nkt * W::Rec::TILE : 0u);
   const unsigned smem_lds = lds_addr(smem);
   auto issue_k = [&](int t) {
-    const unsigned sl = smem_lds + (t % W::NSLOT) * W::T16;
-#pragma unroll
-    for (int i = 0; i < W::IPK; ++i)
-      dma16_buf(krsrc[i], kvoff[i], (unsigned)min(t, nt - 1) * W::T16, sl + klds[i]);
+    kdma.issue(smem_lds + (t % W::NSLOT) * W::T16, (unsigned)min(t, nt - 1) * W::T16);
   };
   auto issue_r = [&](int t) {   // each record is read once: non-temporal
-    const unsigned sl = smem_lds + W::RBASE + (t % W::RSLOT) * W::REC + wave * 2048;
-    const unsigned so = (unsigned)min(t, nt - 1) * 2048u;
+    const unsigned sl = smem_lds + W::RBASE + (t % W::RSLOT) * W::REC + wave * W::Rec::TILE;
+    const unsigned so = (unsigned)min(t, nt - 1) * W::Rec::TILE;
     dma16_buf_nt(rrsrc, 16u * lane, so, sl);
     dma16_buf_nt(rrsrc, 16u * lane, so + 1024u, sl + 1024u);
   };
@@ -689,17 +656,10 @@ __global__ __launch_bounds__(512, 2) void bf16_bwd_dqw_kernel(const __bf16* __re
     for (int i = 0; i < W::RSLOT - 1; ++i) issue_r(i);
   }
   int troff[W::NDB];
-  int rtro;
-  {
-    const int gg = (lane >> 4) & 1, i16 = lane & 15;
-    const int row = 4 * h + (i16 >> 2);
+  const auto trl = W::Tr::tr_lane(lane, h);
 #pragma unroll
-    for (int b = 0; b < W::NDB; ++b) {
-      const int d = 32 * b + 16 * gg + 4 * (i16 & 3);
-      troff[b] = row * W::ROWB + 16 * ((d / 8) ^ b16_tsw<D>(row)) + (d % 8) * 2;
-    }
-    rtro = row * 64 + 2 * (16 * gg + 4 * (i16 & 3));
-  }
+  for (int b = 0; b < W::NDB; ++b) troff[b] = W::Tr::tr_off(trl, b);
+  const int rtro = W::Rec::tr_off(W::Rec::tr_lane(lane, h), 0);
   v16f acc[W::NDB];
 #pragma unroll
   for (int b = 0; b < W::NDB; ++b) acc[b] = v16f{};
@@ -714,17 +674,10 @@ __global__ __launch_bounds__(512, 2) void bf16_bwd_dqw_kernel(const __bf16* __re
     issue_r(t + W::RSLOT - 1);
     if (active && t < ntw) {
       const char* kb = smem + (t % W::NSLOT) * W::T16;
-      const char* rb = smem + W::RBASE + (t % W::RSLOT) * W::REC + wave * 2048 + rtro;
+      const char* rb = smem + W::RBASE + (t % W::RSLOT) * W::REC + wave * W::Rec::TILE;
       v8bf ta[2 * W::NDB], op[2];
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-#pragma unroll
-        for (int b = 0; b < W::NDB; ++b) {
-          const char* a = kb + troff[b] + 16 * s * W::ROWB;
-          ta[s * W::NDB + b] = __builtin_bit_cast(v8bf, ds_read_tr16_x2(a, a + 8 * W::ROWB));
-        }
-        op[s] = __builtin_bit_cast(v8bf, ds_read_tr16_x2(rb + 16 * s * 64, rb + 16 * s * 64 + 8 * 64));
-      }
+      W::Tr::tr_load(kb, troff, ta);
+      W::Rec::tr_load(rb, &rtro, op);
 #pragma unroll
       for (int s = 0; s < 2; ++s)
 #pragma unroll

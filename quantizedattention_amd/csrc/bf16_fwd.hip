@@ -29,7 +29,7 @@
 // skips the tiles past its own, replacing the masked half of the P.V MFMAs by one FMA per output.
 #include <type_traits>
 
-#include "common.h"
+#include "tile_image.h"
 
 
 namespace qattn {
@@ -62,32 +62,21 @@ struct Bf16FwdCfg {
   static constexpr int QROWS = 32 * WAVES;
   static constexpr int KT = 32;                 // keys per ring slot
   static constexpr int NSLOT = QA_BF_FWD_NSLOT;
-  static constexpr int ROWB = 2 * D;            // bytes per K / V row
-  static constexpr int NCH = ROWB / 16;         // 16-B chunks per row
-  static constexpr int TILE = KT * ROWB;        // bytes per K (or V) tile
+  using KImg = B16Rows<D>;                      // K: read by rows (tile_image.h)
+  using VImg = B16Tr<D>;                        // V: read transposed
+  static constexpr int ROWB = KImg::ROWB;       // bytes per K / V row
+  static constexpr int NCH = KImg::NCH;         // 16-B chunks per row
+  static constexpr int TILE = KImg::TILE;       // bytes per K (or V) tile
   static constexpr int SLOT = 2 * TILE;
   static constexpr int NKS = D / 16;            // f16 k-steps of QK^T
   static constexpr int NDB = D / 32;
   static constexpr int PIECES = SLOT / 1024;    // 1-KiB LDS-DMA pieces per slot
   static constexpr int IPW = PIECES / WAVES;
-  static constexpr int K_SHIFT = (D == 128) ? 0 : 1;   // K swizzle = (row >> K_SHIFT) & (NCH-1)
-  static constexpr int V_SHIFT = (D == 128) ? 2 : 1;   // V swizzle = (row & 3) << V_SHIFT
   // output staging passes (two halves of the columns when the ring is 3 slots: 3 workgroups per CU)
   static constexpr int STAGE_PASSES = NSLOT == 3 ? 2 : 1;
   static constexpr int STAGE_BYTES = WAVES * RowTile<D, float, STAGE_PASSES>::BYTES;
   static constexpr int LDS = (NSLOT * SLOT > STAGE_BYTES) ? NSLOT * SLOT : STAGE_BYTES;
 };
-
-template <int D>
-QA_DEVICE int bk_sw(int row) {
-  using C = Bf16FwdCfg<D>;
-  return (row >> C::K_SHIFT) & (C::NCH - 1);
-}
-template <int D>
-QA_DEVICE int bv_sw(int row) {
-  using C = Bf16FwdCfg<D>;
-  return (row & 3) << C::V_SHIFT;
-}
 
 // LDS-DMA plan of one 32-key tile: piece p < TILE/1024 is K, the rest V; lane-constant offsets.
 template <int D>
@@ -97,15 +86,14 @@ struct Bf16Dma {
   unsigned lds_off[C::IPW];
   v4u rsrc[C::IPW];
   QA_DEVICE void init(int wave, int lane, int Sk, const void* kbase, const void* vbase) {
-    constexpr int RPI = 64 / C::NCH;
     constexpr int KP = C::TILE / 1024;
 #pragma unroll
     for (int i = 0; i < C::IPW; ++i) {
       const int p = wave + C::WAVES * i;
       const bool isv = p >= KP;
       const int piece = isv ? p - KP : p;
-      const int row = piece * RPI + lane / C::NCH, c = lane % C::NCH;
-      voff[i] = row * C::ROWB + 16 * (c ^ (isv ? bv_sw<D>(row) : bk_sw<D>(row)));
+      const int row = C::KImg::piece_row(piece, lane), c = lane % C::NCH;
+      voff[i] = C::KImg::chunk_at(row, c, isv ? C::VImg::sw(row) : C::KImg::sw(row));
       lds_off[i] = (isv ? C::TILE : 0) + piece * 1024;
       rsrc[i] = make_rsrc(isv ? vbase : kbase, (unsigned)Sk * C::ROWB);
     }
@@ -216,15 +204,11 @@ __global__ __launch_bounds__(64 * QA_BF_FWD_WAVES, QA_BF_FWD_OCC) void bf16_fwd_
   // lane-constant LDS offsets: K A-operand chunk (2s+h) of key row c32; V^T A-operand per d block
   int koff[C::NKS], voff[C::NDB];
 #pragma unroll
-  for (int s = 0; s < C::NKS; ++s) koff[s] = c32 * C::ROWB + 16 * ((2 * s + h) ^ bk_sw<D>(c32));
+  for (int s = 0; s < C::NKS; ++s) koff[s] = C::KImg::row_off(c32, 2 * s + h);
   {
-    const int gg = (lane >> 4) & 1, i16 = lane & 15;
-    const int key_a = 4 * h + (i16 >> 2);
+    const auto trl = C::VImg::tr_lane(lane, h);
 #pragma unroll
-    for (int b = 0; b < C::NDB; ++b) {
-      const int d = 32 * b + 16 * gg + 4 * (i16 & 3);
-      voff[b] = C::TILE + key_a * C::ROWB + 16 * ((d / 8) ^ bv_sw<D>(key_a)) + (d % 8) * 2;
-    }
+    for (int b = 0; b < C::NDB; ++b) voff[b] = C::TILE + C::VImg::tr_off(trl, b);
   }
   v16f o[C::NDB];
 #pragma unroll
@@ -339,8 +323,7 @@ __global__ __launch_bounds__(64 * QA_BF_FWD_WAVES, QA_BF_FWD_OCC) void bf16_fwd_
     const char* vl = smem + decltype(SLc)::value * C::SLOT;
 #pragma unroll
     for (int b = 0; b < C::NDB; ++b) {
-      const char* a = vl + voff[b] + 16 * u * C::ROWB;
-      const v8bf va = __builtin_bit_cast(v8bf, ds_read_tr16_x2(a, a + 8 * C::ROWB));
+      const v8bf va = C::VImg::tr_frag(vl + voff[b] + 16 * u * C::ROWB);
       o[b] = mfma_bf16(va, pb8, o[b]);                               // bf16:285
     }
   };

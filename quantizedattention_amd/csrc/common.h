@@ -33,6 +33,7 @@ typedef unsigned v2u __attribute__((ext_vector_type(2)));
 typedef int v2i __attribute__((ext_vector_type(2)));
 
 #define QA_DEVICE __device__ __forceinline__
+#define QA_IMG __host__ __device__ __forceinline__ constexpr   // index arithmetic, also in static_asserts
 #define LDS_PTR(T, p) ((__attribute__((address_space(3))) T*)(p))
 
 // ---------------------------------------------------------------- host: dynamic-LDS grants

@@ -354,7 +354,7 @@ QA_DEVICE __attribute__((always_inline)) void int8_attn_fwd_body(
   // image, 16 B per lane
   int koff[C::NKS], voff[C::NDB];
 #pragma unroll
-  for (int s = 0; s < C::NKS; ++s) koff[s] = c32 * D + 16 * ((2 * s + h) ^ k_sw<D>(c32));
+  for (int s = 0; s < C::NKS; ++s) koff[s] = C::KImg::row_off(c32, 2 * s + h);
 #pragma unroll
   for (int b = 0; b < C::NDB; ++b) voff[b] = C::K_BYTES + b * 1024 + 16 * lane;
 

@@ -31,23 +31,19 @@
 #include <type_traits>
 #include <cstdlib>
 
-#include "common.h"
+#include "tile_image.h"
 
 namespace qattn {
 
+// The streamed tiles are I8Rows images (read by rows for the int8 MFMAs) and B16Tr images (read
+// transposed for the bf16 MFMAs), tile_image.h.
 template <int D>
 struct I8BwdCfg {
   static constexpr int NKS8 = D / 32;    // i8 k-steps over D
   static constexpr int NDB = D / 32;     // 32-wide d blocks of the accumulators
-  static constexpr int T8 = 32 * D;      // 32-row int8 tile bytes
-  static constexpr int T16 = 64 * D;     // 32-row bf16 tile bytes
+  static constexpr int T8 = I8Rows<D>::TILE;
+  static constexpr int T16 = B16Tr<D>::TILE;
 };
-// LDS image swizzles: int8 rows (read by rows for the int8 MFMAs) and bf16 tr images (read by
-// ds_read_b64_tr_b16 for the bf16 MFMAs); conflict-free for both access patterns.
-template <int D>
-QA_DEVICE int i8_sw(int row) { return (row >> ((D == 128) ? 1 : 2)) & (D / 16 - 1); }
-template <int D>
-QA_DEVICE int t16_sw(int row) { return (row & 3) << ((D == 128) ? 2 : 1); }
 
 // Quantise 16 values with the tile scale and emit the bf16 operand  trunc(x / s) * c.
 QA_DEVICE void quant_operand(const float* x, float inv, float c, v8bf* out) {
@@ -244,7 +240,7 @@ struct BwdCfg {
   static constexpr int LDO = TR + NTR * C::T16;
   static constexpr int SLOT = LDO + (HAS_LD ? 256 : 0);
   static constexpr int NSLOT = (ROLE == ROLE_DKV) ? QA_DKV_NSLOT : 4;
-  static constexpr int NP8 = C::T8 / 1024, NP16 = C::T16 / 1024;
+  static constexpr int NP8 = I8Rows<D>::NP, NP16 = B16Tr<D>::NP;
   static constexpr int INST = NP8 * (TWO ? 2 : 1) + NTR * NP16;   // 1-KiB pieces per tile
   static constexpr int IPW16 = (INST + WAVES - 1) / WAVES;
   // every wave also loads the tile's 256-B LD block (duplicate writes of the same bytes): one
@@ -278,22 +274,18 @@ struct BwdDmaT {
         int q = p - (G::TWO ? 2 : 1) * G::NP8;
         const bool second = q >= G::NP16;
         if (second) q -= G::NP16;
-        constexpr int NCH = 2 * D / 16, RPI = 64 / NCH;
-        const int row = q * RPI + lane / NCH, c = lane % NCH;
-        voff[i] = row * 2 * D + 16 * (c ^ t16_sw<D>(row));
+        voff[i] = B16Tr<D>::dma_src(q, lane);
         lds_off[i] = (second ? G::TR2 : G::TR) + q * 1024;
-        stride[i] = 64 * D;
+        stride[i] = B16Tr<D>::TILE;
         rsrc[i] = make_rsrc(second ? tr2 : tr, (unsigned)S * 2 * D);
       }
     }
     if constexpr (G::HAS_LD) ld_rsrc = make_rsrc(ld, (unsigned)S * 8);
   }
   QA_DEVICE void set_i8(int i, int region, int piece, int lane) {
-    constexpr int NCH = D / 16, RPI = 64 / NCH;
-    const int row = piece * RPI + lane / NCH, c = lane % NCH;
-    voff[i] = row * D + 16 * (c ^ i8_sw<D>(row));
+    voff[i] = I8Rows<D>::dma_src(piece, lane);
     lds_off[i] = region + piece * 1024;
-    stride[i] = 32 * D;
+    stride[i] = I8Rows<D>::TILE;
   }
   // slot_lds: LDS byte address of the ring slot
   QA_DEVICE void issue(unsigned slot_lds, int t, int lane) const {
@@ -368,6 +360,23 @@ QA_DEVICE float max16_abs3(const float* x) {
 #pragma unroll
   for (int i = 3; i < 15; i += 2) m = fmaxf(fmaxf(m, fabsf(x[i])), fabsf(x[i + 1]));
   return fmaxf(m, fabsf(x[15]));
+}
+
+// A wave's accumulators (transposed 32x32 layout: acc[b][4g + j] is element d = 32b + 8g + 4h + j of
+// the lane's row), scaled, stored as fp16 straight from the MFMA layout to row `row` of dst.  row and
+// h by reference, as a lambda captures them: hipcc then places the address arithmetic as it did.
+template <int D>
+QA_DEVICE void store_acc_row(const v16f* acc, float sc, _Float16* dst, const long& row, const int& h) {
+#pragma unroll
+  for (int b = 0; b < D / 32; ++b) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      v4h w;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) w[j] = (_Float16)(acc[b][4 * g + j] * sc);
+      *reinterpret_cast<v4h*>(dst + row * D + 32 * b + 8 * g + 4 * h) = w;
+    }
+  }
 }
 
 // Shapes: the own side has BHx heads of Sx rows; own head bh streams the Ny rows
@@ -466,16 +475,10 @@ void int8_bwd_kernel(
   // lane-constant LDS offsets: int8 A-operand rows, tr-image A-operand (per 32-wide d block)
   int roff[C::NKS8], troff[C::NDB];
 #pragma unroll
-  for (int s = 0; s < C::NKS8; ++s) roff[s] = c32 * D + 16 * ((2 * s + h) ^ i8_sw<D>(c32));
-  {
-    const int gg = (lane >> 4) & 1, i16 = lane & 15;
-    const int row = 4 * h + (i16 >> 2);
+  for (int s = 0; s < C::NKS8; ++s) roff[s] = I8Rows<D>::row_off(c32, 2 * s + h);
+  const auto trl = B16Tr<D>::tr_lane(lane, h);
 #pragma unroll
-    for (int b = 0; b < C::NDB; ++b) {
-      const int d = 32 * b + 16 * gg + 4 * (i16 & 3);
-      troff[b] = row * 2 * D + 16 * ((d / 8) ^ t16_sw<D>(row)) + (d % 8) * 2;
-    }
-  }
+  for (int b = 0; b < C::NDB; ++b) troff[b] = B16Tr<D>::tr_off(trl, b);
   v16f acc[C::NDB], acc2[ROLE == ROLE_DKV ? C::NDB : 1];
 #pragma unroll
   for (int b = 0; b < C::NDB; ++b) acc[b] = v16f{};
@@ -591,16 +594,7 @@ void int8_bwd_kernel(
       op[s] = __builtin_bit_cast(v8bf, w);
     }
   };
-  auto tr_load = [&](int t, int region, v8bf* ta) {
-    const char* base = slot(t) + region;
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int b = 0; b < C::NDB; ++b) {
-        const char* a = base + troff[b] + 16 * s * 2 * D;
-        ta[s * C::NDB + b] = __builtin_bit_cast(v8bf, ds_read_tr16_x2(a, a + 8 * 2 * D));
-      }
-  };
+  auto tr_load = [&](int t, int region, v8bf* ta) { B16Tr<D>::tr_load(slot(t) + region, troff, ta); };
   // Timing-only cost model (A/B builds, -DQA_DKV_I8DV_COST=1; results are wrong): dV on the int8
   // MFMA as the reference's hl.dot(P_i8^T, dO_i8) (int8:375-378) -- 4 v_mfma_i32_32x32x32_i8 from a
   // biased seed and the per-tile dequantisation of the 64 accumulator elements per lane -- in place
@@ -822,20 +816,8 @@ void int8_bwd_kernel(
     for (int t = t0 + lane; t < nt; t += 64) sds[ws_first + (long)t * nkt + x0 / 32] = sds_lds[wave * nt + t];
   }
   const long r = hrow + x0 + c32;
-  auto store = [&](const v16f* ac, float osc, _Float16* dst) {
-#pragma unroll
-    for (int b = 0; b < C::NDB; ++b) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        v4h w;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = (_Float16)(ac[b][4 * g + j] * osc);
-        *reinterpret_cast<v4h*>(dst + r * D + 32 * b + 8 * g + 4 * h) = w;
-      }
-    }
-  };
-  store(acc, ROLE == ROLE_DV ? 1.0f : sms, out);
-  if constexpr (ROLE == ROLE_DKV) store(acc2, 1.0f, out2);
+  store_acc_row<D>(acc, ROLE == ROLE_DV ? 1.0f : sms, out, r, h);
+  if constexpr (ROLE == ROLE_DKV) store_acc_row<D>(acc2, 1.0f, out2, r, h);
 #if QA_DKV_STAMP
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   DKV_STAMP(3);
@@ -885,7 +867,7 @@ static_assert(QA_DQW_WAVES <= 8, "dQ-from-records workgroups may not exceed the 
 template <int D>
 struct DqwCfg {
   static constexpr int WAVES = QA_DQW_WAVES;
-  static constexpr int T16 = 64 * D;               // bf16 k image of a 32-key tile (L2-resident)
+  static constexpr int T16 = B16Tr<D>::TILE;       // bf16 k image of a 32-key tile (L2-resident)
   static constexpr int NSLOT = QA_DQW_NSLOT;       // k image ring: NSLOT - 1 tiles ahead
 #ifdef QA_DQW_RSLOT
   static constexpr int RSLOT = QA_DQW_RSLOT;
@@ -894,10 +876,8 @@ struct DqwCfg {
 #endif
   static constexpr int REC = WAVES * 1024;         // the waves' dS records of one tile
   static constexpr int RBASE = NSLOT * T16;
-  static constexpr int NP16 = T16 / 1024;
-  // k image pieces per wave per tile; with more waves than pieces the extra waves re-issue a
-  // piece (the same bytes to the same place), so every wave issues IPK + 1 DMAs per tile
-  static constexpr int IPK = (NP16 + WAVES - 1) / WAVES;
+  // k image pieces per wave per tile: every wave issues IPK + 1 DMAs per tile
+  static constexpr int IPK = TrImageDma<D, WAVES>::IPK;
   // the pipelined loop reads tile t+1's record with tile t's k image: records run >= 1 tile ahead
   static_assert(RSLOT - 1 >= NSLOT, "record ring must run ahead of the k image ring");
 };
@@ -926,27 +906,15 @@ __global__ __launch_bounds__(64 * QA_DQW_WAVES, QA_DQW_WAVES >= 16 ? 4 : 2) void
   const int nt = CAUSAL ? min(nkt, (qb * 32 * W::WAVES + 32 * W::WAVES) / 32) : nkt;
   const long rec0 = ((long)bh * nqt + (active ? q0 / 32 : 0)) * nkt;   // this wave's first record
 
-  // DMA plan: pieces of the k image (swizzled rows, as BwdDma's TR region), and the own record
-  unsigned kvoff[W::IPK], klds[W::IPK];
-  v4u krsrc[W::IPK];
-#pragma unroll
-  for (int i = 0; i < W::IPK; ++i) {
-    int pc = wave + W::WAVES * i;
-    if (pc >= W::NP16) pc = wave % W::NP16;
-    constexpr int NCH = 2 * D / 16, RPI = 64 / NCH;
-    const int row = pc * RPI + lane / NCH, c = lane % NCH;
-    kvoff[i] = row * 2 * D + 16 * (c ^ t16_sw<D>(row));
-    klds[i] = pc * 1024;
-    krsrc[i] = make_rsrc(kbf + kv_row0 * D, (unsigned)Sk * 2 * D);
-  }
+  // DMA plan: the k image, and the own record
+  TrImageDma<D, W::WAVES> kdma;
+  kdma.init(wave, lane, kbf + kv_row0 * D, (unsigned)Sk);
   // an inactive wave's descriptor has no records: its loads return zeros, nothing is read
   const v4u rrsrc = make_rsrc(ds8 + rec0 * 1024, active ? (unsigned)nkt * 1024u : 0u);
   const unsigned smem_lds = lds_addr(smem);
   auto issue_k = [&](int t) {
-    const unsigned sl = smem_lds + (t % W::NSLOT) * W::T16;
-#pragma unroll
-    for (int i = 0; i < W::IPK; ++i)
-      if (!(QA_DQW_DIAG & 8)) dma16_buf(krsrc[i], kvoff[i], (QA_DQW_DIAG & 2) ? 0u : (unsigned)min(t, nt - 1) * 64u * D, sl + klds[i]);
+    if (!(QA_DQW_DIAG & 8))
+      kdma.issue(smem_lds + (t % W::NSLOT) * W::T16, (QA_DQW_DIAG & 2) ? 0u : (unsigned)min(t, nt - 1) * W::T16);
   };
   auto issue_r = [&](int t, int rs) {   // record of tile t into ring slot rs; read once: non-temporal
     if (QA_DQW_DIAG & 4) return;
@@ -990,15 +958,9 @@ __global__ __launch_bounds__(64 * QA_DQW_WAVES, QA_DQW_WAVES >= 16 ? 4 : 2) void
   }
 #endif
   int troff[C::NDB];
-  {
-    const int gg = (lane >> 4) & 1, i16 = lane & 15;
-    const int row = 4 * h + (i16 >> 2);
+  const auto trl = B16Tr<D>::tr_lane(lane, h);
 #pragma unroll
-    for (int b = 0; b < C::NDB; ++b) {
-      const int d = 32 * b + 16 * gg + 4 * (i16 & 3);
-      troff[b] = row * 2 * D + 16 * ((d / 8) ^ t16_sw<D>(row)) + (d % 8) * 2;
-    }
-  }
+  for (int b = 0; b < C::NDB; ++b) troff[b] = B16Tr<D>::tr_off(trl, b);
   v16f acc[C::NDB];
 #pragma unroll
   for (int b = 0; b < C::NDB; ++b) acc[b] = v16f{};
@@ -1056,15 +1018,8 @@ __global__ __launch_bounds__(64 * QA_DQW_WAVES, QA_DQW_WAVES >= 16 ? 4 : 2) void
     ring_wait_barrier<(W::RSLOT - 1 > W::NSLOT ? 1 : 0) + (W::NSLOT - 2) * (W::IPK + 1)>();
     issue_k(t + W::NSLOT - 1);
     issue_r(t + W::RSLOT - 1, rs_issue);
-    const char* kb = smem + (t % W::NSLOT) * W::T16;
     v8bf ta[2 * C::NDB];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int b = 0; b < C::NDB; ++b) {
-        const char* a = kb + troff[b] + 16 * s * 2 * D;
-        ta[s * C::NDB + b] = __builtin_bit_cast(v8bf, ds_read_tr16_x2(a, a + 8 * 2 * D));
-      }
+    B16Tr<D>::tr_load(smem + (t % W::NSLOT) * W::T16, troff, ta);
     // (the last iteration forms an operand from slot nt % RSLOT and the scale after the wave's
     // last: discarded)
     v8bf opn[2];
@@ -1091,16 +1046,7 @@ __global__ __launch_bounds__(64 * QA_DQW_WAVES, QA_DQW_WAVES >= 16 ? 4 : 2) void
 #else
   const long r = (long)bh * Sq + q0 + c32;
 #endif
-#pragma unroll
-  for (int b = 0; b < C::NDB; ++b) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      v4h w;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) w[j] = (_Float16)(acc[b][4 * g + j] * sms);
-      *reinterpret_cast<v4h*>(dq + r * D + 32 * b + 8 * g + 4 * h) = w;
-    }
-  }
+  store_acc_row<D>(acc, sms, dq, r, h);
 }
 
 }  // namespace qattn

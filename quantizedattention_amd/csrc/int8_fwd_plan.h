@@ -1,7 +1,7 @@
-// Tile configuration, K / V swizzles and the LDS-DMA plan of one 32-key tile of the int8 attention
-// forward (int8_attn_fwd.hip).
+// Tile configuration and the LDS-DMA plan of one 32-key tile of the int8 attention forward
+// (int8_attn_fwd.hip).
 #pragma once
-#include "common.h"
+#include "tile_image.h"
 #include "exp2_corr.h"
 
 namespace qattn {
@@ -39,13 +39,13 @@ struct Int8FwdCfg {
   static constexpr int QROWS = 32 * WAVES;      // query rows per workgroup
   static constexpr int KT = 32;                 // keys per tile / ring slot
   static constexpr int NSLOT = 4;               // ring slots
-  static constexpr int K_BYTES = KT * D;        // int8 K tile
+  using KImg = I8Rows<D>;                       // K: int8 rows read by rows (tile_image.h)
+  static constexpr int K_BYTES = KImg::TILE;    // int8 K tile
   static constexpr int V_BYTES = KT * D;        // int8 V^T operand image
   static constexpr int SLOT = K_BYTES + V_BYTES;
   static constexpr int NKS = D / 32;            // i8 k-steps for QK^T
   static constexpr int NDB = D / 32;            // 32-wide d blocks of O^T
-  static constexpr int K_CH = D / 16;           // 16-B chunks per K row
-  static constexpr int K_INST = K_BYTES / 1024; // 1-KiB LDS-DMA wave instructions per tile
+  static constexpr int K_INST = KImg::NP;       // 1-KiB LDS-DMA wave instructions per tile
   static constexpr int V_INST = V_BYTES / 1024;
   static constexpr int INST = K_INST + V_INST;
   static constexpr int IPW = (INST + WAVES - 1) / WAVES;   // per wave, padded (counted vmcnt)
@@ -65,18 +65,12 @@ struct Int8FwdCfg {
   static constexpr int lds_bytes(int nt) { return RING + ((nt + 3) / 4 * 4) * 8 + VOTE_OR_CORR; }
 };
 
-template <int D>
-QA_DEVICE int k_sw(int row) {
-  constexpr int K_CH = D / 16;
-  return (row >> ((D == 128) ? 1 : 2)) & (K_CH - 1);
-}
-
 // LDS-DMA plan of one 32-key tile (K rows, then the V operand), IPW instructions per wave.  Waves
 // whose padded slots run past INST re-issue their first instruction (same bytes to the same place:
 // benign), so every wave has exactly IPW DMAs in flight per tile and vmcnt(IPW) means "all but the
 // last tile".  Per instruction: a lane-constant source byte offset (swizzle applied), a wave-uniform
 // LDS offset inside the slot and the tile stride; the tile's base pointers are scalar.
-//   K: row-major int8 rows, 16-B chunks XOR-swizzled by row.
+//   K: an I8Rows image.
 //   V: the vt operand image, already in MFMA-operand order: a plain 1-KiB copy per piece.
 template <int D>
 struct DmaPlan {
@@ -91,9 +85,7 @@ struct DmaPlan {
       int inst = wave + C::WAVES * i;
       if (inst >= C::INST) inst = wave % C::INST;   // (more waves than pieces: re-issue one)
       if (inst < C::K_INST) {
-        constexpr int RPI = 64 / C::K_CH;
-        const int row = inst * RPI + lane / C::K_CH, p = lane % C::K_CH;
-        voff[i] = row * D + 16 * (p ^ k_sw<D>(row));
+        voff[i] = C::KImg::dma_src(inst, lane);
         lds_off[i] = inst * 1024;
         stride[i] = C::K_BYTES;
         rsrc[i] = make_rsrc(kbase, (unsigned)S * D);

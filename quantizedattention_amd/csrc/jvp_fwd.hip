@@ -13,7 +13,7 @@
 // (global_load_lds_dwordx4, swizzle applied on the per-lane source address, LDS destination
 // lane-linear), 64 keys per stage, 2 stages (128 KiB): no staging registers, which the 4 fp32
 // accumulators of this kernel cannot spare.
-#include "common.h"
+#include "tile_image.h"
 
 namespace qattn {
 
@@ -41,46 +41,25 @@ template <int D, bool X3, bool TAN = true>
 struct JvpCfg {
   static constexpr int KB = X3 ? 32 : 64;     // keys per stage
   static constexpr int NIMG = X3 ? 2 : 1;     // bf16 images per operand
-  static constexpr int ROWB = 2 * D;
-  static constexpr int NCH = ROWB / 16;
-  static constexpr int TILE = KB * ROWB;
+  using Rows = B16Rows<D>;                    // K, tK: read by rows (tile_image.h)
+  using Tr = B16Tr<D>;                        // V, tV: read transposed
+  static constexpr int TILE = KB / 32 * Tr::TILE;   // a stage holds KB / 32 tiles back to back
   static constexpr int NOPS = TAN ? 4 : 2;    // K, tK, V, tV / K, V
   static constexpr int STAGE = NOPS * NIMG * TILE;
   static constexpr int SK = 0, STK = 1, SV = TAN ? 2 : 1, STV = 3;   // operand slots in a stage
   static constexpr int NKS = D / 16;
   static constexpr int NDB = D / 32;
 };
-template <int D>
-QA_DEVICE int jrow_sw(int row) { return (D == 128) ? (row & 15) : ((row >> 1) & 7); }
-template <int D>
-QA_DEVICE int jtr_sw(int row) { return (row & 3) << ((D == 128) ? 2 : 1); }
 
-// LDS-DMA one [KB rows][ROWB] tile: lane-linear destination, swizzled source chunk.
-template <int D, bool X3, bool TR>
+// LDS-DMA one stage tile of image I (KB rows): one 1-KiB piece per wave-instruction, 4 waves.
+template <int D, bool X3, typename I>
 QA_DEVICE void dma_tile(const char* gsrc, char* lds_tile, int wave, int lane) {
-  using C = JvpCfg<D, X3>;
-  constexpr int RPI = 64 / C::NCH;                 // rows per wave-instruction (1 KiB)
-  constexpr int IPW = C::TILE / 1024 / 4;          // instructions per wave (4 waves)
+  constexpr int IPW = JvpCfg<D, X3>::TILE / 1024 / 4;   // instructions per wave
 #pragma unroll
   for (int i = 0; i < IPW; ++i) {
     const int inst = wave * IPW + i;
-    const int row = inst * RPI + lane / C::NCH;
-    const int p = lane % C::NCH;
-    const int ch = p ^ (TR ? jtr_sw<D>(row) : jrow_sw<D>(row));
-    glds16(gsrc + (long)row * C::ROWB + 16 * ch, lds_tile + inst * 1024);
+    glds16(gsrc + I::dma_src(inst, lane), lds_tile + inst * 1024);
   }
-}
-
-template <int D>
-QA_DEVICE v8bf jtr_frag(const char* base, int row_base, int b, int lane) {
-  constexpr int ROWB = 2 * D;
-  const int h = lane >> 5, gg = (lane >> 4) & 1, i16 = lane & 15;
-  const int d = 32 * b + 16 * gg + 4 * (i16 & 3);
-  const int row = row_base + 4 * h + (i16 >> 2);
-  const int ch = d / 8, within = (d % 8) * 2;
-  return __builtin_bit_cast(
-      v8bf, ds_read_tr16_x2(base + row * ROWB + 16 * (ch ^ jtr_sw<D>(row)) + within,
-                            base + (row + 8) * ROWB + 16 * (ch ^ jtr_sw<D>(row + 8)) + within));
 }
 
 // Operand images: [0] = hi (the bf16 operand itself in the bf16 mode), [1] = lo (X3 only).
@@ -137,11 +116,11 @@ __global__ __launch_bounds__(256, 1) void jvp_fwd_kernel(JvpArgs a) {
     const long off = (long)kb * C::TILE;
 #pragma unroll
     for (int x = 0; x < NI; ++x) {
-      dma_tile<D, X3, false>(reinterpret_cast<const char*>(a.k[x] + kv0) + off, base + (C::SK * NI + x) * C::TILE, wave, lane);
-      dma_tile<D, X3, true>(reinterpret_cast<const char*>(a.v[x] + kv0) + off, base + (C::SV * NI + x) * C::TILE, wave, lane);
+      dma_tile<D, X3, typename C::Rows>(reinterpret_cast<const char*>(a.k[x] + kv0) + off, base + (C::SK * NI + x) * C::TILE, wave, lane);
+      dma_tile<D, X3, typename C::Tr>(reinterpret_cast<const char*>(a.v[x] + kv0) + off, base + (C::SV * NI + x) * C::TILE, wave, lane);
       if constexpr (TAN) {
-        dma_tile<D, X3, false>(reinterpret_cast<const char*>(a.tk[x] + kv0) + off, base + (C::STK * NI + x) * C::TILE, wave, lane);
-        dma_tile<D, X3, true>(reinterpret_cast<const char*>(a.tv[x] + kv0) + off, base + (C::STV * NI + x) * C::TILE, wave, lane);
+        dma_tile<D, X3, typename C::Rows>(reinterpret_cast<const char*>(a.tk[x] + kv0) + off, base + (C::STK * NI + x) * C::TILE, wave, lane);
+        dma_tile<D, X3, typename C::Tr>(reinterpret_cast<const char*>(a.tv[x] + kv0) + off, base + (C::STV * NI + x) * C::TILE, wave, lane);
       }
     }
   };
@@ -167,8 +146,7 @@ __global__ __launch_bounds__(256, 1) void jvp_fwd_kernel(JvpArgs a) {
         v16f sacc = v16f{}, tacc = v16f{};
 #pragma unroll
         for (int s = 0; s < C::NKS; ++s) {
-          const int row = 32 * u + c32, ch = 2 * s + h;
-          const int off = row * C::ROWB + 16 * (ch ^ jrow_sw<D>(row));
+          const int off = u * C::Rows::TILE + C::Rows::row_off(c32, 2 * s + h);
           v8bf ka[NI], tka[NI], qq[NI], tqq[NI];
 #pragma unroll
           for (int x = 0; x < NI; ++x) {
@@ -254,8 +232,9 @@ __global__ __launch_bounds__(256, 1) void jvp_fwd_kernel(JvpArgs a) {
             v8bf va[NI], tva[NI];
 #pragma unroll
             for (int x = 0; x < NI; ++x) {
-              va[x] = jtr_frag<D>(base + (C::SV * NI + x) * C::TILE, 32 * u + 16 * s, b, lane);
-              if constexpr (TAN) tva[x] = jtr_frag<D>(base + (C::STV * NI + x) * C::TILE, 32 * u + 16 * s, b, lane);
+              const int off = C::Tr::tr_off(C::Tr::tr_lane(lane, h), b, 32 * u + 16 * s);
+              va[x] = C::Tr::tr_frag(base + (C::SV * NI + x) * C::TILE + off);
+              if constexpr (TAN) tva[x] = C::Tr::tr_frag(base + (C::STV * NI + x) * C::TILE + off);
             }
             o[b] = mm(va, pb[s], o[b]);      // jvp:171
             if constexpr (TAN) {
