@@ -387,6 +387,43 @@ int qattn_mxfp4_attn_fwd_split(const void* q4, const void* qscale, const void* k
                                long rows, long sq_head, long sk, int causal, int keys_per_split,
                                int head_dim, float qks, void* stream);
 
+/* qattn_mxfp4_attn_fwd_split over a preallocated cache with one length per sequence
+ * (kv_cache_mxfp4.py PreallocatedKVFP4).  The operands are laid out as above with cap tokens per
+ * key/value head (k4 u8 [bhv][cap][64], kscale u8 [bhv][cap][4], vt u8 [bhv][cap/64][128][32], vscale
+ * u8 [bhv][cap/64][128][2]); lens is a DEVICE array i32 [bhv / heads_per_seq], and key/value head h
+ * holds L = lens[h / heads_per_seq] keys.  nsplit = ceil(sk_max / keys_per_split); split y runs the
+ * tiles [y*kps/64, min(ceil(L/64), (y+1)*kps/64)) of its head and writes the empty state (m_s = -inf,
+ * l_s = 0, O_s = 0) when that range is empty; no byte of a tile >= ceil(L/64) is read, and what K rows
+ * >= L hold never matters.  Row r sees key j iff j <= L - 1 (causal 0) or j <= r % sq_head + L -
+ * sq_head (causal 2: the queries are the sequence's last sq_head positions).  opart / ml and the merge
+ * (qattn_mxfp4_split_combine) are those of the entry above.
+ * Preconditions the caller guarantees (the entry cannot read lens): 1 <= lens[b] <= sk_max <= cap, and
+ * with causal == 2 lens[b] >= sq_head.
+ * Returns 1 for head_dim != 128, cap or sk_max not multiples of 64, sk_max > cap, sk_max < 64,
+ * cap > 2^25, keys_per_split < 64 or % 64, sq_head < 1, rows % sq_head, heads_per_seq < 1,
+ * bhv % heads_per_seq, causal not 0 or 2, lens == NULL; 0 without a launch for bhv == 0 or rows == 0. */
+int qattn_mxfp4_attn_fwd_split_len(const void* q4, const void* qscale, const void* k4, const void* kscale,
+                                   const void* vt, const void* vscale, void* opart, void* ml,
+                                   const void* lens, long bhv, long heads_per_seq, long rows, long sq_head,
+                                   long cap, long sk_max, int causal, int keys_per_split, int head_dim,
+                                   float qks, void* stream);
+
+/* Append to a preallocated MX-FP4 cache, stream-ordered, without reading anything back.  k, v f16
+ * [batch*kv_heads][n][128] are n >= 1 new tokens per head; sequence b takes the first counts[b] of
+ * them (counts i32 [batch] on the device, 0 <= counts[b] <= n; NULL: n for all) at tokens lens[b] ..
+ * of its heads, and lens[b] (i32 [batch], device) grows by that count.  K rows are quantised as
+ * qattn_mxfp4_quant_rows does (k_mean f16 [batch*kv_heads][128] or NULL); the V tiles the new tokens
+ * touch are quantised again as qattn_mxfp4_quant_vt does, the older keys of a partial tile coming from
+ * vtail f16 [batch*kv_heads][64][128], which keeps the fp16 V rows of each sequence's last partial
+ * tile at slot token % 64.  Afterwards rows [0, L) of k4 / kscale and tiles [0, ceil(L/64)) of vt /
+ * vscale equal, bit for bit, the two quantisers' output for the sequence zero-padded to a multiple of
+ * 64.  The caller guarantees lens[b] + counts[b] <= cap (a sequence that would pass cap is left
+ * untouched, as one whose count is outside [0, n]).  Returns 1 for head_dim != 128, n < 1, cap % 64,
+ * a NULL pointer other than k_mean / counts. */
+int qattn_mxfp4_cache_append(const void* k, const void* v, const void* k_mean, void* k4, void* kscale,
+                             void* vt, void* vscale, void* vtail, void* lens, const void* counts,
+                             long batch, long kv_heads, long n, long cap, int head_dim, void* stream);
+
 /* Merge of the splits, per row of rows_total = bhv*rows: M = max_s m_s, w_s = 2^(m_s - M) (exact; 0
  * for m_s = -inf), L = sum_s w_s l_s, out f16 [rows_total, 128] = (sum_s w_s O_s) * (1 / L), lse f32
  * [rows_total] = M + log2(L).  With nsplit == 1 this is the one-pass forward's epilogue bit for bit. */

@@ -30,7 +30,9 @@
 // body both kernels share, over a range of the keys, from m = -inf, writing the unnormalised (O_s, m_s,
 // l_s); the merge weighs the splits by 2^(m_s - max_s m_s), exact because every m_s is an integer, and
 // applies the epilogue above.  tests/mxfp4_split_ref.py restates it; tests/test_gpu_mxfp4_cache.py
-// checks it.
+// checks it.  Its LEN instantiation reads a preallocated cache with one length per sequence, which
+// the "cache append" kernels below grow in place (tests/mxfp4_ragged_ref.py restates it,
+// tests/test_gpu_mxfp4_ragged.py checks both).
 #include "common.h"
 
 namespace qattn {
@@ -63,18 +65,9 @@ QA_DEVICE v4i pack_fp4x32(const float* x, float s) {
 }
 
 // ------------------------------------------------------------------------------ quantisers
-// Q / K: one thread per 32-element block of a row.  x f16 [rows, D] -> q4 [rows, D/2], sc [rows, D/32].
-// With ``mean`` (f16 [rows/seq, D], SageAttention smoothing) the row is first f16(x - mean[row/seq]).
-template <int D>
-__global__ __launch_bounds__(256) void mx_quant_rows_kernel(const _Float16* __restrict__ x,
-                                                            const _Float16* __restrict__ mean,
-                                                            uint8_t* __restrict__ q4,
-                                                            uint8_t* __restrict__ sc, long nblk, long seq) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= nblk) return;
-  const v8h* src = reinterpret_cast<const v8h*>(x + i * 32);
-  constexpr int NB = D / 32;
-  const v8h* mu = mean ? reinterpret_cast<const v8h*>(mean + (i / NB / seq) * D + (i % NB) * 32) : nullptr;
+// One 32-element block of a Q / K row: src (and mu, the block of the mean, or null) -> 16 B of codes
+// and the scale byte.  With mu the block is first f16(x - mu).
+QA_DEVICE void mx_quant_row_block(const v8h* src, const v8h* mu, v4i* q4, uint8_t* sc) {
   float f[32];
   float amax = 0.f;
 #pragma unroll
@@ -92,8 +85,22 @@ __global__ __launch_bounds__(256) void mx_quant_rows_kernel(const _Float16* __re
     }
   }
   const unsigned e = e8m0_of(amax);
-  reinterpret_cast<v4i*>(q4)[i] = pack_fp4x32(f, e8m0_value(e));
-  sc[i] = (uint8_t)e;
+  *q4 = pack_fp4x32(f, e8m0_value(e));
+  *sc = (uint8_t)e;
+}
+
+// Q / K: one thread per 32-element block of a row.  x f16 [rows, D] -> q4 [rows, D/2], sc [rows, D/32].
+// With ``mean`` (f16 [rows/seq, D], SageAttention smoothing) the row is first f16(x - mean[row/seq]).
+template <int D>
+__global__ __launch_bounds__(256) void mx_quant_rows_kernel(const _Float16* __restrict__ x,
+                                                            const _Float16* __restrict__ mean,
+                                                            uint8_t* __restrict__ q4,
+                                                            uint8_t* __restrict__ sc, long nblk, long seq) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nblk) return;
+  constexpr int NB = D / 32;
+  const v8h* mu = mean ? reinterpret_cast<const v8h*>(mean + (i / NB / seq) * D + (i % NB) * 32) : nullptr;
+  mx_quant_row_block(reinterpret_cast<const v8h*>(x + i * 32), mu, reinterpret_cast<v4i*>(q4) + i, sc + i);
 }
 
 // V: one thread per (head, 64-key tile g, column d, half h).  v f16 [BH*Sk, D] ->
@@ -122,6 +129,107 @@ __global__ __launch_bounds__(256) void mx_quant_vt_kernel(const _Float16* __rest
   const unsigned e = e8m0_of(amax);
   reinterpret_cast<v4i*>(vt)[i] = pack_fp4x32(f, e8m0_value(e));
   vs[i] = (uint8_t)e;
+}
+
+// ------------------------------------------------------------------------------ cache append
+// The preallocated cache (kv_cache_mxfp4.py PreallocatedKVFP4): k4 / ks / vt / vs in the layouts above
+// with cap tokens per key/value head, len[b] of them valid for every head of sequence b, and vtail
+// f16 [B*Hkv][64][D], the fp16 V rows of the sequence's last partial tile at slot token % 64.
+// Invariant: rows [0, L) of k4 / ks and tiles [0, ceil(L / 64)) of vt / vs are, bit for bit, the
+// quantisers' output for the sequence zero-padded to a multiple of 64; the rest is unspecified.
+// An append of n new tokens (sequence b takes the first cnt = counts[b] <= n, null counts: n) is
+// three launches in stream order: V (reads vtail), then K and vtail, then the lengths.
+
+// The tokens sequence b takes of an append, with its length L before it: 0 (nothing is written) for a
+// count outside [0, n] or a length that would pass cap, which the host refuses before it launches.
+QA_DEVICE int mx_append_count(const int* lens, const int* counts, int b, int n, int cap, int& L) {
+  L = lens[b];
+  const int cnt = counts ? counts[b] : n;
+  return cnt > 0 && cnt <= n && L >= 0 && L <= cap - cnt ? cnt : 0;
+}
+
+// V: one thread per (head, touched tile j, column d, half h).  Tile g = L / 64 + j of the touched
+// range [L / 64, (L + cnt - 1) / 64] is quantised again from its 32 keys per block in
+// mx_quant_vt_kernel's order: token t < L from vtail[t % 64], t < L + cnt from the new v[t - L], else 0.
+template <int D>
+__global__ __launch_bounds__(256) void mx_append_vt_kernel(const _Float16* __restrict__ v,
+                                                           const _Float16* __restrict__ vtail,
+                                                           uint8_t* __restrict__ vt, uint8_t* __restrict__ vs,
+                                                           const int* __restrict__ lens,
+                                                           const int* __restrict__ counts, long nthr,
+                                                           int Hkv, int n, int ntile, int cap) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nthr) return;
+  const int h = (int)(i & 1);
+  const int d = (int)((i >> 1) % D);
+  const long gt = (i >> 1) / D;                 // head * ntile + j
+  const long bh = gt / ntile;
+  const int b = (int)(bh / Hkv);
+  int L;
+  const int cnt = mx_append_count(lens, counts, b, n, cap, L);
+  const int g = L / 64 + (int)(gt % ntile);
+  if (cnt == 0 || 64 * g >= L + cnt) return;   // L + cnt <= cap = 64 * tiles: the tile lies inside
+  const _Float16* tail = vtail + bh * 64 * D + d;
+  const _Float16* col = v + bh * (long)n * D + d;
+  float f[32];
+  float amax = 0.f;
+#pragma unroll
+  for (int j = 0; j < 32; ++j) {
+    const int key = 32 * (j >> 4) + 8 * ((j >> 2) & 3) + 4 * h + (j & 3);
+    const int t = 64 * g + key;
+    f[j] = t < L ? (float)tail[(long)key * D] : t < L + cnt ? (float)col[(long)(t - L) * D] : 0.f;
+    amax = fmaxf(amax, fabsf(f[j]));
+  }
+  const unsigned e = e8m0_of(amax);
+  const long o = ((bh * (cap / 64) + g) * D + d) * 2 + h;
+  reinterpret_cast<v4i*>(vt)[o] = pack_fp4x32(f, e8m0_value(e));
+  vs[o] = (uint8_t)e;
+}
+
+// K and vtail: one thread per 32-element block of a new row.  Row i < cnt of head bh goes to token
+// L + i of k4 / ks, quantised as mx_quant_rows_kernel does (mean: f16 [B*Hkv, D] or null); the same
+// 32 elements of v go to vtail when the token lies in the new last partial tile.
+template <int D>
+__global__ __launch_bounds__(256) void mx_append_k_kernel(const _Float16* __restrict__ k,
+                                                          const _Float16* __restrict__ v,
+                                                          const _Float16* __restrict__ mean,
+                                                          uint8_t* __restrict__ k4, uint8_t* __restrict__ ks,
+                                                          _Float16* __restrict__ vtail,
+                                                          const int* __restrict__ lens,
+                                                          const int* __restrict__ counts, long nblk,
+                                                          int Hkv, int n, int cap) {
+  constexpr int NB = D / 32;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nblk) return;
+  const int blk = (int)(i % NB);
+  const int tok = (int)(i / NB % n);
+  const long bh = i / NB / n;
+  const int b = (int)(bh / Hkv);
+  int L;
+  const int cnt = mx_append_count(lens, counts, b, n, cap, L);
+  const int t = L + tok;
+  if (tok >= cnt) return;   // t < L + cnt <= cap
+  const v8h* mu = mean ? reinterpret_cast<const v8h*>(mean + bh * D + blk * 32) : nullptr;
+  const long o = (bh * cap + t) * NB + blk;
+  mx_quant_row_block(reinterpret_cast<const v8h*>(k + i * 32), mu, reinterpret_cast<v4i*>(k4) + o, ks + o);
+  const int end = L + cnt;
+  if (end % 64 != 0 && t / 64 == end / 64) {
+    const v8h* src = reinterpret_cast<const v8h*>(v + i * 32);
+    v8h* dst = reinterpret_cast<v8h*>(vtail + (bh * 64 + t % 64) * D + blk * 32);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) dst[c] = src[c];
+  }
+}
+
+// lens[b] += cnt, one thread per sequence
+__global__ __launch_bounds__(256) void mx_append_len_kernel(int* __restrict__ lens,
+                                                            const int* __restrict__ counts, int B, int n,
+                                                            int cap) {
+  const int b = (int)blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  int L;
+  const int cnt = mx_append_count(lens, counts, b, n, cap, L);
+  if (cnt) lens[b] = L + cnt;
 }
 
 // ------------------------------------------------------------------------------ attention
@@ -382,13 +490,22 @@ __global__ __launch_bounds__(256, CAUSAL ? QA_MX_OCC_CAUSAL : QA_MX_OCC) void mx
 // sees key j iff j <= r % sq_head + qoff.  A row that sees no key of a split keeps m = -inf, l = 0,
 // O = 0: its scores never raise m, its P is selected to 0 before the quantisation (exp2 of a masked
 // score is inf there) and the P block is scale byte 0 with zero codes; the merge gives it weight 0.
-template <int D, bool CAUSAL>
+// LEN (the preallocated cache of kv_cache_mxfp4.py): Sk is the capacity, the stride of a key/value head,
+// and sequence b = bh / hps holds L = lens[b] keys, 1 <= L <= Sk (causal: L >= sq_head; the host
+// checks both).  The head has nt = ceil(L / 64) tiles; a split past them writes the empty state
+// (-inf, 0, 0) and returns before any DMA or barrier; the ring's bounds end at the split's last tile
+// of this sequence, so no byte of a tile >= nt is requested.  Row r sees key j iff j <= vis, vis =
+// L - 1 non-causal and r % sq_head + L - sq_head causal: mx_tile's masked path, `diag` on the last
+// tile when L % 64 != 0 and on the diagonal tiles.  K rows >= L of that tile may hold anything (their
+// scores are selected away, NaN included); V tiles < nt are whole by the cache's invariant.
+template <int D, bool CAUSAL, bool LEN = false>
 __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
     const uint8_t* __restrict__ q4, const uint8_t* __restrict__ qs, const uint8_t* __restrict__ k4,
     const uint8_t* __restrict__ ks, const uint8_t* __restrict__ vt, const uint8_t* __restrict__ vs,
     float* __restrict__ opart, float2* __restrict__ ml, int BHV, int rows, int sq_head, int Sk,
-    int kps, float qks, int qoff) {
+    int kps, float qks, int qoff, const int* __restrict__ lens, int hps) {
   using C = MxCfg<D>;
+  constexpr bool MASK = CAUSAL || LEN;
   static_assert(sizeof(float) == 4 && D == 128, "fp32 staging in two passes fills the ring exactly");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int nrb = (rows + C::QROWS - 1) / C::QROWS;
@@ -400,9 +517,28 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
   const int q0 = qt * C::QROWS + wave * 32;
   const bool active = q0 < rows;
   const int qi = min(q0 + c32, rows - 1);
-  const int nt = Sk / C::KT;
+  int len = Sk;   // keys of this head (workgroup-uniform)
+  if constexpr (LEN) {
+    len = min(__builtin_amdgcn_readfirstlane(lens[bh / hps]), Sk);   // never a tile past the capacity
+    qoff = len - sq_head;
+  }
+  const int nt = LEN ? (len + C::KT - 1) / C::KT : Sk / C::KT;
+  const int ntc = Sk / C::KT;   // tile stride of a key/value head in vt / vs
   // this workgroup's tiles [t0, t0 + ntw) of the key/value head: ntw >= 1 (nsplit = ceil(Sk / kps))
   const int t0 = (int)blockIdx.y * (kps / C::KT);
+  if constexpr (LEN) {
+    if (t0 >= nt) {   // a split past the sequence: the empty state for the workgroup's rows
+      if (!active) return;
+      const long row0 = ((long)blockIdx.y * BHV + bh) * rows + q0;
+      const int nr = min(32, rows - q0);
+      if (h == 0 && c32 < nr) ml[row0 + c32] = make_float2(-INFINITY, 0.f);
+      v4f* dst = reinterpret_cast<v4f*>(opart + row0 * D);
+#pragma unroll
+      for (int i = 0; i < 32 * (D / 4) / 64; ++i)
+        if (i * 64 + lane < nr * (D / 4)) dst[i * 64 + lane] = v4f{0.f, 0.f, 0.f, 0.f};
+      return;
+    }
+  }
   const int ntw = min(nt - t0, kps / C::KT);
   // causal: query positions of the wave's rows (a wave that crosses a head boundary holds both ends)
   int wmin = 0, wmax = 0, pos = 0;
@@ -417,8 +553,8 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
   // the ring over the split's own byte range: the buffer bounds end at its last tile
   const long kvh = bh;
   const MxRing<D> ring(k4 + (kvh * Sk + (long)t0 * C::KT) * C::KROWB,
-                       ks + (kvh * Sk + (long)t0 * C::KT) * (D / 32), vt + (kvh * nt + t0) * C::V_BYTES,
-                       vs + (kvh * nt + t0) * C::VS_BYTES, ntw, smem, wave, lane);
+                       ks + (kvh * Sk + (long)t0 * C::KT) * (D / 32), vt + (kvh * ntc + t0) * C::V_BYTES,
+                       vs + (kvh * ntc + t0) * C::VS_BYTES, ntw, smem, wave, lane);
   ring.prologue(ntw);
 
   v4i qf[C::NKS];
@@ -442,8 +578,12 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
       if (k0 > wmax + qoff) continue;           // no row of the wave sees the tile: m, l, O unchanged
       diag = k0 + C::KT - 1 > wmin + qoff;
       lim = pos + qoff - k0 - 4 * h;
+    } else if constexpr (LEN) {   // every row sees the keys <= len - 1
+      const int k0 = C::KT * (t0 + t);
+      diag = k0 + C::KT > len;
+      lim = len - 1 - k0 - 4 * h;
     }
-    mx_tile<D, CAUSAL>(smem + (t & 3) * C::SLOT, qf, qsw, o, m, l, diag, lim, qks, lane, h, c32);
+    mx_tile<D, MASK>(smem + (t & 3) * C::SLOT, qf, qsw, o, m, l, diag, lim, qks, lane, h, c32);
   }
   vmcnt_wait_all();
   __syncthreads();
@@ -581,7 +721,26 @@ static int mxfp4_split_launch(const void* q4, const void* qscale, const void* k4
                      dim3(256), lds, (hipStream_t)stream, (const uint8_t*)q4, (const uint8_t*)qscale,
                      (const uint8_t*)k4, (const uint8_t*)kscale, (const uint8_t*)vt,
                      (const uint8_t*)vscale, (float*)opart, (float2*)ml, (int)bhv, (int)rows,
-                     (int)sq_head, (int)sk, kps, qks, (int)(sk - sq_head));
+                     (int)sq_head, (int)sk, kps, qks, (int)(sk - sq_head), (const int*)nullptr, 1);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+template <bool CAUSAL>
+static int mxfp4_split_len_launch(const void* q4, const void* qscale, const void* k4, const void* kscale,
+                                  const void* vt, const void* vscale, void* opart, void* ml,
+                                  const void* lens, long bhv, long hps, long rows, long sq_head, long cap,
+                                  long sk_max, int kps, float qks, void* stream) {
+  using C = MxCfg<128>;
+  const long nrb = (rows + C::QROWS - 1) / C::QROWS;
+  const long nsplit = (sk_max + kps - 1) / kps;
+  if (nrb * bhv > 0x7fffffffL || nsplit > 65535) return 1;
+  const int lds = C::NSLOT * C::SLOT;
+  { static LdsGrant granted_; if (!lds_grant((const void*)mxfp4_attn_split_kernel<128, CAUSAL, true>, lds, granted_)) return 1; }
+  hipLaunchKernelGGL((mxfp4_attn_split_kernel<128, CAUSAL, true>), dim3((unsigned)(nrb * bhv), (unsigned)nsplit),
+                     dim3(256), lds, (hipStream_t)stream, (const uint8_t*)q4, (const uint8_t*)qscale,
+                     (const uint8_t*)k4, (const uint8_t*)kscale, (const uint8_t*)vt,
+                     (const uint8_t*)vscale, (float*)opart, (float2*)ml, (int)bhv, (int)rows,
+                     (int)sq_head, (int)cap, kps, qks, 0, (const int*)lens, (int)hps);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -604,6 +763,58 @@ extern "C" int qattn_mxfp4_attn_fwd_split(const void* q4, const void* qscale, co
                                     keys_per_split, qks, stream);
   return mxfp4_split_launch<false>(q4, qscale, k4, kscale, vt, vscale, opart, ml, bhv, rows, sq_head, sk,
                                    keys_per_split, qks, stream);
+}
+
+// the same over a preallocated cache of cap tokens per head with one length per sequence (lens i32
+// [bhv / heads_per_seq] on the device; the host guarantees 1 <= lens[b] <= sk_max and, causal,
+// lens[b] >= sq_head); grid.y = ceil(sk_max / keys_per_split)
+extern "C" int qattn_mxfp4_attn_fwd_split_len(const void* q4, const void* qscale, const void* k4,
+                                              const void* kscale, const void* vt, const void* vscale,
+                                              void* opart, void* ml, const void* lens, long bhv,
+                                              long heads_per_seq, long rows, long sq_head, long cap,
+                                              long sk_max, int causal, int keys_per_split, int head_dim,
+                                              float qks, void* stream) {
+  if (head_dim != 128 || bhv < 0 || rows < 0 || !lens) return 1;
+  if (cap % 64 != 0 || sk_max % 64 != 0 || sk_max < 64 || sk_max > cap || cap > (1L << 25)) return 1;
+  if (keys_per_split < 64 || keys_per_split % 64 != 0) return 1;
+  if (sq_head < 1 || rows % sq_head != 0 || heads_per_seq < 1 || bhv % heads_per_seq != 0) return 1;
+  if (causal != 0 && causal != 2) return 1;
+  if (bhv == 0 || rows == 0) return 0;
+  if (rows > (1L << 30) || bhv > 0x7fffffffL) return 1;
+  if (causal)
+    return mxfp4_split_len_launch<true>(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, bhv,
+                                        heads_per_seq, rows, sq_head, cap, sk_max, keys_per_split, qks,
+                                        stream);
+  return mxfp4_split_len_launch<false>(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, bhv,
+                                       heads_per_seq, rows, sq_head, cap, sk_max, keys_per_split, qks,
+                                       stream);
+}
+
+// append n new tokens per sequence to a preallocated cache (kernels and format: "cache append" above);
+// stream-ordered, nothing is read back
+extern "C" int qattn_mxfp4_cache_append(const void* k, const void* v, const void* k_mean, void* k4,
+                                        void* kscale, void* vt, void* vscale, void* vtail, void* lens,
+                                        const void* counts, long batch, long kv_heads, long n, long cap,
+                                        int head_dim, void* stream) {
+  if (head_dim != 128 || n < 1 || cap < 0 || cap % 64 != 0 || batch < 0 || kv_heads < 0) return 1;
+  if (!k || !v || !k4 || !kscale || !vt || !vscale || !vtail || !lens) return 1;
+  if (cap > (1L << 25) || n > (1L << 25) || batch > 0x7fffffffL || kv_heads > 0x7fffffffL) return 1;
+  const long bhv = batch * kv_heads;
+  if (bhv == 0 || cap == 0) return 0;
+  const long ntile = (n + 62) / 64 + 1;   // tiles n tokens can touch from any start
+  const long nthr = bhv * ntile * 128 * 2, nblk = bhv * n * (128 / 32);
+  if ((nthr + 255) / 256 > 0x7fffffffL || (nblk + 255) / 256 > 0x7fffffffL) return 1;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(mx_append_vt_kernel<128>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st,
+                     (const _Float16*)v, (const _Float16*)vtail, (uint8_t*)vt, (uint8_t*)vscale,
+                     (const int*)lens, (const int*)counts, nthr, (int)kv_heads, (int)n, (int)ntile, (int)cap);
+  hipLaunchKernelGGL(mx_append_k_kernel<128>, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st,
+                     (const _Float16*)k, (const _Float16*)v, (const _Float16*)k_mean, (uint8_t*)k4,
+                     (uint8_t*)kscale, (_Float16*)vtail, (const int*)lens, (const int*)counts, nblk,
+                     (int)kv_heads, (int)n, (int)cap);
+  hipLaunchKernelGGL(mx_append_len_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st,
+                     (int*)lens, (const int*)counts, (int)batch, (int)n, (int)cap);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
 extern "C" int qattn_mxfp4_split_combine(const void* opart, const void* ml, void* out, void* lse,

@@ -24,6 +24,8 @@
 //   mxfp4_cached(q, k4, ks, vt, vs, causal, keys_per_split) -> (O, lse)
 //       kv_cache_mxfp4.attention_mxfp4_cached on the cache's four operands (causal 0 / 1 bottom-right
 //       over the cache; keys_per_split 0: the plan of qattn_split_keys)
+//   mxfp4_decode(q, k4, ks, vt, vs, lens, sk_max, causal, keys_per_split) -> (O, lse)
+//       kv_cache_mxfp4.attention_mxfp4_decode on a preallocated cache's operands and device lengths
 // Workspaces, head chunks and key splits are planned by the library (csrc/plan.hip), as in the drop-ins.
 // Errors: TORCH_CHECK (c10::Error, RuntimeError in Python) with the drop-ins' messages; int8_quant's
 // argument checks raise ValueError (TORCH_CHECK_VALUE) as its Python predecessor did.
@@ -431,6 +433,56 @@ std::tuple<Tensor, Tensor> mxfp4_cached(const Tensor& q_in, const Tensor& k4, co
   return {out, lse};
 }
 
+// kv_cache_mxfp4.attention_mxfp4_decode on a preallocated cache's operands: k4 [B, Hkv, cap, 64] with
+// lens i32 [B] on the device.  The operator cannot read lens without a synchronisation, so the caller
+// guarantees 1 <= lens[b] <= sk_max (a multiple of 64, <= cap) and, causal, lens[b] >= Sq; the Python
+// wrapper ops.mxfp4_decode checks them on the cache's host mirror.
+std::tuple<Tensor, Tensor> mxfp4_decode(const Tensor& q_in, const Tensor& k4, const Tensor& ks,
+                                        const Tensor& vt, const Tensor& vs, const Tensor& lens,
+                                        int64_t sk_max, int64_t causal, int64_t keys_per_split) {
+  require_gpu({&q_in, &k4, &ks, &vt, &vs, &lens});
+  TORCH_CHECK(q_in.dim() == 4 && k4.dim() == 4 && q_in.size(3) == 128 && k4.size(3) == 64,
+              "qattn mxfp4 kv cache: head_dim must be 128 in q and in the cache");
+  const int64_t B = k4.size(0), Hkv = k4.size(1), cap = k4.size(2), D = 128;
+  TORCH_CHECK(q_in.size(0) == B && Hkv > 0 && q_in.size(1) % Hkv == 0,
+              "qattn mxfp4 kv cache: q must be [B, G*Hkv, Sq, D] for the cache's B, Hkv");
+  const int64_t Hq = q_in.size(1), Sq = q_in.size(2);
+  TORCH_CHECK(Sq >= 1 && cap >= 64 && cap % 64 == 0,
+              "qattn mxfp4 kv cache: Sq >= 1 and a capacity of 64*n tokens expected");
+  TORCH_CHECK(sk_max >= 64 && sk_max % 64 == 0 && sk_max <= cap,
+              "qattn mxfp4 kv cache: sk_max must be a multiple of 64 in [64, capacity]");
+  TORCH_CHECK(causal == 0 || causal == 1, "qattn mxfp4 kv cache: causal must be 0 or 1");
+  TORCH_CHECK(!causal || Sq <= sk_max, "qattn mxfp4 kv cache: causal attention needs Sq <= the cached tokens");
+  for (const Tensor* t : {&k4, &ks, &vt, &vs})
+    TORCH_CHECK(t->scalar_type() == at::kByte && t->is_contiguous(),
+                "qattn mxfp4 kv cache: the quantised operands must be contiguous uint8");
+  TORCH_CHECK(ks.sizes() == at::IntArrayRef({B, Hkv, cap, D / 32}) &&
+                  vt.sizes() == at::IntArrayRef({B * Hkv, cap / 64, D, 32}) &&
+                  vs.sizes() == at::IntArrayRef({B * Hkv, cap / 64, D, 2}),
+              "qattn mxfp4 kv cache: ks / vt / vs do not match k4");
+  TORCH_CHECK(lens.scalar_type() == at::kInt && lens.is_contiguous() && lens.dim() == 1 && lens.size(0) == B,
+              "qattn mxfp4 kv cache: lens must be contiguous int32 [B]");
+  const int64_t bhv = B * Hkv, rows = (Hq / Hkv) * Sq;
+  int64_t kps = keys_per_split == 0 ? qattn_split_keys(bhv, rows, sk_max, 64) : keys_per_split;
+  TORCH_CHECK(kps >= 64 && kps % 64 == 0, "qattn mxfp4 kv cache: keys_per_split must be a multiple of 64");
+  kps = std::min(kps, sk_max);
+  const int64_t nsplit = (sk_max + kps - 1) / kps;
+  Ctx c(q_in);
+  const Tensor q = q_in.to(at::kHalf).contiguous();
+  Tensor q4 = empty({B * Hq * Sq, D / 2}, at::kByte, q), qs = empty({B * Hq * Sq, D / 32}, at::kByte, q);
+  Tensor out = empty({B, Hq, Sq, D}, at::kHalf, q), lse = empty({B * Hq, Sq}, at::kFloat, q);
+  if (out.numel() == 0) return {out, lse};
+  call(qattn_mxfp4_quant_rows(P(q), nullptr, P(q4), P(qs), B * Hq * Sq, Sq, (int)D, c.stream), "quantise q");
+  Tensor opart = empty({nsplit, bhv * rows, D}, at::kFloat, q), ml = empty({nsplit, bhv * rows, 2}, at::kFloat, q);
+  call(qattn_mxfp4_attn_fwd_split_len(P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens), bhv,
+                                      Hkv, rows, Sq, cap, sk_max, causal ? 2 : 0, (int)kps, (int)D,
+                                      qk_scale(D), c.stream),
+       "mxfp4 decode forward");
+  call(qattn_mxfp4_split_combine(P(opart), P(ml), P(out), P(lse), bhv * rows, (int)nsplit, (int)D, c.stream),
+       "mxfp4 split merge");
+  return {out, lse};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(qattn, m) {
@@ -447,6 +499,8 @@ TORCH_LIBRARY(qattn, m) {
   m.def("mxfp4_fwd_ex(Tensor q, Tensor k, Tensor v, int causal) -> Tensor");
   m.def("mxfp4_cached(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, int causal, int keys_per_split) -> "
         "(Tensor, Tensor)");
+  m.def("mxfp4_decode(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, int sk_max, int causal, "
+        "int keys_per_split) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
@@ -459,4 +513,5 @@ TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
   m.impl("mxfp4_fwd", &mxfp4_fwd);
   m.impl("mxfp4_fwd_ex", &mxfp4_fwd_ex);
   m.impl("mxfp4_cached", &mxfp4_cached);
+  m.impl("mxfp4_decode", &mxfp4_decode);
 }

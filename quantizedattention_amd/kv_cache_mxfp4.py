@@ -12,10 +12,21 @@ workgroup reads each key/value tile once for the whole group), long caches are s
 splits keep the unnormalised fp32 state and integer running maxima, so the merge's weights are exact
 powers of two; with one split the result is the one-pass forward's bit for bit.
 
-Granularity: a cache grows by 64 tokens.  A caller with a shorter tail keeps it in fp16, attends to
-it separately and merges the two results by their ``lse`` (base 2), which is why ``lse`` is returned.
-With a smoothed cache that ``lse`` is the one of the scores q . (k - k_mean), so the tail keys must
-have the cache's ``k_mean`` subtracted before they are attended.
+Granularity: a :class:`QuantizedKVFP4` grows by 64 tokens and every ``append`` copies it (it is the
+immutable form: what is quantised once, serialised and moved).  A decode loop uses
+:class:`PreallocatedKVFP4`: the same four operands at a fixed capacity per key/value head, one length
+per sequence on the device (``lens``) with a host mirror (``lengths``), and ``append`` of ANY token
+count, a different one per sequence if wanted, written in place by ``qattn_mxfp4_cache_append``
+without a host synchronisation.  K is quantised per key row, so a key is appended alone; V's blocks
+lie inside one 64-key tile, so only the sequence's last partial tile is quantised again, from its fp16
+rows kept in ``vtail``.  The invariant that defines the format: after any sequence of appends, rows
+[0, L) of ``k4`` / ``ks`` and tiles [0, ceil(L / 64)) of ``vt`` / ``vs`` equal, bit for bit, what
+``quantize_kv_fp4(k, v, smooth=False, k_mean=...)`` gives for the sequence zero-padded to the next
+multiple of 64; K rows at or past L and V tiles at or past ceil(L / 64) are unspecified and never
+influence a result.  :func:`attention_mxfp4_decode` attends to such a cache
+(``qattn_mxfp4_attn_fwd_split_len``: the key-split forward with a length per sequence; a split past a
+sequence's end exits at once).  ``lse`` (base 2) is returned so that results can still be merged with
+attention over keys held elsewhere; with a smoothed cache it is that of the scores q . (k - k_mean).
 
 Wire format (little-endian), the container of kv_cache.py with a magic of its own::
 
@@ -49,7 +60,8 @@ BLOCK = 64
 _ALIGN = 256
 _DTYPES = {"uint8": torch.uint8, "float16": torch.float16}
 
-__all__ = ["QuantizedKVFP4", "quantize_kv_fp4", "attention_mxfp4_cached"]
+__all__ = ["QuantizedKVFP4", "quantize_kv_fp4", "attention_mxfp4_cached", "PreallocatedKVFP4",
+           "attention_mxfp4_decode"]
 
 
 @dataclass
@@ -226,6 +238,174 @@ def attention_mxfp4_cached(q: torch.Tensor, kv: QuantizedKVFP4, causal: bool = F
     _lib.call("qattn_mxfp4_attn_fwd_split", _lib.ptr(q4), _lib.ptr(qs), _lib.ptr(kv.k4), _lib.ptr(kv.ks),
               _lib.ptr(kv.vt), _lib.ptr(kv.vs), _lib.ptr(opart), _lib.ptr(ml), bhv, rows, Sq, Sk,
               2 if causal else 0, kps, D, _qk_scale(D), st)
+    _lib.call("qattn_mxfp4_split_combine", _lib.ptr(opart), _lib.ptr(ml), _lib.ptr(O), _lib.ptr(lse),
+              bhv * rows, nsplit, D, st)
+    return O, lse
+
+
+# ------------------------------------------------------------------------------ preallocated cache
+def _ceil64(n: int) -> int:
+    return -(-n // BLOCK) * BLOCK
+
+
+class PreallocatedKVFP4:
+    """MX-FP4 keys/values of ``batch`` sequences x ``kv_heads`` heads at a fixed ``capacity`` (a
+    multiple of 64) with one length per sequence; format and invariant: the module docstring.
+
+    ``k4`` u8 [B, Hkv, cap, D/2], ``ks`` u8 [B, Hkv, cap, D/32], ``vt`` u8 [B*Hkv, cap/64, D, 32], ``vs``
+    u8 [B*Hkv, cap/64, D, 2] (QuantizedKVFP4's layouts at S = cap), ``vtail`` f16 [B*Hkv, 64, D] (the
+    fp16 V rows of each sequence's last partial tile), ``lens`` i32 [B] on the device and ``lengths``,
+    its host mirror, which ``append`` and ``reset`` keep without reading the device; ``k_mean`` f16
+    [B, Hkv, 1, D] or None is subtracted from every appended key.
+    """
+
+    def __init__(self, k4, ks, vt, vs, vtail, lens, lengths, k_mean=None):
+        self.k4, self.ks, self.vt, self.vs = k4, ks, vt, vs
+        self.vtail, self.lens, self.lengths, self.k_mean = vtail, lens, list(lengths), k_mean
+
+    @classmethod
+    def allocate(cls, batch: int, kv_heads: int, capacity: int, device,
+                 k_mean: Optional[torch.Tensor] = None) -> "PreallocatedKVFP4":
+        """An empty cache (every length 0), zero-filled."""
+        D = 128
+        if batch < 1 or kv_heads < 1 or capacity < BLOCK or capacity % BLOCK or capacity > 1 << 25:
+            raise _lib.QAttnError("qattn mxfp4 kv cache: batch, kv_heads >= 1 and a capacity of 64*n "
+                                  "tokens (at most 2^25) expected")
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.QAttnError(f"qattn kernels run on the GPU only; got device {dev} "
+                                  "(no CPU fallback by design)")
+        if k_mean is not None:
+            if tuple(k_mean.shape) != (batch, kv_heads, 1, D):
+                raise _lib.QAttnError("qattn mxfp4 kv cache: k_mean must be [B, Hkv, 1, 128]")
+            k_mean = k_mean.to(device=dev, dtype=torch.float16).contiguous()
+        z = lambda *shape, dt=torch.uint8: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        return cls(z(batch, kv_heads, capacity, D // 2), z(batch, kv_heads, capacity, D // 32),
+                   z(batch * kv_heads, capacity // BLOCK, D, 32), z(batch * kv_heads, capacity // BLOCK, D, 2),
+                   z(batch * kv_heads, BLOCK, D, dt=torch.float16), z(batch, dt=torch.int32),
+                   [0] * batch, k_mean)
+
+    @property
+    def shape(self):
+        """(B, Hkv, capacity, D)"""
+        B, H, S, D2 = self.k4.shape
+        return (B, H, S, 2 * D2)
+
+    @property
+    def capacity(self) -> int:
+        return self.k4.shape[2]
+
+    @property
+    def kv(self):
+        return (self.k4, self.ks, self.vt, self.vs)
+
+    def append(self, k: torch.Tensor, v: torch.Tensor, counts=None) -> "PreallocatedKVFP4":
+        """Append fp16 ``k, v`` [B, Hkv, n, D] (any n >= 1) in place; with ``counts`` (B ints in
+        [0, n]) sequence b takes only the first ``counts[b]`` tokens.  Raises before anything is
+        launched if a length would pass the capacity.  Stream-ordered; returns ``self``."""
+        B, H, cap, D = self.shape
+        if (k.dim() != 4 or tuple(k.shape[:2]) != (B, H) or k.shape[3] != D or k.shape != v.shape
+                or k.shape[2] < 1):
+            raise _lib.QAttnError("qattn mxfp4 kv cache: appended tokens must be k, v [B, Hkv, n >= 1, D]")
+        n = k.shape[2]
+        if counts is None:
+            cnt = [n] * B
+        else:
+            cnt = [int(c) for c in (counts.tolist() if isinstance(counts, torch.Tensor) else counts)]
+            if len(cnt) != B or any(c < 0 or c > n for c in cnt):
+                raise _lib.QAttnError("qattn mxfp4 kv cache: counts must be B values in [0, n]")
+        if any(L + c > cap for L, c in zip(self.lengths, cnt)):
+            raise _lib.QAttnError(f"qattn mxfp4 kv cache: append past the capacity of {cap} tokens "
+                                  f"(lengths {self.lengths}, counts {cnt})")
+        _lib.require_gpu(k, v, self.k4)
+        k = k.to(torch.float16).contiguous()
+        v = v.to(torch.float16).contiguous()
+        cdev = None if counts is None else torch.tensor(cnt, dtype=torch.int32).to(k.device, non_blocking=True)
+        _lib.call("qattn_mxfp4_cache_append", _lib.ptr(k), _lib.ptr(v), _lib.ptr(self.k_mean),
+                  _lib.ptr(self.k4), _lib.ptr(self.ks), _lib.ptr(self.vt), _lib.ptr(self.vs),
+                  _lib.ptr(self.vtail), _lib.ptr(self.lens), _lib.ptr(cdev), B, H, n, cap, D,
+                  _lib.stream_of(k))
+        self.lengths = [L + c for L, c in zip(self.lengths, cnt)]
+        return self
+
+    def reset(self, seqs) -> None:
+        """Empty the sequences ``seqs`` (indices).  Their stale bytes are harmless by the invariant."""
+        seqs = [int(b) for b in seqs]
+        if any(b < 0 or b >= len(self.lengths) for b in seqs):
+            raise _lib.QAttnError("qattn mxfp4 kv cache: reset of a sequence the cache does not have")
+        for b in seqs:
+            self.lengths[b] = 0
+        self.lens.copy_(torch.tensor(self.lengths, dtype=torch.int32), non_blocking=True)
+
+    def snapshot(self, b: int) -> QuantizedKVFP4:
+        """A :class:`QuantizedKVFP4` copy (batch 1) of sequence ``b``, whose length must be a
+        multiple of 64 (and not 0)."""
+        B, H, cap, D = self.shape
+        if not 0 <= b < B:
+            raise _lib.QAttnError("qattn mxfp4 kv cache: snapshot of a sequence the cache does not have")
+        L = self.lengths[b]
+        if L == 0 or L % BLOCK:
+            raise _lib.QAttnError(f"qattn mxfp4 kv cache: snapshot needs a length of 64*n tokens, got {L}")
+        hs = slice(b * H, b * H + H)
+        return QuantizedKVFP4(self.k4[b:b + 1, :, :L].clone(), self.ks[b:b + 1, :, :L].clone(),
+                              self.vt[hs, :L // BLOCK].clone(), self.vs[hs, :L // BLOCK].clone(),
+                              None if self.k_mean is None else self.k_mean[b:b + 1].clone())
+
+
+def _decode_plan(q: torch.Tensor, cache: "PreallocatedKVFP4", causal: bool, keys_per_split):
+    """The host checks of a decode call -> (bhv, rows, sk_max, kps, nsplit)."""
+    if not isinstance(cache, PreallocatedKVFP4):
+        raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PreallocatedKVFP4")
+    B, Hkv, cap, D = cache.shape
+    if D != 128 or q.dim() != 4 or q.shape[3] != D:
+        raise _lib.QAttnError("qattn mxfp4 kv cache: head_dim must be 128 in q and in the cache")
+    if q.shape[0] != B or q.shape[1] == 0 or q.shape[1] % Hkv:
+        raise _lib.QAttnError("qattn mxfp4 kv cache: q must be [B, G*Hkv, Sq, D] for the cache's B, Hkv")
+    Hq, Sq = q.shape[1], q.shape[2]
+    if Sq < 1:
+        raise _lib.QAttnError("qattn mxfp4 kv cache: Sq >= 1 expected")
+    if min(cache.lengths) < 1:
+        raise _lib.QAttnError("qattn mxfp4 kv cache: every sequence needs at least one cached token "
+                              f"(lengths {cache.lengths})")
+    if causal and Sq > min(cache.lengths):
+        raise _lib.QAttnError("qattn mxfp4 kv cache: causal attention needs Sq <= every sequence's "
+                              "cached tokens")
+    sk_max = _ceil64(max(cache.lengths))
+    bhv, rows = B * Hkv, (Hq // Hkv) * Sq
+    kps = _split_plan_fp4(bhv, rows, sk_max) if keys_per_split is None else int(keys_per_split)
+    if kps < BLOCK or kps % BLOCK:
+        raise _lib.QAttnError("qattn mxfp4 kv cache: keys_per_split must be a multiple of 64")
+    kps = min(kps, sk_max)
+    return bhv, rows, sk_max, kps, -(-sk_max // kps)
+
+
+@torch.no_grad()
+def attention_mxfp4_decode(q: torch.Tensor, cache: PreallocatedKVFP4, causal: bool = False,
+                           keys_per_split: Optional[int] = None):
+    """MX-FP4 attention of fp16 queries [B, Hq, Sq, D] (one Sq >= 1 for the batch) against a
+    preallocated cache, sequence b over its own ``lengths[b]`` keys -> (O fp16 [B, Hq, Sq, D], lse
+    fp32 [B*Hq, Sq] base 2).  Inference; no autograd; stream-ordered (the lengths come from the host
+    mirror, the kernel reads ``lens``).
+
+    ``causal``: the queries are each sequence's LAST Sq positions (query i of sequence b keeps the
+    keys <= lengths[b] - Sq + i).  Raises for a sequence of length 0 and, causal, for Sq >
+    min(lengths).  ``keys_per_split`` as in :func:`attention_mxfp4_cached`; the plan is taken at
+    ceil64(max(lengths)).
+    """
+    bhv, rows, sk_max, kps, nsplit = _decode_plan(q, cache, causal, keys_per_split)
+    _lib.require_gpu(q, cache.k4)
+    B, Hkv, cap, D = cache.shape
+    Hq, Sq = q.shape[1], q.shape[2]
+    dev, st = q.device, _lib.stream_of(q)
+    q4, qs = mxfp4_quantize_rows(q)
+    O = torch.empty((B, Hq, Sq, D), dtype=torch.float16, device=dev)
+    lse = torch.empty((B * Hq, Sq), dtype=torch.float32, device=dev)
+    opart = torch.empty((nsplit, bhv * rows, D), dtype=torch.float32, device=dev)
+    ml = torch.empty((nsplit, bhv * rows, 2), dtype=torch.float32, device=dev)
+    _lib.call("qattn_mxfp4_attn_fwd_split_len", _lib.ptr(q4), _lib.ptr(qs), _lib.ptr(cache.k4),
+              _lib.ptr(cache.ks), _lib.ptr(cache.vt), _lib.ptr(cache.vs), _lib.ptr(opart), _lib.ptr(ml),
+              _lib.ptr(cache.lens), bhv, Hkv, rows, Sq, cap, sk_max, 2 if causal else 0, kps, D,
+              _qk_scale(D), st)
     _lib.call("qattn_mxfp4_split_combine", _lib.ptr(opart), _lib.ptr(ml), _lib.ptr(O), _lib.ptr(lse),
               bhv * rows, nsplit, D, st)
     return O, lse

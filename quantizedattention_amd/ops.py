@@ -17,6 +17,7 @@ the autograd rules of ``int8_fwd`` and ``bf16_fwd`` (their backward operators).
     torch.ops.qattn.mxfp4_fwd(q, k, v) -> O
     torch.ops.qattn.mxfp4_fwd_ex(q, k, v, causal) -> O      (causal 0 / 1 top-left / 2 bottom-right)
     torch.ops.qattn.mxfp4_cached(q, k4, ks, vt, vs, causal, keys_per_split) -> (O, lse)
+    torch.ops.qattn.mxfp4_decode(q, k4, ks, vt, vs, lens, sk_max, causal, keys_per_split) -> (O, lse)
 
 Shapes follow the drop-in functions (attention_int8.py:259-262 for the int8 outputs) except that
 k_i8 is returned row-major [B*Hkv*Sk, D] (the drop-in's k_i8T is its transposed view: an operator
@@ -31,7 +32,7 @@ import torch
 from . import _lib
 
 __all__ = ["int8_quant", "int8_fwd", "int8_bwd", "bf16_fwd", "bf16_bwd", "jvp_fwd", "mxfp4_fwd",
-           "mxfp4_fwd_ex", "mxfp4_cached"]
+           "mxfp4_fwd_ex", "mxfp4_cached", "mxfp4_decode"]
 
 _lib.load_ops()
 _ops = torch.ops.qattn
@@ -96,6 +97,13 @@ def _(q, k, v, causal):
 
 @torch.library.register_fake("qattn::mxfp4_cached")
 def _(q, k4, ks, vt, vs, causal, keys_per_split):
+    B, H, S, D = q.shape
+    return (q.new_empty((B, H, S, D), dtype=torch.float16),
+            q.new_empty((B * H, S), dtype=torch.float32))
+
+
+@torch.library.register_fake("qattn::mxfp4_decode")
+def _(q, k4, ks, vt, vs, lens, sk_max, causal, keys_per_split):
     B, H, S, D = q.shape
     return (q.new_empty((B, H, S, D), dtype=torch.float16),
             q.new_empty((B * H, S), dtype=torch.float32))
@@ -199,3 +207,14 @@ def mxfp4_cached(q, kv, causal=False, keys_per_split=None):
     against a ``QuantizedKVFP4`` -> (O fp16, lse fp32 [B*Hq, Sq]); ``keys_per_split`` None: the plan."""
     return _ops.mxfp4_cached(q, kv.k4, kv.ks, kv.vt, kv.vs, int(bool(causal)),
                              0 if keys_per_split is None else int(keys_per_split))
+
+
+def mxfp4_decode(q, cache, causal=False, keys_per_split=None):
+    """``kv_cache_mxfp4.attention_mxfp4_decode`` as one operator: q [B, Hq, Sq, 128] against a
+    ``PreallocatedKVFP4``, sequence b over its own length -> (O fp16, lse fp32 [B*Hq, Sq]).  The
+    lengths are checked here, on the cache's host mirror (the operator reads only ``lens`` on the
+    device); ``keys_per_split`` None: the plan."""
+    from .kv_cache_mxfp4 import _decode_plan
+    _, _, sk_max, _, _ = _decode_plan(q, cache, causal, keys_per_split)
+    return _ops.mxfp4_decode(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens, sk_max,
+                             int(bool(causal)), 0 if keys_per_split is None else int(keys_per_split))
