@@ -424,6 +424,41 @@ int qattn_mxfp4_cache_append(const void* k, const void* v, const void* k_mean, v
                              void* vt, void* vscale, void* vtail, void* lens, const void* counts,
                              long batch, long kv_heads, long n, long cap, int head_dim, void* stream);
 
+/* The paged pool (kv_cache_mxfp4.py PagedKVFP4): the four operands cut into num_pages pages of
+ * page_tokens = P tokens (64 * 2^k, 64 <= P <= 1024), a page holding P tokens of all kv_heads heads of
+ * ONE sequence: k4 u8 [num_pages][kv_heads][P][64], kscale u8 [num_pages][kv_heads][P][4], vt u8
+ * [num_pages][kv_heads][P/64][128][32], vscale u8 [num_pages][kv_heads][P/64][128][2].  block_table is
+ * a DEVICE array i32 [sequences][max_pages_per_seq] naming each sequence's pages in order: logical
+ * 64-key tile t of head h of sequence b is physical tile (block_table[b][t / (P/64)] * kv_heads + h) *
+ * (P/64) + t % (P/64) of all four operands.  Gathered through its table, a sequence holds exactly the
+ * bytes the preallocated cache holds.  A table entry is read only below ceil(L / P), L the sequence's
+ * length (an append: its length after the append), and an id outside [0, num_pages) is clamped into
+ * the pool.  An operand may be larger than 4 GiB; num_pages * kv_heads * P/64, the number of physical
+ * tiles, must be below 2^31 and max_pages_per_seq * P at most 2^25 (both return 1).
+ *
+ * qattn_mxfp4_attn_fwd_split_len over the pool (heads_per_seq = the pool's kv_heads): the same splits,
+ * partial results and preconditions (1 <= lens[b] <= sk_max, the tokens of a sequence lie in pages its
+ * table row names; causal == 2: lens[b] >= sq_head), and bit for bit the same opart / ml as that entry
+ * gives on a preallocated cache with the same tokens.  keys_per_split is independent of P.  Returns 1
+ * as that entry does, with sk_max > max_pages_per_seq * P for sk_max > cap, and for a bad page_tokens,
+ * num_pages < 1, max_pages_per_seq < 1 or block_table == NULL. */
+int qattn_mxfp4_attn_fwd_split_paged(const void* q4, const void* qscale, const void* k4, const void* kscale,
+                                     const void* vt, const void* vscale, void* opart, void* ml,
+                                     const void* lens, const void* block_table, long bhv,
+                                     long heads_per_seq, long rows, long sq_head, long num_pages,
+                                     long page_tokens, long max_pages_per_seq, long sk_max, int causal,
+                                     int keys_per_split, int head_dim, float qks, void* stream);
+
+/* qattn_mxfp4_cache_append into the pool: the same arguments, quantisers, vtail (f16
+ * [batch*kv_heads][64][128]) and lens update, the destination of every row and tile going through
+ * block_table i32 [batch][max_pages_per_seq] (device), which the caller has filled for the lengths
+ * AFTER the append before this call in stream order.  The caller guarantees lens[b] + counts[b] <=
+ * (pages of sequence b) * P.  Returns 1 as that entry does, and for the pool's limits above. */
+int qattn_mxfp4_paged_append(const void* k, const void* v, const void* k_mean, void* k4, void* kscale,
+                             void* vt, void* vscale, void* vtail, void* lens, const void* counts,
+                             const void* block_table, long batch, long kv_heads, long n, long num_pages,
+                             long page_tokens, long max_pages_per_seq, int head_dim, void* stream);
+
 /* Merge of the splits, per row of rows_total = bhv*rows: M = max_s m_s, w_s = 2^(m_s - M) (exact; 0
  * for m_s = -inf), L = sum_s w_s l_s, out f16 [rows_total, 128] = (sum_s w_s O_s) * (1 / L), lse f32
  * [rows_total] = M + log2(L).  With nsplit == 1 this is the one-pass forward's epilogue bit for bit. */

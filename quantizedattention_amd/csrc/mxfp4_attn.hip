@@ -32,8 +32,12 @@
 // applies the epilogue above.  tests/mxfp4_split_ref.py restates it; tests/test_gpu_mxfp4_cache.py
 // checks it.  Its LEN instantiation reads a preallocated cache with one length per sequence, which
 // the "cache append" kernels below grow in place (tests/mxfp4_ragged_ref.py restates it,
-// tests/test_gpu_mxfp4_ragged.py checks both).
+// tests/test_gpu_mxfp4_ragged.py checks both).  Its PAGED instantiation reads the same tiles from a
+// pool of pages through a block table ("paged pool" below; tests/test_gpu_mxfp4_paged.py holds it to
+// the LEN instantiation bit for bit).
 #include "common.h"
+
+#include <type_traits>
 
 namespace qattn {
 
@@ -148,16 +152,32 @@ QA_DEVICE int mx_append_count(const int* lens, const int* counts, int b, int n, 
   return cnt > 0 && cnt <= n && L >= 0 && L <= cap - cnt ? cnt : 0;
 }
 
+// ---- paged pool (kv_cache_mxfp4.py PagedKVFP4)
+// The same four operands cut into pages of P = 64 << lgt tokens that hold every head of ONE sequence:
+// k4 [npool][Hkv][P][D/2], ks [npool][Hkv][P][D/32], vt [npool][Hkv][P/64][D][32 B], vs [npool][Hkv][P/64]
+// [D][2].  btab i32 [B][mpp] names the pages of sequence b in order, so logical tile g of head hd is
+// physical tile (btab[b][g >> lgt] * Hkv + hd) << lgt | (g & (P/64 - 1)) of all four operands.  An
+// entry is read only below ceil(L / P) (appends: of the length after the append) and is clamped to
+// [0, npool): a wrong table gives a wrong answer, never an address outside the pool.  Tile indices are
+// 64-bit products here; the C entries hold npool * Hkv * P/64 below 2^31.
+QA_DEVICE long mx_paged_tile(const int* btab, int b, int hd, int g, int Hkv, int mpp, int lgt, int npool) {
+  const int page = min(max(btab[(long)b * mpp + (g >> lgt)], 0), npool - 1);
+  return (((long)page * Hkv + hd) << lgt) + (g & ((1 << lgt) - 1));
+}
+
 // V: one thread per (head, touched tile j, column d, half h).  Tile g = L / 64 + j of the touched
 // range [L / 64, (L + cnt - 1) / 64] is quantised again from its 32 keys per block in
 // mx_quant_vt_kernel's order: token t < L from vtail[t % 64], t < L + cnt from the new v[t - L], else 0.
-template <int D>
+// PAGED: cap = mpp * P and the tile is written where the block table puts it.
+template <int D, bool PAGED = false>
 __global__ __launch_bounds__(256) void mx_append_vt_kernel(const _Float16* __restrict__ v,
                                                            const _Float16* __restrict__ vtail,
                                                            uint8_t* __restrict__ vt, uint8_t* __restrict__ vs,
                                                            const int* __restrict__ lens,
                                                            const int* __restrict__ counts, long nthr,
-                                                           int Hkv, int n, int ntile, int cap) {
+                                                           int Hkv, int n, int ntile, int cap,
+                                                           const int* __restrict__ btab, int mpp, int lgt,
+                                                           int npool) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= nthr) return;
   const int h = (int)(i & 1);
@@ -181,15 +201,17 @@ __global__ __launch_bounds__(256) void mx_append_vt_kernel(const _Float16* __res
     amax = fmaxf(amax, fabsf(f[j]));
   }
   const unsigned e = e8m0_of(amax);
-  const long o = ((bh * (cap / 64) + g) * D + d) * 2 + h;
+  long tile = bh * (cap / 64) + g;
+  if constexpr (PAGED) tile = mx_paged_tile(btab, b, (int)(bh % Hkv), g, Hkv, mpp, lgt, npool);
+  const long o = (tile * D + d) * 2 + h;
   reinterpret_cast<v4i*>(vt)[o] = pack_fp4x32(f, e8m0_value(e));
   vs[o] = (uint8_t)e;
 }
 
 // K and vtail: one thread per 32-element block of a new row.  Row i < cnt of head bh goes to token
 // L + i of k4 / ks, quantised as mx_quant_rows_kernel does (mean: f16 [B*Hkv, D] or null); the same
-// 32 elements of v go to vtail when the token lies in the new last partial tile.
-template <int D>
+// 32 elements of v go to vtail when the token lies in the new last partial tile.  PAGED as above.
+template <int D, bool PAGED = false>
 __global__ __launch_bounds__(256) void mx_append_k_kernel(const _Float16* __restrict__ k,
                                                           const _Float16* __restrict__ v,
                                                           const _Float16* __restrict__ mean,
@@ -197,7 +219,9 @@ __global__ __launch_bounds__(256) void mx_append_k_kernel(const _Float16* __rest
                                                           _Float16* __restrict__ vtail,
                                                           const int* __restrict__ lens,
                                                           const int* __restrict__ counts, long nblk,
-                                                          int Hkv, int n, int cap) {
+                                                          int Hkv, int n, int cap,
+                                                          const int* __restrict__ btab, int mpp, int lgt,
+                                                          int npool) {
   constexpr int NB = D / 32;
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= nblk) return;
@@ -210,7 +234,10 @@ __global__ __launch_bounds__(256) void mx_append_k_kernel(const _Float16* __rest
   const int t = L + tok;
   if (tok >= cnt) return;   // t < L + cnt <= cap
   const v8h* mu = mean ? reinterpret_cast<const v8h*>(mean + bh * D + blk * 32) : nullptr;
-  const long o = (bh * cap + t) * NB + blk;
+  long row = bh * cap + t;
+  if constexpr (PAGED)
+    row = mx_paged_tile(btab, b, (int)(bh % Hkv), t / 64, Hkv, mpp, lgt, npool) * 64 + t % 64;
+  const long o = row * NB + blk;
   mx_quant_row_block(reinterpret_cast<const v8h*>(k + i * 32), mu, reinterpret_cast<v4i*>(k4) + o, ks + o);
   const int end = L + cnt;
   if (end % 64 != 0 && t / 64 == end / 64) {
@@ -302,6 +329,88 @@ struct MxRing {
 #pragma unroll
     for (int i = 0; i < C::NSLOT - 1; ++i) issue(i, ntw);
   }
+};
+
+// The same plan over the paged pool ("paged pool" above): the wave's tiles are t0 .. of head hd of the
+// sequence whose table row is tbl, npages = ceil(L / P) entries of which may be read.  When the ring
+// enters a page it rebases its four buffer resources: base = operand + (64-bit) first tile of the
+// head's part of that page * bytes, bounds that part alone, so an operand may pass 4 GiB and no byte of
+// another page or head can be fetched; inside the page the tile is the 32-bit soffset, as in MxRing.
+// Tile indices are 32-bit (the C entry holds the pool below 2^31 tiles), byte offsets 64-bit.  The
+// table is read through the constant address space (wave-uniform: scalar loads, which the ring's vmcnt
+// counts do not see) and one page ahead: while the ring is in page i it holds the entry of page
+// min(i + 1, npages - 1), loaded a tile before the rebase that needs it.  All of this is scalar ALU
+// work on every wave's own instruction stream (tools/time_decode_paged.py measures what it costs).
+template <int D>
+struct MxPagedRing {
+  using C = MxCfg<D>;
+  typedef const __attribute__((address_space(4))) int* table_ptr;
+  unsigned voff[C::IPW16], loff[C::IPW16], bytes[C::IPW16];
+  const uint8_t* base[C::IPW16];
+  const uint8_t *ksbase, *vsbase;
+  v4u rs[C::IPW16], ks_rs, vs_rs;   // of the page the ring is in
+  table_ptr tbl;
+  int npages, lgt, hkv, hd, npool, t0;
+  int cur, next;   // the page index the ring is in and the table entry after it
+  unsigned smem_lds;
+  int lane;
+  QA_DEVICE void rebase(int id) {
+    const unsigned long first = ((unsigned)min(max(id, 0), npool - 1) * (unsigned)hkv + hd) << lgt;
+#pragma unroll
+    for (int i = 0; i < C::IPW16; ++i) rs[i] = make_rsrc(base[i] + first * bytes[i], bytes[i] << lgt);
+    ks_rs = make_rsrc(ksbase + first * C::KS_BYTES, (unsigned)C::KS_BYTES << lgt);
+    vs_rs = make_rsrc(vsbase + first * C::VS_BYTES, (unsigned)C::VS_BYTES << lgt);
+  }
+  QA_DEVICE MxPagedRing(const uint8_t* k4, const uint8_t* ks, const uint8_t* vt, const uint8_t* vs,
+                        const int* row, int npages_, int lgt_, int hkv_, int hd_, int npool_, int t0_,
+                        const char* smem, int wave, int lane_)
+      : ksbase(ks), vsbase(vs), tbl((table_ptr)(unsigned long)row), npages(npages_), lgt(lgt_), hkv(hkv_),
+        hd(hd_), npool(npool_), t0(t0_), lane(lane_) {
+#pragma unroll
+    for (int i = 0; i < C::IPW16; ++i) {
+      const int p = wave + C::WAVES * i;
+      const bool isv = p >= C::K_BYTES / 1024;
+      const int piece = isv ? p - C::K_BYTES / 1024 : p;
+      voff[i] = piece * 1024 + 16 * lane;
+      loff[i] = (isv ? C::VOFF : C::KOFF) + piece * 1024;
+      bytes[i] = isv ? C::V_BYTES : C::K_BYTES;
+      base[i] = isv ? vt : k4;
+    }
+    cur = t0 >> lgt;
+    rebase(tbl[cur]);
+    next = tbl[min(cur + 1, npages - 1)];
+    smem_lds = lds_addr(smem);
+  }
+  // tile min(t, ntw - 1) of the wave into slot t & 3, from the page the ring is in; then the ring moves
+  // to the page of the FOLLOWING issue, so that the rebase stands behind the DMA, where the scheduler
+  // can sink it into the tile's matrix work, not between the barrier and the DMA
+  QA_DEVICE void issue(int t, int ntw) {
+    const unsigned slot = smem_lds + (t & 3) * C::SLOT;
+    const unsigned in = (t0 + min(t, ntw - 1)) & ((1 << lgt) - 1);
+#pragma unroll
+    for (int i = 0; i < C::IPW16; ++i) dma16_buf(rs[i], voff[i], in * bytes[i], slot + loff[i]);
+    dma4_buf(ks_rs, 4 * lane, in * C::KS_BYTES, slot + C::KSOFF);
+    dma4_buf(vs_rs, 4 * lane, in * C::VS_BYTES, slot + C::VSOFF);
+    const int g = t0 + min(t + 1, ntw - 1);
+    if ((g >> lgt) != cur) {   // tiles advance one at a time: the page after cur
+      cur = g >> lgt;
+      rebase(next);
+    }
+    // every tile, without a branch: the loaded word is then the loop-carried register itself, and the
+    // first instruction to wait for it is in the next issue (a load under `if` is copied, and waited
+    // for, at once)
+    next = tbl[min(cur + 1, npages - 1)];
+  }
+  QA_DEVICE void prologue(int ntw) {
+#pragma unroll
+    for (int i = 0; i < C::NSLOT - 1; ++i) issue(i, ntw);
+  }
+};
+
+// what the split kernel declares in place of the ring it does not use
+struct MxNoRing {
+  template <class... A>
+  QA_DEVICE MxNoRing(A...) {}
 };
 
 // Query fragments of row r (B operand of S^T): the lane holds Q[r][64s + 32h .. +32] and the row's
@@ -498,14 +607,19 @@ __global__ __launch_bounds__(256, CAUSAL ? QA_MX_OCC_CAUSAL : QA_MX_OCC) void mx
 // L - 1 non-causal and r % sq_head + L - sq_head causal: mx_tile's masked path, `diag` on the last
 // tile when L % 64 != 0 and on the diagonal tiles.  K rows >= L of that tile may hold anything (their
 // scores are selected away, NaN included); V tiles < nt are whole by the cache's invariant.
-template <int D, bool CAUSAL, bool LEN = false>
+// PAGED (with LEN; the paged pool of kv_cache_mxfp4.py): the same tiles fetched through the block table
+// btab i32 [B][mpp] by MxPagedRing, hps = Hkv heads per page, Sk = mpp * P (what a table row can hold).
+// Only the ring differs: the prelude, the tile body and the epilogue are the LEN instantiation's.
+template <int D, bool CAUSAL, bool LEN = false, bool PAGED = false>
 __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
     const uint8_t* __restrict__ q4, const uint8_t* __restrict__ qs, const uint8_t* __restrict__ k4,
     const uint8_t* __restrict__ ks, const uint8_t* __restrict__ vt, const uint8_t* __restrict__ vs,
     float* __restrict__ opart, float2* __restrict__ ml, int BHV, int rows, int sq_head, int Sk,
-    int kps, float qks, int qoff, const int* __restrict__ lens, int hps) {
+    int kps, float qks, int qoff, const int* __restrict__ lens, int hps, const int* __restrict__ btab,
+    int mpp, int lgt, int npool) {
   using C = MxCfg<D>;
   constexpr bool MASK = CAUSAL || LEN;
+  static_assert(LEN || !PAGED, "the paged pool has a length per sequence");
   static_assert(sizeof(float) == 4 && D == 128, "fp32 staging in two passes fills the ring exactly");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int nrb = (rows + C::QROWS - 1) / C::QROWS;
@@ -552,10 +666,15 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
 
   // the ring over the split's own byte range: the buffer bounds end at its last tile
   const long kvh = bh;
-  const MxRing<D> ring(k4 + (kvh * Sk + (long)t0 * C::KT) * C::KROWB,
-                       ks + (kvh * Sk + (long)t0 * C::KT) * (D / 32), vt + (kvh * ntc + t0) * C::V_BYTES,
-                       vs + (kvh * ntc + t0) * C::VS_BYTES, ntw, smem, wave, lane);
-  ring.prologue(ntw);
+  // (one of the two is an MxNoRing, which holds nothing; the LEN statement stays as it was)
+  std::conditional_t<PAGED, MxNoRing, const MxRing<D>> lring(
+      k4 + (kvh * Sk + (long)t0 * C::KT) * C::KROWB, ks + (kvh * Sk + (long)t0 * C::KT) * (D / 32),
+      vt + (kvh * ntc + t0) * C::V_BYTES, vs + (kvh * ntc + t0) * C::VS_BYTES, ntw, smem, wave, lane);
+  std::conditional_t<PAGED, MxPagedRing<D>, MxNoRing> pring(
+      k4, ks, vt, vs, btab + (long)(bh / hps) * mpp, (nt + (1 << lgt) - 1) >> lgt, lgt, hps, bh % hps, npool,
+      t0, smem, wave, lane);
+  if constexpr (PAGED) pring.prologue(ntw);
+  else lring.prologue(ntw);
 
   v4i qf[C::NKS];
   const unsigned qsw = mx_load_q<D>(q4, qs, (long)bh * rows + qi, h, qf);
@@ -569,7 +688,8 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
   __syncthreads();
   for (int t = 0; t < ntw; ++t) {
     ring_wait_barrier<2 * C::IPW>();
-    ring.issue(t + 3, ntw);
+    if constexpr (PAGED) pring.issue(t + 3, ntw);
+    else lring.issue(t + 3, ntw);
     if (!active) continue;   // a wave without rows keeps its share of the DMA and the barrier
     bool diag = false;
     int lim = 0;
@@ -721,7 +841,8 @@ static int mxfp4_split_launch(const void* q4, const void* qscale, const void* k4
                      dim3(256), lds, (hipStream_t)stream, (const uint8_t*)q4, (const uint8_t*)qscale,
                      (const uint8_t*)k4, (const uint8_t*)kscale, (const uint8_t*)vt,
                      (const uint8_t*)vscale, (float*)opart, (float2*)ml, (int)bhv, (int)rows,
-                     (int)sq_head, (int)sk, kps, qks, (int)(sk - sq_head), (const int*)nullptr, 1);
+                     (int)sq_head, (int)sk, kps, qks, (int)(sk - sq_head), (const int*)nullptr, 1,
+                     (const int*)nullptr, 0, 0, 0);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -740,7 +861,28 @@ static int mxfp4_split_len_launch(const void* q4, const void* qscale, const void
                      dim3(256), lds, (hipStream_t)stream, (const uint8_t*)q4, (const uint8_t*)qscale,
                      (const uint8_t*)k4, (const uint8_t*)kscale, (const uint8_t*)vt,
                      (const uint8_t*)vscale, (float*)opart, (float2*)ml, (int)bhv, (int)rows,
-                     (int)sq_head, (int)cap, kps, qks, 0, (const int*)lens, (int)hps);
+                     (int)sq_head, (int)cap, kps, qks, 0, (const int*)lens, (int)hps, (const int*)nullptr, 0, 0, 0);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+template <bool CAUSAL>
+static int mxfp4_split_paged_launch(const void* q4, const void* qscale, const void* k4, const void* kscale,
+                                    const void* vt, const void* vscale, void* opart, void* ml,
+                                    const void* lens, const void* btab, long bhv, long hps, long rows,
+                                    long sq_head, long npool, int lgt, long mpp, long sk_max, int kps,
+                                    float qks, void* stream) {
+  using C = MxCfg<128>;
+  const long nrb = (rows + C::QROWS - 1) / C::QROWS;
+  const long nsplit = (sk_max + kps - 1) / kps;
+  if (nrb * bhv > 0x7fffffffL || nsplit > 65535) return 1;
+  const int lds = C::NSLOT * C::SLOT;
+  { static LdsGrant granted_; if (!lds_grant((const void*)mxfp4_attn_split_kernel<128, CAUSAL, true, true>, lds, granted_)) return 1; }
+  hipLaunchKernelGGL((mxfp4_attn_split_kernel<128, CAUSAL, true, true>),
+                     dim3((unsigned)(nrb * bhv), (unsigned)nsplit), dim3(256), lds, (hipStream_t)stream,
+                     (const uint8_t*)q4, (const uint8_t*)qscale, (const uint8_t*)k4, (const uint8_t*)kscale,
+                     (const uint8_t*)vt, (const uint8_t*)vscale, (float*)opart, (float2*)ml, (int)bhv,
+                     (int)rows, (int)sq_head, (int)(mpp * (64L << lgt)), kps, qks, 0, (const int*)lens,
+                     (int)hps, (const int*)btab, (int)mpp, lgt, (int)npool);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -807,11 +949,84 @@ extern "C" int qattn_mxfp4_cache_append(const void* k, const void* v, const void
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(mx_append_vt_kernel<128>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st,
                      (const _Float16*)v, (const _Float16*)vtail, (uint8_t*)vt, (uint8_t*)vscale,
-                     (const int*)lens, (const int*)counts, nthr, (int)kv_heads, (int)n, (int)ntile, (int)cap);
+                     (const int*)lens, (const int*)counts, nthr, (int)kv_heads, (int)n, (int)ntile, (int)cap,
+                     (const int*)nullptr, 0, 0, 0);
   hipLaunchKernelGGL(mx_append_k_kernel<128>, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st,
                      (const _Float16*)k, (const _Float16*)v, (const _Float16*)k_mean, (uint8_t*)k4,
                      (uint8_t*)kscale, (_Float16*)vtail, (const int*)lens, (const int*)counts, nblk,
-                     (int)kv_heads, (int)n, (int)cap);
+                     (int)kv_heads, (int)n, (int)cap, (const int*)nullptr, 0, 0, 0);
+  hipLaunchKernelGGL(mx_append_len_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st,
+                     (int*)lens, (const int*)counts, (int)batch, (int)n, (int)cap);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// log2(page_tokens / 64) of a page size 64 * 2^k in [64, 1024], else -1
+static int mx_page_lgt(long page_tokens) {
+  for (int k = 0; k <= 4; ++k)
+    if (page_tokens == 64L << k) return k;
+  return -1;
+}
+
+// the pool's limits both paged entries share: a physical tile index below 2^31 and 32-bit token indices
+// inside a sequence
+static bool mx_pool_ok(long num_pages, long kv_heads, int lgt, long mpp) {
+  if (lgt < 0 || num_pages < 1 || kv_heads < 1 || mpp < 1 || num_pages > 0x7fffffffL) return false;
+  if (kv_heads > 0x7fffffffL || mpp > (1L << 25) || mpp * (64L << lgt) > (1L << 25)) return false;
+  return num_pages * kv_heads <= (0x7fffffffL >> lgt);
+}
+
+// qattn_mxfp4_attn_fwd_split_len over the paged pool: the operands are pages of page_tokens tokens x
+// heads_per_seq heads, block_table i32 [bhv / heads_per_seq][max_pages_per_seq] on the device
+extern "C" int qattn_mxfp4_attn_fwd_split_paged(const void* q4, const void* qscale, const void* k4,
+                                                const void* kscale, const void* vt, const void* vscale,
+                                                void* opart, void* ml, const void* lens,
+                                                const void* block_table, long bhv, long heads_per_seq,
+                                                long rows, long sq_head, long num_pages, long page_tokens,
+                                                long max_pages_per_seq, long sk_max, int causal,
+                                                int keys_per_split, int head_dim, float qks, void* stream) {
+  if (head_dim != 128 || bhv < 0 || rows < 0 || !lens || !block_table) return 1;
+  const int lgt = mx_page_lgt(page_tokens);
+  if (!mx_pool_ok(num_pages, heads_per_seq, lgt, max_pages_per_seq)) return 1;
+  if (sk_max % 64 != 0 || sk_max < 64 || sk_max > max_pages_per_seq * page_tokens) return 1;
+  if (keys_per_split < 64 || keys_per_split % 64 != 0) return 1;
+  if (sq_head < 1 || rows % sq_head != 0 || bhv % heads_per_seq != 0) return 1;
+  if (causal != 0 && causal != 2) return 1;
+  if (bhv == 0 || rows == 0) return 0;
+  if (rows > (1L << 30) || bhv > 0x7fffffffL) return 1;
+  if (causal)
+    return mxfp4_split_paged_launch<true>(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table,
+                                          bhv, heads_per_seq, rows, sq_head, num_pages, lgt,
+                                          max_pages_per_seq, sk_max, keys_per_split, qks, stream);
+  return mxfp4_split_paged_launch<false>(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table,
+                                         bhv, heads_per_seq, rows, sq_head, num_pages, lgt,
+                                         max_pages_per_seq, sk_max, keys_per_split, qks, stream);
+}
+
+// qattn_mxfp4_cache_append into the paged pool: the pages the new tokens need are in block_table already
+extern "C" int qattn_mxfp4_paged_append(const void* k, const void* v, const void* k_mean, void* k4,
+                                        void* kscale, void* vt, void* vscale, void* vtail, void* lens,
+                                        const void* counts, const void* block_table, long batch,
+                                        long kv_heads, long n, long num_pages, long page_tokens,
+                                        long max_pages_per_seq, int head_dim, void* stream) {
+  if (head_dim != 128 || n < 1 || n > (1L << 25) || batch < 0 || batch > 0x7fffffffL) return 1;
+  if (!k || !v || !k4 || !kscale || !vt || !vscale || !vtail || !lens || !block_table) return 1;
+  const int lgt = mx_page_lgt(page_tokens);
+  if (!mx_pool_ok(num_pages, kv_heads, lgt, max_pages_per_seq)) return 1;
+  const long bhv = batch * kv_heads, cap = max_pages_per_seq * page_tokens;
+  if (bhv == 0) return 0;
+  const long ntile = (n + 62) / 64 + 1;   // tiles n tokens can touch from any start
+  const long nthr = bhv * ntile * 128 * 2, nblk = bhv * n * (128 / 32);
+  if ((nthr + 255) / 256 > 0x7fffffffL || (nblk + 255) / 256 > 0x7fffffffL) return 1;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL((mx_append_vt_kernel<128, true>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st,
+                     (const _Float16*)v, (const _Float16*)vtail, (uint8_t*)vt, (uint8_t*)vscale,
+                     (const int*)lens, (const int*)counts, nthr, (int)kv_heads, (int)n, (int)ntile, (int)cap,
+                     (const int*)block_table, (int)max_pages_per_seq, lgt, (int)num_pages);
+  hipLaunchKernelGGL((mx_append_k_kernel<128, true>), dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st,
+                     (const _Float16*)k, (const _Float16*)v, (const _Float16*)k_mean, (uint8_t*)k4,
+                     (uint8_t*)kscale, (_Float16*)vtail, (const int*)lens, (const int*)counts, nblk,
+                     (int)kv_heads, (int)n, (int)cap, (const int*)block_table, (int)max_pages_per_seq, lgt,
+                     (int)num_pages);
   hipLaunchKernelGGL(mx_append_len_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st,
                      (int*)lens, (const int*)counts, (int)batch, (int)n, (int)cap);
   return hipGetLastError() == hipSuccess ? 0 : 2;

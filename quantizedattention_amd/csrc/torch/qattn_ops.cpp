@@ -26,6 +26,8 @@
 //       over the cache; keys_per_split 0: the plan of qattn_split_keys)
 //   mxfp4_decode(q, k4, ks, vt, vs, lens, sk_max, causal, keys_per_split) -> (O, lse)
 //       kv_cache_mxfp4.attention_mxfp4_decode on a preallocated cache's operands and device lengths
+//   mxfp4_decode_paged(q, k4, ks, vt, vs, lens, block_table, sk_max, causal, keys_per_split) -> (O, lse)
+//       kv_cache_mxfp4.attention_mxfp4_decode_paged on a page pool's operands, lengths and block table
 // Workspaces, head chunks and key splits are planned by the library (csrc/plan.hip), as in the drop-ins.
 // Errors: TORCH_CHECK (c10::Error, RuntimeError in Python) with the drop-ins' messages; int8_quant's
 // argument checks raise ValueError (TORCH_CHECK_VALUE) as its Python predecessor did.
@@ -483,6 +485,63 @@ std::tuple<Tensor, Tensor> mxfp4_decode(const Tensor& q_in, const Tensor& k4, co
   return {out, lse};
 }
 
+// kv_cache_mxfp4.attention_mxfp4_decode_paged on a page pool's operands: k4 [num_pages, Hkv, P, 64] with
+// lens i32 [B] and block_table i32 [B, max_pages_per_seq] on the device.  As for mxfp4_decode the caller
+// guarantees what the operator cannot read: 1 <= lens[b] <= sk_max, the pages of every sequence named in
+// its table row and, causal, lens[b] >= Sq; the Python wrapper ops.mxfp4_decode_paged checks the lengths
+// on the cache's host mirror.
+std::tuple<Tensor, Tensor> mxfp4_decode_paged(const Tensor& q_in, const Tensor& k4, const Tensor& ks,
+                                              const Tensor& vt, const Tensor& vs, const Tensor& lens,
+                                              const Tensor& block_table, int64_t sk_max, int64_t causal,
+                                              int64_t keys_per_split) {
+  require_gpu({&q_in, &k4, &ks, &vt, &vs, &lens, &block_table});
+  TORCH_CHECK(q_in.dim() == 4 && k4.dim() == 4 && q_in.size(3) == 128 && k4.size(3) == 64,
+              "qattn mxfp4 paged cache: head_dim must be 128 in q and in the pool");
+  const int64_t NP = k4.size(0), Hkv = k4.size(1), PT = k4.size(2), D = 128;
+  TORCH_CHECK(PT >= 64 && PT <= 1024 && (PT & (PT - 1)) == 0,
+              "qattn mxfp4 paged cache: page_tokens must be 64 * 2^k in [64, 1024]");
+  TORCH_CHECK(block_table.scalar_type() == at::kInt && block_table.is_contiguous() && block_table.dim() == 2 &&
+                  block_table.size(1) >= 1,
+              "qattn mxfp4 paged cache: block_table must be contiguous int32 [B, max_pages_per_seq]");
+  const int64_t B = block_table.size(0), mpp = block_table.size(1);
+  TORCH_CHECK(q_in.size(0) == B && Hkv > 0 && NP > 0 && q_in.size(1) % Hkv == 0,
+              "qattn mxfp4 paged cache: q must be [B, G*Hkv, Sq, D] for the table's B and the pool's Hkv");
+  const int64_t Hq = q_in.size(1), Sq = q_in.size(2);
+  TORCH_CHECK(Sq >= 1, "qattn mxfp4 paged cache: Sq >= 1 expected");
+  TORCH_CHECK(sk_max >= 64 && sk_max % 64 == 0 && sk_max <= mpp * PT,
+              "qattn mxfp4 paged cache: sk_max must be a multiple of 64 in [64, max_pages_per_seq * page_tokens]");
+  TORCH_CHECK(causal == 0 || causal == 1, "qattn mxfp4 paged cache: causal must be 0 or 1");
+  TORCH_CHECK(!causal || Sq <= sk_max, "qattn mxfp4 paged cache: causal attention needs Sq <= the cached tokens");
+  for (const Tensor* t : {&k4, &ks, &vt, &vs})
+    TORCH_CHECK(t->scalar_type() == at::kByte && t->is_contiguous(),
+                "qattn mxfp4 paged cache: the quantised operands must be contiguous uint8");
+  TORCH_CHECK(ks.sizes() == at::IntArrayRef({NP, Hkv, PT, D / 32}) &&
+                  vt.sizes() == at::IntArrayRef({NP, Hkv, PT / 64, D, 32}) &&
+                  vs.sizes() == at::IntArrayRef({NP, Hkv, PT / 64, D, 2}),
+              "qattn mxfp4 paged cache: ks / vt / vs do not match k4");
+  TORCH_CHECK(lens.scalar_type() == at::kInt && lens.is_contiguous() && lens.dim() == 1 && lens.size(0) == B,
+              "qattn mxfp4 paged cache: lens must be contiguous int32 [B]");
+  const int64_t bhv = B * Hkv, rows = (Hq / Hkv) * Sq;
+  int64_t kps = keys_per_split == 0 ? qattn_split_keys(bhv, rows, sk_max, 64) : keys_per_split;
+  TORCH_CHECK(kps >= 64 && kps % 64 == 0, "qattn mxfp4 paged cache: keys_per_split must be a multiple of 64");
+  kps = std::min(kps, sk_max);
+  const int64_t nsplit = (sk_max + kps - 1) / kps;
+  Ctx c(q_in);
+  const Tensor q = q_in.to(at::kHalf).contiguous();
+  Tensor q4 = empty({B * Hq * Sq, D / 2}, at::kByte, q), qs = empty({B * Hq * Sq, D / 32}, at::kByte, q);
+  Tensor out = empty({B, Hq, Sq, D}, at::kHalf, q), lse = empty({B * Hq, Sq}, at::kFloat, q);
+  if (out.numel() == 0) return {out, lse};
+  call(qattn_mxfp4_quant_rows(P(q), nullptr, P(q4), P(qs), B * Hq * Sq, Sq, (int)D, c.stream), "quantise q");
+  Tensor opart = empty({nsplit, bhv * rows, D}, at::kFloat, q), ml = empty({nsplit, bhv * rows, 2}, at::kFloat, q);
+  call(qattn_mxfp4_attn_fwd_split_paged(P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens),
+                                        P(block_table), bhv, Hkv, rows, Sq, NP, PT, mpp, sk_max,
+                                        causal ? 2 : 0, (int)kps, (int)D, qk_scale(D), c.stream),
+       "mxfp4 paged decode forward");
+  call(qattn_mxfp4_split_combine(P(opart), P(ml), P(out), P(lse), bhv * rows, (int)nsplit, (int)D, c.stream),
+       "mxfp4 split merge");
+  return {out, lse};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(qattn, m) {
@@ -501,6 +560,8 @@ TORCH_LIBRARY(qattn, m) {
         "(Tensor, Tensor)");
   m.def("mxfp4_decode(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, int sk_max, int causal, "
         "int keys_per_split) -> (Tensor, Tensor)");
+  m.def("mxfp4_decode_paged(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, Tensor block_table, "
+        "int sk_max, int causal, int keys_per_split) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
@@ -514,4 +575,5 @@ TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
   m.impl("mxfp4_fwd_ex", &mxfp4_fwd_ex);
   m.impl("mxfp4_cached", &mxfp4_cached);
   m.impl("mxfp4_decode", &mxfp4_decode);
+  m.impl("mxfp4_decode_paged", &mxfp4_decode_paged);
 }

@@ -28,6 +28,34 @@ influence a result.  :func:`attention_mxfp4_decode` attends to such a cache
 sequence's end exits at once).  ``lse`` (base 2) is returned so that results can still be merged with
 attention over keys held elsewhere; with a smoothed cache it is that of the scores q . (k - k_mean).
 
+A server uses :class:`PagedKVFP4`: the preallocated cache reserves ``capacity`` tokens for every
+sequence, cannot hand a finished sequence's memory to another and stores a shared prompt once per
+sequence.  K is quantised per key row and V per 64-key tile, so a sequence's operands are a
+concatenation of independent 64-key tiles, each four fixed-size blocks (4096 B of ``k4``, 256 B of
+``ks``, 4096 B of ``vt``, 256 B of ``vs``), and can lie anywhere.  The pool cuts them into pages of
+``page_tokens`` P = 64 * 2^k tokens, 64 <= P <= 1024; a page belongs to one sequence and holds all
+``kv_heads`` heads::
+
+    k4           uint8   [num_pages, Hkv, P, D/2]
+    ks           uint8   [num_pages, Hkv, P, D/32]
+    vt           uint8   [num_pages, Hkv, P/64, D, 32]
+    vs           uint8   [num_pages, Hkv, P/64, D, 2]
+    vtail        float16 [max_seqs, Hkv, 64, D]
+    lens         int32   [max_seqs]                      host mirror: lengths
+    block_table  int32   [max_seqs, max_pages_per_seq]   host mirror: table
+    k_mean       float16 [max_seqs, Hkv, 1, D] or None
+
+Logical tile t of head h of sequence b is physical tile ``(block_table[b][t // (P/64)] * Hkv + h) *
+(P/64) + t % (P/64)`` of all four operands.  Invariant: gathering a sequence's pages through its table
+gives exactly the bytes :class:`PreallocatedKVFP4` holds after the same appends, rows [0, L) of ``k4``
+/ ``ks`` and tiles [0, ceil(L / 64)) of ``vt`` / ``vs``.  Everything else -- the tail of a sequence's
+last page, pages it does not own, table entries at or past ceil(L / P) -- is unspecified and never
+influences a result.  :class:`PageAllocator` keeps the free list, the reference counts and the page
+lists on the host; ``append`` reserves pages there first and uploads the changed table in stream
+order, ``fork`` shares a prefix's full pages by reference count, and
+:func:`attention_mxfp4_decode_paged` (``qattn_mxfp4_attn_fwd_split_paged``) gives, bit for bit, what
+:func:`attention_mxfp4_decode` gives on a preallocated cache with the same tokens.
+
 Wire format (little-endian), the container of kv_cache.py with a magic of its own::
 
     offset 0   8 B   magic  b"QATTNKF4"
@@ -61,7 +89,7 @@ _ALIGN = 256
 _DTYPES = {"uint8": torch.uint8, "float16": torch.float16}
 
 __all__ = ["QuantizedKVFP4", "quantize_kv_fp4", "attention_mxfp4_cached", "PreallocatedKVFP4",
-           "attention_mxfp4_decode"]
+           "attention_mxfp4_decode", "PageAllocator", "PagedKVFP4", "attention_mxfp4_decode_paged"]
 
 
 @dataclass
@@ -352,10 +380,12 @@ class PreallocatedKVFP4:
                               None if self.k_mean is None else self.k_mean[b:b + 1].clone())
 
 
-def _decode_plan(q: torch.Tensor, cache: "PreallocatedKVFP4", causal: bool, keys_per_split):
-    """The host checks of a decode call -> (bhv, rows, sk_max, kps, nsplit)."""
-    if not isinstance(cache, PreallocatedKVFP4):
-        raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PreallocatedKVFP4")
+def _decode_plan(q: torch.Tensor, cache, causal: bool, keys_per_split, kind=None):
+    """The host checks of a decode call on a cache of class ``kind`` (None: PreallocatedKVFP4) ->
+    (bhv, rows, sk_max, kps, nsplit)."""
+    kind = PreallocatedKVFP4 if kind is None else kind
+    if not isinstance(cache, kind):
+        raise _lib.QAttnError(f"qattn mxfp4 kv cache: cache must be a {kind.__name__}")
     B, Hkv, cap, D = cache.shape
     if D != 128 or q.dim() != 4 or q.shape[3] != D:
         raise _lib.QAttnError("qattn mxfp4 kv cache: head_dim must be 128 in q and in the cache")
@@ -405,6 +435,300 @@ def attention_mxfp4_decode(q: torch.Tensor, cache: PreallocatedKVFP4, causal: bo
     _lib.call("qattn_mxfp4_attn_fwd_split_len", _lib.ptr(q4), _lib.ptr(qs), _lib.ptr(cache.k4),
               _lib.ptr(cache.ks), _lib.ptr(cache.vt), _lib.ptr(cache.vs), _lib.ptr(opart), _lib.ptr(ml),
               _lib.ptr(cache.lens), bhv, Hkv, rows, Sq, cap, sk_max, 2 if causal else 0, kps, D,
+              _qk_scale(D), st)
+    _lib.call("qattn_mxfp4_split_combine", _lib.ptr(opart), _lib.ptr(ml), _lib.ptr(O), _lib.ptr(lse),
+              bhv * rows, nsplit, D, st)
+    return O, lse
+
+
+# ------------------------------------------------------------------------------ paged cache
+PAGE_TOKENS = (64, 128, 256, 512, 1024)
+
+
+class PageAllocator:
+    """The host side of a page pool: a free list, a reference count per page and the page list of
+    every sequence, which ``table`` mirrors.  No tensors, no device: plain Python.
+
+    ``free_order`` (a permutation of range(num_pages); default ascending) is the order in which the
+    pages are first handed out; a page that returns to the pool is the next one handed out.
+    ``table[b][i]`` is page i of sequence b for i < len(pages[b]); the entries past that keep
+    whatever they held.  Every operation either happens completely or raises
+    :class:`QAttnError` before anything has changed.
+    """
+
+    def __init__(self, num_pages: int, page_tokens: int, max_seqs: int, max_pages_per_seq: int,
+                 free_order=None):
+        if page_tokens not in PAGE_TOKENS:
+            raise _lib.QAttnError("qattn mxfp4 paged cache: page_tokens must be 64 * 2^k in [64, 1024], "
+                                  f"got {page_tokens}")
+        if num_pages < 1 or max_seqs < 1 or max_pages_per_seq < 1:
+            raise _lib.QAttnError("qattn mxfp4 paged cache: num_pages, max_seqs and max_pages_per_seq >= 1 "
+                                  "expected")
+        order = list(range(num_pages)) if free_order is None else [int(p) for p in free_order]
+        if sorted(order) != list(range(num_pages)):
+            raise _lib.QAttnError("qattn mxfp4 paged cache: free_order must be a permutation of the pages")
+        self.num_pages, self.page_tokens = num_pages, page_tokens
+        self.max_seqs, self.max_pages_per_seq = max_seqs, max_pages_per_seq
+        self._free = order[::-1]                  # handed out from the end
+        self.refcount = [0] * num_pages
+        self.pages = [[] for _ in range(max_seqs)]
+        self.table = [[0] * max_pages_per_seq for _ in range(max_seqs)]
+
+    @property
+    def free_pages(self) -> int:
+        return len(self._free)
+
+    def _seq(self, b) -> int:
+        b = int(b)
+        if not 0 <= b < self.max_seqs:
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: no sequence {b} (max_seqs {self.max_seqs})")
+        return b
+
+    def pages_for(self, tokens: int) -> int:
+        return -(-tokens // self.page_tokens)
+
+    def _take(self, b: int, count: int) -> list:
+        new = [self._free.pop() for _ in range(count)]
+        for p in new:
+            self.refcount[p] = 1
+            self.table[b][len(self.pages[b])] = p
+            self.pages[b].append(p)
+        return new
+
+    def reserve(self, requests) -> list:
+        """Give every ``(seq, new_length)`` of ``requests`` the pages its new length needs (a
+        sequence never shrinks here) -> the sequences whose page list grew.  All or nothing: raises,
+        naming "pages", before anything changes when a sequence would pass ``max_pages_per_seq`` or the
+        pool has too few free pages."""
+        need = {}
+        for b, length in requests:
+            b = self._seq(b)
+            need[b] = max(need.get(b, 0), self.pages_for(int(length)) - len(self.pages[b]), 0)
+        over = [b for b, n in need.items() if len(self.pages[b]) + n > self.max_pages_per_seq]
+        if over:
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: sequences {over} would pass max_pages_per_seq = "
+                                  f"{self.max_pages_per_seq} pages of {self.page_tokens} tokens")
+        total = sum(need.values())
+        if total > len(self._free):
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: out of pages ({total} needed, "
+                                  f"{len(self._free)} of {self.num_pages} free)")
+        grown = sorted(b for b, n in need.items() if n)
+        for b in grown:
+            self._take(b, need[b])
+        return grown
+
+    def release(self, b) -> None:
+        """Empty sequence ``b``: each of its pages loses a reference and returns to the free list at 0."""
+        b = self._seq(b)
+        for p in self.pages[b]:
+            self.refcount[p] -= 1
+            if self.refcount[p] == 0:
+                self._free.append(p)
+        self.pages[b] = []
+
+    def share(self, src, dst, shared: int, fresh: int = 0) -> list:
+        """Make the empty sequence ``dst`` the first ``shared`` pages of ``src`` (one more reference
+        each) followed by ``fresh`` new pages -> the new pages.  All or nothing."""
+        src, dst = self._seq(src), self._seq(dst)
+        if self.pages[dst]:
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: sequence {dst} is not empty "
+                                  f"({len(self.pages[dst])} pages)")
+        if not 0 <= shared <= len(self.pages[src]) or fresh < 0:
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: sequence {src} has no {shared} pages to share")
+        if shared + fresh > self.max_pages_per_seq or fresh > len(self._free):
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: out of pages ({fresh} needed, "
+                                  f"{len(self._free)} of {self.num_pages} free, max_pages_per_seq "
+                                  f"{self.max_pages_per_seq})")
+        for p in self.pages[src][:shared]:
+            self.refcount[p] += 1
+            self.table[dst][len(self.pages[dst])] = p
+            self.pages[dst].append(p)
+        return self._take(dst, fresh)
+
+
+class PagedKVFP4:
+    """MX-FP4 keys/values of up to ``max_seqs`` sequences x ``kv_heads`` heads in a pool of
+    ``num_pages`` pages of ``page_tokens`` tokens; layout and invariant: the module docstring.
+
+    ``k4``, ``ks``, ``vt``, ``vs`` are the pool, ``vtail``, ``lens`` and ``k_mean`` as in
+    :class:`PreallocatedKVFP4` with one row per sequence slot, ``block_table`` i32 [max_seqs,
+    max_pages_per_seq] on the device; ``alloc`` (:class:`PageAllocator`) and ``lengths`` are the host
+    mirrors, kept without reading the device.  A sequence's memory is the pages it holds: ``free``
+    gives them back, and ``fork`` lets two sequences hold the same full pages.  Shared pages are
+    always full and ``append`` only writes at or past a sequence's length, so a shared page is never
+    written and no copy-on-write is needed.
+    """
+
+    def __init__(self, k4, ks, vt, vs, vtail, lens, block_table, alloc: PageAllocator, k_mean=None):
+        self.k4, self.ks, self.vt, self.vs = k4, ks, vt, vs
+        self.vtail, self.lens, self.block_table, self.alloc, self.k_mean = vtail, lens, block_table, alloc, k_mean
+        self.lengths = [0] * alloc.max_seqs
+
+    @classmethod
+    def allocate(cls, num_pages: int, page_tokens: int, max_seqs: int, kv_heads: int, max_pages_per_seq: int,
+                 device, k_mean: Optional[torch.Tensor] = None, free_order=None) -> "PagedKVFP4":
+        """An empty pool (every length 0, every page free), zero-filled."""
+        D = 128
+        alloc = PageAllocator(num_pages, page_tokens, max_seqs, max_pages_per_seq, free_order)
+        tpp = page_tokens // BLOCK
+        if (kv_heads < 1 or num_pages * kv_heads * tpp >= 1 << 31
+                or max_pages_per_seq * page_tokens > 1 << 25):
+            raise _lib.QAttnError("qattn mxfp4 paged cache: kv_heads >= 1, fewer than 2^31 tiles in the pool "
+                                  "and at most 2^25 tokens per sequence expected")
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.QAttnError(f"qattn kernels run on the GPU only; got device {dev} "
+                                  "(no CPU fallback by design)")
+        if k_mean is not None:
+            if tuple(k_mean.shape) != (max_seqs, kv_heads, 1, D):
+                raise _lib.QAttnError("qattn mxfp4 paged cache: k_mean must be [max_seqs, Hkv, 1, 128]")
+            k_mean = k_mean.to(device=dev, dtype=torch.float16).contiguous()
+        z = lambda *shape, dt=torch.uint8: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        return cls(z(num_pages, kv_heads, page_tokens, D // 2), z(num_pages, kv_heads, page_tokens, D // 32),
+                   z(num_pages, kv_heads, tpp, D, 32), z(num_pages, kv_heads, tpp, D, 2),
+                   z(max_seqs, kv_heads, BLOCK, D, dt=torch.float16), z(max_seqs, dt=torch.int32),
+                   z(max_seqs, max_pages_per_seq, dt=torch.int32), alloc, k_mean)
+
+    @property
+    def shape(self):
+        """(max_seqs, Hkv, max_pages_per_seq * page_tokens, D): what one table row can hold"""
+        return (self.alloc.max_seqs, self.k4.shape[1], self.alloc.max_pages_per_seq * self.page_tokens, 128)
+
+    @property
+    def page_tokens(self) -> int:
+        return self.alloc.page_tokens
+
+    @property
+    def num_pages(self) -> int:
+        return self.alloc.num_pages
+
+    @property
+    def free_pages(self) -> int:
+        return self.alloc.free_pages
+
+    @property
+    def table(self):
+        """The host mirror of ``block_table`` (the allocator's)."""
+        return self.alloc.table
+
+    @property
+    def kv(self):
+        return (self.k4, self.ks, self.vt, self.vs)
+
+    def capacity_tokens(self, b: int) -> int:
+        """The tokens sequence ``b`` can hold in the pages it has."""
+        return len(self.alloc.pages[self.alloc._seq(b)]) * self.page_tokens
+
+    def _upload(self, table: bool) -> None:
+        # from fresh pageable host tensors: the copies are staged before they return, so the mirrors
+        # may change again at once
+        if table:
+            self.block_table.copy_(torch.tensor(self.alloc.table, dtype=torch.int32), non_blocking=True)
+        self.lens.copy_(torch.tensor(self.lengths, dtype=torch.int32), non_blocking=True)
+
+    def append(self, k: torch.Tensor, v: torch.Tensor, counts=None) -> "PagedKVFP4":
+        """Append fp16 ``k, v`` [max_seqs, Hkv, n, D] (any n >= 1) in place; with ``counts`` (max_seqs
+        ints in [0, n]) sequence b takes only the first ``counts[b]`` tokens.  The pages the new
+        lengths need are reserved on the host first (all or nothing: out of pages, or a sequence past
+        ``max_pages_per_seq``, raises before anything is launched or changed), the changed table is
+        uploaded in stream order and ``qattn_mxfp4_paged_append`` writes in place.  No host
+        synchronisation, nothing is read back; returns ``self``."""
+        B, H, _, D = self.shape
+        if (k.dim() != 4 or tuple(k.shape[:2]) != (B, H) or k.shape[3] != D or k.shape != v.shape
+                or k.shape[2] < 1):
+            raise _lib.QAttnError("qattn mxfp4 paged cache: appended tokens must be k, v [max_seqs, Hkv, "
+                                  "n >= 1, D]")
+        n = k.shape[2]
+        if counts is None:
+            cnt = [n] * B
+        else:
+            cnt = [int(c) for c in (counts.tolist() if isinstance(counts, torch.Tensor) else counts)]
+            if len(cnt) != B or any(c < 0 or c > n for c in cnt):
+                raise _lib.QAttnError("qattn mxfp4 paged cache: counts must be max_seqs values in [0, n]")
+        _lib.require_gpu(k, v, self.k4)
+        grown = self.alloc.reserve([(b, L + c) for b, (L, c) in enumerate(zip(self.lengths, cnt)) if c])
+        k = k.to(torch.float16).contiguous()
+        v = v.to(torch.float16).contiguous()
+        if grown:
+            self.block_table.copy_(torch.tensor(self.alloc.table, dtype=torch.int32), non_blocking=True)
+        cdev = None if counts is None else torch.tensor(cnt, dtype=torch.int32).to(k.device, non_blocking=True)
+        _lib.call("qattn_mxfp4_paged_append", _lib.ptr(k), _lib.ptr(v), _lib.ptr(self.k_mean),
+                  _lib.ptr(self.k4), _lib.ptr(self.ks), _lib.ptr(self.vt), _lib.ptr(self.vs),
+                  _lib.ptr(self.vtail), _lib.ptr(self.lens), _lib.ptr(cdev), _lib.ptr(self.block_table), B, H,
+                  n, self.num_pages, self.page_tokens, self.alloc.max_pages_per_seq, D, _lib.stream_of(k))
+        self.lengths = [L + c for L, c in zip(self.lengths, cnt)]
+        return self
+
+    def free(self, seqs) -> None:
+        """Empty the sequences ``seqs`` (indices) and give their pages back to the pool."""
+        seqs = [self.alloc._seq(b) for b in seqs]
+        for b in seqs:
+            self.lengths[b] = 0
+            self.alloc.release(b)
+        self._upload(table=False)
+
+    def fork(self, src: int, dst: int) -> None:
+        """Make the empty sequence ``dst`` a copy of ``src`` that shares its memory: the ``L // P``
+        full pages by reference count; a partial last page is copied into a fresh page on the device
+        (all heads, four operands), as are the ``vtail`` and ``k_mean`` rows.  Stream-ordered."""
+        src, dst = self.alloc._seq(src), self.alloc._seq(dst)
+        if self.lengths[dst]:
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: fork into sequence {dst}, which is not empty "
+                                  f"({self.lengths[dst]} tokens)")
+        L, P = self.lengths[src], self.page_tokens
+        fresh = self.alloc.share(src, dst, L // P, 1 if L % P else 0)
+        if fresh:
+            old = self.alloc.pages[src][L // P]
+            for t in self.kv:
+                t[fresh[0]].copy_(t[old])
+        self.vtail[dst].copy_(self.vtail[src])
+        if self.k_mean is not None:
+            self.k_mean[dst].copy_(self.k_mean[src])
+        self.lengths[dst] = L
+        self._upload(table=True)
+
+    def gather(self, b: int):
+        """Copies of sequence ``b``'s pages in order, per head: (k4 [Hkv, n*P, D/2], ks [Hkv, n*P, D/32],
+        vt [Hkv, n*P/64, D, 32], vs [Hkv, n*P/64, D, 2]) for its n pages."""
+        pages = torch.tensor(self.alloc.pages[self.alloc._seq(b)], dtype=torch.long, device=self.k4.device)
+        H = self.k4.shape[1]
+        return tuple(t[pages].transpose(0, 1).reshape(H, -1, *t.shape[3:]) for t in self.kv)
+
+    def snapshot(self, b: int) -> QuantizedKVFP4:
+        """A :class:`QuantizedKVFP4` copy (batch 1) of sequence ``b``, whose length must be a
+        multiple of 64 (and not 0)."""
+        L = self.lengths[self.alloc._seq(b)]
+        if L == 0 or L % BLOCK:
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: snapshot needs a length of 64*n tokens, got {L}")
+        k4, ks, vt, vs = self.gather(b)
+        return QuantizedKVFP4(k4[None, :, :L].contiguous(), ks[None, :, :L].contiguous(),
+                              vt[:, :L // BLOCK].contiguous(), vs[:, :L // BLOCK].contiguous(),
+                              None if self.k_mean is None else self.k_mean[b:b + 1].clone())
+
+
+@torch.no_grad()
+def attention_mxfp4_decode_paged(q: torch.Tensor, cache: PagedKVFP4, causal: bool = False,
+                                 keys_per_split: Optional[int] = None):
+    """:func:`attention_mxfp4_decode` against a paged cache: fp16 queries [max_seqs, Hq, Sq, D],
+    sequence b over its own ``lengths[b]`` keys, found through ``block_table`` -> (O fp16 [max_seqs,
+    Hq, Sq, D], lse fp32 [max_seqs*Hq, Sq] base 2), bit for bit what a preallocated cache with the same
+    tokens gives.  The same contract: every sequence slot needs a length >= 1 (raises otherwise),
+    causal needs Sq <= min(lengths); the plan is ``_split_plan_fp4`` at ceil64(max(lengths)), and
+    ``keys_per_split`` is any multiple of 64, whatever the page size."""
+    bhv, rows, sk_max, kps, nsplit = _decode_plan(q, cache, causal, keys_per_split, PagedKVFP4)
+    _lib.require_gpu(q, cache.k4)
+    B, Hkv, _, D = cache.shape
+    Hq, Sq = q.shape[1], q.shape[2]
+    dev, st = q.device, _lib.stream_of(q)
+    q4, qs = mxfp4_quantize_rows(q)
+    O = torch.empty((B, Hq, Sq, D), dtype=torch.float16, device=dev)
+    lse = torch.empty((B * Hq, Sq), dtype=torch.float32, device=dev)
+    opart = torch.empty((nsplit, bhv * rows, D), dtype=torch.float32, device=dev)
+    ml = torch.empty((nsplit, bhv * rows, 2), dtype=torch.float32, device=dev)
+    _lib.call("qattn_mxfp4_attn_fwd_split_paged", _lib.ptr(q4), _lib.ptr(qs), _lib.ptr(cache.k4),
+              _lib.ptr(cache.ks), _lib.ptr(cache.vt), _lib.ptr(cache.vs), _lib.ptr(opart), _lib.ptr(ml),
+              _lib.ptr(cache.lens), _lib.ptr(cache.block_table), bhv, Hkv, rows, Sq, cache.num_pages,
+              cache.page_tokens, cache.alloc.max_pages_per_seq, sk_max, 2 if causal else 0, kps, D,
               _qk_scale(D), st)
     _lib.call("qattn_mxfp4_split_combine", _lib.ptr(opart), _lib.ptr(ml), _lib.ptr(O), _lib.ptr(lse),
               bhv * rows, nsplit, D, st)

@@ -18,6 +18,8 @@ the autograd rules of ``int8_fwd`` and ``bf16_fwd`` (their backward operators).
     torch.ops.qattn.mxfp4_fwd_ex(q, k, v, causal) -> O      (causal 0 / 1 top-left / 2 bottom-right)
     torch.ops.qattn.mxfp4_cached(q, k4, ks, vt, vs, causal, keys_per_split) -> (O, lse)
     torch.ops.qattn.mxfp4_decode(q, k4, ks, vt, vs, lens, sk_max, causal, keys_per_split) -> (O, lse)
+    torch.ops.qattn.mxfp4_decode_paged(q, k4, ks, vt, vs, lens, block_table, sk_max, causal,
+                                       keys_per_split) -> (O, lse)
 
 Shapes follow the drop-in functions (attention_int8.py:259-262 for the int8 outputs) except that
 k_i8 is returned row-major [B*Hkv*Sk, D] (the drop-in's k_i8T is its transposed view: an operator
@@ -32,7 +34,7 @@ import torch
 from . import _lib
 
 __all__ = ["int8_quant", "int8_fwd", "int8_bwd", "bf16_fwd", "bf16_bwd", "jvp_fwd", "mxfp4_fwd",
-           "mxfp4_fwd_ex", "mxfp4_cached", "mxfp4_decode"]
+           "mxfp4_fwd_ex", "mxfp4_cached", "mxfp4_decode", "mxfp4_decode_paged"]
 
 _lib.load_ops()
 _ops = torch.ops.qattn
@@ -104,6 +106,13 @@ def _(q, k4, ks, vt, vs, causal, keys_per_split):
 
 @torch.library.register_fake("qattn::mxfp4_decode")
 def _(q, k4, ks, vt, vs, lens, sk_max, causal, keys_per_split):
+    B, H, S, D = q.shape
+    return (q.new_empty((B, H, S, D), dtype=torch.float16),
+            q.new_empty((B * H, S), dtype=torch.float32))
+
+
+@torch.library.register_fake("qattn::mxfp4_decode_paged")
+def _(q, k4, ks, vt, vs, lens, block_table, sk_max, causal, keys_per_split):
     B, H, S, D = q.shape
     return (q.new_empty((B, H, S, D), dtype=torch.float16),
             q.new_empty((B * H, S), dtype=torch.float32))
@@ -218,3 +227,14 @@ def mxfp4_decode(q, cache, causal=False, keys_per_split=None):
     _, _, sk_max, _, _ = _decode_plan(q, cache, causal, keys_per_split)
     return _ops.mxfp4_decode(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens, sk_max,
                              int(bool(causal)), 0 if keys_per_split is None else int(keys_per_split))
+
+
+def mxfp4_decode_paged(q, cache, causal=False, keys_per_split=None):
+    """``kv_cache_mxfp4.attention_mxfp4_decode_paged`` as one operator: q [max_seqs, Hq, Sq, 128]
+    against a ``PagedKVFP4``, sequence b over its own length and pages -> (O fp16, lse fp32
+    [max_seqs*Hq, Sq]).  The lengths are checked here, on the cache's host mirror (the operator reads
+    only ``lens`` and ``block_table`` on the device); ``keys_per_split`` None: the plan."""
+    from .kv_cache_mxfp4 import PagedKVFP4, _decode_plan
+    _, _, sk_max, _, _ = _decode_plan(q, cache, causal, keys_per_split, PagedKVFP4)
+    return _ops.mxfp4_decode_paged(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens, cache.block_table,
+                                   sk_max, int(bool(causal)), 0 if keys_per_split is None else int(keys_per_split))
