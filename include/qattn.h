@@ -40,6 +40,21 @@ extern "C" {
 int qattn_abi_version(void);
 const char* qattn_source_hash(void);
 
+/* ---------------------------------------------------------------- what every attention entry keeps
+ * Status: 0 done (or nothing to do), 1 an argument the entry does not support (nothing was launched),
+ * 2 a launch failed.
+ * Empty problems.  No query rows (bh == 0 or sq == 0, whatever sk is) is nothing to do: status 0,
+ * no launch, no pointer read -- for arguments that are valid otherwise: the shape checks come first,
+ * so group >= 1 and bh % group == 0 still hold (a host with no query heads passes group = 1, not
+ * Hq / Hkv = 0, or skips the call as the Python wrappers do).  Query rows without keys (sk == 0 with bh > 0 and sq > 0) are refused
+ * with status 1 by every forward and backward entry of every path -- int8, bf16, JVP and MX-FP4
+ * alike: every query keeps a key (a softmax over no keys has no value, and a gradient through it
+ * none either).
+ * Addresses.  Every tensor pointer is 16-byte aligned: the kernels read 16-byte vectors and LDS-DMA
+ * dwordx4 from the base addresses.  The entries do not check it (qattn_bf16_fwd_ws_ex's ws apart);
+ * the Python binding and the TORCH_LIBRARY operators copy a misaligned input and refuse a misaligned
+ * buffer before they call. */
+
 /* ---------------------------------------------------------------- int8 path (attention_int8.py) */
 
 /* Per-32-row block quantiser (attention_int8.py:178-186 q, 188-195 k, 241-247 v).
@@ -171,7 +186,13 @@ int qattn_int8_attn_bwd_ex(const void* dO_i8, const void* sdO, const void* q_i8,
  * s_dS) in ws, and the dQ kernel reads them back instead of recomputing S, dP, P and dS
  * (attention_int8.py:399-420).  dq, dk, dv are bit-identical to qattn_int8_attn_bwd_ex's.
  * ws must hold qattn_int8_bwd_ws_bytes(bh, sq_tok, sk_tok) bytes, 16-byte aligned; it is scratch
- * (overwritten, not read before written).  Returns 1 for ws == NULL. */
+ * (overwritten, not read before written).  Returns 1 for ws == NULL, and for a shape whose records the
+ * kernels cannot address: group * (sq_tok/32) * (sk_tok/32) KiB per key/value head of 2^31 bytes or
+ * more, group * sq_tok/32 > QATTN_WS_MAX_QUERY_TILES or sk_tok/32 > QATTN_WS_MAX_KEY_TILES (the
+ * per-tile tables the dK+dV and the dQ kernel keep in LDS; qattn_int8_bwd_plan answers 0, recompute,
+ * for the same shapes). */
+#define QATTN_WS_MAX_QUERY_TILES 1790
+#define QATTN_WS_MAX_KEY_TILES 2800
 long qattn_int8_bwd_ws_bytes(long bh, long sq_tok, long sk_tok);
 /* The largest dS-record workspace the backwards (int8 and bf16 alike) allocate before they fall back
  * to recomputation: QATTN_BWD_WS_MAX bytes if that is set, else 16 GiB (a workspace allocation
@@ -480,7 +501,8 @@ long qattn_split_keys(long bhv, long rows, long sk, int tile);
  * chunk_req: key/value heads per chunk; < 0 = auto (QATTN_BWD_WS_CHUNK if set and >= 0, else the
  * measured rule), 0 = all heads.  cap: byte limit, < 0 = qattn_bwd_ws_cap().
  * Writes the chunk (1..bkv) to *kv_chunk; returns the workspace bytes of one chunk, 0 when the dQ
- * pass must recompute (region >= 2 GiB per key/value head, or over the cap), -1 for bad shapes.
+ * pass must recompute (a shape qattn_int8_attn_bwd_ws refuses: region >= 2 GiB per key/value head,
+ * more than QATTN_WS_MAX_QUERY_TILES / _KEY_TILES tiles; or over the cap), -1 for bad shapes.
  * With bytes > 0: qattn_int8_attn_bwd_wsc(..., ws, *kv_chunk, ...); with 0: qattn_int8_attn_bwd_ex. */
 long qattn_int8_bwd_plan(long bkv, int group, long sq_tok, long sk_tok, int causal,
                          long chunk_req, long cap, long* kv_chunk);

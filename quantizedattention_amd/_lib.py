@@ -202,8 +202,41 @@ def exported_symbols() -> list[str]:
     return [n for n in SIGNATURES if hasattr(lib, n)]
 
 
+ALIGN = 16   # bytes: the kernels read 16-byte vectors and LDS-DMA dwordx4 from every base address
+
+
+def kernel_input(t: torch.Tensor | None, dtype=None):
+    """``t`` in the form a kernel reads: ``dtype`` (None: its own), contiguous, and at an address that
+    is a multiple of ALIGN.  A contiguous view at a misaligned storage offset (``flat[1:1 + n]``) is
+    copied; an aligned one (``big[1:]``) is passed as it is.  The caller binds the result to a name
+    that outlives the launch (a copy freed at once hands its block to the next copy)."""
+    if t is None:
+        return None
+    if dtype is not None:
+        t = t.to(dtype)
+    t = t.contiguous()
+    if t.data_ptr() % ALIGN:
+        t = t.clone(memory_format=torch.contiguous_format)
+    return t
+
+
 def ptr(t: torch.Tensor | None):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
+    """The address of ``t`` as a kernel argument; a misaligned one never reaches a kernel."""
+    if t is None:
+        return None
+    p = t.data_ptr()
+    if p % ALIGN:
+        raise QAttnError(f"qattn: a tensor at address {p:#x}, not a multiple of {ALIGN} (storage offset "
+                         f"{t.storage_offset()}); pass it through _lib.kernel_input")
+    return ctypes.c_void_p(p)
+
+
+def refuse_empty_keys(what: str, rows: int, sk: int) -> None:
+    """Every query keeps a key: Sk = 0 with rows > 0 is refused on every path (status 1 of the C
+    entries, include/qattn.h), here before anything is allocated."""
+    if rows > 0 and sk == 0:
+        raise QAttnError(f"{what}: an empty key sequence (Sk = 0) with {rows} query rows; every query "
+                         "keeps a key")
 
 
 class _Stream(ctypes.c_void_p):

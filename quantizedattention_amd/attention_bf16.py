@@ -55,9 +55,11 @@ def helion_atten_bf16_fwd_training(
     """bf16:111-296 -> (O fp32 [B,H,S,D], lse fp32 [B*H, S], base-2 units)."""
     _check(q_fp16_input, k_fp16_input, v_bf16_input)
     _lib.require_gpu(q_fp16_input, k_fp16_input, v_bf16_input)
-    q = q_fp16_input.to(torch.float16).contiguous()
-    k = k_fp16_input.to(torch.float16).contiguous()
-    v = v_bf16_input.to(torch.bfloat16).contiguous()
+    _lib.refuse_empty_keys("qattn bf16", q_fp16_input.numel() // q_fp16_input.shape[3],
+                           k_fp16_input.shape[2])
+    q = _lib.kernel_input(q_fp16_input, torch.float16)
+    k = _lib.kernel_input(k_fp16_input, torch.float16)
+    v = _lib.kernel_input(v_bf16_input, torch.bfloat16)
     B, H, S, D = q.shape
     Sk = k.shape[2]
     O = torch.empty((B, H, S, D), dtype=torch.float32, device=q.device)
@@ -67,10 +69,11 @@ def helion_atten_bf16_fwd_training(
     # causal: the per-head V suffix sums stand in for the fully masked key tiles (include/qattn.h);
     # without room for them the kernel runs the whole masked tile loop (same results)
     ws = None
-    if causal and Sk > 0:
+    if causal and B * H * S > 0:
         ws = _lib.try_workspace(_lib.load().qattn_bf16_fwd_ws_bytes(B * k.shape[1], Sk, D), q.device)
-    _lib.call("qattn_bf16_fwd_ws_ex", _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(O), _lib.ptr(lse),
-              B * H, S, Sk, H // k.shape[1], int(bool(causal)), D, qks, _lib.ptr(ws), _lib.stream_of(q))
+    if B * H * S:   # (without query rows there is nothing to launch: empty outputs)
+        _lib.call("qattn_bf16_fwd_ws_ex", _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(O), _lib.ptr(lse),
+                  B * H, S, Sk, H // k.shape[1], int(bool(causal)), D, qks, _lib.ptr(ws), _lib.stream_of(q))
     return O, lse
 
 
@@ -86,15 +89,19 @@ def helion_flash_atten_2_algo_4_bwd(
     """bf16:309-448 (corrected) -> fp32 (dq, dk, dv)."""
     _check(q_input, k_input, v_input)
     _lib.require_gpu(q_input, k_input, v_input, O_input, lse_input, dO_input)
-    q = q_input.to(torch.float16).contiguous()
-    k = k_input.to(torch.float16).contiguous()
-    v = v_input.to(torch.bfloat16).contiguous()
-    O = O_input.to(torch.float32).contiguous()
-    dO = dO_input.to(torch.float32).contiguous()
-    lse = lse_input.to(torch.float32).contiguous()
+    _lib.refuse_empty_keys("qattn bf16 backward", q_input.numel() // q_input.shape[3], k_input.shape[2])
+    q = _lib.kernel_input(q_input, torch.float16)
+    k = _lib.kernel_input(k_input, torch.float16)
+    v = _lib.kernel_input(v_input, torch.bfloat16)
+    O = _lib.kernel_input(O_input, torch.float32)
+    dO = _lib.kernel_input(dO_input, torch.float32)
+    lse = _lib.kernel_input(lse_input, torch.float32)
     B, H, S, D = q.shape
     Sk = k.shape[2]
     dev = q.device
+    if B * H * S == 0:   # no query rows: dq is empty, dk and dv are zero
+        z = dict(dtype=torch.float32, device=dev)
+        return torch.zeros(q.shape, **z), torch.zeros(k.shape, **z), torch.zeros(k.shape, **z)
     st = _lib.stream_of(q)
     dO_bf = torch.empty((B, H, S, D), dtype=torch.bfloat16, device=dev)
     LD = torch.empty((B * H, S, 2), dtype=torch.float32, device=dev)

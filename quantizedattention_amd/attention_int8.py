@@ -74,9 +74,10 @@ def _int8_forward(q, k, v, smooth: bool, images: bool = False, causal: bool = Fa
     """
     _check_shapes(q, k, v)
     _lib.require_gpu(q, k, v)
-    q = q.to(torch.float16).contiguous()
-    k = k.to(torch.float16).contiguous()
-    v = v.to(torch.float16).contiguous()
+    _lib.refuse_empty_keys("qattn int8", q.numel() // q.shape[3], k.shape[2])
+    q = _lib.kernel_input(q, torch.float16)
+    k = _lib.kernel_input(k, torch.float16)
+    v = _lib.kernel_input(v, torch.float16)
     B, H, S, D = q.shape
     Hkv, Sk = k.shape[1], k.shape[2]
     N = B * H * S
@@ -114,10 +115,12 @@ def _int8_forward(q, k, v, smooth: bool, images: bool = False, causal: bool = Fa
         _lib.call("qattn_int8_quant_img", _lib.ptr(k), _lib.ptr(k_i8), _lib.ptr(sk), None, _lib.ptr(k_bf),
                   None, Nkv, Sk, D, st)
     _lib.call("qattn_int8_quant_vt", _lib.ptr(v), _lib.ptr(v_i8), _lib.ptr(sv), _lib.ptr(vt), Nkv, D, st)
-    # q is quantised inside the attention kernel (q_i8, sq and the bf16 image written there)
-    _lib.call("qattn_int8_attn_fwd_qf", _lib.ptr(q), _lib.ptr(q_i8), _lib.ptr(sq), _lib.ptr(q_bf),
-              _lib.ptr(k_i8), _lib.ptr(sk), _lib.ptr(vt), _lib.ptr(sv), _lib.ptr(O), _lib.ptr(lse),
-              B * H, S, Sk, H // Hkv, int(bool(causal)), D, qks, st)
+    # q is quantised inside the attention kernel (q_i8, sq and the bf16 image written there); without
+    # query rows (B, Hq or Sq of 0) there is nothing to launch and the outputs are empty
+    if N:
+        _lib.call("qattn_int8_attn_fwd_qf", _lib.ptr(q), _lib.ptr(q_i8), _lib.ptr(sq), _lib.ptr(q_bf),
+                  _lib.ptr(k_i8), _lib.ptr(sk), _lib.ptr(vt), _lib.ptr(sv), _lib.ptr(O), _lib.ptr(lse),
+                  B * H, S, Sk, H // Hkv, int(bool(causal)), D, qks, st)
     # k_i8T is returned as the [D, N] view of the row-major [N, D] tensor (same values/shape as
     # int8:165, zero-copy).
     return O, lse, q_i8, k_i8.t(), v_i8, sq, sk, sv, k_mean, q_bf, k_bf
@@ -148,14 +151,15 @@ def _int8_backward(dO, q_i8, sq, k_i8T, sk, v_i8, sv, O, lse, q_bf=None, k_bf=No
     kv_len: key/value tokens, needed only to shape the (empty) gradients of an empty batch.
     ws_poison: a byte to fill the dS workspace with before the launch (protocol checks: every record
     the dQ pass reads must have been written by the dK+dV pass, so results cannot depend on it)."""
-    O = O.to(torch.float16).contiguous()
-    dO = dO.to(torch.float16).contiguous()
     _lib.require_gpu(dO, O, q_i8)
     B, H, S, D = O.shape
     Hkv = H if kv_heads is None else int(kv_heads)
     Nkv = k_i8T.shape[1]
-    if B * H * S == 0 or Nkv == 0:
-        # nothing attends: zero gradients (an empty batch gives empty ones)
+    _lib.refuse_empty_keys("qattn int8 backward", B * H * S, Nkv)
+    O = _lib.kernel_input(O, torch.float16)
+    dO = _lib.kernel_input(dO, torch.float16)
+    if B * H * S == 0:
+        # no query rows: dq is empty, dk and dv are zero
         Sk = Nkv // (B * Hkv) if B * Hkv else int(kv_len if kv_len is not None else S)
         z = dict(dtype=torch.float16, device=O.device)
         return (torch.zeros((B, H, S, D), **z), torch.zeros((B, Hkv, Sk, D), **z),
@@ -166,29 +170,33 @@ def _int8_backward(dO, q_i8, sq, k_i8T, sk, v_i8, sv, O, lse, q_bf=None, k_bf=No
     N = B * H * S
     dev = O.device
     st = _lib.stream_of(O)
-    k_i8 = k_i8T.t().contiguous()  # [N, D] (a no-op for the view our forward returns)
-    q_i8 = q_i8.contiguous()
-    v_i8 = v_i8.contiguous()
+    k_i8 = _lib.kernel_input(k_i8T.t())  # [N, D] (a no-op for the view our forward returns)
+    q_i8 = _lib.kernel_input(q_i8)
+    v_i8 = _lib.kernel_input(v_i8)
     dO_i8 = torch.empty((N, D), dtype=torch.int8, device=dev)
     sdO = torch.empty((N // BQ,), dtype=torch.float16, device=dev)
     LD = torch.empty((N, 2), dtype=torch.float32, device=dev)  # {lse, D} per row
     dO_bf = torch.empty((N, D), dtype=torch.bfloat16, device=dev)
-    lse = lse.to(torch.float16).contiguous()
+    lse = _lib.kernel_input(lse, torch.float16)
     _lib.call("qattn_int8_bwd_prep", _lib.ptr(dO), _lib.ptr(O), _lib.ptr(lse), _lib.ptr(dO_i8),
               _lib.ptr(sdO), _lib.ptr(LD), _lib.ptr(dO_bf), B * H, S, D, st)
     # exact bf16 images of the int8 operands read column-wise by the accumulating products
     if q_bf is None:
         q_bf = torch.empty((N, D), dtype=torch.bfloat16, device=dev)
         _lib.call("qattn_i8_to_bf16", _lib.ptr(q_i8), _lib.ptr(q_bf), N * D, st)
+    else:
+        q_bf = _lib.kernel_input(q_bf, torch.bfloat16)
     if k_bf is None:
         k_bf = torch.empty((Nkv, D), dtype=torch.bfloat16, device=dev)
         _lib.call("qattn_i8_to_bf16", _lib.ptr(k_i8), _lib.ptr(k_bf), Nkv * D, st)
+    else:
+        k_bf = _lib.kernel_input(k_bf, torch.bfloat16)
     dq = torch.empty((B, H, S, D), dtype=torch.float16, device=dev)
     dk = torch.empty((B, Hkv, Sk, D), dtype=torch.float16, device=dev)
     dv = torch.empty((B, Hkv, Sk, D), dtype=torch.float16, device=dev)
     qks, sms = _lib.qk_scale(D), _lib.sm_scale(D)
     # (contiguous copies bound to names: they must outlive the launches that read them)
-    sq, sk, sv = sq.contiguous(), sk.contiguous(), sv.contiguous()
+    sq, sk, sv = _lib.kernel_input(sq), _lib.kernel_input(sk), _lib.kernel_input(sv)
     common = (_lib.ptr(dO_i8), _lib.ptr(sdO), _lib.ptr(q_i8), _lib.ptr(sq), _lib.ptr(k_i8),
               _lib.ptr(sk), _lib.ptr(v_i8), _lib.ptr(sv), _lib.ptr(LD),
               _lib.ptr(q_bf), _lib.ptr(k_bf), _lib.ptr(dO_bf), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv))
@@ -198,8 +206,9 @@ def _int8_backward(dO, q_i8, sq, k_i8T, sk, v_i8, sv, O, lse, q_bf=None, k_bf=No
         ws_bytes, chunk = _lib.int8_bwd_plan(B * Hkv, H // Hkv, S, Sk, causal, ws_chunk,
                                              _lib.UNBOUNDED if use_ws else WS_MAX_BYTES)
         if use_ws and ws_bytes == 0:
-            raise _lib.QAttnError("qattn int8 backward: dS workspace region exceeds 2 GiB per key/value "
-                                  "head; use the recomputing backward (use_ws=False)")
+            raise _lib.QAttnError("qattn int8 backward: the dS records of a key/value head exceed what "
+                                  "the record kernels address (2 GiB, or their per-tile LDS tables: "
+                                  "include/qattn.h); use the recomputing backward (use_ws=False)")
         if ws_bytes > 0:
             # (None when there is no room: recompute dS in the dQ pass, same results)
             ws = _lib.try_workspace(ws_bytes, dev)

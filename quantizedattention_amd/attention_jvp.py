@@ -64,6 +64,7 @@ def _jvp(q_fp32_input, k_fp32_input, v_fp32_input, tangents, out_O=None):
         if t.shape != ref.shape:
             raise _lib.QAttnError("qattn jvp: tangents must have the primals' shapes")
     B, H, S, D = q_fp32_input.shape
+    _lib.refuse_empty_keys("qattn jvp", B * H * S, k_tokens)
     # grouped-query attention (SURVEY §8f N2 extension): k, v may have fewer heads than q
     Hkv = k_head
     if k_batch != batch or v_batch != batch or v_head != Hkv or H % Hkv != 0:
@@ -77,6 +78,8 @@ def _jvp(q_fp32_input, k_fp32_input, v_fp32_input, tangents, out_O=None):
     LAUNCHES["primal" if tangents is None else "tangent"] += 1
     tO = torch.empty_like(O) if tangents is not None else None
     lse = torch.empty((B * H, S), dtype=torch.float32, device=dev)
+    if B * H * S == 0:   # no query rows: nothing to launch, empty outputs
+        return O, tO, lse
     qks, sm = _lib.qk_scale(D), _lib.sm_scale(D)
     st = _lib.stream_of(q_fp32_input)
     shape = (B * H, S, k_tokens, group, D, qks, sm, st)
@@ -86,7 +89,7 @@ def _jvp(q_fp32_input, k_fp32_input, v_fp32_input, tangents, out_O=None):
         # keep the contiguous copies alive through the launch: a copy freed as soon as its address
         # is taken hands its block to the next input's copy (the caching allocator), and the
         # kernel would read the wrong tensor
-        xs = [t.contiguous() for t in ins]
+        xs = [_lib.kernel_input(t) for t in ins]
         ptrs = [_lib.ptr(t) for t in xs]
         if tangents is None:
             _lib.call("qattn_jvp_primal_ex", *ptrs, _lib.ptr(O), _lib.ptr(lse), *shape)
@@ -95,7 +98,7 @@ def _jvp(q_fp32_input, k_fp32_input, v_fp32_input, tangents, out_O=None):
         return O, tO, lse
     imgs = []
     for t in ins:
-        x = t.to(torch.float32).contiguous()
+        x = _lib.kernel_input(t, torch.float32)
         hi = torch.empty(x.shape, dtype=torch.bfloat16, device=dev)
         lo = torch.empty_like(hi)
         _lib.call("qattn_split_bf16", _lib.ptr(x), _lib.ptr(hi), _lib.ptr(lo), x.numel(), st)

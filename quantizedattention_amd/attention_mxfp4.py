@@ -41,11 +41,11 @@ def mxfp4_quantize_rows(x: torch.Tensor, mean: torch.Tensor | None = None):
     D = x.shape[-1]
     if D not in (64, 128):
         raise _lib.QAttnError("qattn mxfp4: head_dim must be 64 or 128")
-    x = x.to(torch.float16).contiguous()
+    x = _lib.kernel_input(x, torch.float16)
     rows = x.numel() // D
     seq = x.shape[-2] if x.dim() >= 2 else rows
     if mean is not None:
-        mean = mean.to(torch.float16).contiguous()
+        mean = _lib.kernel_input(mean, torch.float16)
         if mean.numel() * seq != x.numel():
             raise _lib.QAttnError("qattn mxfp4: mean must hold one row per sequence")
     q4 = torch.empty((rows, D // 2), dtype=torch.uint8, device=x.device)
@@ -63,7 +63,7 @@ def mxfp4_quantize_v(v: torch.Tensor):
         raise _lib.QAttnError("qattn mxfp4: key tokens must be a multiple of 64")
     if D not in (64, 128):
         raise _lib.QAttnError("qattn mxfp4: head_dim must be 64 or 128")
-    v = v.to(torch.float16).contiguous()
+    v = _lib.kernel_input(v, torch.float16)
     vt = torch.empty((B * H, S // 64, D, 32), dtype=torch.uint8, device=v.device)
     vs = torch.empty((B * H, S // 64, D, 2), dtype=torch.uint8, device=v.device)
     _lib.call("qattn_mxfp4_quant_vt", _lib.ptr(v), _lib.ptr(vt), _lib.ptr(vs), B * H, S, D,
@@ -94,9 +94,10 @@ def _causal_mode(causal, Sq: int, Sk: int) -> int:
 def _attn(q4, qs, k4, ks, vt, vs, B, H, Hkv, Sq, Sk, D, mode, like):
     out = torch.empty((B, H, Sq, D), dtype=torch.float16, device=like.device)
     lse = torch.empty((B * H, Sq), dtype=torch.float32, device=like.device)
-    _lib.call("qattn_mxfp4_attn_fwd_ex", _lib.ptr(q4), _lib.ptr(qs), _lib.ptr(k4), _lib.ptr(ks),
-              _lib.ptr(vt), _lib.ptr(vs), _lib.ptr(out), _lib.ptr(lse), B * H, Sq, Sk, H // Hkv, mode, D,
-              _qk_scale(D), _lib.stream_of(like))
+    if B * H * Sq:   # (without query rows there is nothing to launch: empty outputs)
+        _lib.call("qattn_mxfp4_attn_fwd_ex", _lib.ptr(q4), _lib.ptr(qs), _lib.ptr(k4), _lib.ptr(ks),
+                  _lib.ptr(vt), _lib.ptr(vs), _lib.ptr(out), _lib.ptr(lse), B * H, Sq, Sk, H // Hkv, mode, D,
+                  _qk_scale(D), _lib.stream_of(like))
     return out, lse
 
 
@@ -114,7 +115,8 @@ def mxfp4_attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, smooth_k: 
     B, H, Sq, D = q.shape
     Hkv, Sk = k.shape[1], k.shape[2]
     mode = _causal_mode(causal, Sq, Sk)
-    k = k.to(torch.float16).contiguous()
+    _lib.refuse_empty_keys("qattn mxfp4", B * H * Sq, Sk)
+    k = _lib.kernel_input(k, torch.float16)
     k_mean = None
     if smooth_k:   # f16 token mean per (batch, head), subtracted inside the quantiser
         k_mean = torch.empty((B, Hkv, 1, D), dtype=torch.float16, device=q.device)
@@ -157,6 +159,7 @@ def mxfp4_attn_fwd_kv(q: torch.Tensor, kv, causal=False):
     if any(t.dtype != torch.uint8 or not t.is_contiguous() for t in (k4, ks, vt, vs)):
         raise _lib.QAttnError("qattn mxfp4: the quantised operands must be contiguous uint8")
     mode = _causal_mode(causal, Sq, Sk)
+    _lib.refuse_empty_keys("qattn mxfp4", B * H * Sq, Sk)
     q4, qs = mxfp4_quantize_rows(q)
     return _attn(q4, qs, k4, ks, vt, vs, B, H, Hkv, Sq, Sk, D, mode, q)
 

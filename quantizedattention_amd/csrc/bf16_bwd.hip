@@ -807,7 +807,8 @@ static int bf16_bwd_entry(const void* q, const void* k, const void* v, const voi
   if (sq % 32 != 0 || sk % 32 != 0 || group < 1 || bh % group != 0 ||
       (head_dim != 64 && head_dim != 128))
     return 1;
-  if (bh == 0 || sq == 0 || sk == 0) return 0;
+  if (bh == 0 || sq == 0) return 0;
+  if (sk == 0) return 1;   // every query keeps a key
   hipStream_t st = (hipStream_t)stream;
   if (head_dim == 128)
     bf16_bwd_d<128>(q, k, v, dO_bf, LD, q_bf, k_bf, dq, dk, dv, bh, sq, sk, group, causal, qks, sms,

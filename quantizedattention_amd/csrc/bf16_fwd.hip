@@ -441,6 +441,7 @@ extern "C" int qattn_bf16_fwd_ws_ex(const void* q, const void* k, const void* v,
       (head_dim != 64 && head_dim != 128))
     return 1;
   if (bh == 0 || sq == 0) return 0;
+  if (sk == 0) return 1;   // every query keeps a key
   if (ws != nullptr && (reinterpret_cast<uintptr_t>(ws) & 15) != 0) return 1;
   hipStream_t st = (hipStream_t)stream;
   const int nt = (int)(sk / 32);

@@ -1165,7 +1165,8 @@ static int int8_bwd_launch(int which, const BwdArgs& a) {
   if (a.sqt % 32 != 0 || a.skt % 32 != 0 || a.group < 1 || a.bh % a.group != 0 ||
       (a.head_dim != 64 && a.head_dim != 128))
     return 1;
-  if (a.bh == 0 || a.sqt == 0 || a.skt == 0) return 0;
+  if (a.bh == 0 || a.sqt == 0) return 0;
+  if (a.skt == 0) return 1;   // every query keeps a key
   if (a.head_dim == 128) bwd_launch_d<128>(which, a);
   else bwd_launch_d<64>(which, a);
   return hipGetLastError() == hipSuccess ? 0 : 2;
@@ -1222,8 +1223,17 @@ extern "C" int qattn_int8_bwd_dq(const void* dO_i8, const void* sdO, const void*
 }
 
 // (plan.hip, with the size and cap functions of the dS workspace: the records of one key/value head
-// must stay below 2^31 bytes)
+// must stay below 2^31 bytes, and the per-tile LDS tables of launch_bwd_c<WS> and launch_dqw_c must
+// fit beside the tile rings in the 160 KiB of a workgroup)
 namespace qattn { bool ws_region_fits(long group, long sq_tok, long sk_tok); }
+static_assert(BwdCfg<128, ROLE_DKV>::NSLOT * BwdCfg<128, ROLE_DKV>::SLOT + 16 +
+                      QATTN_WS_MAX_QUERY_TILES * (4 + 4 * BwdCfg<128, ROLE_DKV>::WAVES) <= 160 * 1024 &&
+                  BwdCfg<64, ROLE_DKV>::SLOT <= BwdCfg<128, ROLE_DKV>::SLOT,
+              "QATTN_WS_MAX_QUERY_TILES: the record dK+dV kernel's LDS");
+static_assert(DqwCfg<128>::RBASE + DqwCfg<128>::RSLOT * DqwCfg<128>::REC + 16 +
+                      QATTN_WS_MAX_KEY_TILES * 4 * DqwCfg<128>::WAVES <= 160 * 1024 &&
+                  DqwCfg<64>::RBASE <= DqwCfg<128>::RBASE,
+              "QATTN_WS_MAX_KEY_TILES: the record dQ kernel's LDS");
 
 extern "C" int qattn_int8_attn_bwd_ws(const void* dO_i8, const void* sdO, const void* q_i8,
                                       const void* sq, const void* k_i8, const void* sk,
@@ -1257,6 +1267,7 @@ extern "C" int qattn_int8_attn_bwd_wsc(const void* dO_i8, const void* sdO, const
   if (ws == nullptr || group < 1 || kv_chunk < 1 || !ws_region_fits(group, sq_tok, sk_tok)) return 1;
   if (sq_tok % 32 != 0 || sk_tok % 32 != 0 || bh % group != 0 || (head_dim != 64 && head_dim != 128))
     return 1;
+  if (bh != 0 && sq_tok != 0 && sk_tok == 0) return 1;   // every query keeps a key
   const long bkv = bh / group, D = head_dim;
   auto at = [](const void* p, long bytes) { return (void*)((const char*)p + bytes); };
   for (long k0 = 0; k0 < bkv; k0 += kv_chunk) {

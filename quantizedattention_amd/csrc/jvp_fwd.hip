@@ -324,6 +324,7 @@ extern "C" int qattn_jvp_fwd_ex(const void* q, const void* k, const void* v, con
       (head_dim != 64 && head_dim != 128))
     return 1;
   if (bh == 0 || sq == 0) return 0;
+  if (sk == 0) return 1;   // every query keeps a key
   const void* img[6] = {q, k, v, tq, tk, tv};
   const JvpArgs a = jvp_args(img, out, tout, lse, bh, sq, sk, group, qks, sm, 1);
   hipStream_t st = (hipStream_t)stream;
@@ -347,6 +348,7 @@ extern "C" int qattn_jvp_fwd_x3_ex(const void* q_hi, const void* q_lo, const voi
       (head_dim != 64 && head_dim != 128))
     return 1;
   if (bh == 0 || sq == 0) return 0;
+  if (sk == 0) return 1;   // every query keeps a key
   const void* img[12] = {q_hi, q_lo, k_hi, k_lo, v_hi, v_lo, tq_hi, tq_lo, tk_hi, tk_lo, tv_hi, tv_lo};
   const JvpArgs a = jvp_args(img, out, tout, lse, bh, sq, sk, group, qks, sm, 2);
   hipStream_t st = (hipStream_t)stream;
@@ -371,6 +373,7 @@ extern "C" int qattn_jvp_primal_ex(const void* q, const void* k, const void* v, 
       (head_dim != 64 && head_dim != 128))
     return 1;
   if (bh == 0 || sq == 0) return 0;
+  if (sk == 0) return 1;   // every query keeps a key
   const void* img[6] = {q, k, v, q, k, v};
   const JvpArgs a = jvp_args(img, out, out, lse, bh, sq, sk, group, qks, sm, 1);
   hipStream_t st = (hipStream_t)stream;
@@ -386,6 +389,7 @@ extern "C" int qattn_jvp_primal_x3_ex(const void* q_hi, const void* q_lo, const 
       (head_dim != 64 && head_dim != 128))
     return 1;
   if (bh == 0 || sq == 0) return 0;
+  if (sk == 0) return 1;   // every query keeps a key
   const void* img[12] = {q_hi, q_lo, k_hi, k_lo, v_hi, v_lo, q_hi, q_lo, k_hi, k_lo, v_hi, v_lo};
   const JvpArgs a = jvp_args(img, out, out, lse, bh, sq, sk, group, qks, sm, 2);
   hipStream_t st = (hipStream_t)stream;

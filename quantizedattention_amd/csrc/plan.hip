@@ -14,9 +14,15 @@
 namespace qattn {
 
 // The dK+dV kernel addresses the records of one key/value head (its G query heads) with 32-bit
-// buffer offsets: that region, G * (sq/32) * (sk/32) KiB, must stay below 2^31 bytes.
+// buffer offsets: that region, G * (sq/32) * (sk/32) KiB, must stay below 2^31 bytes.  Both record
+// kernels also keep per-tile tables in LDS beside their tile rings (int8_bwd.hip, launch_bwd_c and
+// launch_dqw_c): dK+dV 36 bytes per streamed query tile of the key/value head (its scales and one dS
+// scale per wave), dQ 32 bytes per key tile.  Past QATTN_WS_MAX_QUERY_TILES = G * sq/32 or QATTN_WS_MAX_KEY_TILES =
+// sk/32 the 160 KiB of a workgroup do not hold them and the launch would be refused, so such shapes
+// recompute (int8_bwd.hip asserts both constants against its configurations).
 bool ws_region_fits(long group, long sq_tok, long sk_tok) {
-  return group * (sq_tok / 32) * (sk_tok / 32) * 1024 < (1L << 31);
+  return group * (sq_tok / 32) <= QATTN_WS_MAX_QUERY_TILES && sk_tok / 32 <= QATTN_WS_MAX_KEY_TILES &&
+         group * (sq_tok / 32) * (sk_tok / 32) * 1024 < (1L << 31);
 }
 
 }  // namespace qattn

@@ -38,7 +38,9 @@
 
 #include <c10/hip/HIPCachingAllocator.h>
 
+#include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <map>
 #include <mutex>
 #include <string>
@@ -51,7 +53,31 @@ namespace {
 using at::Tensor;
 using T3 = std::tuple<Tensor, Tensor, Tensor>;
 
-void* P(const Tensor& t) { return t.defined() ? t.data_ptr() : nullptr; }
+// The address of a kernel argument: the kernels read 16-byte vectors and LDS-DMA dwordx4 from every
+// base address, so one that is no multiple of 16 never reaches them (_lib.ptr)
+void* P(const Tensor& t) {
+  if (!t.defined()) return nullptr;
+  void* p = t.data_ptr();
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(p) % 16 == 0, "qattn: a tensor at an address that is not a "
+              "multiple of 16 (storage offset ", t.storage_offset(), ")");
+  return p;
+}
+
+// A tensor in the form a kernel reads (_lib.kernel_input): dtype dt, contiguous, at a 16-byte aligned
+// address; a contiguous view at a misaligned storage offset is copied
+Tensor kin(const Tensor& t, at::ScalarType dt) {
+  Tensor x = t.to(dt).contiguous();
+  if (reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 != 0) x = x.clone(at::MemoryFormat::Contiguous);
+  return x;
+}
+Tensor kin(const Tensor& t) { return kin(t, t.scalar_type()); }
+
+// Every query keeps a key: Sk = 0 with rows > 0 is refused on every path, before anything is allocated
+// (status 1 of the C entries, include/qattn.h)
+void refuse_empty_keys(const char* what, int64_t rows, int64_t sk) {
+  TORCH_CHECK(!(rows > 0 && sk == 0), "qattn ", what, ": an empty key sequence (Sk = 0) with ", rows,
+              " query rows; every query keeps a key");
+}
 
 struct Ctx {   // device guard + the current stream of the inputs' device
   c10::hip::HIPGuardMasqueradingAsCUDA guard;
@@ -120,7 +146,7 @@ std::tuple<Tensor, Tensor> int8_quant(const Tensor& x, int64_t block) {
               "qattn::int8_quant needs x [..., S, D] with S % 32 == 0 and D in (64, 128)");
   require_gpu({&x});
   Ctx c(x);
-  const Tensor xh = x.to(at::kHalf).contiguous();
+  const Tensor xh = kin(x, at::kHalf);
   const int64_t D = x.size(-1), rows = xh.numel() / D, S = x.size(-2);
   Tensor idx = empty(xh.sizes(), at::kChar, xh);
   std::vector<int64_t> ss(xh.sizes().begin(), xh.sizes().end() - 2);
@@ -149,9 +175,9 @@ using T8 = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Te
 T8 int8_fwd(const Tensor& q_in, const Tensor& k_in, const Tensor& v_in, bool smooth, bool causal) {
   check_int8(q_in, k_in, v_in);
   require_gpu({&q_in, &k_in, &v_in});
+  refuse_empty_keys("int8", q_in.size(0) * q_in.size(1) * q_in.size(2), k_in.size(2));
   Ctx c(q_in);
-  const Tensor q = q_in.to(at::kHalf).contiguous(), k = k_in.to(at::kHalf).contiguous(),
-               v = v_in.to(at::kHalf).contiguous();
+  const Tensor q = kin(q_in, at::kHalf), k = kin(k_in, at::kHalf), v = kin(v_in, at::kHalf);
   const int64_t B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
   const int64_t Hkv = k.size(1), Sk = k.size(2), N = B * H * S, Nkv = B * Hkv * Sk;
   Tensor q_i8 = empty({N, D}, at::kChar, q), k_i8 = empty({Nkv, D}, at::kChar, q),
@@ -161,11 +187,6 @@ T8 int8_fwd(const Tensor& q_in, const Tensor& k_in, const Tensor& v_in, bool smo
   Tensor vt = empty({Nkv, D}, at::kChar, q);   // the int8 V^T operand image
   Tensor O = empty({B, H, S, D}, at::kHalf, q), lse = empty({N}, at::kHalf, q);
   Tensor k_mean;
-  if (N == 0 || Nkv == 0) {   // an empty problem: nothing to read, zero outputs
-    O.zero_();
-    lse.zero_();
-    return {O, lse, q_i8, k_i8, v_i8, sq, sk, sv};
-  }
   if (smooth) {
     k_mean = empty({B, Hkv, 1, D}, at::kHalf, q);
     call(qattn_kmean(P(k), P(k_mean), B * Hkv, Sk, (int)D, c.stream), "kmean");
@@ -175,6 +196,7 @@ T8 int8_fwd(const Tensor& q_in, const Tensor& k_in, const Tensor& v_in, bool smo
   call(qattn_int8_quant(P(k), P(k_i8), P(sk), nullptr, P(k_mean), Nkv, (int)Sk, (int)D, c.stream),
        "quantise k");
   call(qattn_int8_quant_vt(P(v), P(v_i8), P(sv), P(vt), Nkv, (int)D, c.stream), "quantise v");
+  if (N == 0) return {O, lse, q_i8, k_i8, v_i8, sq, sk, sv};   // no query rows: empty O, lse, q_i8, sq
   call(qattn_int8_attn_fwd_qf(P(q), P(q_i8), P(sq), nullptr, P(k_i8), P(sk), P(vt), P(sv), P(O), P(lse),
                               B * H, S, Sk, (int)(H / Hkv), causal ? 1 : 0, (int)D, qks, c.stream),
        "int8 forward");
@@ -188,11 +210,12 @@ T3 int8_bwd(const Tensor& dO_in, const Tensor& q_i8_in, const Tensor& sq, const 
             const Tensor& lse_in, bool causal, int64_t kv_heads) {
   require_gpu({&dO_in, &q_i8_in, &O_in});
   TORCH_CHECK(O_in.dim() == 4, "qattn int8 backward: O must be [B, H, S, D]");
+  refuse_empty_keys("int8 backward", O_in.numel() / std::max<int64_t>(O_in.size(3), 1), k_i8_in.size(0));
   Ctx c(O_in);
-  const Tensor O = O_in.to(at::kHalf).contiguous(), dO = dO_in.to(at::kHalf).contiguous();
+  const Tensor O = kin(O_in, at::kHalf), dO = kin(dO_in, at::kHalf);
   const int64_t B = O.size(0), H = O.size(1), S = O.size(2), D = O.size(3), Hkv = kv_heads;
   const int64_t Nkv = k_i8_in.size(0);
-  if (B * H * S == 0 || Nkv == 0) {   // nothing attends: zero gradients
+  if (B * H * S == 0) {   // no query rows: dq is empty, dk and dv are zero
     TORCH_CHECK(Hkv > 0, "qattn int8 backward: inconsistent key/value heads");
     const int64_t Sk0 = B * Hkv ? Nkv / (B * Hkv) : 0;
     auto z = O_in.options().dtype(at::kHalf);
@@ -201,9 +224,9 @@ T3 int8_bwd(const Tensor& dO_in, const Tensor& q_i8_in, const Tensor& sq, const 
   TORCH_CHECK(Hkv > 0 && H % Hkv == 0 && Nkv % (B * Hkv) == 0,
               "qattn int8 backward: inconsistent key/value heads");
   const int64_t Sk = Nkv / (B * Hkv), N = B * H * S, G = H / Hkv;
-  const Tensor q_i8 = q_i8_in.contiguous(), k_i8 = k_i8_in.contiguous(), v_i8 = v_i8_in.contiguous();
-  const Tensor sqc = sq.contiguous(), skc = sk.contiguous(), svc = sv.contiguous();
-  const Tensor lse = lse_in.to(at::kHalf).contiguous();
+  const Tensor q_i8 = kin(q_i8_in), k_i8 = kin(k_i8_in), v_i8 = kin(v_i8_in);
+  const Tensor sqc = kin(sq), skc = kin(sk), svc = kin(sv);
+  const Tensor lse = kin(lse_in, at::kHalf);
   Tensor dO_i8 = empty({N, D}, at::kChar, O), sdO = empty({N / 32}, at::kHalf, O);
   Tensor LD = empty({N, 2}, at::kFloat, O), dO_bf = empty({N, D}, at::kBFloat16, O);
   call(qattn_int8_bwd_prep(P(dO), P(O), P(lse), P(dO_i8), P(sdO), P(LD), P(dO_bf), B * H, S, (int)D,
@@ -250,12 +273,12 @@ std::tuple<Tensor, Tensor> bf16_fwd(const Tensor& q_in, const Tensor& k_in, cons
                                     bool causal) {
   check_bf16(q_in, k_in, v_in);
   require_gpu({&q_in, &k_in, &v_in});
+  refuse_empty_keys("bf16", q_in.size(0) * q_in.size(1) * q_in.size(2), k_in.size(2));
   Ctx c(q_in);
-  const Tensor q = q_in.to(at::kHalf).contiguous(), k = k_in.to(at::kHalf).contiguous(),
-               v = v_in.to(at::kBFloat16).contiguous();
+  const Tensor q = kin(q_in, at::kHalf), k = kin(k_in, at::kHalf), v = kin(v_in, at::kBFloat16);
   const int64_t B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3), Sk = k.size(2);
   Tensor O = empty({B, H, S, D}, at::kFloat, q), lse = empty({B * H, S}, at::kFloat, q);
-  if (O.numel() == 0 || k.numel() == 0) return {O.zero_(), lse.zero_()};
+  if (O.numel() == 0) return {O, lse};   // no query rows: empty outputs
   // causal: the per-head V suffix sums stand in for the fully masked key tiles (include/qattn.h);
   // without room for them the kernel runs the whole masked tile loop (same results)
   Tensor ws;
@@ -271,13 +294,13 @@ T3 bf16_bwd(const Tensor& q_in, const Tensor& k_in, const Tensor& v_in, const Te
             const Tensor& lse_in, bool causal, const Tensor& dO_in) {
   check_bf16(q_in, k_in, v_in);
   require_gpu({&q_in, &k_in, &v_in, &O_in, &lse_in, &dO_in});
+  refuse_empty_keys("bf16 backward", q_in.size(0) * q_in.size(1) * q_in.size(2), k_in.size(2));
   Ctx c(q_in);
-  const Tensor q = q_in.to(at::kHalf).contiguous(), k = k_in.to(at::kHalf).contiguous(),
-               v = v_in.to(at::kBFloat16).contiguous(), O = O_in.to(at::kFloat).contiguous(),
-               dO = dO_in.to(at::kFloat).contiguous(), lse = lse_in.to(at::kFloat).contiguous();
+  const Tensor q = kin(q_in, at::kHalf), k = kin(k_in, at::kHalf), v = kin(v_in, at::kBFloat16),
+               O = kin(O_in, at::kFloat), dO = kin(dO_in, at::kFloat), lse = kin(lse_in, at::kFloat);
   const int64_t B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
   const int64_t Hkv = k.size(1), Sk = k.size(2);
-  if (q.numel() == 0 || k.numel() == 0) {   // nothing attends: zero gradients
+  if (q.numel() == 0) {   // no query rows: dq is empty, dk and dv are zero
     auto z = q.options().dtype(at::kFloat);
     return {at::zeros(q.sizes(), z), at::zeros(k.sizes(), z), at::zeros(v.sizes(), z)};
   }
@@ -322,10 +345,11 @@ T3 jvp_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& tq, 
   const int64_t Sk = k.size(2);
   TORCH_CHECK(k.size(0) == B && v.size(0) == B && v.size(1) == Hkv && H % Hkv == 0,
               "qattn jvp: k and v need q's batch and a head count dividing q's");
+  refuse_empty_keys("jvp", B * H * S, Sk);
   Ctx c(q);
   Tensor O = empty({B, H, S, D}, at::kFloat, q), tO = empty({B, H, S, D}, at::kFloat, q),
          lse = empty({B * H, S}, at::kFloat, q);
-  if (O.numel() == 0 || k.numel() == 0) return {O.zero_(), tO.zero_(), lse.zero_()};
+  if (O.numel() == 0) return {O, tO, lse};   // no query rows: empty outputs
   const float qks = qk_scale(D), sm = sm_scale(D);
   const int G = (int)(H / Hkv);
   const Tensor* ins[6] = {&q, &k, &v, &tq, &tk, &tv};
@@ -334,7 +358,7 @@ T3 jvp_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& tq, 
   if (all_bf16) {
     TORCH_CHECK(Sk % 64 == 0, "qattn jvp: k tokens must be a multiple of 64 for bf16 inputs");
     Tensor x[6];
-    for (int i = 0; i < 6; ++i) x[i] = ins[i]->contiguous();
+    for (int i = 0; i < 6; ++i) x[i] = kin(*ins[i]);
     call(qattn_jvp_fwd_ex(P(x[0]), P(x[1]), P(x[2]), P(x[3]), P(x[4]), P(x[5]), P(O), P(tO), P(lse), B * H,
                           S, Sk, G, (int)D, qks, sm, c.stream),
          "jvp forward");
@@ -342,7 +366,7 @@ T3 jvp_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& tq, 
   }
   Tensor hi[6], lo[6];
   for (int i = 0; i < 6; ++i) {
-    const Tensor x = ins[i]->to(at::kFloat).contiguous();
+    const Tensor x = kin(*ins[i], at::kFloat);
     hi[i] = empty(x.sizes(), at::kBFloat16, x);
     lo[i] = empty(x.sizes(), at::kBFloat16, x);
     call(qattn_split_bf16(P(x), P(hi[i]), P(lo[i]), x.numel(), c.stream), "split fp32");
@@ -368,12 +392,12 @@ Tensor mxfp4_fwd_ex(const Tensor& q_in, const Tensor& k_in, const Tensor& v_in, 
   TORCH_CHECK(causal >= 0 && causal <= 2, "qattn mxfp4: causal must be 0, 1 (top-left) or 2 (bottom-right)");
   TORCH_CHECK(causal != 2 || q_in.size(2) <= k_in.size(2), "qattn mxfp4: causal=2 (bottom-right) needs Sk >= Sq");
   require_gpu({&q_in, &k_in, &v_in});
+  refuse_empty_keys("mxfp4", q_in.size(0) * q_in.size(1) * q_in.size(2), k_in.size(2));
   Ctx c(q_in);
-  const Tensor q = q_in.to(at::kHalf).contiguous(), k = k_in.to(at::kHalf).contiguous(),
-               v = v_in.to(at::kHalf).contiguous();
+  const Tensor q = kin(q_in, at::kHalf), k = kin(k_in, at::kHalf), v = kin(v_in, at::kHalf);
   const int64_t B = q.size(0), H = q.size(1), Sq = q.size(2), D = q.size(3), Hkv = k.size(1),
                 Sk = k.size(2);
-  if (q.numel() == 0 || k.numel() == 0) return at::zeros({B, H, Sq, D}, q.options());
+  if (q.numel() == 0) return empty({B, H, Sq, D}, at::kHalf, q);   // no query rows: an empty output
   Tensor k_mean = empty({B, Hkv, 1, D}, at::kHalf, q);
   call(qattn_kmean(P(k), P(k_mean), B * Hkv, Sk, (int)D, c.stream), "kmean");
   Tensor q4 = empty({B * H * Sq, D / 2}, at::kByte, q), qs = empty({B * H * Sq, D / 32}, at::kByte, q);
@@ -421,7 +445,7 @@ std::tuple<Tensor, Tensor> mxfp4_cached(const Tensor& q_in, const Tensor& k4, co
   kps = std::min(kps, Sk);
   const int64_t nsplit = (Sk + kps - 1) / kps;
   Ctx c(q_in);
-  const Tensor q = q_in.to(at::kHalf).contiguous();
+  const Tensor q = kin(q_in, at::kHalf);
   Tensor q4 = empty({B * Hq * Sq, D / 2}, at::kByte, q), qs = empty({B * Hq * Sq, D / 32}, at::kByte, q);
   Tensor out = empty({B, Hq, Sq, D}, at::kHalf, q), lse = empty({B * Hq, Sq}, at::kFloat, q);
   if (out.numel() == 0) return {out, lse};
@@ -470,7 +494,7 @@ std::tuple<Tensor, Tensor> mxfp4_decode(const Tensor& q_in, const Tensor& k4, co
   kps = std::min(kps, sk_max);
   const int64_t nsplit = (sk_max + kps - 1) / kps;
   Ctx c(q_in);
-  const Tensor q = q_in.to(at::kHalf).contiguous();
+  const Tensor q = kin(q_in, at::kHalf);
   Tensor q4 = empty({B * Hq * Sq, D / 2}, at::kByte, q), qs = empty({B * Hq * Sq, D / 32}, at::kByte, q);
   Tensor out = empty({B, Hq, Sq, D}, at::kHalf, q), lse = empty({B * Hq, Sq}, at::kFloat, q);
   if (out.numel() == 0) return {out, lse};
@@ -527,7 +551,7 @@ std::tuple<Tensor, Tensor> mxfp4_decode_paged(const Tensor& q_in, const Tensor& 
   kps = std::min(kps, sk_max);
   const int64_t nsplit = (sk_max + kps - 1) / kps;
   Ctx c(q_in);
-  const Tensor q = q_in.to(at::kHalf).contiguous();
+  const Tensor q = kin(q_in, at::kHalf);
   Tensor q4 = empty({B * Hq * Sq, D / 2}, at::kByte, q), qs = empty({B * Hq * Sq, D / 32}, at::kByte, q);
   Tensor out = empty({B, Hq, Sq, D}, at::kHalf, q), lse = empty({B * Hq, Sq}, at::kFloat, q);
   if (out.numel() == 0) return {out, lse};

@@ -83,7 +83,7 @@ class QuantizedKV:
             B, H, S, D = self.shape
             _lib.require_gpu(self.v_i8)
             out = torch.empty((B * H * S, D), dtype=torch.int8, device=self.v_i8.device)
-            vi = self.v_i8.contiguous()   # (bound: it must outlive the launch)
+            vi = _lib.kernel_input(self.v_i8)   # (bound: it must outlive the launch)
             _lib.call("qattn_int8_v_image", _lib.ptr(vi), _lib.ptr(out), B * H * S, D,
                       _lib.stream_of(self.v_i8))
             self._vt = out
@@ -186,8 +186,8 @@ def quantize_kv(k: torch.Tensor, v: torch.Tensor, smooth: bool = True,
     if S % BLOCK or D not in (64, 128):
         raise _lib.QAttnError("qattn kv cache: tokens must be a multiple of 32, head_dim 64 or 128")
     _lib.require_gpu(k, v)
-    k = k.to(torch.float16).contiguous()
-    v = v.to(torch.float16).contiguous()
+    k = _lib.kernel_input(k, torch.float16)
+    v = _lib.kernel_input(v, torch.float16)
     dev, st = k.device, _lib.stream_of(k)
     N = B * H * S
     if smooth and k_mean is None:
@@ -197,7 +197,7 @@ def quantize_kv(k: torch.Tensor, v: torch.Tensor, smooth: bool = True,
     v_i8 = torch.empty((B, H, S, D), dtype=torch.int8, device=dev)
     sk = torch.empty((N // BLOCK,), dtype=torch.float16, device=dev)
     sv = torch.empty((N // BLOCK,), dtype=torch.float16, device=dev)
-    km = None if k_mean is None else k_mean.to(torch.float16).contiguous()
+    km = _lib.kernel_input(k_mean, torch.float16)
     _lib.call("qattn_int8_quant", _lib.ptr(k), _lib.ptr(k_i8), _lib.ptr(sk), None, _lib.ptr(km), N, S, D,
               st)
     # v: indices, scales and the P.V operand image in one pass, 1 B per element
@@ -223,7 +223,7 @@ def attention_int8_cached(q: torch.Tensor, kv: QuantizedKV, causal: bool = False
     if causal and q.shape[2] > Sk:
         raise _lib.QAttnError("qattn kv cache: causal attention needs Sq <= the cached tokens")
     _lib.require_gpu(q, kv.k_i8)
-    q = q.to(torch.float16).contiguous()
+    q = _lib.kernel_input(q, torch.float16)
     Hq, Sq = q.shape[1], q.shape[2]
     N = B * Hq * Sq
     dev, st = q.device, _lib.stream_of(q)

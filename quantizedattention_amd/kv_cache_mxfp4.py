@@ -195,11 +195,11 @@ def quantize_kv_fp4(k: torch.Tensor, v: torch.Tensor, smooth: bool = True,
     if S % BLOCK or D != 128:
         raise _lib.QAttnError("qattn mxfp4 kv cache: tokens must be a multiple of 64, head_dim 128")
     _lib.require_gpu(k, v)
-    k = k.to(torch.float16).contiguous()
+    k = _lib.kernel_input(k, torch.float16)
     if smooth and k_mean is None:
         k_mean = torch.empty((B, H, 1, D), dtype=torch.float16, device=k.device)
         _lib.call("qattn_kmean", _lib.ptr(k), _lib.ptr(k_mean), B * H, S, D, _lib.stream_of(k))
-    km = None if k_mean is None else k_mean.to(torch.float16).contiguous()
+    km = _lib.kernel_input(k_mean, torch.float16)
     k4, ks = mxfp4_quantize_rows(k, km)
     vt, vs = mxfp4_quantize_v(v)
     return QuantizedKVFP4(k4.view(B, H, S, D // 2), ks.view(B, H, S, D // 32), vt, vs, km)
@@ -306,7 +306,7 @@ class PreallocatedKVFP4:
         if k_mean is not None:
             if tuple(k_mean.shape) != (batch, kv_heads, 1, D):
                 raise _lib.QAttnError("qattn mxfp4 kv cache: k_mean must be [B, Hkv, 1, 128]")
-            k_mean = k_mean.to(device=dev, dtype=torch.float16).contiguous()
+            k_mean = _lib.kernel_input(k_mean.to(device=dev), torch.float16)
         z = lambda *shape, dt=torch.uint8: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
         return cls(z(batch, kv_heads, capacity, D // 2), z(batch, kv_heads, capacity, D // 32),
                    z(batch * kv_heads, capacity // BLOCK, D, 32), z(batch * kv_heads, capacity // BLOCK, D, 2),
@@ -346,8 +346,8 @@ class PreallocatedKVFP4:
             raise _lib.QAttnError(f"qattn mxfp4 kv cache: append past the capacity of {cap} tokens "
                                   f"(lengths {self.lengths}, counts {cnt})")
         _lib.require_gpu(k, v, self.k4)
-        k = k.to(torch.float16).contiguous()
-        v = v.to(torch.float16).contiguous()
+        k = _lib.kernel_input(k, torch.float16)
+        v = _lib.kernel_input(v, torch.float16)
         cdev = None if counts is None else torch.tensor(cnt, dtype=torch.int32).to(k.device, non_blocking=True)
         _lib.call("qattn_mxfp4_cache_append", _lib.ptr(k), _lib.ptr(v), _lib.ptr(self.k_mean),
                   _lib.ptr(self.k4), _lib.ptr(self.ks), _lib.ptr(self.vt), _lib.ptr(self.vs),
@@ -582,7 +582,7 @@ class PagedKVFP4:
         if k_mean is not None:
             if tuple(k_mean.shape) != (max_seqs, kv_heads, 1, D):
                 raise _lib.QAttnError("qattn mxfp4 paged cache: k_mean must be [max_seqs, Hkv, 1, 128]")
-            k_mean = k_mean.to(device=dev, dtype=torch.float16).contiguous()
+            k_mean = _lib.kernel_input(k_mean.to(device=dev), torch.float16)
         z = lambda *shape, dt=torch.uint8: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
         return cls(z(num_pages, kv_heads, page_tokens, D // 2), z(num_pages, kv_heads, page_tokens, D // 32),
                    z(num_pages, kv_heads, tpp, D, 32), z(num_pages, kv_heads, tpp, D, 2),
@@ -647,8 +647,8 @@ class PagedKVFP4:
                 raise _lib.QAttnError("qattn mxfp4 paged cache: counts must be max_seqs values in [0, n]")
         _lib.require_gpu(k, v, self.k4)
         grown = self.alloc.reserve([(b, L + c) for b, (L, c) in enumerate(zip(self.lengths, cnt)) if c])
-        k = k.to(torch.float16).contiguous()
-        v = v.to(torch.float16).contiguous()
+        k = _lib.kernel_input(k, torch.float16)
+        v = _lib.kernel_input(v, torch.float16)
         if grown:
             self.block_table.copy_(torch.tensor(self.alloc.table, dtype=torch.int32), non_blocking=True)
         cdev = None if counts is None else torch.tensor(cnt, dtype=torch.int32).to(k.device, non_blocking=True)

@@ -12,6 +12,8 @@ from oracle import restate as R
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 2, 128, 64), (1, 2, 256, 128), (2, 3, 96, 128), (1, 1, 64, 64), (1, 4, 512, 128)]
+FWD_BAR = 5e-3   # max|O - O_oracle| and max|lse - lse_oracle| at the oracle's k-tile of 16
+BWD_REL = 1e-2   # relL2 of each gradient against the corrected restatement
 
 
 def _inputs(shape, seed=0):
@@ -34,9 +36,9 @@ def test_bf16_fwd_matches_oracle(lib, shape, causal):
     torch.cuda.synchronize()
     assert O.dtype == torch.float32 and lse.shape == (shape[0] * shape[1], shape[2])
     err = (O.cpu() - O_ref).abs().max().item()
-    assert err <= 5e-3, err
+    assert err <= FWD_BAR, err
     lerr = (lse.cpu() - lse_ref).abs().max().item()
-    assert lerr <= 5e-3, lerr
+    assert lerr <= FWD_BAR, lerr
 
 
 def test_bf16_fwd_beta_rule_forced(lib):
@@ -66,7 +68,7 @@ def test_bf16_bwd_matches_oracle(lib, shape, causal):
     rq, rk, rv = R.bf16_bwd(q, k, v, O.cpu(), lse.cpu(), causal, dO)
     for name, a, b in (("dq", dq, rq), ("dk", dk, rk), ("dv", dv, rv)):
         assert a.dtype == torch.float32
-        assert _rel(a.cpu(), b) <= 1e-2, (name, _rel(a.cpu(), b))
+        assert _rel(a.cpu(), b) <= BWD_REL, (name, _rel(a.cpu(), b))
     if not causal:
         tq, tk, tv = R.attention_grads_truth(q, k, v, dO, False)
         for name, a, b in (("dq", dq, tq), ("dk", dk, tk), ("dv", dv, tv)):

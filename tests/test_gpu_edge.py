@@ -47,6 +47,208 @@ def test_empty_batch(lib):
     torch.cuda.synchronize()
 
 
+def _z(shape, dt=torch.float16):
+    return torch.zeros(shape, dtype=dt, device="cuda")
+
+
+# (q shape, k / v shape): no batch entry, no query head, no query token -- each with keys to attend to
+# wherever a key/value head exists
+EMPTY_ROWS = {"B=0": ((0, 4, 64, 128), (0, 2, 64, 128)), "Hq=0": ((1, 0, 64, 128), (1, 2, 64, 128)),
+              "Sq=0": ((1, 4, 0, 128), (1, 2, 64, 128))}
+
+
+@pytest.mark.parametrize("which", list(EMPTY_ROWS))
+def test_empty_query_rows(lib, which):
+    """B = 0, Hq = 0 and Sq = 0: every path returns empty outputs of the right shapes (and zero dk, dv
+    of k's shape where it has a backward) without launching an attention kernel."""
+    from quantizedattention_amd import ops
+    from quantizedattention_amd.attention_bf16 import flash_atten_2_bf16, helion_atten_bf16_fwd_training
+    from quantizedattention_amd.attention_int8 import helion_atten_int8_hl_dot_fwd, sage_attention_3_int8
+    from quantizedattention_amd.attention_jvp import attention_jvp, helion_attention_jvp_forward_fp32
+    from quantizedattention_amd.attention_mxfp4 import mxfp4_attn_fwd, sage_attention_3_fp4
+    qs, ks = EMPTY_ROWS[which]
+    rows = qs[0] * qs[1] * qs[2]
+    assert rows == 0
+    # int8, through autograd and the reference-shaped forward
+    q, k, v = _z(qs).requires_grad_(True), _z(ks).requires_grad_(True), _z(ks).requires_grad_(True)
+    for causal in (False, True):
+        O = sage_attention_3_int8(q, k, v, causal)
+        assert O.shape == qs and O.dtype == torch.float16
+        O.sum().backward()
+        assert q.grad.shape == qs and k.grad.shape == ks and v.grad.shape == ks
+        assert not k.grad.any() and not v.grad.any()
+    out = helion_atten_int8_hl_dot_fwd(q.detach(), k.detach(), v.detach())
+    assert out[0].shape == qs and out[1].numel() == 0 and out[2].shape == (0, 128) and out[5].numel() == 0
+    assert out[3].shape == (128, ks[0] * ks[1] * ks[2])
+    # bf16, forward and autograd
+    qb, kb, vb = _z(qs).requires_grad_(True), _z(ks).requires_grad_(True), _z(ks, torch.bfloat16).requires_grad_(True)
+    for causal in (False, True):
+        O, lse = helion_atten_bf16_fwd_training(qb.detach(), kb.detach(), vb.detach(), causal)
+        assert O.shape == qs and O.dtype == torch.float32 and lse.shape == (qs[0] * qs[1], qs[2])
+        O = flash_atten_2_bf16(qb, kb, vb, causal)
+        O.sum().backward()
+        assert qb.grad.shape == qs and kb.grad.shape == ks and vb.grad.shape == ks
+        assert not kb.grad.any() and not vb.grad.any()
+    # JVP, both modes, and the autograd Function's plain forward
+    for dt in (torch.bfloat16, torch.float32):
+        x, y = _z(qs, dt), _z(ks, dt)
+        O, tO, lse = helion_attention_jvp_forward_fp32(x, y, y, x, y, y)
+        assert O.shape == qs and tO.shape == qs and lse.shape == (qs[0] * qs[1], qs[2])
+        assert attention_jvp(x, y, y).shape == qs
+        O, tO, lse = ops.jvp_fwd(x, y, y, x, y, y)
+        assert O.shape == qs and tO.shape == qs and lse.shape == (qs[0] * qs[1], qs[2])
+    # MX-FP4
+    for causal in (0, 1, 2):
+        O, lse, _ = mxfp4_attn_fwd(q.detach(), k.detach(), v.detach(), causal=causal)
+        assert O.shape == qs and lse.shape == (qs[0] * qs[1], qs[2])
+        assert ops.mxfp4_fwd_ex(q.detach(), k.detach(), v.detach(), causal).shape == qs
+    assert sage_attention_3_fp4(q.detach(), k.detach(), v.detach()).shape == qs
+    assert ops.mxfp4_fwd(q.detach(), k.detach(), v.detach()).shape == qs
+    # the other operators
+    for smooth in (False, True):
+        outs = ops.int8_fwd(q.detach(), k.detach(), v.detach(), smooth, False)
+        assert outs[0].shape == qs and outs[2].numel() == 0 and outs[3].shape == (ks[0] * ks[1] * ks[2], 128)
+        dq, dk, dv = ops.int8_bwd(_z(qs), outs[2], outs[5], outs[3], outs[6], outs[4], outs[7], outs[0],
+                                  outs[1], False, ks[1])
+        # (the operator reads Sk off k_i8 [B*Hkv*Sk, D], which an empty batch does not tell)
+        ks_op = ks if ks[0] else (0, ks[1], 0, 128)
+        assert dq.shape == qs and dk.shape == ks_op and dv.shape == ks_op and not dk.any() and not dv.any()
+    O, lse = ops.bf16_fwd(qb.detach(), kb.detach(), vb.detach(), True)
+    assert O.shape == qs and lse.shape == (qs[0] * qs[1], qs[2])
+    dq, dk, dv = ops.bf16_bwd(qb.detach(), kb.detach(), vb.detach(), O, lse, True, _z(qs, torch.float32))
+    assert dq.shape == qs and dk.shape == ks and dv.shape == ks and not dk.any() and not dv.any()
+    torch.cuda.synchronize()
+
+
+def _raises_without_allocating(exc, fn, *args, **kw):
+    """``fn`` raises ``exc`` and the allocator's peak does not move: the refusal comes first."""
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    before = torch.cuda.max_memory_allocated()
+    with pytest.raises(exc, match="empty key sequence"):
+        fn(*args, **kw)
+    assert torch.cuda.max_memory_allocated() == before
+
+
+def test_empty_keys_refused(lib):
+    """Sk = 0 with rows > 0: every public entry raises QAttnError and every ``torch.ops.qattn``
+    operator RuntimeError, before anything is allocated.  (Every query keeps a key: an empty softmax
+    has no value, and the JVP kernels would stage key tiles from an empty tensor.)"""
+    from quantizedattention_amd import _lib, ops
+    from quantizedattention_amd import attention_bf16 as A16
+    from quantizedattention_amd import attention_int8 as A8
+    from quantizedattention_amd import attention_jvp as AJ
+    from quantizedattention_amd import attention_mxfp4 as A4
+    E = _lib.QAttnError
+    qs, ks = (1, 4, 64, 128), (1, 2, 0, 128)
+    q, k, dO = _z(qs), _z(ks), _z(qs)
+    vb = _z(ks, torch.bfloat16)
+    for causal in (False, True):
+        _raises_without_allocating(E, A8.sage_attention_3_int8, q, k, k, causal)
+        _raises_without_allocating(E, A8.helion_atten_int8_hl_dot_fwd, q, k, k, causal=causal)
+        _raises_without_allocating(E, A16.flash_atten_2_bf16, q, k, vb, causal)
+        _raises_without_allocating(E, A16.helion_atten_bf16_fwd_training, q, k, vb, causal)
+        _raises_without_allocating(E, A16.helion_flash_atten_2_algo_4_bwd, q, k, vb, _z(qs, torch.float32),
+                                   _z((4, 64), torch.float32), causal, _z(qs, torch.float32))
+        _raises_without_allocating(E, A4.mxfp4_attn_fwd, q, k, k, causal=causal)
+        _raises_without_allocating(E, A4.sage_attention_3_fp4, q, k, k, causal=causal)
+    # the int8 backward, on forward outputs of an empty key sequence's shapes
+    qi, sq, lse = _z((256, 128), torch.int8), _z((8,)), _z((256,))
+    kiT, vi, s0 = _z((128, 0), torch.int8), _z((0, 128), torch.int8), _z((0,))
+    _raises_without_allocating(E, A8.helion_atten_int8_hl_dot_bwd, dO, qi, sq, kiT, None, s0, vi, s0, q, lse,
+                               32, 32, kv_heads=2)
+    _raises_without_allocating(E, A8._int8_backward, dO, qi, sq, kiT, s0, vi, s0, q, lse, kv_heads=2, use_ws=True)
+    _raises_without_allocating(E, A8._int8_backward, dO, qi, sq, kiT, s0, vi, s0, q, lse, kv_heads=2, use_ws=False)
+    for dt in (torch.bfloat16, torch.float32):
+        x, y = _z(qs, dt), _z(ks, dt)
+        _raises_without_allocating(E, AJ.helion_attention_jvp_forward_fp32, x, y, y, x, y, y)
+        _raises_without_allocating(E, AJ.attention_jvp, x, y, y)
+        _raises_without_allocating(E, AJ._jvp, x, y, y, None)
+        _raises_without_allocating(RuntimeError, ops.jvp_fwd, x, y, y, x, y, y)
+    R = RuntimeError
+    _raises_without_allocating(R, ops.int8_fwd, q, k, k, True, False)
+    _raises_without_allocating(R, ops.int8_fwd, q, k, k, False, True)
+    _raises_without_allocating(R, ops.int8_bwd, dO, qi, sq, kiT.t(), s0, vi, s0, q, lse, False, 2)
+    _raises_without_allocating(R, ops.bf16_fwd, q, k, vb, True)
+    _raises_without_allocating(R, ops.bf16_bwd, q, k, vb, _z(qs, torch.float32), _z((4, 64), torch.float32), False,
+                               _z(qs, torch.float32))
+    _raises_without_allocating(R, ops.mxfp4_fwd, q, k, k)
+    _raises_without_allocating(R, ops.mxfp4_fwd_ex, q, k, k, 1)
+    torch.cuda.synchronize()
+
+
+# C entries that take (bh, sq, sk): (pointer arguments before the sizes, the scalars after the sizes,
+# pointer arguments after them, the stream excluded); D = 128, group 1, not causal
+_QKS, _SMS = 0.1275174, 0.0883883
+EMPTY_KEY_ENTRIES = {
+    "qattn_int8_attn_fwd_ex": (8, (1, 0, 128, _QKS), 0),
+    "qattn_int8_attn_fwd_qf": (10, (1, 0, 128, _QKS), 0),
+    "qattn_int8_attn_bwd_ex": (15, (1, 0, 128, _QKS, _SMS), 0),
+    "qattn_int8_attn_bwd_ws": (16, (1, 0, 128, _QKS, _SMS), 0),
+    "qattn_bf16_fwd": (5, (128, 0, _QKS), 0),
+    "qattn_bf16_fwd_ex": (5, (1, 0, 128, _QKS), 0),
+    "qattn_bf16_fwd_ws_ex": (5, (1, 1, 128, _QKS), 1),
+    "qattn_bf16_bwd": (10, (128, 0, _QKS, _SMS), 0),
+    "qattn_bf16_bwd_ex": (10, (1, 0, 128, _QKS, _SMS), 0),
+    "qattn_bf16_bwd_ws_ex": (10, (1, 1, 128, _QKS, _SMS), 1),
+    "qattn_bf16_bwd_split_ex": (10, (1, 0, 128, _QKS, _SMS), 0),
+    "qattn_jvp_fwd": (9, (128, 0, _QKS, _SMS), 0),
+    "qattn_jvp_fwd_ex": (9, (1, 128, _QKS, _SMS), 0),
+    "qattn_jvp_fwd_x3": (15, (128, _QKS, _SMS), 0),
+    "qattn_jvp_fwd_x3_ex": (15, (1, 128, _QKS, _SMS), 0),
+    "qattn_jvp_primal_ex": (5, (1, 128, _QKS, _SMS), 0),
+    "qattn_jvp_primal_x3_ex": (8, (1, 128, _QKS, _SMS), 0),
+    "qattn_mxfp4_attn_fwd_ex": (8, (1, 0, 128, _QKS), 0),
+}
+
+
+def test_empty_keys_status(lib):
+    """The C entries called directly: status 1 for sk = 0 with rows > 0, status 0 (nothing to do) for
+    bh = 0 or sq = 0, each decided before a pointer is read.  Every pointer names one 1 MiB buffer,
+    several times the largest operand of these sizes (4 heads of 64 rows: 128 KiB of fp32 O; the 64 key
+    rows a JVP stage reads: 16 KiB), so an entry that stopped refusing would show as a wrong status and
+    a changed fill, not as an access out of range."""
+    from quantizedattention_amd import _lib
+    buf = torch.full((1 << 20,), 0x5A, dtype=torch.uint8, device="cuda")
+    st = _lib.stream_of(buf)
+
+    def status(name, bh, sq, sk):
+        nptr, tail, nafter = EMPTY_KEY_ENTRIES[name]
+        assert len(_lib.SIGNATURES[name]) == nptr + 3 + len(tail) + nafter + 1, name
+        return getattr(lib, name)(*([_lib.ptr(buf)] * nptr), bh, sq, sk, *tail, *([_lib.ptr(buf)] * nafter), st)
+
+    for name in EMPTY_KEY_ENTRIES:
+        assert status(name, 4, 64, 0) == 1, name
+        assert status(name, 0, 64, 0) == 0 and status(name, 4, 0, 0) == 0, name
+        assert status(name, 0, 64, 64) == 0 and status(name, 4, 0, 64) == 0, name
+    # the head-chunked record backward takes the chunk size before the sizes
+    wsc = lambda bh, sq, sk: lib.qattn_int8_attn_bwd_wsc(*([_lib.ptr(buf)] * 16), 1, bh, sq, sk, 1, 0, 128,  # noqa: E731
+                                                         _QKS, _SMS, st)
+    assert wsc(4, 64, 0) == 1
+    assert wsc(0, 64, 0) == 0 and wsc(4, 0, 0) == 0 and wsc(0, 64, 64) == 0 and wsc(4, 0, 64) == 0
+    torch.cuda.synchronize()
+    assert bool((buf == 0x5A).all())
+
+
+def test_record_limits_status(lib):
+    """The int8 record entries refuse the shapes whose per-tile LDS tables do not fit (the plan's
+    limits, tests/test_plan.py::test_int8_plan_lds_tables) with status 1 before they launch.  Every
+    pointer names one 64 MiB buffer, more than the largest operand of these shapes (8 heads of 8160
+    rows: 16 MiB of bf16 images; 89632 keys: 22 MiB), so a lost refusal is a wrong status and a changed
+    fill."""
+    from quantizedattention_amd import _lib
+    buf = torch.full((64 << 20,), 0x5A, dtype=torch.uint8, device="cuda")
+    st, p = _lib.stream_of(buf), _lib.ptr(buf)
+    for causal in (0, 1):
+        tail = (causal, 128, _QKS, _SMS, st)
+        assert lib.qattn_int8_attn_bwd_ws(*([p] * 16), 8, 8160, 128, 8, *tail) == 1       # 2040 query tiles
+        assert lib.qattn_int8_attn_bwd_wsc(*([p] * 16), 1, 8, 8160, 128, 8, *tail) == 1
+        assert lib.qattn_int8_attn_bwd_ws(*([p] * 16), 1, 32, 2801 * 32, 1, *tail) == 1   # 2801 key tiles
+        assert lib.qattn_int8_attn_bwd_wsc(*([p] * 16), 1, 1, 32, 2801 * 32, 1, *tail) == 1
+    torch.cuda.synchronize()
+    assert bool((buf == 0x5A).all())
+
+
 def test_zero_and_constant_inputs(lib):
     """All-zero q (every quantisation scale 0, indices 0): uniform softmax, O = the mean of v over the
     keys (within the int8 bar), lse = log2(Sk); a constant v gives O = v."""

@@ -8,8 +8,10 @@ other heads and in which workspace chunk may not change a bit of it.  The schedu
 ``xcd_remap``, ``xcd_remap_lpt`` and ``xcd_remap_lpt_grouped`` (csrc/common.h; both of their branches,
 heads a multiple of 8 or not), the causal dK+dV groups of ``QA_DKV_HG`` = 4 heads per XCD, the
 head-chunked dS workspace (``qattn_int8_attn_bwd_wsc``), the grouped-query "virtual head" of the
-non-causal int8 forward, the bf16 forward's per-head V-suffix workspace, and every head offset that is
-computed in 64 bits.  The other exact comparisons of the suite hold two entries to each other that run
+non-causal int8 forward and the bf16 forward's per-head V-suffix workspace.  (The largest tensor here
+holds 3.4e7 elements, so a head offset computed in 32 bits would pass: tests/test_gpu_big_index.py is
+where the 64-bit offsets are exercised, with this instrument on tensors past 2^31 elements.)  The other
+exact comparisons of the suite hold two entries to each other that run
 the same dK+dV kernel on the same grid; this one gives every head of the grid a second opinion.
 
 No tolerance appears in this module: ``torch.equal`` on the bit patterns.  The full launch runs
@@ -38,10 +40,10 @@ launch 189 and 357.)  *The headline*: (4, 32, 4096, 128), G = 1, the benchmark's
 default workspace plan (4 chunks of 32 heads non-causal, one pass causal; 128 heads take the
 multiple-of-8 branches and the grouped causal order): all 128 heads against their own single-head run.
 """
-import zlib
-
 import pytest
 import torch
+
+from head_alone import _Diff, _cut, _gen, _groups, _heads, _randn  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -50,55 +52,6 @@ S_LONG, S_SHORT, SK_JVP = 2080, 1056, 2112
 # (causal, Sq, Sk)
 SEQ = [(True, S_LONG, S_LONG), (False, S_LONG, S_LONG), (False, S_SHORT, S_LONG)]
 SEQ_IDS = ["causal-2080", "full-2080", "full-1056x2080"]
-
-
-def _gen(*key):
-    """A generator seeded from the test's own parameters: no two tests draw the same inputs."""
-    return torch.Generator(device="cuda").manual_seed(zlib.crc32(repr(key).encode()))
-
-
-def _randn(shape, g, dtype, scale=1.0):
-    return (torch.randn(shape, device="cuda", generator=g) * scale).to(dtype)
-
-
-def _bits(t):
-    t = t.contiguous()
-    if t.dtype in (torch.float16, torch.bfloat16):
-        return t.view(torch.int16)
-    return t.view(torch.int32) if t.dtype == torch.float32 else t
-
-
-def _groups(B, Hq, Hkv):
-    """(batch entry, key/value head, slice of its query heads)."""
-    G = Hq // Hkv
-    return [(b, kh, slice(kh * G, kh * G + G)) for b in range(B) for kh in range(Hkv)]
-
-
-def _heads(x, B, H):
-    """[B, H, the rest flattened]: a view of a contiguous head-major tensor of any rank."""
-    return x.reshape(B, H, -1)
-
-
-def _cut(x, B, H, b, hs):
-    """A copy of the heads ``hs`` of batch entry ``b`` of a head-major tensor, flattened per head."""
-    return _heads(x, B, H)[b:b + 1, hs].clone()
-
-
-class _Diff:
-    """Collects the outputs that differ, to name every (output, batch entry, key/value head)."""
-
-    def __init__(self):
-        self.bad, self.n = [], 0
-
-    def eq(self, name, where, alone, full_part):
-        self.n += 1
-        a, f = _bits(alone).reshape(-1), _bits(full_part).reshape(-1)
-        if a.shape != f.shape or not torch.equal(a, f):
-            self.bad.append((name,) + tuple(where) + (int((a != f).sum()) if a.shape == f.shape else "shape",))
-
-    def done(self):
-        assert self.n > 0
-        assert not self.bad, (len(self.bad), "of", self.n, "differ; first:", self.bad[:8])
 
 
 def _finite(*xs):

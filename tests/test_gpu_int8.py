@@ -15,6 +15,13 @@ from oracle import restate as R
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 2, 128, 64), (1, 2, 256, 128), (2, 3, 96, 128), (1, 1, 32, 64), (1, 8, 512, 128)]
+O_BAR = 1e-2   # max|O - O_oracle| (the north star)
+
+
+def lse_within_bar(lse, ref):
+    """lse within 2 fp16 ulp of |lse_oracle| (+1e-3 abs), elementwise -> (ok, max error)."""
+    lerr = (lse.float() - ref.float()).abs()
+    return bool((lerr <= 2 * 2.0 ** -10 * ref.float().abs() + 1e-3).all()), lerr.max().item()
 
 
 def _inputs(shape, seed=0, scale=1.0):
@@ -36,9 +43,9 @@ def test_int8_fwd_matches_oracle(lib, shape):
     assert out[8] == ref[8] == 32 and out[9] == ref[9] == 32
     assert out[0].shape == ref[0].shape and out[0].dtype == torch.float16
     err = (out[0].float().cpu() - ref[0].float()).abs().max().item()
-    assert err <= 1e-2, err
-    lerr = (out[1].float().cpu() - ref[1].float()).abs()
-    assert (lerr <= 2 * 2.0 ** -10 * ref[1].float().abs() + 1e-3).all(), lerr.max().item()
+    assert err <= O_BAR, err
+    ok, lerr = lse_within_bar(out[1].cpu(), ref[1])
+    assert ok, lerr
 
 
 def test_int8_quant_edge_cases(lib):

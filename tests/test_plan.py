@@ -104,6 +104,22 @@ def test_int8_plan_region_and_shapes(lib, causal):
     assert int8_plan(lib, 4, 0, 256, 256, causal, -1)[0] == -1
 
 
+@pytest.mark.parametrize("causal", [0, 1])
+def test_int8_plan_lds_tables(lib, causal):
+    """The record kernels keep per-tile tables in LDS (dK+dV: 36 B per streamed query tile of the
+    key/value head, dQ: 32 B per key tile), so past QATTN_WS_MAX_QUERY_TILES = 1790 tiles of G * Sq / 32
+    or QATTN_WS_MAX_KEY_TILES = 2800 of Sk / 32 the plan recomputes (the launch would be refused: G = 8
+    query heads of 8160 rows are 2040 tiles); tests/test_gpu_edge.py::test_record_limits_status holds
+    the record entries, which return 1 for the same shapes, on buffers of the operands' size."""
+    big = 2 ** 62
+    assert int8_plan(lib, 260, 8, 8160, 128, causal, 0, big)[0] == 0            # 2040 query tiles
+    assert int8_plan(lib, 520, 4, 8160, 128, causal, 0, big)[0] == 520 * 4 * 255 * 4 * REC
+    assert int8_plan(lib, 2, 1, 1790 * 32, 128, causal, 0, big)[0] == 2 * 1790 * 4 * REC
+    assert int8_plan(lib, 2, 2, 1790 * 16 + 32, 128, causal, 0, big)[0] == 0    # 1792 with the group
+    assert int8_plan(lib, 2, 1, 32, 2800 * 32, causal, 0, big)[0] == 2 * 2800 * REC
+    assert int8_plan(lib, 2, 1, 32, 2801 * 32, causal, 0, big)[0] == 0
+
+
 def test_int8_plan_environment(lib, monkeypatch):
     monkeypatch.setenv("QATTN_BWD_WS_CHUNK", "3")
     assert int8_plan(lib, 8, 2, 512, 512, 0, -1) == (1579008, 3)
