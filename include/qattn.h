@@ -480,6 +480,62 @@ int qattn_mxfp4_paged_append(const void* k, const void* v, const void* k_mean, v
                              const void* block_table, long batch, long kv_heads, long n, long num_pages,
                              long page_tokens, long max_pages_per_seq, int head_dim, void* stream);
 
+/* The packed ("varlen") step over the pool: a ragged batch in one attention launch, one merge and one
+ * append (kv_cache_mxfp4.py attention_mxfp4_varlen_paged / PagedKVFP4.append_packed, whose plan_varlen
+ * builds the tables).  nseq sequences take part; sequence j lives in slot s_j of lens / block_table
+ * (distinct slots in [0, max_seqs)) and brings n_j >= 1 packed tokens, tokens = sum n_j, packed in the
+ * order of j.  q4 / qscale are qattn_mxfp4_quant_rows of q f16 [tokens][group * kv_heads][128] (seq =
+ * 1, no mean), so packed row (token, query head) is row token * group * kv_heads + head.  Tables, DEVICE
+ * i32, written by the caller before the call in stream order:
+ *   seq_rec [nseq][8]  {s_j, first packed token (ascending), n_j, ns_j, first partial row, 0, 0, 0},
+ *                      ns_j = ceil(ceil64(L_j) / keys_per_split) splits, L_j = lens[s_j];
+ *   work    [nwork][4] {j, 128-row block of the virtual head, split < ns_j, 0}: one record per
+ *                      workgroup and key/value head, in any order (longest first is fastest).
+ * The virtual head of key/value head h of sequence j has group * n_j rows, row r = g * n_j + i being
+ * packed token i of query head h * group + g; its partial rows are opart f32 [part_rows][128] / ml f32
+ * x 2 [part_rows] at (first partial row of j) + (split * kv_heads + h) * group * n_j + r, so sequence j
+ * owns ns_j * kv_heads * group * n_j rows and part_rows is their sum.  Tiles, masks (causal 2: packed
+ * token i of j sees keys <= L_j - n_j + i) and arithmetic are qattn_mxfp4_attn_fwd_split_paged's: every
+ * sequence gets, bit for bit, that entry's opart / ml for it alone at the same keys_per_split.  Slots
+ * that are not listed are never read.  A slot, row or partial row outside the sizes given is clamped or
+ * skipped (a wrong table gives a wrong answer, never an address outside the buffers).
+ * Preconditions the caller guarantees: 1 <= L_j <= (pages of s_j) * P, causal == 2: n_j <= L_j.
+ * Returns 1 for head_dim != 128, a NULL lens / block_table / seq_rec / work, the pool's limits above,
+ * keys_per_split < 64 or % 64, causal not 0 or 2, group < 1, max_seqs < 1, nseq > max_seqs or > tokens,
+ * tokens * group * kv_heads, part_rows, nwork * kv_heads or max_seqs * kv_heads >= 2^31; 0 without a
+ * launch for nseq, nwork or tokens == 0.  Allocates nothing. */
+int qattn_mxfp4_attn_fwd_varlen_paged(const void* q4, const void* qscale, const void* k4, const void* kscale,
+                                      const void* vt, const void* vscale, void* opart, void* ml,
+                                      const void* lens, const void* block_table, const void* seq_rec,
+                                      const void* work, long nseq, long nwork, long tokens, long part_rows,
+                                      long max_seqs, long kv_heads, long group, long num_pages,
+                                      long page_tokens, long max_pages_per_seq, int causal,
+                                      int keys_per_split, int head_dim, float qks, void* stream);
+
+/* The merge of the packed step: qattn_mxfp4_split_combine's arithmetic in its order, per packed row
+ * (token, query head), over the ns_j partial rows of the token's own sequence (found by binary search
+ * over seq_rec's first-token column): out f16 [tokens][q_heads][128], lse f32 [tokens][q_heads].
+ * Returns 1 for head_dim != 128, seq_rec == NULL, q_heads % kv_heads, nseq > tokens, tokens * q_heads
+ * or part_rows >= 2^31; 0 without a launch for nseq or tokens == 0. */
+int qattn_mxfp4_varlen_combine(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
+                               long nseq, long tokens, long q_heads, long kv_heads, long part_rows,
+                               int head_dim, void* stream);
+
+/* qattn_mxfp4_paged_append for packed tokens: k, v f16 [tokens][kv_heads][128] token-major; seq_tab
+ * i32 [nseq][4] = {slot, count >= 1, first packed token (ascending), 0} and tiles i32 [ntiles][2] = {j,
+ * logical 64-key tile}, the tiles [lens/64, (lens + count - 1)/64] of every record j (exactly the V
+ * tiles the appends touch), both on the device.  The same quantisers, vtail and lens update; block_table
+ * filled for the lengths AFTER the append; the caller guarantees lens[slot] + count <= (pages of the
+ * slot) * P and distinct slots.  A record outside those bounds writes nothing.  Returns 1 as that entry
+ * does, and for a NULL table, nseq > max_seqs or > tokens, ntiles < nseq, tokens * kv_heads >= 2^31; 0
+ * without a launch for nseq or tokens == 0.  Allocates nothing. */
+int qattn_mxfp4_paged_append_packed(const void* k, const void* v, const void* k_mean, void* k4, void* kscale,
+                                    void* vt, void* vscale, void* vtail, void* lens,
+                                    const void* block_table, const void* seq_tab, const void* tiles,
+                                    long nseq, long ntiles, long tokens, long max_seqs, long kv_heads,
+                                    long num_pages, long page_tokens, long max_pages_per_seq, int head_dim,
+                                    void* stream);
+
 /* Merge of the splits, per row of rows_total = bhv*rows: M = max_s m_s, w_s = 2^(m_s - M) (exact; 0
  * for m_s = -inf), L = sum_s w_s l_s, out f16 [rows_total, 128] = (sum_s w_s O_s) * (1 / L), lse f32
  * [rows_total] = M + log2(L).  With nsplit == 1 this is the one-pass forward's epilogue bit for bit. */

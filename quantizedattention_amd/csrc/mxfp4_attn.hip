@@ -34,7 +34,9 @@
 // the "cache append" kernels below grow in place (tests/mxfp4_ragged_ref.py restates it,
 // tests/test_gpu_mxfp4_ragged.py checks both).  Its PAGED instantiation reads the same tiles from a
 // pool of pages through a block table ("paged pool" below; tests/test_gpu_mxfp4_paged.py holds it to
-// the LEN instantiation bit for bit).
+// the LEN instantiation bit for bit).  Its VARLEN instantiation runs a ragged batch of packed queries
+// over that pool in one launch, from two host-built tables, with compact partials, a merge and a packed
+// append of its own (tests/test_gpu_mxfp4_varlen.py holds every sequence to its run alone bit for bit).
 #include "common.h"
 
 #include <type_traits>
@@ -610,26 +612,59 @@ __global__ __launch_bounds__(256, CAUSAL ? QA_MX_OCC_CAUSAL : QA_MX_OCC) void mx
 // PAGED (with LEN; the paged pool of kv_cache_mxfp4.py): the same tiles fetched through the block table
 // btab i32 [B][mpp] by MxPagedRing, hps = Hkv heads per page, Sk = mpp * P (what a table row can hold).
 // Only the ring differs: the prelude, the tile body and the epilogue are the LEN instantiation's.
-template <int D, bool CAUSAL, bool LEN = false, bool PAGED = false>
+// VARLEN (with PAGED; the packed step of kv_cache_mxfp4.py): a ragged batch in one launch.  The grid is
+// one-dimensional, workgroup x = work record x / hps for key/value head x % hps; the record {j, 128-row
+// block, split, 0} and sequence j's record {slot, first packed token, sq, splits, first partial row, ..}
+// are read through the constant address space (wave-uniform: scalar loads).  From them: bh = slot * hps
+// + head, sq_head = sq, rows = group * sq; len = lens[slot] as in LEN.  Two things differ from the PAGED
+// instantiation: q is token-major, f16 [T][group * hps][D] quantised row by row, so virtual row r is
+// packed row (first + r % sq) * (group * hps) + head * group + r / sq; and the partials are compact,
+// row base = first partial row + (split * hps + head) * rows + q0 (opart f32 [part_rows][D], ml f32 x 2
+// [part_rows]).  Slot, packed row and partial rows are clamped / bounded by the sizes in MxVarlen, so
+// a wrong table gives a wrong answer, never an address outside q, the tables' slots or the partials.
+struct MxVarlen {
+  const int* work;      // i32 [nwork][4]
+  const int* seq_rec;   // i32 [nseq][8]
+  int nseq, group;      // sequences of the call, query heads per key/value head
+  long qrows;           // T * group * hps packed query rows
+  long part_rows;
+};
+
+template <int D, bool CAUSAL, bool LEN = false, bool PAGED = false, bool VARLEN = false>
 __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
     const uint8_t* __restrict__ q4, const uint8_t* __restrict__ qs, const uint8_t* __restrict__ k4,
     const uint8_t* __restrict__ ks, const uint8_t* __restrict__ vt, const uint8_t* __restrict__ vs,
     float* __restrict__ opart, float2* __restrict__ ml, int BHV, int rows, int sq_head, int Sk,
     int kps, float qks, int qoff, const int* __restrict__ lens, int hps, const int* __restrict__ btab,
-    int mpp, int lgt, int npool) {
+    int mpp, int lgt, int npool, MxVarlen vl) {
   using C = MxCfg<D>;
   constexpr bool MASK = CAUSAL || LEN;
   static_assert(LEN || !PAGED, "the paged pool has a length per sequence");
+  static_assert(PAGED || !VARLEN, "the packed step runs over the paged pool");
   static_assert(sizeof(float) == 4 && D == 128, "fp32 staging in two passes fills the ring exactly");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int nrb = (rows + C::QROWS - 1) / C::QROWS;
-  int bh, qt;
-  xcd_remap(blockIdx.x, nrb, BHV, bh, qt);
+  int bh, qt, split = (int)blockIdx.y;
+  long qbase = 0, pbase = 0;   // VARLEN: the sequence's first packed token and first partial row
+  if constexpr (VARLEN) {
+    typedef const __attribute__((address_space(4))) int* table_ptr;
+    const int hd = (int)(blockIdx.x % (unsigned)hps);
+    const table_ptr w = (table_ptr)(unsigned long)(vl.work + 4L * (blockIdx.x / (unsigned)hps));
+    const table_ptr rec = (table_ptr)(unsigned long)(vl.seq_rec + 8L * min(max(w[0], 0), vl.nseq - 1));
+    qt = max(w[1], 0);
+    split = max(w[2], 0);
+    bh = min(max(rec[0], 0), BHV / hps - 1) * hps + hd;
+    qbase = rec[1];
+    sq_head = max(rec[2], 1);
+    pbase = rec[4];
+    rows = vl.group * sq_head;
+  } else {
+    const int nrb = (rows + C::QROWS - 1) / C::QROWS;
+    xcd_remap(blockIdx.x, nrb, BHV, bh, qt);
+  }
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63, h = lane >> 5, c32 = lane & 31;
   const int q0 = qt * C::QROWS + wave * 32;
-  const bool active = q0 < rows;
   const int qi = min(q0 + c32, rows - 1);
   int len = Sk;   // keys of this head (workgroup-uniform)
   if constexpr (LEN) {
@@ -639,11 +674,19 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
   const int nt = LEN ? (len + C::KT - 1) / C::KT : Sk / C::KT;
   const int ntc = Sk / C::KT;   // tile stride of a key/value head in vt / vs
   // this workgroup's tiles [t0, t0 + ntw) of the key/value head: ntw >= 1 (nsplit = ceil(Sk / kps))
-  const int t0 = (int)blockIdx.y * (kps / C::KT);
+  const int t0 = split * (kps / C::KT);
+  // the wave's first row of opart / ml
+  const auto part_row0 = [&]() -> long {
+    if constexpr (VARLEN) return pbase + ((long)split * hps + bh % hps) * rows + q0;
+    else return ((long)split * BHV + bh) * rows + q0;
+  };
+  bool active = q0 < rows;
+  if constexpr (VARLEN)   // a wave whose rows would pass the partials stores nothing
+    active = active && part_row0() >= 0 && part_row0() + min(32, rows - q0) <= vl.part_rows;
   if constexpr (LEN) {
     if (t0 >= nt) {   // a split past the sequence: the empty state for the workgroup's rows
       if (!active) return;
-      const long row0 = ((long)blockIdx.y * BHV + bh) * rows + q0;
+      const long row0 = part_row0();
       const int nr = min(32, rows - q0);
       if (h == 0 && c32 < nr) ml[row0 + c32] = make_float2(-INFINITY, 0.f);
       v4f* dst = reinterpret_cast<v4f*>(opart + row0 * D);
@@ -677,7 +720,11 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
   else lring.prologue(ntw);
 
   v4i qf[C::NKS];
-  const unsigned qsw = mx_load_q<D>(q4, qs, (long)bh * rows + qi, h, qf);
+  long qrow = (long)bh * rows + qi;
+  if constexpr (VARLEN)   // token-major q: (token, query head) of virtual row qi
+    qrow = min(max((qbase + qi % sq_head) * (vl.group * hps) + (bh % hps) * vl.group + qi / sq_head, 0L),
+               vl.qrows - 1);
+  const unsigned qsw = mx_load_q<D>(q4, qs, qrow, h, qf);
 
   v16f o[C::NDB];
 #pragma unroll
@@ -708,7 +755,7 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
   vmcnt_wait_all();
   __syncthreads();
   if (!active) return;
-  const long row0 = ((long)blockIdx.y * BHV + bh) * rows + q0;
+  const long row0 = part_row0();
   const int nr = min(32, rows - q0);
   if (h == 0 && c32 < nr) ml[row0 + c32] = make_float2(m, l);
   static_assert(C::WAVES * RowTile<D, float, 2>::BYTES <= C::NSLOT * C::SLOT, "staging fits the ring");
@@ -751,6 +798,184 @@ __global__ __launch_bounds__(256) void mxfp4_split_combine_kernel(const float* _
   for (int i = 0; i < 8; ++i) o[i] = (_Float16)(acc[i] * inv);
   *reinterpret_cast<v8h*>(out + row * D + 8 * c) = o;
   if (c == 0) lse[row] = M + log2_f32(L);
+}
+
+// The largest j in [0, n) with tab[j * stride + col] <= x (0 if there is none): the sequence of a
+// packed token, from the ascending first-token column of a host-built table.
+QA_DEVICE int mx_find_seq(const int* tab, int n, int stride, int col, int x) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[(long)mid * stride + col] <= x) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// f16 of the exact product a * b, rounded once (v_fma_mixlo_f16 with fp32 sources)
+QA_DEVICE _Float16 mul_f16_once(float a, float b) {
+  unsigned r = 0;
+  asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "+v"(r) : "v"(a), "v"(b));
+  return __builtin_bit_cast(_Float16, (unsigned short)r);
+}
+
+// The merge above over the compact partials of the packed step (mxfp4_attn_split_kernel VARLEN): one
+// thread per 8 columns of a packed output row (token, query head).  The thread finds its sequence j by
+// binary search over the first-token column of seq_rec, and merges that sequence's own rec[3] splits,
+// rows first + (s * Hkv + head / group) * group * sq + (head % group) * sq + token - first of opart /
+// ml, with the arithmetic above in the order above.  A row whose partial rows would pass part_rows
+// (a wrong table) is not merged.
+template <int D>
+__global__ __launch_bounds__(256) void mxfp4_varlen_combine_kernel(const float* __restrict__ opart,
+                                                                   const float2* __restrict__ ml,
+                                                                   _Float16* __restrict__ out,
+                                                                   float* __restrict__ lse,
+                                                                   const int* __restrict__ seq_rec, int nseq,
+                                                                   long rows, int Hq, int Hkv,
+                                                                   long part_rows) {
+  constexpr int TPR = D / 8;
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+  const long row = gid / TPR;
+  const int c = (int)(gid % TPR);
+  if (row >= rows) return;
+  const int token = (int)(row / Hq), head = (int)(row % Hq), G = Hq / Hkv;
+  const int* rec = seq_rec + 8L * mx_find_seq(seq_rec, nseq, 8, 1, token);
+  const int sq = max(rec[2], 1), nsplit = rec[3];
+  const long rows_j = (long)G * sq, step = (long)Hkv * rows_j;
+  const long first = rec[4] + (head / G) * rows_j + (long)(head % G) * sq + (token - rec[1]);
+  if (nsplit < 1 || first < 0 || first + (nsplit - 1) * step >= part_rows) return;
+  float M = -INFINITY;
+  for (int s = 0; s < nsplit; ++s) M = fmaxf(M, ml[first + s * step].x);
+  float L = 0.f, acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int s = 0; s < nsplit; ++s) {
+    const float2 v = ml[first + s * step];
+    const float w = v.x == -INFINITY ? 0.f : __builtin_ldexpf(1.f, (int)(v.x - M));
+    L = fmaf(w, v.y, L);
+    const v4f* a = reinterpret_cast<const v4f*>(opart + (first + s * step) * D + 8 * c);
+    const v4f a0 = a[0], a1 = a[1];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      acc[i] = fmaf(w, a0[i], acc[i]);
+      acc[4 + i] = fmaf(w, a1[i], acc[4 + i]);
+    }
+  }
+  const float inv = 1.0f / L;
+  // f16(acc * inv) as mxfp4_split_combine_kernel computes it.  Under the default contraction the compiler
+  // fuses that kernel's product and conversion of columns 8c and 8c + 7 into v_fma_mix (the exact product
+  // rounded to f16 once) and builds the six between them as an fp32 product converted afterwards (rounded
+  // twice); the two differ by one f16 ulp about once in 10^4 elements.  This kernel must give that
+  // kernel's bits (tests/test_gpu_mxfp4_varlen.py), so both forms are spelled out here and left to no
+  // heuristic: an empty asm keeps the fp32 product a value of its own.
+  v8h o;
+  o[0] = mul_f16_once(acc[0], inv);
+#pragma unroll
+  for (int i = 1; i < 7; ++i) {
+    float p = acc[i] * inv;
+    asm volatile("" : "+v"(p));
+    o[i] = (_Float16)p;
+  }
+  o[7] = mul_f16_once(acc[7], inv);
+  *reinterpret_cast<v8h*>(out + row * D + 8 * c) = o;
+  if (c == 0) lse[row] = M + log2_f32(L);
+}
+
+// ---- packed append into the paged pool (kv_cache_mxfp4.py PagedKVFP4.append_packed)
+// k, v f16 [T][Hkv][D] are token-major; tab i32 [nseq][4] = {slot, count, first packed token, 0} (first
+// ascending, the slots distinct) says that packed tokens [first, first + count) go to tokens lens[slot]
+// .. of sequence slot.  The same three launches as the padded append, the same quantisers, in the same
+// order: V (reads vtail), then K and vtail, then the lengths.  A record whose slot is outside [0, B),
+// whose count is < 1, whose tokens pass T or whose sequence would pass cap = mpp * P writes nothing
+// (the host refuses all of these before it launches).
+
+// the record j of a packed append with the sequence's length L before it -> its count, 0: nothing
+QA_DEVICE int mx_packed_count(const int* tab, const int* lens, int j, int B, long T, int cap, int& slot,
+                              int& first, int& L) {
+  slot = tab[4L * j];
+  const int cnt = tab[4L * j + 1];
+  first = tab[4L * j + 2];
+  if (slot < 0 || slot >= B || cnt < 1 || first < 0 || (long)first + cnt > T) return 0;
+  L = lens[slot];
+  return L >= 0 && L <= cap - cnt ? cnt : 0;
+}
+
+// V: one thread per (entry of tiles, head, column d, half h); tiles i32 [ntile][2] = {j, logical tile g}
+// lists exactly the tiles the appends touch, g in [L / 64, (L + cnt - 1) / 64] (another g: nothing).
+template <int D>
+__global__ __launch_bounds__(256) void mx_append_vt_packed_kernel(
+    const _Float16* __restrict__ v, const _Float16* __restrict__ vtail, uint8_t* __restrict__ vt,
+    uint8_t* __restrict__ vs, const int* __restrict__ lens, const int* __restrict__ tab,
+    const int* __restrict__ tiles, long nthr, int nseq, int B, int Hkv, long T, int cap,
+    const int* __restrict__ btab, int mpp, int lgt, int npool) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nthr) return;
+  const int h = (int)(i & 1);
+  const int d = (int)((i >> 1) % D);
+  const long gt = (i >> 1) / D;                 // entry * Hkv + head
+  const int hd = (int)(gt % Hkv);
+  const int j = tiles[2 * (gt / Hkv)], g = tiles[2 * (gt / Hkv) + 1];
+  if (j < 0 || j >= nseq) return;
+  int slot, first, L;
+  const int cnt = mx_packed_count(tab, lens, j, B, T, cap, slot, first, L);
+  if (cnt == 0 || g < L / 64 || 64L * g >= L + cnt) return;   // L + cnt <= cap: the tile lies inside
+  const long bh = (long)slot * Hkv + hd;
+  const _Float16* tail = vtail + bh * 64 * D + d;
+  const _Float16* col = v + ((long)first * Hkv + hd) * D + d;
+  float f[32];
+  float amax = 0.f;
+#pragma unroll
+  for (int jj = 0; jj < 32; ++jj) {
+    const int key = 32 * (jj >> 4) + 8 * ((jj >> 2) & 3) + 4 * h + (jj & 3);
+    const int t = 64 * g + key;
+    f[jj] = t < L ? (float)tail[(long)key * D] : t < L + cnt ? (float)col[(long)(t - L) * Hkv * D] : 0.f;
+    amax = fmaxf(amax, fabsf(f[jj]));
+  }
+  const unsigned e = e8m0_of(amax);
+  const long o = (mx_paged_tile(btab, slot, hd, g, Hkv, mpp, lgt, npool) * D + d) * 2 + h;
+  reinterpret_cast<v4i*>(vt)[o] = pack_fp4x32(f, e8m0_value(e));
+  vs[o] = (uint8_t)e;
+}
+
+// K and vtail: one thread per 32-element block of a packed row (token, head); its record is found by
+// binary search over the first-token column of tab.
+template <int D>
+__global__ __launch_bounds__(256) void mx_append_k_packed_kernel(
+    const _Float16* __restrict__ k, const _Float16* __restrict__ v, const _Float16* __restrict__ mean,
+    uint8_t* __restrict__ k4, uint8_t* __restrict__ ks, _Float16* __restrict__ vtail,
+    const int* __restrict__ lens, const int* __restrict__ tab, long nblk, int nseq, int B, int Hkv, long T,
+    int cap, const int* __restrict__ btab, int mpp, int lgt, int npool) {
+  constexpr int NB = D / 32;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nblk) return;
+  const int blk = (int)(i % NB);
+  const int hd = (int)(i / NB % Hkv);
+  const int token = (int)(i / NB / Hkv);
+  int slot, first, L;
+  const int cnt = mx_packed_count(tab, lens, mx_find_seq(tab, nseq, 4, 2, token), B, T, cap, slot, first, L);
+  const int tok = token - first;
+  if (tok < 0 || tok >= cnt) return;   // t < L + cnt <= cap
+  const int t = L + tok;
+  const long bh = (long)slot * Hkv + hd;
+  const v8h* mu = mean ? reinterpret_cast<const v8h*>(mean + bh * D + blk * 32) : nullptr;
+  const long o = (mx_paged_tile(btab, slot, hd, t / 64, Hkv, mpp, lgt, npool) * 64 + t % 64) * NB + blk;
+  mx_quant_row_block(reinterpret_cast<const v8h*>(k + i * 32), mu, reinterpret_cast<v4i*>(k4) + o, ks + o);
+  const int end = L + cnt;
+  if (end % 64 != 0 && t / 64 == end / 64) {
+    const v8h* src = reinterpret_cast<const v8h*>(v + i * 32);
+    v8h* dst = reinterpret_cast<v8h*>(vtail + (bh * 64 + t % 64) * D + blk * 32);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) dst[c] = src[c];
+  }
+}
+
+// lens[slot] += cnt, one thread per record
+__global__ __launch_bounds__(256) void mx_append_len_packed_kernel(int* __restrict__ lens,
+                                                                   const int* __restrict__ tab, int nseq,
+                                                                   int B, long T, int cap) {
+  const int j = (int)blockIdx.x * 256 + threadIdx.x;
+  if (j >= nseq) return;
+  int slot, first, L;
+  const int cnt = mx_packed_count(tab, lens, j, B, T, cap, slot, first, L);
+  if (cnt) lens[slot] = L + cnt;
 }
 
 }  // namespace qattn
@@ -842,7 +1067,7 @@ static int mxfp4_split_launch(const void* q4, const void* qscale, const void* k4
                      (const uint8_t*)k4, (const uint8_t*)kscale, (const uint8_t*)vt,
                      (const uint8_t*)vscale, (float*)opart, (float2*)ml, (int)bhv, (int)rows,
                      (int)sq_head, (int)sk, kps, qks, (int)(sk - sq_head), (const int*)nullptr, 1,
-                     (const int*)nullptr, 0, 0, 0);
+                     (const int*)nullptr, 0, 0, 0, MxVarlen{});
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -861,7 +1086,8 @@ static int mxfp4_split_len_launch(const void* q4, const void* qscale, const void
                      dim3(256), lds, (hipStream_t)stream, (const uint8_t*)q4, (const uint8_t*)qscale,
                      (const uint8_t*)k4, (const uint8_t*)kscale, (const uint8_t*)vt,
                      (const uint8_t*)vscale, (float*)opart, (float2*)ml, (int)bhv, (int)rows,
-                     (int)sq_head, (int)cap, kps, qks, 0, (const int*)lens, (int)hps, (const int*)nullptr, 0, 0, 0);
+                     (int)sq_head, (int)cap, kps, qks, 0, (const int*)lens, (int)hps, (const int*)nullptr, 0, 0, 0,
+                     MxVarlen{});
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -882,7 +1108,25 @@ static int mxfp4_split_paged_launch(const void* q4, const void* qscale, const vo
                      (const uint8_t*)q4, (const uint8_t*)qscale, (const uint8_t*)k4, (const uint8_t*)kscale,
                      (const uint8_t*)vt, (const uint8_t*)vscale, (float*)opart, (float2*)ml, (int)bhv,
                      (int)rows, (int)sq_head, (int)(mpp * (64L << lgt)), kps, qks, 0, (const int*)lens,
-                     (int)hps, (const int*)btab, (int)mpp, lgt, (int)npool);
+                     (int)hps, (const int*)btab, (int)mpp, lgt, (int)npool, MxVarlen{});
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+template <bool CAUSAL>
+static int mxfp4_varlen_paged_launch(const void* q4, const void* qscale, const void* k4, const void* kscale,
+                                     const void* vt, const void* vscale, void* opart, void* ml,
+                                     const void* lens, const void* btab, const MxVarlen& vl, long nwork,
+                                     long slots, long hps, long npool, int lgt, long mpp, int kps, float qks,
+                                     void* stream) {
+  using C = MxCfg<128>;
+  const int lds = C::NSLOT * C::SLOT;
+  { static LdsGrant granted_; if (!lds_grant((const void*)mxfp4_attn_split_kernel<128, CAUSAL, true, true, true>, lds, granted_)) return 1; }
+  // rows, sq_head and qoff come from the records
+  hipLaunchKernelGGL((mxfp4_attn_split_kernel<128, CAUSAL, true, true, true>), dim3((unsigned)(nwork * hps)),
+                     dim3(256), lds, (hipStream_t)stream, (const uint8_t*)q4, (const uint8_t*)qscale,
+                     (const uint8_t*)k4, (const uint8_t*)kscale, (const uint8_t*)vt, (const uint8_t*)vscale,
+                     (float*)opart, (float2*)ml, (int)(slots * hps), 0, 1, (int)(mpp * (64L << lgt)), kps, qks,
+                     0, (const int*)lens, (int)hps, (const int*)btab, (int)mpp, lgt, (int)npool, vl);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -1029,6 +1273,92 @@ extern "C" int qattn_mxfp4_paged_append(const void* k, const void* v, const void
                      (int)num_pages);
   hipLaunchKernelGGL(mx_append_len_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st,
                      (int*)lens, (const int*)counts, (int)batch, (int)n, (int)cap);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// the packed (varlen) step over the paged pool: nwork work records x kv_heads workgroups in one launch
+// (kernel: mxfp4_attn_split_kernel VARLEN; the tables are the host plan of kv_cache_mxfp4.plan_varlen)
+extern "C" int qattn_mxfp4_attn_fwd_varlen_paged(const void* q4, const void* qscale, const void* k4,
+                                                 const void* kscale, const void* vt, const void* vscale,
+                                                 void* opart, void* ml, const void* lens,
+                                                 const void* block_table, const void* seq_rec,
+                                                 const void* work, long nseq, long nwork, long tokens,
+                                                 long part_rows, long max_seqs, long kv_heads, long group,
+                                                 long num_pages, long page_tokens, long max_pages_per_seq,
+                                                 int causal, int keys_per_split, int head_dim, float qks,
+                                                 void* stream) {
+  if (head_dim != 128 || nseq < 0 || nwork < 0 || tokens < 0 || part_rows < 0) return 1;
+  if (!lens || !block_table || !seq_rec || !work) return 1;
+  const int lgt = mx_page_lgt(page_tokens);
+  if (!mx_pool_ok(num_pages, kv_heads, lgt, max_pages_per_seq)) return 1;
+  if (keys_per_split < 64 || keys_per_split % 64 != 0) return 1;
+  if (max_seqs < 1 || group < 1 || group > 0x7fffffffL || (causal != 0 && causal != 2)) return 1;
+  if (nseq == 0 || nwork == 0 || tokens == 0) return 0;
+  if (nseq > max_seqs || nseq > tokens || part_rows < 1) return 1;
+  // 32-bit packed rows, partial rows, workgroups and slot heads
+  if (tokens > 0x7fffffffL / (group * kv_heads) || part_rows > 0x7fffffffL) return 1;
+  if (nwork > 0x7fffffffL / kv_heads || max_seqs > 0x7fffffffL / kv_heads) return 1;
+  const MxVarlen vl{(const int*)work, (const int*)seq_rec, (int)nseq, (int)group, tokens * group * kv_heads,
+                    part_rows};
+  if (causal)
+    return mxfp4_varlen_paged_launch<true>(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table,
+                                           vl, nwork, max_seqs, kv_heads, num_pages, lgt, max_pages_per_seq,
+                                           keys_per_split, qks, stream);
+  return mxfp4_varlen_paged_launch<false>(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table,
+                                          vl, nwork, max_seqs, kv_heads, num_pages, lgt, max_pages_per_seq,
+                                          keys_per_split, qks, stream);
+}
+
+// the merge of the packed step's compact partials into O f16 [tokens][q_heads][128], lse [tokens][q_heads]
+extern "C" int qattn_mxfp4_varlen_combine(const void* opart, const void* ml, void* out, void* lse,
+                                          const void* seq_rec, long nseq, long tokens, long q_heads,
+                                          long kv_heads, long part_rows, int head_dim, void* stream) {
+  if (head_dim != 128 || nseq < 0 || tokens < 0 || part_rows < 0 || !seq_rec) return 1;
+  if (kv_heads < 1 || q_heads < 1 || q_heads % kv_heads != 0 || q_heads > 0x7fffffffL) return 1;
+  if (nseq == 0 || tokens == 0) return 0;
+  if (nseq > tokens || part_rows < 1) return 1;
+  if (tokens > 0x7fffffffL / q_heads || part_rows > 0x7fffffffL) return 1;
+  const long rows = tokens * q_heads, nthr = rows * (128 / 8);
+  hipLaunchKernelGGL(mxfp4_varlen_combine_kernel<128>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)opart, (const float2*)ml, (_Float16*)out,
+                     (float*)lse, (const int*)seq_rec, (int)nseq, rows, (int)q_heads, (int)kv_heads,
+                     part_rows);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// a packed append into the paged pool ("packed append" above): seq_tab i32 [nseq][4] and tiles i32
+// [ntiles][2] on the device, the pages the new tokens need in block_table already
+extern "C" int qattn_mxfp4_paged_append_packed(const void* k, const void* v, const void* k_mean, void* k4,
+                                               void* kscale, void* vt, void* vscale, void* vtail,
+                                               void* lens, const void* block_table, const void* seq_tab,
+                                               const void* tiles, long nseq, long ntiles, long tokens,
+                                               long max_seqs, long kv_heads, long num_pages,
+                                               long page_tokens, long max_pages_per_seq, int head_dim,
+                                               void* stream) {
+  if (head_dim != 128 || nseq < 0 || ntiles < 0 || tokens < 0 || max_seqs < 1) return 1;
+  if (!k || !v || !k4 || !kscale || !vt || !vscale || !vtail || !lens || !block_table || !seq_tab || !tiles)
+    return 1;
+  const int lgt = mx_page_lgt(page_tokens);
+  if (!mx_pool_ok(num_pages, kv_heads, lgt, max_pages_per_seq)) return 1;
+  if (nseq == 0 || tokens == 0) return 0;
+  if (nseq > max_seqs || nseq > tokens || ntiles < nseq) return 1;
+  if (tokens > 0x7fffffffL / kv_heads || max_seqs > 0x7fffffffL / kv_heads) return 1;
+  const long cap = max_pages_per_seq * page_tokens;
+  const long nthr = ntiles * kv_heads * 128 * 2, nblk = tokens * kv_heads * (128 / 32);
+  if ((nthr + 255) / 256 > 0x7fffffffL || (nblk + 255) / 256 > 0x7fffffffL) return 1;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(mx_append_vt_packed_kernel<128>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st,
+                     (const _Float16*)v, (const _Float16*)vtail, (uint8_t*)vt, (uint8_t*)vscale,
+                     (const int*)lens, (const int*)seq_tab, (const int*)tiles, nthr, (int)nseq, (int)max_seqs,
+                     (int)kv_heads, tokens, (int)cap, (const int*)block_table, (int)max_pages_per_seq, lgt,
+                     (int)num_pages);
+  hipLaunchKernelGGL(mx_append_k_packed_kernel<128>, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st,
+                     (const _Float16*)k, (const _Float16*)v, (const _Float16*)k_mean, (uint8_t*)k4,
+                     (uint8_t*)kscale, (_Float16*)vtail, (const int*)lens, (const int*)seq_tab, nblk,
+                     (int)nseq, (int)max_seqs, (int)kv_heads, tokens, (int)cap, (const int*)block_table,
+                     (int)max_pages_per_seq, lgt, (int)num_pages);
+  hipLaunchKernelGGL(mx_append_len_packed_kernel, dim3((unsigned)((nseq + 255) / 256)), dim3(256), 0, st,
+                     (int*)lens, (const int*)seq_tab, (int)nseq, (int)max_seqs, tokens, (int)cap);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

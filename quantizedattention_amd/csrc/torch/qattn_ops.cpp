@@ -28,6 +28,9 @@
 //       kv_cache_mxfp4.attention_mxfp4_decode on a preallocated cache's operands and device lengths
 //   mxfp4_decode_paged(q, k4, ks, vt, vs, lens, block_table, sk_max, causal, keys_per_split) -> (O, lse)
 //       kv_cache_mxfp4.attention_mxfp4_decode_paged on a page pool's operands, lengths and block table
+//   mxfp4_varlen_paged(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal,
+//                      keys_per_split) -> (O, lse)
+//       kv_cache_mxfp4.attention_mxfp4_varlen_paged: packed q [T, Hq, 128] and the two plan tables
 // Workspaces, head chunks and key splits are planned by the library (csrc/plan.hip), as in the drop-ins.
 // Errors: TORCH_CHECK (c10::Error, RuntimeError in Python) with the drop-ins' messages; int8_quant's
 // argument checks raise ValueError (TORCH_CHECK_VALUE) as its Python predecessor did.
@@ -566,6 +569,67 @@ std::tuple<Tensor, Tensor> mxfp4_decode_paged(const Tensor& q_in, const Tensor& 
   return {out, lse};
 }
 
+// kv_cache_mxfp4.attention_mxfp4_varlen_paged on a page pool's operands: packed q [T, Hq, 128], lens i32
+// [B] and block_table i32 [B, max_pages_per_seq] on the device, and the two tables of
+// kv_cache_mxfp4.plan_varlen as device tensors, seq_rec i32 [nseq, 8] and work i32 [nwork, 4], with the
+// plan's part_rows and keys_per_split.  The operator cannot read any of them without a synchronisation:
+// the caller guarantees that they are a plan of the pool's lengths (the Python wrapper
+// ops.mxfp4_varlen_paged builds them from the cache's host mirror); the kernels keep every address a
+// wrong table names inside the buffers.
+std::tuple<Tensor, Tensor> mxfp4_varlen_paged(const Tensor& q_in, const Tensor& k4, const Tensor& ks,
+                                              const Tensor& vt, const Tensor& vs, const Tensor& lens,
+                                              const Tensor& block_table, const Tensor& seq_rec,
+                                              const Tensor& work, int64_t part_rows, int64_t causal,
+                                              int64_t keys_per_split) {
+  require_gpu({&q_in, &k4, &ks, &vt, &vs, &lens, &block_table, &seq_rec, &work});
+  TORCH_CHECK(q_in.dim() == 3 && k4.dim() == 4 && q_in.size(2) == 128 && k4.size(3) == 64,
+              "qattn mxfp4 paged cache: packed queries must be q [T, Hq, 128], head_dim 128 in the pool");
+  const int64_t NP = k4.size(0), Hkv = k4.size(1), PT = k4.size(2), D = 128;
+  TORCH_CHECK(PT >= 64 && PT <= 1024 && (PT & (PT - 1)) == 0,
+              "qattn mxfp4 paged cache: page_tokens must be 64 * 2^k in [64, 1024]");
+  TORCH_CHECK(block_table.scalar_type() == at::kInt && block_table.is_contiguous() && block_table.dim() == 2 &&
+                  block_table.size(1) >= 1,
+              "qattn mxfp4 paged cache: block_table must be contiguous int32 [B, max_pages_per_seq]");
+  const int64_t B = block_table.size(0), mpp = block_table.size(1);
+  const int64_t T = q_in.size(0), Hq = q_in.size(1);
+  TORCH_CHECK(Hkv > 0 && NP > 0 && Hq > 0 && Hq % Hkv == 0,
+              "qattn mxfp4 paged cache: q must have G * Hkv heads for the pool's Hkv");
+  TORCH_CHECK(causal == 0 || causal == 1, "qattn mxfp4 paged cache: causal must be 0 or 1");
+  for (const Tensor* t : {&k4, &ks, &vt, &vs})
+    TORCH_CHECK(t->scalar_type() == at::kByte && t->is_contiguous(),
+                "qattn mxfp4 paged cache: the quantised operands must be contiguous uint8");
+  TORCH_CHECK(ks.sizes() == at::IntArrayRef({NP, Hkv, PT, D / 32}) &&
+                  vt.sizes() == at::IntArrayRef({NP, Hkv, PT / 64, D, 32}) &&
+                  vs.sizes() == at::IntArrayRef({NP, Hkv, PT / 64, D, 2}),
+              "qattn mxfp4 paged cache: ks / vt / vs do not match k4");
+  TORCH_CHECK(lens.scalar_type() == at::kInt && lens.is_contiguous() && lens.dim() == 1 && lens.size(0) == B,
+              "qattn mxfp4 paged cache: lens must be contiguous int32 [B]");
+  TORCH_CHECK(seq_rec.scalar_type() == at::kInt && seq_rec.is_contiguous() && seq_rec.dim() == 2 &&
+                  seq_rec.size(1) == 8 && seq_rec.size(0) >= 1 && seq_rec.size(0) <= B,
+              "qattn mxfp4 paged cache: seq_rec must be contiguous int32 [nseq, 8], 1 <= nseq <= B");
+  TORCH_CHECK(work.scalar_type() == at::kInt && work.is_contiguous() && work.dim() == 2 && work.size(1) == 4,
+              "qattn mxfp4 paged cache: work must be contiguous int32 [nwork, 4]");
+  TORCH_CHECK(keys_per_split >= 64 && keys_per_split % 64 == 0,
+              "qattn mxfp4 paged cache: keys_per_split must be a multiple of 64 (the plan's)");
+  TORCH_CHECK(T >= seq_rec.size(0) && part_rows >= 1 && work.size(0) >= 1,
+              "qattn mxfp4 paged cache: every listed sequence brings a token, a partial row and a work record");
+  Ctx c(q_in);
+  const Tensor q = kin(q_in, at::kHalf);
+  Tensor q4 = empty({T * Hq, D / 2}, at::kByte, q), qs = empty({T * Hq, D / 32}, at::kByte, q);
+  Tensor out = empty({T, Hq, D}, at::kHalf, q), lse = empty({T, Hq}, at::kFloat, q);
+  call(qattn_mxfp4_quant_rows(P(q), nullptr, P(q4), P(qs), T * Hq, Hq, (int)D, c.stream), "quantise q");
+  Tensor opart = empty({part_rows, D}, at::kFloat, q), ml = empty({part_rows, 2}, at::kFloat, q);
+  call(qattn_mxfp4_attn_fwd_varlen_paged(P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens),
+                                         P(block_table), P(seq_rec), P(work), seq_rec.size(0), work.size(0),
+                                         T, part_rows, B, Hkv, Hq / Hkv, NP, PT, mpp, causal ? 2 : 0,
+                                         (int)keys_per_split, (int)D, qk_scale(D), c.stream),
+       "mxfp4 varlen forward");
+  call(qattn_mxfp4_varlen_combine(P(opart), P(ml), P(out), P(lse), P(seq_rec), seq_rec.size(0), T, Hq, Hkv,
+                                  part_rows, (int)D, c.stream),
+       "mxfp4 varlen merge");
+  return {out, lse};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(qattn, m) {
@@ -586,6 +650,8 @@ TORCH_LIBRARY(qattn, m) {
         "int keys_per_split) -> (Tensor, Tensor)");
   m.def("mxfp4_decode_paged(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, Tensor block_table, "
         "int sk_max, int causal, int keys_per_split) -> (Tensor, Tensor)");
+  m.def("mxfp4_varlen_paged(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, Tensor block_table, "
+        "Tensor seq_rec, Tensor work, int part_rows, int causal, int keys_per_split) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
@@ -600,4 +666,5 @@ TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
   m.impl("mxfp4_cached", &mxfp4_cached);
   m.impl("mxfp4_decode", &mxfp4_decode);
   m.impl("mxfp4_decode_paged", &mxfp4_decode_paged);
+  m.impl("mxfp4_varlen_paged", &mxfp4_varlen_paged);
 }

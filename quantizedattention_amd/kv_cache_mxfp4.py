@@ -56,6 +56,32 @@ order, ``fork`` shares a prefix's full pages by reference count, and
 :func:`attention_mxfp4_decode_paged` (``qattn_mxfp4_attn_fwd_split_paged``) gives, bit for bit, what
 :func:`attention_mxfp4_decode` gives on a preallocated cache with the same tokens.
 
+A continuous-batching step is ragged: some slots are free, some sequences decode one token, one or two
+prefill a chunk.  The packed ("varlen") step serves it without padding.  Queries and new keys/values
+are token-major, as a model produces them: ``q`` fp16 [T, Hq, D] and ``k, v`` fp16 [T, Hkv, D] hold the
+n_0 tokens of sequence ``seq_ids[0]`` first, then the n_1 of ``seq_ids[1]``, ...; ``seq_ids`` are
+distinct slots of the pool and the slots that are not listed are never read (they may be empty).
+:meth:`PagedKVFP4.append_packed` (``qattn_mxfp4_paged_append_packed``) writes the new tokens from a
+host-built int32 table [nseq][4] = {slot, count, first packed token, 0} and a list of {j, logical
+tile}, exactly the V tiles the appends touch; the pool keeps the invariant above.
+:func:`attention_mxfp4_varlen_paged` is one attention launch
+(``qattn_mxfp4_attn_fwd_varlen_paged``) and one merge (``qattn_mxfp4_varlen_combine``) from the two
+tables of :func:`plan_varlen`, which is pure Python on the host mirror::
+
+    seq_rec  int32 [nseq][8]   {slot, first packed token, n_j, ns_j, first partial row, 0, 0, 0}
+    work     int32 [nwork][4]  {j, 128-row block, split < ns_j, 0}, one per workgroup and kv head,
+                               longest split first
+    opart    fp32  [part_rows][D], ml fp32 [part_rows][2]   the compact partials
+
+One ``kps`` serves the call; sequence j has ns_j = ceil(ceil64(L_j) / kps) splits and owns ns_j * Hkv * G
+* n_j partial rows from its first one, laid out [split][kv head][virtual row g * n_j + i] (the virtual
+head order of the decoding layout), so a long sequence beside a large chunk pays for its own splits
+only and no workgroup exists to write an empty state.  Virtual row r of key/value head h is packed row
+(first + r % n_j) * Hq + h * G + r // n_j of ``q``.  Causal is bottom-right per sequence: query i of
+sequence j keeps the keys <= L_j - n_j + i, what a prefill chunk needs after its own append.  Every
+sequence gets, bit for bit, what :func:`attention_mxfp4_decode` gives for it alone with Sq = n_j and the
+same keys per split.
+
 Wire format (little-endian), the container of kv_cache.py with a magic of its own::
 
     offset 0   8 B   magic  b"QATTNKF4"
@@ -89,7 +115,8 @@ _ALIGN = 256
 _DTYPES = {"uint8": torch.uint8, "float16": torch.float16}
 
 __all__ = ["QuantizedKVFP4", "quantize_kv_fp4", "attention_mxfp4_cached", "PreallocatedKVFP4",
-           "attention_mxfp4_decode", "PageAllocator", "PagedKVFP4", "attention_mxfp4_decode_paged"]
+           "attention_mxfp4_decode", "PageAllocator", "PagedKVFP4", "attention_mxfp4_decode_paged",
+           "plan_varlen", "attention_mxfp4_varlen_paged"]
 
 
 @dataclass
@@ -659,6 +686,44 @@ class PagedKVFP4:
         self.lengths = [L + c for L, c in zip(self.lengths, cnt)]
         return self
 
+    def append_packed(self, k: torch.Tensor, v: torch.Tensor, seq_ids, counts) -> "PagedKVFP4":
+        """Append packed fp16 ``k, v`` [T, Hkv, D], token-major as a model produces them: the first
+        ``counts[0]`` tokens go to sequence ``seq_ids[0]``, the next ``counts[1]`` to ``seq_ids[1]``,
+        ... (distinct slots, every count >= 1, T = sum(counts)); the slots that are not listed are
+        not touched.  As :meth:`append`: the pages are reserved on the host first (all or nothing,
+        raises before anything is launched or changed), the changed table is uploaded in stream
+        order and ``qattn_mxfp4_paged_append_packed`` writes in place, over exactly the V tiles the
+        appends touch (listed here from the host mirror).  No host synchronisation, nothing is read
+        back; returns ``self``."""
+        _, H, _, D = self.shape
+        ids, cnt = _packed_lists(self.alloc.max_seqs, seq_ids, counts, "counts")
+        if (k.dim() != 3 or tuple(k.shape[1:]) != (H, D) or k.shape != v.shape or k.shape[0] != sum(cnt)):
+            raise _lib.QAttnError("qattn mxfp4 paged cache: packed tokens must be k, v [sum(counts), Hkv, D]")
+        if k.shape[0] * H >= 1 << 31:
+            raise _lib.QAttnError("qattn mxfp4 paged cache: fewer than 2^31 packed rows expected")
+        _lib.require_gpu(k, v, self.k4)
+        grown = self.alloc.reserve([(b, self.lengths[b] + c) for b, c in zip(ids, cnt)])
+        k = _lib.kernel_input(k, torch.float16)
+        v = _lib.kernel_input(v, torch.float16)
+        if grown:
+            self.block_table.copy_(torch.tensor(self.alloc.table, dtype=torch.int32), non_blocking=True)
+        tab, tiles, first = [], [], 0
+        for j, (b, c) in enumerate(zip(ids, cnt)):
+            L = self.lengths[b]
+            tab += [b, c, first, 0]
+            tiles += [x for g in range(L // BLOCK, (L + c - 1) // BLOCK + 1) for x in (j, g)]
+            first += c
+        # one upload: the records, then the tile list (the record block is a multiple of 16 bytes)
+        dev = torch.tensor(tab + tiles, dtype=torch.int32).to(k.device, non_blocking=True)
+        _lib.call("qattn_mxfp4_paged_append_packed", _lib.ptr(k), _lib.ptr(v), _lib.ptr(self.k_mean),
+                  _lib.ptr(self.k4), _lib.ptr(self.ks), _lib.ptr(self.vt), _lib.ptr(self.vs),
+                  _lib.ptr(self.vtail), _lib.ptr(self.lens), _lib.ptr(self.block_table), _lib.ptr(dev),
+                  _lib.ptr(dev[len(tab):]), len(ids), len(tiles) // 2, k.shape[0], self.alloc.max_seqs, H,
+                  self.num_pages, self.page_tokens, self.alloc.max_pages_per_seq, D, _lib.stream_of(k))
+        for b, c in zip(ids, cnt):
+            self.lengths[b] += c
+        return self
+
     def free(self, seqs) -> None:
         """Empty the sequences ``seqs`` (indices) and give their pages back to the pool."""
         seqs = [self.alloc._seq(b) for b in seqs]
@@ -732,4 +797,140 @@ def attention_mxfp4_decode_paged(q: torch.Tensor, cache: PagedKVFP4, causal: boo
               _qk_scale(D), st)
     _lib.call("qattn_mxfp4_split_combine", _lib.ptr(opart), _lib.ptr(ml), _lib.ptr(O), _lib.ptr(lse),
               bhv * rows, nsplit, D, st)
+    return O, lse
+
+
+# ------------------------------------------------------------------------------ packed (varlen) step
+QROWS = 128   # query rows of a workgroup (csrc/mxfp4_attn.hip MxCfg::QROWS)
+
+
+def _packed_lists(max_seqs: int, seq_ids, counts, what: str):
+    """``seq_ids`` and ``counts`` of a packed call as lists of ints, checked: nseq >= 1 distinct slots
+    in [0, max_seqs), every count >= 1."""
+    as_list = lambda x: [int(i) for i in (x.tolist() if isinstance(x, torch.Tensor) else x)]  # noqa: E731
+    ids, cnt = as_list(seq_ids), as_list(counts)
+    if not ids or len(ids) != len(cnt):
+        raise _lib.QAttnError(f"qattn mxfp4 paged cache: seq_ids and {what} must list the same nseq >= 1 "
+                              "sequences")
+    if any(not 0 <= b < max_seqs for b in ids) or len(set(ids)) != len(ids):
+        raise _lib.QAttnError(f"qattn mxfp4 paged cache: seq_ids must be distinct slots in [0, {max_seqs}), "
+                              f"got {ids}")
+    if any(c < 1 for c in cnt):
+        raise _lib.QAttnError(f"qattn mxfp4 paged cache: every entry of {what} must be >= 1, got {cnt}")
+    return ids, cnt
+
+
+def plan_varlen(lengths, seq_ids, q_lens, Hq: int, Hkv: int, keys_per_split: Optional[int] = None,
+                causal: bool = False):
+    """The host plan of :func:`attention_mxfp4_varlen_paged` -> (kps, seq_rec, work, part_rows); pure
+    Python on the host mirror ``lengths`` (one entry per slot), no device and no tensor.
+
+    ``kps``: one key split size per call.  None takes ``qattn_split_keys(W, 1, sk_max, 64)``, the
+    library's rule (two workgroups per CU, no split under 1024 keys) at the call's real workgroup count
+    W = Hkv * sum_j ceil(G * q_lens[j] / 128) and sk_max = ceil64(max_j L_j), L_j the length of
+    ``seq_ids[j]``.  Sequence j then has ns_j = ceil(ceil64(L_j) / kps) splits of its own.  The rule's
+    constants (512 workgroups, 1024 keys) were measured on uniform batches only (``_split_plan_fp4``)
+    and are not tuned for mixed ones.  What mixed batches gave on one MI355X (tools/time_decode_varlen.py,
+    2026-10-20, 32 / 8 heads, P = 256, causal, whole call, median us of 3 x 20 alternating calls, pass
+    medians within 0.1 to 2.3 %): a 2048-token chunk at 8192 cached beside 63 decodes over 512 .. 8192
+    keys, rule 8192 keys (no split) 260.5, 4096 keys 237.2, 1024 keys 401.8 (kernel alone 230.8 against
+    202.3 at 4096); a 512-token chunk beside 15 decodes, rule 2752 keys 114.9, 1408 keys 136.8, 5504
+    keys 111.0, 1024 keys 151.7.  The rule loses to half its value on the first shape by more than the
+    spread and wins on the second, so it is left as it is; the long chunk, whose workgroups the rule
+    counts like a decode's, is what a better rule would split.
+
+    ``seq_rec`` [nseq][8] = [slot, first packed token, q_lens[j], ns_j, first partial row, 0, 0, 0].
+    Sequence j owns the ns_j * Hkv * G * q_lens[j] partial rows from its first one, laid out [split][kv
+    head][virtual row g * q_lens[j] + i]; the blocks are dense in [0, ``part_rows``).
+    ``work`` [nwork][4] = [j, 128-row block, split, 0]: one record per workgroup and key/value head,
+    every split < ns_j of every row block of every sequence once, ordered by descending tile count of
+    the split (the longest workgroups start first); results do not depend on the order.
+
+    Raises :class:`QAttnError` for an empty, duplicate or out-of-range slot list, a q_lens entry < 1, a
+    listed slot of length 0, ``causal`` with q_lens[j] > L_j, Hq % Hkv != 0, a ``keys_per_split`` that
+    is not a multiple of 64, and when T * Hq, part_rows or nwork * Hkv reach 2^31.  The slots that are
+    not listed are not looked at.
+    """
+    lengths = [int(x) for x in lengths]
+    ids, sq = _packed_lists(len(lengths), seq_ids, q_lens, "q_lens")
+    if Hkv < 1 or Hq < 1 or Hq % Hkv:
+        raise _lib.QAttnError("qattn mxfp4 paged cache: q must have G * Hkv heads for the cache's Hkv")
+    Ls = [lengths[b] for b in ids]
+    if min(Ls) < 1:
+        raise _lib.QAttnError("qattn mxfp4 paged cache: every listed sequence needs at least one cached "
+                              f"token (slots {ids}, lengths {Ls})")
+    if causal and any(n > L for n, L in zip(sq, Ls)):
+        raise _lib.QAttnError("qattn mxfp4 paged cache: causal attention needs q_lens[j] <= the cached "
+                              f"tokens of every listed sequence (q_lens {sq}, lengths {Ls})")
+    G = Hq // Hkv
+    nrb = [-(-G * n // QROWS) for n in sq]
+    sk_max = _ceil64(max(Ls))
+    if keys_per_split is None:
+        kps = _lib.load().qattn_split_keys(Hkv * sum(nrb), 1, sk_max, BLOCK)
+    else:
+        kps = int(keys_per_split)
+    if kps < BLOCK or kps % BLOCK:
+        raise _lib.QAttnError("qattn mxfp4 paged cache: keys_per_split must be a multiple of 64")
+    kps = min(kps, sk_max)
+    nsp = [-(-_ceil64(L) // kps) for L in Ls]
+    if (sum(sq) * Hq >= 1 << 31 or sum(ns * Hkv * G * n for ns, n in zip(nsp, sq)) >= 1 << 31
+            or sum(ns * r for ns, r in zip(nsp, nrb)) * Hkv >= 1 << 31):
+        raise _lib.QAttnError("qattn mxfp4 paged cache: a packed call of 2^31 or more query rows, partial "
+                              "rows or workgroups")
+    seq_rec, work, first, base = [], [], 0, 0
+    for j, (b, n, L, ns) in enumerate(zip(ids, sq, Ls, nsp)):
+        seq_rec.append([b, first, n, ns, base, 0, 0, 0])
+        nt = -(-L // BLOCK)
+        for s in range(ns):
+            tiles = min(nt, (s + 1) * (kps // BLOCK)) - s * (kps // BLOCK)
+            work += [(tiles, [j, rb, s, 0]) for rb in range(nrb[j])]
+        first += n
+        base += ns * Hkv * G * n
+    work.sort(key=lambda w: -w[0])   # stable: equal tile counts stay in sequence order
+    return kps, seq_rec, [w for _, w in work], base
+
+
+@torch.no_grad()
+def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_lens, causal: bool = False,
+                                 keys_per_split: Optional[int] = None):
+    """A ragged batch against a paged cache in one attention launch and one merge: packed fp16 queries
+    ``q`` [T, Hq, D], token-major, the ``q_lens[0]`` tokens of sequence ``seq_ids[0]`` first, then
+    those of ``seq_ids[1]``, ... (nseq >= 1 distinct slots, every q_lens[j] >= 1, T = sum(q_lens)) ->
+    (O fp16 [T, Hq, D], lse fp32 [T, Hq] base 2).  Sequence ``seq_ids[j]`` is attended over its own
+    ``lengths[slot]`` keys through its table row; ``causal`` is bottom-right per sequence (query i of
+    sequence j keeps the keys <= L_j - q_lens[j] + i: a prefill chunk after its own append).  The slots
+    that are not listed may be empty or hold anything: their lengths, table rows and pages are never
+    read.  Every sequence gets, bit for bit, what :func:`attention_mxfp4_decode` gives for it alone
+    with Sq = q_lens[j] and the same keys per split.  Raises before any launch as :func:`plan_varlen`
+    does, and for sum(q_lens) != T.  Stream-ordered: the plan comes from the host mirror, its two
+    tables are uploaded without a synchronisation, nothing is read back."""
+    if not isinstance(cache, PagedKVFP4):
+        raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PagedKVFP4")
+    _, Hkv, _, D = cache.shape
+    if q.dim() != 3 or q.shape[2] != D:
+        raise _lib.QAttnError("qattn mxfp4 paged cache: packed queries must be q [T, Hq, 128]")
+    T, Hq = q.shape[0], q.shape[1]
+    if Hq == 0 or Hq % Hkv:
+        raise _lib.QAttnError("qattn mxfp4 paged cache: q must have G * Hkv heads for the cache's Hkv")
+    ids, sq = _packed_lists(cache.alloc.max_seqs, seq_ids, q_lens, "q_lens")
+    if sum(sq) != T:
+        raise _lib.QAttnError(f"qattn mxfp4 paged cache: q holds {T} tokens, q_lens sum to {sum(sq)}")
+    kps, seq_rec, work, part_rows = plan_varlen(cache.lengths, ids, sq, Hq, Hkv, keys_per_split, causal)
+    _lib.require_gpu(q, cache.k4)
+    dev, st = q.device, _lib.stream_of(q)
+    # from fresh pageable host tensors, as PagedKVFP4._upload: staged before the copies return
+    rec_d = torch.tensor(seq_rec, dtype=torch.int32).to(dev, non_blocking=True)
+    work_d = torch.tensor(work, dtype=torch.int32).to(dev, non_blocking=True)
+    q4, qs = mxfp4_quantize_rows(q)
+    O = torch.empty((T, Hq, D), dtype=torch.float16, device=dev)
+    lse = torch.empty((T, Hq), dtype=torch.float32, device=dev)
+    opart = torch.empty((part_rows, D), dtype=torch.float32, device=dev)
+    ml = torch.empty((part_rows, 2), dtype=torch.float32, device=dev)
+    _lib.call("qattn_mxfp4_attn_fwd_varlen_paged", _lib.ptr(q4), _lib.ptr(qs), _lib.ptr(cache.k4),
+              _lib.ptr(cache.ks), _lib.ptr(cache.vt), _lib.ptr(cache.vs), _lib.ptr(opart), _lib.ptr(ml),
+              _lib.ptr(cache.lens), _lib.ptr(cache.block_table), _lib.ptr(rec_d), _lib.ptr(work_d), len(ids),
+              len(work), T, part_rows, cache.alloc.max_seqs, Hkv, Hq // Hkv, cache.num_pages,
+              cache.page_tokens, cache.alloc.max_pages_per_seq, 2 if causal else 0, kps, D, _qk_scale(D), st)
+    _lib.call("qattn_mxfp4_varlen_combine", _lib.ptr(opart), _lib.ptr(ml), _lib.ptr(O), _lib.ptr(lse),
+              _lib.ptr(rec_d), len(ids), T, Hq, Hkv, part_rows, D, st)
     return O, lse

@@ -20,6 +20,8 @@ the autograd rules of ``int8_fwd`` and ``bf16_fwd`` (their backward operators).
     torch.ops.qattn.mxfp4_decode(q, k4, ks, vt, vs, lens, sk_max, causal, keys_per_split) -> (O, lse)
     torch.ops.qattn.mxfp4_decode_paged(q, k4, ks, vt, vs, lens, block_table, sk_max, causal,
                                        keys_per_split) -> (O, lse)
+    torch.ops.qattn.mxfp4_varlen_paged(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows,
+                                       causal, keys_per_split) -> (O, lse)
 
 Shapes follow the drop-in functions (attention_int8.py:259-262 for the int8 outputs) except that
 k_i8 is returned row-major [B*Hkv*Sk, D] (the drop-in's k_i8T is its transposed view: an operator
@@ -34,7 +36,7 @@ import torch
 from . import _lib
 
 __all__ = ["int8_quant", "int8_fwd", "int8_bwd", "bf16_fwd", "bf16_bwd", "jvp_fwd", "mxfp4_fwd",
-           "mxfp4_fwd_ex", "mxfp4_cached", "mxfp4_decode", "mxfp4_decode_paged"]
+           "mxfp4_fwd_ex", "mxfp4_cached", "mxfp4_decode", "mxfp4_decode_paged", "mxfp4_varlen_paged"]
 
 _lib.load_ops()
 _ops = torch.ops.qattn
@@ -116,6 +118,12 @@ def _(q, k4, ks, vt, vs, lens, block_table, sk_max, causal, keys_per_split):
     B, H, S, D = q.shape
     return (q.new_empty((B, H, S, D), dtype=torch.float16),
             q.new_empty((B * H, S), dtype=torch.float32))
+
+
+@torch.library.register_fake("qattn::mxfp4_varlen_paged")
+def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal, keys_per_split):
+    T, H, D = q.shape
+    return (q.new_empty((T, H, D), dtype=torch.float16), q.new_empty((T, H), dtype=torch.float32))
 
 
 # ---------------------------------------------------------------------------- autograd rules
@@ -238,3 +246,26 @@ def mxfp4_decode_paged(q, cache, causal=False, keys_per_split=None):
     _, _, sk_max, _, _ = _decode_plan(q, cache, causal, keys_per_split, PagedKVFP4)
     return _ops.mxfp4_decode_paged(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens, cache.block_table,
                                    sk_max, int(bool(causal)), 0 if keys_per_split is None else int(keys_per_split))
+
+
+def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=None):
+    """``kv_cache_mxfp4.attention_mxfp4_varlen_paged`` as one operator: packed q [T, Hq, 128] against
+    a ``PagedKVFP4``, the ``q_lens[j]`` tokens of slot ``seq_ids[j]`` over that sequence's own length
+    and pages -> (O fp16 [T, Hq, 128], lse fp32 [T, Hq]).  The plan (``plan_varlen``) is made and checked
+    here, on the cache's host mirror, and its two tables are uploaded without a synchronisation; the
+    operator reads only ``lens``, ``block_table`` and the tables on the device."""
+    from .kv_cache_mxfp4 import PagedKVFP4, _packed_lists, plan_varlen
+    if not isinstance(cache, PagedKVFP4):
+        raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PagedKVFP4")
+    if q.dim() != 3:
+        raise _lib.QAttnError("qattn mxfp4 paged cache: packed queries must be q [T, Hq, 128]")
+    ids, sq = _packed_lists(cache.alloc.max_seqs, seq_ids, q_lens, "q_lens")
+    if sum(sq) != q.shape[0]:
+        raise _lib.QAttnError(f"qattn mxfp4 paged cache: q holds {q.shape[0]} tokens, q_lens sum to {sum(sq)}")
+    kps, seq_rec, work, part_rows = plan_varlen(cache.lengths, ids, sq, q.shape[1], cache.k4.shape[1],
+                                                keys_per_split, causal)
+    _lib.require_gpu(q, cache.k4)
+    rec_d = torch.tensor(seq_rec, dtype=torch.int32).to(q.device, non_blocking=True)
+    work_d = torch.tensor(work, dtype=torch.int32).to(q.device, non_blocking=True)
+    return _ops.mxfp4_varlen_paged(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens, cache.block_table,
+                                   rec_d, work_d, part_rows, int(bool(causal)), kps)
