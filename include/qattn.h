@@ -512,6 +512,29 @@ int qattn_mxfp4_attn_fwd_varlen_paged(const void* q4, const void* qscale, const 
                                       long page_tokens, long max_pages_per_seq, int causal,
                                       int keys_per_split, int head_dim, float qks, void* stream);
 
+/* The packed step with a sliding window and attention sinks: the entry above with causal == 2 and one
+ * (window >= 1, sinks >= 0) for the call.  Packed token i of sequence j sits at position p = L_j - n_j + i
+ * and sees key k iff k <= p and (k > p - window or k < sinks); every token sees itself.  With nt =
+ * ceil(L_j / 64), T = keys_per_split / 64, wt0 = max(0, L_j - n_j - window + 1) / 64 (the first tile any
+ * window of j reaches) and nst = ceil(min(sinks, L_j) / 64) sink tiles:
+ *   wt0 <= nst (the runs touch): seq_rec[j][5] = seq_rec[j][6] = 0, ns_j = ceil(nt / T) and split s runs
+ *     tiles [s T, min(nt, s T + T)), as in the entry above;
+ *   wt0 >  nst (a gap): seq_rec[j][5] = wt0, seq_rec[j][6] = nst, ns_j = 1 + ceil((nt - wt0) / T); split 0
+ *     runs the sink tiles [0, nst) whatever T is, split s >= 1 tiles [wt0 + (s-1) T, min(nt, wt0 + s T)).
+ *     Without sinks (nst = 0) there is no sink split: ns_j = ceil((nt - wt0) / T), split s starts at
+ *     wt0 + s T.
+ * The pages of the tiles in the gap are never fetched and their block_table entries never used, so they
+ * may have been given back to the pool.  Partial rows, work records, clamping and the merge
+ * (qattn_mxfp4_varlen_combine) are the entry's above; a row that sees no key of a split writes the empty
+ * state (-inf, 0).  With window >= every L_j the bits are those of the entry above at causal == 2.
+ * Returns 1 without a launch for window < 1, sinks < 0, causal != 2, and as the entry above. */
+int qattn_mxfp4_attn_fwd_varlen_paged_window(
+    const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt, const void* vscale,
+    void* opart, void* ml, const void* lens, const void* block_table, const void* seq_rec, const void* work,
+    long nseq, long nwork, long tokens, long part_rows, long max_seqs, long kv_heads, long group,
+    long num_pages, long page_tokens, long max_pages_per_seq, int causal, int keys_per_split, int head_dim,
+    float qks, long window, long sinks, void* stream);
+
 /* The merge of the packed step: qattn_mxfp4_split_combine's arithmetic in its order, per packed row
  * (token, query head), over the ns_j partial rows of the token's own sequence (found by binary search
  * over seq_rec's first-token column): out f16 [tokens][q_heads][128], lse f32 [tokens][q_heads].

@@ -430,10 +430,17 @@ QA_DEVICE unsigned mx_load_q(const uint8_t* q4, const uint8_t* qs, long r, int h
 // One 64-key tile, landed in ring slot sl, into the running state (o, m, l) of the lane's query row.
 // CAUSAL and diag (wave-uniform): the tile crosses the diagonal and the lane sees element r of half u
 // iff 32u + 8(r>>2) + (r&3) <= lim; otherwise every key of the tile is visible.
-template <int D, bool CAUSAL>
+// WINDOW (with CAUSAL; a sliding window with sinks): the mask has a lower edge too, element e is
+// visible iff e <= lim && (e >= lo || e <= slim), lo the first element of the lane's window and slim
+// the last sink element, both relative to the tile and the lane half as lim is.  The three limits are
+// all a lane carries; every compare is against a constant e and feeds its select at once.
+template <int D, bool CAUSAL, bool WINDOW = false>
 QA_DEVICE void mx_tile(const char* sl, const v4i (&qf)[MxCfg<D>::NKS], unsigned qsw,
                        v16f (&o)[MxCfg<D>::NDB], float& m, float& l, bool diag, int lim, float qks, int lane,
-                       int h, int c32) {
+                       int h, int c32, int lo = 0, int slim = 0) {
+  static_assert(CAUSAL || !WINDOW, "a window is causal");
+  // WINDOW: element e of the lane is visible
+  const auto seen = [&](int e) { return e <= lim && (e >= lo || e <= slim); };
   using C = MxCfg<D>;
   // S^T for the two 32-key halves u: A = K rows 32u + c32, k = 64s + 32h .. +32
   v16f acc[2];
@@ -456,7 +463,14 @@ QA_DEVICE void mx_tile(const char* sl, const v4i (&qf)[MxCfg<D>::NKS], unsigned 
   // integer (log2 units) raised only when the row max exceeds it by more than MSLACK, so every
   // rescale is an exact power of two and, between raises, P <= 2^MSLACK needs no rescale at all.
   float amx;
-  if (CAUSAL && diag) {
+  if (WINDOW && diag) {
+    amx = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        amx = seen(32 * u + 8 * (r >> 2) + (r & 3)) ? fmaxf(amx, acc[u][r]) : amx;
+  } else if (CAUSAL && diag) {
     amx = -INFINITY;
 #pragma unroll
     for (int u = 0; u < 2; ++u)
@@ -488,7 +502,13 @@ QA_DEVICE void mx_tile(const char* sl, const v4i (&qf)[MxCfg<D>::NKS], unsigned 
   for (int u = 0; u < 2; ++u)
 #pragma unroll
     for (int r = 0; r < 16; ++r) x[16 * u + r] = exp2_f32(__builtin_fmaf(acc[u][r], qks, nm));
-  if (CAUSAL && diag) {   // masked P is exactly 0 (a select: exp2 of a masked score may be inf)
+  if (WINDOW && diag) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        x[16 * u + r] = seen(32 * u + 8 * (r >> 2) + (r & 3)) ? x[16 * u + r] : 0.f;
+  } else if (CAUSAL && diag) {   // masked P is exactly 0 (a select: exp2 of a masked score may be inf)
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -622,15 +642,29 @@ __global__ __launch_bounds__(256, CAUSAL ? QA_MX_OCC_CAUSAL : QA_MX_OCC) void mx
 // row base = first partial row + (split * hps + head) * rows + q0 (opart f32 [part_rows][D], ml f32 x 2
 // [part_rows]).  Slot, packed row and partial rows are clamped / bounded by the sizes in MxVarlen, so
 // a wrong table gives a wrong answer, never an address outside q, the tables' slots or the partials.
+// WINDOW (with VARLEN and CAUSAL; a sliding window of vl.window keys with vl.sinks sink keys): row r at
+// position p = r % sq + len - sq sees key j iff j <= p and (j > p - window or j < sinks).  Three things
+// differ from the VARLEN instantiation.  The mask has a lower edge (mx_tile WINDOW), `diag` being set
+// when any row of the wave masks any key of the tile on either edge.  A wave also skips a tile that lies
+// below the lower edge of all its rows and holds no sink key, as it skips one above its diagonal.  And
+// the tile range need not start at 0: rec[5] = wt0 is the first tile of the window run and rec[6] = nsink
+// the sink tiles when there is a gap between the two (else both are 0 and the tiles are VARLEN's); with
+// sink tiles split 0 is the sink run [0, nsink) and split s >= 1 runs kps keys from tile wt0 + (s - 1) *
+// kps / 64, without them split s starts at wt0 + s * kps / 64.  The workgroup still runs one contiguous
+// range, so MxPagedRing starts at its first tile as it is and never enters a page of the gap (the host
+// may have given those back: PagedKVFP4.trim).  Both numbers are clamped; a first tile past the
+// sequence is the empty state.  tests/mxfp4_window_ref.py restates it, tests/test_gpu_mxfp4_window.py
+// checks it.
 struct MxVarlen {
   const int* work;      // i32 [nwork][4]
   const int* seq_rec;   // i32 [nseq][8]
   int nseq, group;      // sequences of the call, query heads per key/value head
   long qrows;           // T * group * hps packed query rows
   long part_rows;
+  int window, sinks;    // WINDOW: W >= 1 keys a query looks back (itself included), S >= 0 sink keys
 };
 
-template <int D, bool CAUSAL, bool LEN = false, bool PAGED = false, bool VARLEN = false>
+template <int D, bool CAUSAL, bool LEN = false, bool PAGED = false, bool VARLEN = false, bool WINDOW = false>
 __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
     const uint8_t* __restrict__ q4, const uint8_t* __restrict__ qs, const uint8_t* __restrict__ k4,
     const uint8_t* __restrict__ ks, const uint8_t* __restrict__ vt, const uint8_t* __restrict__ vs,
@@ -641,10 +675,12 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
   constexpr bool MASK = CAUSAL || LEN;
   static_assert(LEN || !PAGED, "the paged pool has a length per sequence");
   static_assert(PAGED || !VARLEN, "the packed step runs over the paged pool");
+  static_assert(!WINDOW || (VARLEN && CAUSAL), "the window is the packed step's, and causal");
   static_assert(sizeof(float) == 4 && D == 128, "fp32 staging in two passes fills the ring exactly");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int bh, qt, split = (int)blockIdx.y;
   long qbase = 0, pbase = 0;   // VARLEN: the sequence's first packed token and first partial row
+  int wt0 = 0, nsink = 0;      // WINDOW: first tile of the window run; sink tiles when there is a gap, else 0
   if constexpr (VARLEN) {
     typedef const __attribute__((address_space(4))) int* table_ptr;
     const int hd = (int)(blockIdx.x % (unsigned)hps);
@@ -657,6 +693,10 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
     sq_head = max(rec[2], 1);
     pbase = rec[4];
     rows = vl.group * sq_head;
+    if constexpr (WINDOW) {
+      wt0 = max(rec[5], 0);
+      nsink = max(rec[6], 0);
+    }
   } else {
     const int nrb = (rows + C::QROWS - 1) / C::QROWS;
     xcd_remap(blockIdx.x, nrb, BHV, bh, qt);
@@ -674,7 +714,13 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
   const int nt = LEN ? (len + C::KT - 1) / C::KT : Sk / C::KT;
   const int ntc = Sk / C::KT;   // tile stride of a key/value head in vt / vs
   // this workgroup's tiles [t0, t0 + ntw) of the key/value head: ntw >= 1 (nsplit = ceil(Sk / kps))
-  const int t0 = split * (kps / C::KT);
+  // WINDOW: with a gap split 0 is the sink run [0, nsink) and split s >= 1 starts kps keys after split
+  // s - 1 from tile wt0; without one (nsink = 0, wt0 = 0) the tiles are the ones below.  A first tile past
+  // nt (a wrong table) is nt: the empty state.
+  const bool sink_run = WINDOW && nsink > 0 && split == 0;
+  const int t0 = !WINDOW ? split * (kps / C::KT)
+                         : sink_run ? 0
+                                    : (int)min((long)wt0 + (long)(split - (nsink > 0)) * (kps / C::KT), (long)nt);
   // the wave's first row of opart / ml
   const auto part_row0 = [&]() -> long {
     if constexpr (VARLEN) return pbase + ((long)split * hps + bh % hps) * rows + q0;
@@ -696,7 +742,7 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
       return;
     }
   }
-  const int ntw = min(nt - t0, kps / C::KT);
+  const int ntw = sink_run ? min(nsink, nt) : min(nt - t0, kps / C::KT);
   // causal: query positions of the wave's rows (a wave that crosses a head boundary holds both ends)
   int wmin = 0, wmax = 0, pos = 0;
   if constexpr (CAUSAL) {
@@ -740,17 +786,29 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
     if (!active) continue;   // a wave without rows keeps its share of the DMA and the barrier
     bool diag = false;
     int lim = 0;
+    [[maybe_unused]] int lo = 0, slim = 0;
     if constexpr (CAUSAL) {
       const int k0 = C::KT * (t0 + t);
       if (k0 > wmax + qoff) continue;           // no row of the wave sees the tile: m, l, O unchanged
       diag = k0 + C::KT - 1 > wmin + qoff;
       lim = pos + qoff - k0 - 4 * h;
+      if constexpr (WINDOW) {
+        // the tile lies below every row's window and holds no sink key: skipped like the one above
+        if (k0 + C::KT - 1 < wmin + qoff - vl.window + 1 && k0 >= vl.sinks) continue;
+        // some row's lower edge cuts the tile (the highest edge is the last row's), unless it is all sinks
+        diag = diag || (k0 < wmax + qoff - vl.window + 1 && k0 + C::KT > vl.sinks);
+        lo = pos + qoff - vl.window + 1 - k0 - 4 * h;
+        slim = vl.sinks - 1 - k0 - 4 * h;
+      }
     } else if constexpr (LEN) {   // every row sees the keys <= len - 1
       const int k0 = C::KT * (t0 + t);
       diag = k0 + C::KT > len;
       lim = len - 1 - k0 - 4 * h;
     }
-    mx_tile<D, MASK>(smem + (t & 3) * C::SLOT, qf, qsw, o, m, l, diag, lim, qks, lane, h, c32);
+    if constexpr (WINDOW)
+      mx_tile<D, MASK, true>(smem + (t & 3) * C::SLOT, qf, qsw, o, m, l, diag, lim, qks, lane, h, c32, lo, slim);
+    else
+      mx_tile<D, MASK>(smem + (t & 3) * C::SLOT, qf, qsw, o, m, l, diag, lim, qks, lane, h, c32);
   }
   vmcnt_wait_all();
   __syncthreads();
@@ -1112,7 +1170,7 @@ static int mxfp4_split_paged_launch(const void* q4, const void* qscale, const vo
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
-template <bool CAUSAL>
+template <bool CAUSAL, bool WINDOW = false>
 static int mxfp4_varlen_paged_launch(const void* q4, const void* qscale, const void* k4, const void* kscale,
                                      const void* vt, const void* vscale, void* opart, void* ml,
                                      const void* lens, const void* btab, const MxVarlen& vl, long nwork,
@@ -1120,9 +1178,9 @@ static int mxfp4_varlen_paged_launch(const void* q4, const void* qscale, const v
                                      void* stream) {
   using C = MxCfg<128>;
   const int lds = C::NSLOT * C::SLOT;
-  { static LdsGrant granted_; if (!lds_grant((const void*)mxfp4_attn_split_kernel<128, CAUSAL, true, true, true>, lds, granted_)) return 1; }
+  { static LdsGrant granted_; if (!lds_grant((const void*)mxfp4_attn_split_kernel<128, CAUSAL, true, true, true, WINDOW>, lds, granted_)) return 1; }
   // rows, sq_head and qoff come from the records
-  hipLaunchKernelGGL((mxfp4_attn_split_kernel<128, CAUSAL, true, true, true>), dim3((unsigned)(nwork * hps)),
+  hipLaunchKernelGGL((mxfp4_attn_split_kernel<128, CAUSAL, true, true, true, WINDOW>), dim3((unsigned)(nwork * hps)),
                      dim3(256), lds, (hipStream_t)stream, (const uint8_t*)q4, (const uint8_t*)qscale,
                      (const uint8_t*)k4, (const uint8_t*)kscale, (const uint8_t*)vt, (const uint8_t*)vscale,
                      (float*)opart, (float2*)ml, (int)(slots * hps), 0, 1, (int)(mpp * (64L << lgt)), kps, qks,
@@ -1307,6 +1365,37 @@ extern "C" int qattn_mxfp4_attn_fwd_varlen_paged(const void* q4, const void* qsc
   return mxfp4_varlen_paged_launch<false>(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table,
                                           vl, nwork, max_seqs, kv_heads, num_pages, lgt, max_pages_per_seq,
                                           keys_per_split, qks, stream);
+}
+
+// the packed step with a sliding window and sinks (kernel: mxfp4_attn_split_kernel WINDOW): query i of
+// sequence j at position p = L_j - n_j + i sees key k iff k <= p and (k > p - window or k < sinks).  The
+// arguments and limits of the entry above; seq_rec[j][5], [6] carry the sequence's first window tile and
+// its sink tiles (plan_varlen with a window).  The merge is qattn_mxfp4_varlen_combine.
+extern "C" int qattn_mxfp4_attn_fwd_varlen_paged_window(
+    const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt, const void* vscale,
+    void* opart, void* ml, const void* lens, const void* block_table, const void* seq_rec, const void* work,
+    long nseq, long nwork, long tokens, long part_rows, long max_seqs, long kv_heads, long group,
+    long num_pages, long page_tokens, long max_pages_per_seq, int causal, int keys_per_split, int head_dim,
+    float qks, long window, long sinks, void* stream) {
+  if (window < 1 || sinks < 0 || causal != 2) return 1;
+  if (head_dim != 128 || nseq < 0 || nwork < 0 || tokens < 0 || part_rows < 0) return 1;
+  if (!lens || !block_table || !seq_rec || !work) return 1;
+  const int lgt = mx_page_lgt(page_tokens);
+  if (!mx_pool_ok(num_pages, kv_heads, lgt, max_pages_per_seq)) return 1;
+  if (keys_per_split < 64 || keys_per_split % 64 != 0) return 1;
+  if (max_seqs < 1 || group < 1 || group > 0x7fffffffL) return 1;
+  if (nseq == 0 || nwork == 0 || tokens == 0) return 0;
+  if (nseq > max_seqs || nseq > tokens || part_rows < 1) return 1;
+  if (tokens > 0x7fffffffL / (group * kv_heads) || part_rows > 0x7fffffffL) return 1;
+  if (nwork > 0x7fffffffL / kv_heads || max_seqs > 0x7fffffffL / kv_heads) return 1;
+  // a sequence holds at most 2^25 keys (mx_pool_ok): a larger window or sink count means the same, and
+  // the kernel's 32-bit edges cannot overflow
+  const long big = 1L << 26;
+  const MxVarlen vl{(const int*)work, (const int*)seq_rec, (int)nseq, (int)group, tokens * group * kv_heads,
+                    part_rows, (int)(window < big ? window : big), (int)(sinks < big ? sinks : big)};
+  return mxfp4_varlen_paged_launch<true, true>(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens,
+                                               block_table, vl, nwork, max_seqs, kv_heads, num_pages, lgt,
+                                               max_pages_per_seq, keys_per_split, qks, stream);
 }
 
 // the merge of the packed step's compact partials into O f16 [tokens][q_heads][128], lse [tokens][q_heads]

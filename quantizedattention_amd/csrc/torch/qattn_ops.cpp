@@ -28,6 +28,8 @@
 //       kv_cache_mxfp4.attention_mxfp4_decode on a preallocated cache's operands and device lengths
 //   mxfp4_decode_paged(q, k4, ks, vt, vs, lens, block_table, sk_max, causal, keys_per_split) -> (O, lse)
 //       kv_cache_mxfp4.attention_mxfp4_decode_paged on a page pool's operands, lengths and block table
+//   mxfp4_varlen_paged_window(.. the arguments of mxfp4_varlen_paged .., window, sinks) -> (O, lse)
+//       the same with a sliding window and sinks (causal only)
 //   mxfp4_varlen_paged(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal,
 //                      keys_per_split) -> (O, lse)
 //       kv_cache_mxfp4.attention_mxfp4_varlen_paged: packed q [T, Hq, 128] and the two plan tables
@@ -575,12 +577,14 @@ std::tuple<Tensor, Tensor> mxfp4_decode_paged(const Tensor& q_in, const Tensor& 
 // plan's part_rows and keys_per_split.  The operator cannot read any of them without a synchronisation:
 // the caller guarantees that they are a plan of the pool's lengths (the Python wrapper
 // ops.mxfp4_varlen_paged builds them from the cache's host mirror); the kernels keep every address a
-// wrong table names inside the buffers.
-std::tuple<Tensor, Tensor> mxfp4_varlen_paged(const Tensor& q_in, const Tensor& k4, const Tensor& ks,
-                                              const Tensor& vt, const Tensor& vs, const Tensor& lens,
-                                              const Tensor& block_table, const Tensor& seq_rec,
-                                              const Tensor& work, int64_t part_rows, int64_t causal,
-                                              int64_t keys_per_split) {
+// wrong table names inside the buffers.  With `windowed` the plan is plan_varlen's for (window, sinks) and
+// the forward is qattn_mxfp4_attn_fwd_varlen_paged_window.
+std::tuple<Tensor, Tensor> mxfp4_varlen_paged_run(const Tensor& q_in, const Tensor& k4, const Tensor& ks,
+                                                  const Tensor& vt, const Tensor& vs, const Tensor& lens,
+                                                  const Tensor& block_table, const Tensor& seq_rec,
+                                                  const Tensor& work, int64_t part_rows, int64_t causal,
+                                                  int64_t keys_per_split, bool windowed, int64_t window,
+                                                  int64_t sinks) {
   require_gpu({&q_in, &k4, &ks, &vt, &vs, &lens, &block_table, &seq_rec, &work});
   TORCH_CHECK(q_in.dim() == 3 && k4.dim() == 4 && q_in.size(2) == 128 && k4.size(3) == 64,
               "qattn mxfp4 paged cache: packed queries must be q [T, Hq, 128], head_dim 128 in the pool");
@@ -619,15 +623,44 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged(const Tensor& q_in, const Tensor& 
   Tensor out = empty({T, Hq, D}, at::kHalf, q), lse = empty({T, Hq}, at::kFloat, q);
   call(qattn_mxfp4_quant_rows(P(q), nullptr, P(q4), P(qs), T * Hq, Hq, (int)D, c.stream), "quantise q");
   Tensor opart = empty({part_rows, D}, at::kFloat, q), ml = empty({part_rows, 2}, at::kFloat, q);
-  call(qattn_mxfp4_attn_fwd_varlen_paged(P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens),
-                                         P(block_table), P(seq_rec), P(work), seq_rec.size(0), work.size(0),
-                                         T, part_rows, B, Hkv, Hq / Hkv, NP, PT, mpp, causal ? 2 : 0,
-                                         (int)keys_per_split, (int)D, qk_scale(D), c.stream),
-       "mxfp4 varlen forward");
+  if (windowed)
+    call(qattn_mxfp4_attn_fwd_varlen_paged_window(
+             P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens), P(block_table), P(seq_rec),
+             P(work), seq_rec.size(0), work.size(0), T, part_rows, B, Hkv, Hq / Hkv, NP, PT, mpp, causal ? 2 : 0,
+             (int)keys_per_split, (int)D, qk_scale(D), (long)window, (long)sinks, c.stream),
+         "mxfp4 windowed varlen forward");
+  else
+    call(qattn_mxfp4_attn_fwd_varlen_paged(P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens),
+                                           P(block_table), P(seq_rec), P(work), seq_rec.size(0), work.size(0),
+                                           T, part_rows, B, Hkv, Hq / Hkv, NP, PT, mpp, causal ? 2 : 0,
+                                           (int)keys_per_split, (int)D, qk_scale(D), c.stream),
+         "mxfp4 varlen forward");
   call(qattn_mxfp4_varlen_combine(P(opart), P(ml), P(out), P(lse), P(seq_rec), seq_rec.size(0), T, Hq, Hkv,
                                   part_rows, (int)D, c.stream),
        "mxfp4 varlen merge");
   return {out, lse};
+}
+
+std::tuple<Tensor, Tensor> mxfp4_varlen_paged(const Tensor& q, const Tensor& k4, const Tensor& ks,
+                                              const Tensor& vt, const Tensor& vs, const Tensor& lens,
+                                              const Tensor& block_table, const Tensor& seq_rec,
+                                              const Tensor& work, int64_t part_rows, int64_t causal,
+                                              int64_t keys_per_split) {
+  return mxfp4_varlen_paged_run(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal,
+                                keys_per_split, false, 0, 0);
+}
+
+// the same with a sliding window and sinks (kv_cache_mxfp4.attention_mxfp4_varlen_paged(window=, sinks=)):
+// causal only; seq_rec and work are plan_varlen's for the same (window, sinks)
+std::tuple<Tensor, Tensor> mxfp4_varlen_paged_window(const Tensor& q, const Tensor& k4, const Tensor& ks,
+                                                     const Tensor& vt, const Tensor& vs, const Tensor& lens,
+                                                     const Tensor& block_table, const Tensor& seq_rec,
+                                                     const Tensor& work, int64_t part_rows, int64_t causal,
+                                                     int64_t keys_per_split, int64_t window, int64_t sinks) {
+  TORCH_CHECK(window >= 1 && sinks >= 0, "qattn mxfp4 paged cache: window >= 1 and sinks >= 0 expected");
+  TORCH_CHECK(causal == 1, "qattn mxfp4 paged cache: a window implies causal attention (causal must be 1)");
+  return mxfp4_varlen_paged_run(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal,
+                                keys_per_split, true, window, sinks);
 }
 
 }  // namespace
@@ -652,6 +685,9 @@ TORCH_LIBRARY(qattn, m) {
         "int sk_max, int causal, int keys_per_split) -> (Tensor, Tensor)");
   m.def("mxfp4_varlen_paged(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, Tensor block_table, "
         "Tensor seq_rec, Tensor work, int part_rows, int causal, int keys_per_split) -> (Tensor, Tensor)");
+  m.def("mxfp4_varlen_paged_window(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, "
+        "Tensor block_table, Tensor seq_rec, Tensor work, int part_rows, int causal, int keys_per_split, "
+        "int window, int sinks) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
@@ -667,4 +703,5 @@ TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
   m.impl("mxfp4_decode", &mxfp4_decode);
   m.impl("mxfp4_decode_paged", &mxfp4_decode_paged);
   m.impl("mxfp4_varlen_paged", &mxfp4_varlen_paged);
+  m.impl("mxfp4_varlen_paged_window", &mxfp4_varlen_paged_window);
 }

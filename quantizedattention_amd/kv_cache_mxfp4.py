@@ -82,6 +82,24 @@ sequence j keeps the keys <= L_j - n_j + i, what a prefill chunk needs after its
 sequence gets, bit for bit, what :func:`attention_mxfp4_decode` gives for it alone with Sq = n_j and the
 same keys per split.
 
+A sliding window with sinks (``window=W >= 1, sinks=S >= 0``, Python ints, one pair per call since layers
+differ; causal only) narrows the mask: query i of sequence j at position p = L_j - n_j + i sees key k
+iff ``k <= p and (k > p - W or k < S)``; every query sees itself and ``lse`` is over the visible keys (a
+smoothed cache needs nothing new).  The plan then runs only the tiles the call needs.  With nt =
+ceil(L_j / 64), wt0 = max(0, L_j - n_j - W + 1) // 64 (the first tile any window of j reaches) and nst =
+ceil(min(S, L_j) / 64) sink tiles: when wt0 <= nst the two runs touch and the splits are the causal
+call's; when wt0 > nst there is a gap, split 0 is the sink run [0, nst) (one split whatever ``kps`` is;
+no such split without sinks) and the next splits run kps keys each from tile wt0, so ns_j = (nst > 0) +
+ceil((nt - wt0) * 64 / kps); ``seq_rec[j][5:7]`` = [wt0, nst] (0, 0 when they touch)
+(``qattn_mxfp4_attn_fwd_varlen_paged_window``; the merge is unchanged).  The pages of the gap are never
+fetched, so :meth:`PagedKVFP4.trim` may give them back: it makes the pages p with p * P >= S and (p + 1)
+* P <= L - W + 1 -- those no query at a position >= L can see -- holes (None) in the host page list, one
+reference less each, keeps the logical page count (``append`` and ``reserve`` go on as before) and
+uploads nothing; the table entries of holes are unspecified.  Whatever would read a hole -- a call
+without a window, with a larger window or more sinks, ``attention_mxfp4_decode_paged``, ``gather``,
+``snapshot``, ``fork`` from that sequence -- raises :class:`QAttnError` naming "trimmed" before any
+launch; ``free`` works.
+
 Wire format (little-endian), the container of kv_cache.py with a magic of its own::
 
     offset 0   8 B   magic  b"QATTNKF4"
@@ -499,6 +517,7 @@ class PageAllocator:
         self._free = order[::-1]                  # handed out from the end
         self.refcount = [0] * num_pages
         self.pages = [[] for _ in range(max_seqs)]
+        self.nholes = [0] * max_seqs              # holes (``drop``) in each sequence's page list
         self.table = [[0] * max_pages_per_seq for _ in range(max_seqs)]
 
     @property
@@ -548,10 +567,44 @@ class PageAllocator:
         """Empty sequence ``b``: each of its pages loses a reference and returns to the free list at 0."""
         b = self._seq(b)
         for p in self.pages[b]:
+            if p is None:   # a hole (``drop``): given back already
+                continue
             self.refcount[p] -= 1
             if self.refcount[p] == 0:
                 self._free.append(p)
         self.pages[b] = []
+        self.nholes[b] = 0
+
+    def drop(self, b, first_page: int, last_page: int) -> int:
+        """Make pages ``[first_page, last_page)`` of sequence ``b`` holes -> the pages that returned to
+        the free list.  ``pages[b][i]`` becomes None and the page loses one reference (a page shared by
+        ``share`` just loses that one); ``len(pages[b])`` stays the logical page count, so ``reserve``
+        goes on as before and ``nholes[b]`` counts the holes.  ``table[b][i]`` keeps what it held and means nothing.  A page that is a
+        hole already is left alone.  All or nothing: a range outside the sequence's pages raises."""
+        b = self._seq(b)
+        first_page, last_page = int(first_page), int(last_page)
+        if not 0 <= first_page <= last_page <= len(self.pages[b]):
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: sequence {b} has no pages [{first_page}, "
+                                  f"{last_page}) to drop ({len(self.pages[b])} pages)")
+        freed = 0
+        for i in range(first_page, last_page):
+            p = self.pages[b][i]
+            if p is None:
+                continue
+            self.pages[b][i] = None
+            self.nholes[b] += 1
+            self.refcount[p] -= 1
+            if self.refcount[p] == 0:
+                self._free.append(p)
+                freed += 1
+        return freed
+
+    def holes(self, b, first_page: int = 0, last_page: Optional[int] = None) -> list:
+        """The indices in ``[first_page, last_page)`` (default: all) of sequence ``b``'s pages that are
+        holes."""
+        pages = self.pages[self._seq(b)]
+        last_page = len(pages) if last_page is None else min(int(last_page), len(pages))
+        return [i for i in range(max(int(first_page), 0), last_page) if pages[i] is None]
 
     def share(self, src, dst, shared: int, fresh: int = 0) -> list:
         """Make the empty sequence ``dst`` the first ``shared`` pages of ``src`` (one more reference
@@ -562,6 +615,9 @@ class PageAllocator:
                                   f"({len(self.pages[dst])} pages)")
         if not 0 <= shared <= len(self.pages[src]) or fresh < 0:
             raise _lib.QAttnError(f"qattn mxfp4 paged cache: sequence {src} has no {shared} pages to share")
+        if None in self.pages[src][:shared]:
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: sequence {src} has trimmed pages among its first "
+                                  f"{shared}; they cannot be shared")
         if shared + fresh > self.max_pages_per_seq or fresh > len(self._free):
             raise _lib.QAttnError(f"qattn mxfp4 paged cache: out of pages ({fresh} needed, "
                                   f"{len(self._free)} of {self.num_pages} free, max_pages_per_seq "
@@ -732,11 +788,42 @@ class PagedKVFP4:
             self.alloc.release(b)
         self._upload(table=False)
 
+    def _whole(self, b: int, what: str) -> None:
+        """Raise when sequence ``b`` has had pages trimmed: ``what`` would read them."""
+        if not self.alloc.nholes[b]:   # (a counter: this sits on every packed call's path)
+            return
+        holes = self.alloc.holes(b)
+        if holes:
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: {what} would read trimmed pages {holes} of "
+                                  f"sequence {b} (PagedKVFP4.trim gave them back to the pool)")
+
+    def trim(self, seq_ids, window: int, sinks: int = 0) -> int:
+        """Give back the pages of the listed sequences that no query at a position >= the sequence's
+        length L can see under ``(window, sinks)`` -- the queries of every later step, those of a chunk
+        appended later included: the pages p with ``p * P >= sinks`` and ``(p + 1) * P <= L - window +
+        1`` -> the number of pages that returned to the pool (a page still held by a fork does not).
+        The pages become holes of the sequence (:meth:`PageAllocator.drop`); lengths, logical page
+        counts and ``append`` are as before.  Host only: nothing is uploaded (the table entries of
+        holes are unspecified and never used), nothing is launched or synchronised.  Afterwards every
+        call that would read a hole raises :class:`QAttnError` naming "trimmed" before it launches: a
+        windowed call needs ``window`` and ``sinks`` no larger than the holes allow."""
+        W, S = _window_args(window, sinks, True)
+        seqs = [self.alloc._seq(b) for b in seq_ids]
+        P = self.page_tokens
+        freed = 0
+        for b in seqs:
+            first, last = -(-S // P), (self.lengths[b] - W + 1) // P
+            if last > first:
+                freed += self.alloc.drop(b, first, last)
+        return freed
+
     def fork(self, src: int, dst: int) -> None:
         """Make the empty sequence ``dst`` a copy of ``src`` that shares its memory: the ``L // P``
         full pages by reference count; a partial last page is copied into a fresh page on the device
-        (all heads, four operands), as are the ``vtail`` and ``k_mean`` rows.  Stream-ordered."""
+        (all heads, four operands), as are the ``vtail`` and ``k_mean`` rows.  Stream-ordered.  A
+        trimmed ``src`` is refused."""
         src, dst = self.alloc._seq(src), self.alloc._seq(dst)
+        self._whole(src, "fork")
         if self.lengths[dst]:
             raise _lib.QAttnError(f"qattn mxfp4 paged cache: fork into sequence {dst}, which is not empty "
                                   f"({self.lengths[dst]} tokens)")
@@ -754,7 +841,8 @@ class PagedKVFP4:
 
     def gather(self, b: int):
         """Copies of sequence ``b``'s pages in order, per head: (k4 [Hkv, n*P, D/2], ks [Hkv, n*P, D/32],
-        vt [Hkv, n*P/64, D, 32], vs [Hkv, n*P/64, D, 2]) for its n pages."""
+        vt [Hkv, n*P/64, D, 32], vs [Hkv, n*P/64, D, 2]) for its n pages.  A trimmed sequence is refused."""
+        self._whole(self.alloc._seq(b), "gather")
         pages = torch.tensor(self.alloc.pages[self.alloc._seq(b)], dtype=torch.long, device=self.k4.device)
         H = self.k4.shape[1]
         return tuple(t[pages].transpose(0, 1).reshape(H, -1, *t.shape[3:]) for t in self.kv)
@@ -763,6 +851,7 @@ class PagedKVFP4:
         """A :class:`QuantizedKVFP4` copy (batch 1) of sequence ``b``, whose length must be a
         multiple of 64 (and not 0)."""
         L = self.lengths[self.alloc._seq(b)]
+        self._whole(int(b), "snapshot")
         if L == 0 or L % BLOCK:
             raise _lib.QAttnError(f"qattn mxfp4 paged cache: snapshot needs a length of 64*n tokens, got {L}")
         k4, ks, vt, vs = self.gather(b)
@@ -781,6 +870,9 @@ def attention_mxfp4_decode_paged(q: torch.Tensor, cache: PagedKVFP4, causal: boo
     causal needs Sq <= min(lengths); the plan is ``_split_plan_fp4`` at ceil64(max(lengths)), and
     ``keys_per_split`` is any multiple of 64, whatever the page size."""
     bhv, rows, sk_max, kps, nsplit = _decode_plan(q, cache, causal, keys_per_split, PagedKVFP4)
+    if any(cache.alloc.nholes):   # this entry has no window: it reads every page
+        for b in range(cache.alloc.max_seqs):
+            cache._whole(b, "attention_mxfp4_decode_paged")
     _lib.require_gpu(q, cache.k4)
     B, Hkv, _, D = cache.shape
     Hq, Sq = q.shape[1], q.shape[2]
@@ -820,8 +912,40 @@ def _packed_lists(max_seqs: int, seq_ids, counts, what: str):
     return ids, cnt
 
 
+def _window_args(window, sinks, required: bool = False):
+    """``(window, sinks)`` of a call, checked -> (W, S) as ints, or (None, 0) without a window."""
+    if window is None:
+        if required:
+            raise _lib.QAttnError("qattn mxfp4 paged cache: a window >= 1 expected")
+        if sinks:
+            raise _lib.QAttnError("qattn mxfp4 paged cache: sinks without a window (sinks keep the first "
+                                  "keys visible below a window's lower edge)")
+        return None, 0
+    if not isinstance(window, int) or not isinstance(sinks, int) or window < 1 or sinks < 0:
+        raise _lib.QAttnError(f"qattn mxfp4 paged cache: window must be an int >= 1 and sinks an int >= 0, "
+                              f"got window {window!r}, sinks {sinks!r}")
+    return int(window), int(sinks)
+
+
+def _window_tiles(L: int, n: int, W: int, S: int):
+    """(wt0', nst', nt) of a sequence of L keys and n queries under window W and S sinks: the first tile
+    of the window run and the sink tiles when there is a gap between the two runs, else (0, 0)."""
+    nt = -(-L // BLOCK)
+    wt0, nst = max(0, L - n - W + 1) // BLOCK, -(-min(S, L) // BLOCK)
+    return (wt0, nst, nt) if wt0 > nst else (0, 0, nt)
+
+
+def _window_pages(L: int, n: int, W: int, S: int, P: int) -> list:
+    """The page indices a windowed call reads of a sequence of L keys and n queries: the pages of the
+    tiles it runs (the sink run and the window run, or every tile when the two touch)."""
+    wt0, nst, nt = _window_tiles(L, n, W, S)
+    tpp = P // BLOCK
+    pages = set(range(-(-nst // tpp))) if nst else set()
+    return sorted(pages | set(range(wt0 // tpp, -(-nt // tpp))))
+
+
 def plan_varlen(lengths, seq_ids, q_lens, Hq: int, Hkv: int, keys_per_split: Optional[int] = None,
-                causal: bool = False):
+                causal: bool = False, window: Optional[int] = None, sinks: int = 0):
     """The host plan of :func:`attention_mxfp4_varlen_paged` -> (kps, seq_rec, work, part_rows); pure
     Python on the host mirror ``lengths`` (one entry per slot), no device and no tensor.
 
@@ -846,11 +970,28 @@ def plan_varlen(lengths, seq_ids, q_lens, Hq: int, Hkv: int, keys_per_split: Opt
     every split < ns_j of every row block of every sequence once, ordered by descending tile count of
     the split (the longest workgroups start first); results do not depend on the order.
 
+    ``window`` (with ``sinks``; None: the plan above, unchanged): the windowed call's plan (module
+    docstring).  seq_rec[j][5:7] = [wt0, nst] when sequence j has a gap between its sink tiles and its
+    window's first tile, else [0, 0]; ns_j = (nst > 0) + ceil((nt - wt0) * 64 / kps); the sink split counts
+    nst tiles in the order of ``work``; and ``kps`` (given or the rule's, the rule taken at this sk_max) is
+    clamped to sk_max = 64 * max_j (tiles sequence j runs), not to the cached length.  Raises for window <
+    1, sinks < 0, sinks without a window, and a window without ``causal``.  Measured on one MI355X
+    (tools/time_decode_varlen.py --window 4096 --sinks 4, 2026-10-20, 64 decodes, 32 / 8 heads, P = 256, L
+    = 32768, median us of 3 x 20 alternating calls, range of the pass medians): windowed 217.2
+    (215.3..223.5), causal on the same pool 670.6 (669.2..671.5), causal on a pool of 4160 cached keys
+    164.2 (163.9..165.3): 0.32 of the causal call, 53 us behind the short one, host-bound (128 work
+    records against 64).  Kernels alone 91.2 / 653.8 / 84.7, the windowed one without sinks 90.3: the
+    sink split costs 0.9 us, the rest of the 6.5 us is the windowed instantiation.
+    ``free_pages`` before and after ``trim`` of that batch: 0 -> 7104 of 8192.
+
     Raises :class:`QAttnError` for an empty, duplicate or out-of-range slot list, a q_lens entry < 1, a
     listed slot of length 0, ``causal`` with q_lens[j] > L_j, Hq % Hkv != 0, a ``keys_per_split`` that
     is not a multiple of 64, and when T * Hq, part_rows or nwork * Hkv reach 2^31.  The slots that are
     not listed are not looked at.
     """
+    W, S = _window_args(window, sinks)
+    if W is not None and not causal:
+        raise _lib.QAttnError("qattn mxfp4 paged cache: a window implies causal attention; pass causal=True")
     lengths = [int(x) for x in lengths]
     ids, sq = _packed_lists(len(lengths), seq_ids, q_lens, "q_lens")
     if Hkv < 1 or Hq < 1 or Hq % Hkv:
@@ -865,6 +1006,9 @@ def plan_varlen(lengths, seq_ids, q_lens, Hq: int, Hkv: int, keys_per_split: Opt
     G = Hq // Hkv
     nrb = [-(-G * n // QROWS) for n in sq]
     sk_max = _ceil64(max(Ls))
+    if W is not None:   # (first window tile, sink tiles, tiles) per sequence; the tiles it actually runs
+        wt = [_window_tiles(L, n, W, S) for L, n in zip(Ls, sq)]
+        sk_max = BLOCK * max(nst + nt - wt0 for wt0, nst, nt in wt)
     if keys_per_split is None:
         kps = _lib.load().qattn_split_keys(Hkv * sum(nrb), 1, sk_max, BLOCK)
     else:
@@ -873,16 +1017,25 @@ def plan_varlen(lengths, seq_ids, q_lens, Hq: int, Hkv: int, keys_per_split: Opt
         raise _lib.QAttnError("qattn mxfp4 paged cache: keys_per_split must be a multiple of 64")
     kps = min(kps, sk_max)
     nsp = [-(-_ceil64(L) // kps) for L in Ls]
+    if W is not None:
+        nsp = [(1 if nst else 0) + -(-(nt - wt0) * BLOCK // kps) for wt0, nst, nt in wt]
     if (sum(sq) * Hq >= 1 << 31 or sum(ns * Hkv * G * n for ns, n in zip(nsp, sq)) >= 1 << 31
             or sum(ns * r for ns, r in zip(nsp, nrb)) * Hkv >= 1 << 31):
         raise _lib.QAttnError("qattn mxfp4 paged cache: a packed call of 2^31 or more query rows, partial "
                               "rows or workgroups")
     seq_rec, work, first, base = [], [], 0, 0
     for j, (b, n, L, ns) in enumerate(zip(ids, sq, Ls, nsp)):
-        seq_rec.append([b, first, n, ns, base, 0, 0, 0])
+        wt0, nst = wt[j][:2] if W is not None else (0, 0)
+        seq_rec.append([b, first, n, ns, base, wt0, nst, 0])
         nt = -(-L // BLOCK)
         for s in range(ns):
-            tiles = min(nt, (s + 1) * (kps // BLOCK)) - s * (kps // BLOCK)
+            if nst and s == 0:   # a gap: the sink split, then the window splits from wt0
+                tiles = nst
+            elif W is not None:
+                t0 = wt0 + (s - (1 if nst else 0)) * (kps // BLOCK)
+                tiles = min(nt, t0 + kps // BLOCK) - t0
+            else:
+                tiles = min(nt, (s + 1) * (kps // BLOCK)) - s * (kps // BLOCK)
             work += [(tiles, [j, rb, s, 0]) for rb in range(nrb[j])]
         first += n
         base += ns * Hkv * G * n
@@ -890,9 +1043,28 @@ def plan_varlen(lengths, seq_ids, q_lens, Hq: int, Hkv: int, keys_per_split: Opt
     return kps, seq_rec, [w for _, w in work], base
 
 
+def _check_trimmed(cache: "PagedKVFP4", ids, sq, W, S) -> None:
+    """Raise when a packed call over ``ids`` with ``sq`` queries each and window ``(W, S)`` (W None: no
+    window) would read a page that :meth:`PagedKVFP4.trim` gave back."""
+    P = cache.page_tokens
+    for b, n in zip(ids, sq):
+        if W is None:
+            cache._whole(b, "a call without a window")
+            continue
+        if not cache.alloc.nholes[b]:
+            continue
+        pages = cache.alloc.pages[b]
+        bad = [p for p in _window_pages(cache.lengths[b], n, W, S, P) if p < len(pages) and pages[p] is None]
+        if bad:
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: window {W} with {S} sinks and {n} queries would "
+                                  f"read trimmed pages {bad} of sequence {b} (it was trimmed for a smaller "
+                                  "window or fewer sinks)")
+
+
 @torch.no_grad()
 def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_lens, causal: bool = False,
-                                 keys_per_split: Optional[int] = None):
+                                 keys_per_split: Optional[int] = None, window: Optional[int] = None,
+                                 sinks: int = 0):
     """A ragged batch against a paged cache in one attention launch and one merge: packed fp16 queries
     ``q`` [T, Hq, D], token-major, the ``q_lens[0]`` tokens of sequence ``seq_ids[0]`` first, then
     those of ``seq_ids[1]``, ... (nseq >= 1 distinct slots, every q_lens[j] >= 1, T = sum(q_lens)) ->
@@ -901,8 +1073,12 @@ def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_
     sequence j keeps the keys <= L_j - q_lens[j] + i: a prefill chunk after its own append).  The slots
     that are not listed may be empty or hold anything: their lengths, table rows and pages are never
     read.  Every sequence gets, bit for bit, what :func:`attention_mxfp4_decode` gives for it alone
-    with Sq = q_lens[j] and the same keys per split.  Raises before any launch as :func:`plan_varlen`
-    does, and for sum(q_lens) != T.  Stream-ordered: the plan comes from the host mirror, its two
+    with Sq = q_lens[j] and the same keys per split.  ``window`` (with ``sinks``; causal only) is the
+    sliding window with sinks of the module docstring, through
+    ``qattn_mxfp4_attn_fwd_varlen_paged_window``; a window at least as long as every sequence gives the
+    causal call's bits.  Raises before any launch (and before any tensor is made) as
+    :func:`plan_varlen` does, for sum(q_lens) != T, and when a listed sequence has had a page trimmed
+    that this call would read.  Stream-ordered: the plan comes from the host mirror, its two
     tables are uploaded without a synchronisation, nothing is read back."""
     if not isinstance(cache, PagedKVFP4):
         raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PagedKVFP4")
@@ -915,7 +1091,10 @@ def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_
     ids, sq = _packed_lists(cache.alloc.max_seqs, seq_ids, q_lens, "q_lens")
     if sum(sq) != T:
         raise _lib.QAttnError(f"qattn mxfp4 paged cache: q holds {T} tokens, q_lens sum to {sum(sq)}")
-    kps, seq_rec, work, part_rows = plan_varlen(cache.lengths, ids, sq, Hq, Hkv, keys_per_split, causal)
+    kps, seq_rec, work, part_rows = plan_varlen(cache.lengths, ids, sq, Hq, Hkv, keys_per_split, causal,
+                                                window, sinks)
+    W, S = _window_args(window, sinks)
+    _check_trimmed(cache, ids, sq, W, S)
     _lib.require_gpu(q, cache.k4)
     dev, st = q.device, _lib.stream_of(q)
     # from fresh pageable host tensors, as PagedKVFP4._upload: staged before the copies return
@@ -926,11 +1105,15 @@ def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_
     lse = torch.empty((T, Hq), dtype=torch.float32, device=dev)
     opart = torch.empty((part_rows, D), dtype=torch.float32, device=dev)
     ml = torch.empty((part_rows, 2), dtype=torch.float32, device=dev)
-    _lib.call("qattn_mxfp4_attn_fwd_varlen_paged", _lib.ptr(q4), _lib.ptr(qs), _lib.ptr(cache.k4),
-              _lib.ptr(cache.ks), _lib.ptr(cache.vt), _lib.ptr(cache.vs), _lib.ptr(opart), _lib.ptr(ml),
-              _lib.ptr(cache.lens), _lib.ptr(cache.block_table), _lib.ptr(rec_d), _lib.ptr(work_d), len(ids),
-              len(work), T, part_rows, cache.alloc.max_seqs, Hkv, Hq // Hkv, cache.num_pages,
-              cache.page_tokens, cache.alloc.max_pages_per_seq, 2 if causal else 0, kps, D, _qk_scale(D), st)
+    args = (_lib.ptr(q4), _lib.ptr(qs), _lib.ptr(cache.k4),
+            _lib.ptr(cache.ks), _lib.ptr(cache.vt), _lib.ptr(cache.vs), _lib.ptr(opart), _lib.ptr(ml),
+            _lib.ptr(cache.lens), _lib.ptr(cache.block_table), _lib.ptr(rec_d), _lib.ptr(work_d), len(ids),
+            len(work), T, part_rows, cache.alloc.max_seqs, Hkv, Hq // Hkv, cache.num_pages,
+            cache.page_tokens, cache.alloc.max_pages_per_seq, 2 if causal else 0, kps, D, _qk_scale(D))
+    if W is None:
+        _lib.call("qattn_mxfp4_attn_fwd_varlen_paged", *args, st)
+    else:   # no sequence holds 2^25 keys or more: a larger window or sink count means the same
+        _lib.call("qattn_mxfp4_attn_fwd_varlen_paged_window", *args, min(W, 1 << 26), min(S, 1 << 26), st)
     _lib.call("qattn_mxfp4_varlen_combine", _lib.ptr(opart), _lib.ptr(ml), _lib.ptr(O), _lib.ptr(lse),
               _lib.ptr(rec_d), len(ids), T, Hq, Hkv, part_rows, D, st)
     return O, lse

@@ -22,6 +22,8 @@ the autograd rules of ``int8_fwd`` and ``bf16_fwd`` (their backward operators).
                                        keys_per_split) -> (O, lse)
     torch.ops.qattn.mxfp4_varlen_paged(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows,
                                        causal, keys_per_split) -> (O, lse)
+    torch.ops.qattn.mxfp4_varlen_paged_window(q, k4, ks, vt, vs, lens, block_table, seq_rec, work,
+                                              part_rows, causal, keys_per_split, window, sinks) -> (O, lse)
 
 Shapes follow the drop-in functions (attention_int8.py:259-262 for the int8 outputs) except that
 k_i8 is returned row-major [B*Hkv*Sk, D] (the drop-in's k_i8T is its transposed view: an operator
@@ -122,6 +124,12 @@ def _(q, k4, ks, vt, vs, lens, block_table, sk_max, causal, keys_per_split):
 
 @torch.library.register_fake("qattn::mxfp4_varlen_paged")
 def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal, keys_per_split):
+    T, H, D = q.shape
+    return (q.new_empty((T, H, D), dtype=torch.float16), q.new_empty((T, H), dtype=torch.float32))
+
+
+@torch.library.register_fake("qattn::mxfp4_varlen_paged_window")
+def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal, keys_per_split, window, sinks):
     T, H, D = q.shape
     return (q.new_empty((T, H, D), dtype=torch.float16), q.new_empty((T, H), dtype=torch.float32))
 
@@ -248,13 +256,15 @@ def mxfp4_decode_paged(q, cache, causal=False, keys_per_split=None):
                                    sk_max, int(bool(causal)), 0 if keys_per_split is None else int(keys_per_split))
 
 
-def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=None):
+def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=None, window=None, sinks=0):
     """``kv_cache_mxfp4.attention_mxfp4_varlen_paged`` as one operator: packed q [T, Hq, 128] against
     a ``PagedKVFP4``, the ``q_lens[j]`` tokens of slot ``seq_ids[j]`` over that sequence's own length
     and pages -> (O fp16 [T, Hq, 128], lse fp32 [T, Hq]).  The plan (``plan_varlen``) is made and checked
     here, on the cache's host mirror, and its two tables are uploaded without a synchronisation; the
-    operator reads only ``lens``, ``block_table`` and the tables on the device."""
-    from .kv_cache_mxfp4 import PagedKVFP4, _packed_lists, plan_varlen
+    operator reads only ``lens``, ``block_table`` and the tables on the device.  ``window`` (with
+    ``sinks``) routes to ``torch.ops.qattn.mxfp4_varlen_paged_window``: a sliding window with sinks, as the
+    Python call's."""
+    from .kv_cache_mxfp4 import PagedKVFP4, _check_trimmed, _packed_lists, _window_args, plan_varlen
     if not isinstance(cache, PagedKVFP4):
         raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PagedKVFP4")
     if q.dim() != 3:
@@ -263,9 +273,15 @@ def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=N
     if sum(sq) != q.shape[0]:
         raise _lib.QAttnError(f"qattn mxfp4 paged cache: q holds {q.shape[0]} tokens, q_lens sum to {sum(sq)}")
     kps, seq_rec, work, part_rows = plan_varlen(cache.lengths, ids, sq, q.shape[1], cache.k4.shape[1],
-                                                keys_per_split, causal)
+                                                keys_per_split, causal, window, sinks)
+    W, S = _window_args(window, sinks)
+    _check_trimmed(cache, ids, sq, W, S)
     _lib.require_gpu(q, cache.k4)
     rec_d = torch.tensor(seq_rec, dtype=torch.int32).to(q.device, non_blocking=True)
     work_d = torch.tensor(work, dtype=torch.int32).to(q.device, non_blocking=True)
+    if W is not None:
+        return _ops.mxfp4_varlen_paged_window(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens,
+                                              cache.block_table, rec_d, work_d, part_rows, int(bool(causal)),
+                                              kps, min(W, 1 << 26), min(S, 1 << 26))
     return _ops.mxfp4_varlen_paged(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens, cache.block_table,
                                    rec_d, work_d, part_rows, int(bool(causal)), kps)

@@ -17,6 +17,13 @@ anything is timed (the pools of (b) hold different random tokens).
     [max_seqs, Hkv, longest, D].  Both are followed by the same roll-back of the lengths (a device copy),
     so that every call appends at the same place.
 
+(d) with --window W [--sinks S] (default off; then only (d) runs): a 64-sequence decode batch at 32768 cached
+    keys under the window -- the windowed call, the causal call on the same pool, and the causal call on a
+    pool whose sequences hold W + 64 tokens (the window's amount of work without the window) -- then the
+    three kernels alone, the windowed kernel alone with no sinks and the windowed kernel on the short pool
+    with a window of everything (the causal kernel's tiles through the windowed instantiation), and
+    free_pages before and after PagedKVFP4.trim of the batch.
+
 After (a) and (b) the packed call is taken apart: the host plan alone (plan_varlen, a host clock), the
 two table uploads alone (event-timed) and the attention kernel alone (REPS back-to-back launches of the
 C entry on buffers and tables made once, divided by REPS), beside the paged kernel alone in (a).
@@ -181,16 +188,66 @@ def append(lengths, counts, rand, passes, iters):
     report(alternate({"padded append": padded, "append_packed": packed}, passes, iters))
 
 
+def window_kernel(q, cache, ids, q_lens, W, S):
+    """REPS launches of the attention kernel alone: the windowed entry, or with W None the causal one."""
+    kps, rec, work, rows = plan_varlen(cache.lengths, ids, q_lens, HQ, HKV, None, True, W, S if W else 0)
+    rec_d, work_d = (torch.tensor(x, dtype=torch.int32).cuda() for x in (rec, work))
+    q4, qs = mxfp4_quantize_rows(q)
+    opart = torch.empty((rows, D), dtype=torch.float32, device="cuda")
+    ml = torch.empty((rows, 2), dtype=torch.float32, device="cuda")
+    args = (_lib.ptr(q4), _lib.ptr(qs), *(_lib.ptr(x) for x in cache.kv), _lib.ptr(opart), _lib.ptr(ml),
+            _lib.ptr(cache.lens), _lib.ptr(cache.block_table), _lib.ptr(rec_d), _lib.ptr(work_d), len(rec),
+            len(work), q.shape[0], rows, cache.alloc.max_seqs, HKV, HQ // HKV, cache.num_pages, P,
+            cache.alloc.max_pages_per_seq, 2, kps, D, _qk_scale(D))
+    name = "qattn_mxfp4_attn_fwd_varlen_paged" + ("_window" if W else "")
+    tail = ((W, S) if W else ()) + (_lib.stream_of(q),)
+    print(f"  kernel alone, window {W} sinks {S}: {kps} keys per split, {len(work)} work records", flush=True)
+
+    def kernel(keep=(q4, qs, opart, ml, rec_d, work_d)):
+        for _ in range(REPS):
+            _lib.call(name, *args, *tail)
+    return kernel
+
+
+def windowed(W, S, rand, passes, iters):
+    B, L = 64, 32768
+    cache, short = pool_of([L] * B, rand), pool_of([W + 64] * B, rand)
+    q, ids, lens = rand(B, HQ, D), list(range(B)), [1] * B
+    print(f"(d) window {W}, sinks {S}: {B} decodes x {HQ}/{HKV} heads at {L} cached, P {P}", flush=True)
+    report(alternate({
+        "windowed": lambda: attention_mxfp4_varlen_paged(q, cache, ids, lens, causal=True, window=W, sinks=S),
+        "causal, same pool": lambda: attention_mxfp4_varlen_paged(q, cache, ids, lens, causal=True),
+        f"causal, {W + 64} cached": lambda: attention_mxfp4_varlen_paged(q, short, ids, lens, causal=True),
+    }, passes, iters))
+    report(alternate({f"windowed kernel x{REPS}": window_kernel(q, cache, ids, lens, W, S),
+                      f"windowed kernel, no sinks x{REPS}": window_kernel(q, cache, ids, lens, W, 0),
+                      f"causal kernel x{REPS}": window_kernel(q, cache, ids, lens, None, 0),
+                      f"causal kernel, {W + 64} cached x{REPS}": window_kernel(q, short, ids, lens, None, 0),
+                      # the same tiles as the line above through the windowed instantiation: what its code costs
+                      f"windowed kernel, {W + 64} cached x{REPS}": window_kernel(q, short, ids, lens, W + 64, 0)},
+                     passes, iters))
+    before = cache.free_pages
+    freed = cache.trim(ids, W, S)
+    print(f"  trim: free_pages {before} -> {cache.free_pages} of {cache.num_pages} ({freed} returned)", flush=True)
+    O1, _ = attention_mxfp4_varlen_paged(q, cache, ids, lens, causal=True, window=W, sinks=S)
+    assert torch.isfinite(O1.float()).all()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--window", type=int, default=None, help="run only (d), with this window")
+    ap.add_argument("--sinks", type=int, default=0)
     args = ap.parse_args()
     assert args.passes >= 3
     print(f"device {torch.cuda.get_device_name(0)}; {args.passes} alternating passes x {args.iters} calls, "
           "whole Python call", flush=True)
     g = torch.Generator(device="cuda").manual_seed(0)
     rand = lambda *s: torch.randn(s, device="cuda", generator=g).half()  # noqa: E731
+    if args.window is not None:
+        windowed(args.window, args.sinks, rand, args.passes, args.iters)
+        return
     uniform(rand, args.passes, args.iters)
     torch.cuda.empty_cache()
     for i, (chunk, ndec) in enumerate(MIXED):
