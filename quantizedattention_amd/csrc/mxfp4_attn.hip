@@ -37,6 +37,16 @@
 // the LEN instantiation bit for bit).  Its VARLEN instantiation runs a ragged batch of packed queries
 // over that pool in one launch, from two host-built tables, with compact partials, a merge and a packed
 // append of its own (tests/test_gpu_mxfp4_varlen.py holds every sequence to its run alone bit for bit).
+// What these layers share stands once: mx_load_q and mx_tile (the tile body of every attention kernel);
+// mx_merge_row (the merge of both combine kernels, which also defines the rounding to f16;
+// tests/mxfp4_split_ref.py merge_bits restates it bit for bit); mx_requant_v_block and mx_append_k_block
+// (the bodies of the padded, paged and packed append kernels, which differ in how a thread finds its
+// sequence, head and source row); and on the host MxSplitCall + mx_split_launch (every key-split entry:
+// its own argument checks, the call filled in, a dispatch on `causal`), mx_varlen_paged (the two packed
+// entries) and mx_append (the padded and the paged append).  The two rings, MxRing and MxPagedRing, keep
+// a piece plan each: holding one in common changed the paged kernels' instruction streams.  The C entries
+// stand in the order in which they first use their kernels, which is the order the kernels are emitted
+// in; tools/asm_compare.py compares branch labels too, and those carry the function's number.
 #include "common.h"
 
 #include <type_traits>
@@ -167,10 +177,43 @@ QA_DEVICE long mx_paged_tile(const int* btab, int b, int hd, int g, int Hkv, int
   return (((long)page * Hkv + hd) << lgt) + (g & ((1 << lgt) - 1));
 }
 
-// V: one thread per (head, touched tile j, column d, half h).  Tile g = L / 64 + j of the touched
-// range [L / 64, (L + cnt - 1) / 64] is quantised again from its 32 keys per block in
-// mx_quant_vt_kernel's order: token t < L from vtail[t % 64], t < L + cnt from the new v[t - L], else 0.
-// PAGED: cap = mpp * P and the tile is written where the block table puts it.
+// A touched V tile g of a column, quantised again from its 32 keys per block in mx_quant_vt_kernel's
+// order: token t < L from tail[t % 64] (tail, col: the column's element of vtail's row 0 and of the
+// first new token; rstride: rows of D elements between two new tokens), t < L + cnt from col[t - L], else 0.
+template <int D>
+QA_DEVICE void mx_requant_v_block(const _Float16* tail, const _Float16* col, int rstride, int g, int L,
+                                  int cnt, int h, v4i* q4, uint8_t* sc) {
+  float f[32];
+  float amax = 0.f;
+#pragma unroll
+  for (int j = 0; j < 32; ++j) {
+    const int key = 32 * (j >> 4) + 8 * ((j >> 2) & 3) + 4 * h + (j & 3);
+    const int t = 64 * g + key;
+    f[j] = t < L ? (float)tail[(long)key * D] : t < L + cnt ? (float)col[(long)(t - L) * rstride * D] : 0.f;
+    amax = fmaxf(amax, fabsf(f[j]));
+  }
+  const unsigned e = e8m0_of(amax);
+  *q4 = pack_fp4x32(f, e8m0_value(e));
+  *sc = (uint8_t)e;
+}
+
+// One 32-element block of a new K row at token t: quantised as mx_quant_rows_kernel does (mu: the block of
+// the mean, or null) into block o of k4 / ks; the same 32 elements of v go to vdst, their place in vtail,
+// when the token lies in the new last partial tile (end = L + cnt, the length after the append).
+QA_DEVICE void mx_append_k_block(const _Float16* ksrc, const _Float16* vsrc, const v8h* mu, uint8_t* k4,
+                                 uint8_t* ks, long o, _Float16* vdst, int t, int end) {
+  mx_quant_row_block(reinterpret_cast<const v8h*>(ksrc), mu, reinterpret_cast<v4i*>(k4) + o, ks + o);
+  if (end % 64 != 0 && t / 64 == end / 64) {
+    const v8h* src = reinterpret_cast<const v8h*>(vsrc);
+    v8h* dst = reinterpret_cast<v8h*>(vdst);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) dst[c] = src[c];
+  }
+}
+
+// V: one thread per (head, touched tile j, column d, half h) quantises tile g = L / 64 + j of the touched
+// range [L / 64, (L + cnt - 1) / 64] again (mx_requant_v_block).  PAGED: cap = mpp * P and the tile is
+// written where the block table puts it.
 template <int D, bool PAGED = false>
 __global__ __launch_bounds__(256) void mx_append_vt_kernel(const _Float16* __restrict__ v,
                                                            const _Float16* __restrict__ vtail,
@@ -191,28 +234,15 @@ __global__ __launch_bounds__(256) void mx_append_vt_kernel(const _Float16* __res
   const int cnt = mx_append_count(lens, counts, b, n, cap, L);
   const int g = L / 64 + (int)(gt % ntile);
   if (cnt == 0 || 64 * g >= L + cnt) return;   // L + cnt <= cap = 64 * tiles: the tile lies inside
-  const _Float16* tail = vtail + bh * 64 * D + d;
-  const _Float16* col = v + bh * (long)n * D + d;
-  float f[32];
-  float amax = 0.f;
-#pragma unroll
-  for (int j = 0; j < 32; ++j) {
-    const int key = 32 * (j >> 4) + 8 * ((j >> 2) & 3) + 4 * h + (j & 3);
-    const int t = 64 * g + key;
-    f[j] = t < L ? (float)tail[(long)key * D] : t < L + cnt ? (float)col[(long)(t - L) * D] : 0.f;
-    amax = fmaxf(amax, fabsf(f[j]));
-  }
-  const unsigned e = e8m0_of(amax);
   long tile = bh * (cap / 64) + g;
   if constexpr (PAGED) tile = mx_paged_tile(btab, b, (int)(bh % Hkv), g, Hkv, mpp, lgt, npool);
   const long o = (tile * D + d) * 2 + h;
-  reinterpret_cast<v4i*>(vt)[o] = pack_fp4x32(f, e8m0_value(e));
-  vs[o] = (uint8_t)e;
+  mx_requant_v_block<D>(vtail + bh * 64 * D + d, v + bh * (long)n * D + d, 1, g, L, cnt, h,
+                        reinterpret_cast<v4i*>(vt) + o, vs + o);
 }
 
 // K and vtail: one thread per 32-element block of a new row.  Row i < cnt of head bh goes to token
-// L + i of k4 / ks, quantised as mx_quant_rows_kernel does (mean: f16 [B*Hkv, D] or null); the same
-// 32 elements of v go to vtail when the token lies in the new last partial tile.  PAGED as above.
+// L + i (mx_append_k_block; mean: f16 [B*Hkv, D] or null).  PAGED as above.
 template <int D, bool PAGED = false>
 __global__ __launch_bounds__(256) void mx_append_k_kernel(const _Float16* __restrict__ k,
                                                           const _Float16* __restrict__ v,
@@ -239,15 +269,8 @@ __global__ __launch_bounds__(256) void mx_append_k_kernel(const _Float16* __rest
   long row = bh * cap + t;
   if constexpr (PAGED)
     row = mx_paged_tile(btab, b, (int)(bh % Hkv), t / 64, Hkv, mpp, lgt, npool) * 64 + t % 64;
-  const long o = row * NB + blk;
-  mx_quant_row_block(reinterpret_cast<const v8h*>(k + i * 32), mu, reinterpret_cast<v4i*>(k4) + o, ks + o);
-  const int end = L + cnt;
-  if (end % 64 != 0 && t / 64 == end / 64) {
-    const v8h* src = reinterpret_cast<const v8h*>(v + i * 32);
-    v8h* dst = reinterpret_cast<v8h*>(vtail + (bh * 64 + t % 64) * D + blk * 32);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) dst[c] = src[c];
-  }
+  mx_append_k_block(k + i * 32, v + i * 32, mu, k4, ks, row * NB + blk,
+                    vtail + (bh * 64 + t % 64) * D + blk * 32, t, L + cnt);
 }
 
 // lens[b] += cnt, one thread per sequence
@@ -613,7 +636,7 @@ __global__ __launch_bounds__(256, CAUSAL ? QA_MX_OCC_CAUSAL : QA_MX_OCC) void mx
 // kps)) from m = -inf with a ring of its own.  Shared with the one-pass kernel: MxRing, mx_load_q and
 // mx_tile; its own: the row mapping, the tile range, the causal prelude and the epilogue.  Written: the
 // unnormalised state, opart f32 [nsplit][BHV * rows][D] = O_s and ml f32 x 2 [nsplit][BHV * rows] =
-// {m_s, l_s}; mxfp4_split_combine_kernel merges them.  Every m_s is an integer, so the merge's weights
+// {m_s, l_s}; mx_merge_row merges them.  Every m_s is an integer, so the merge's weights
 // 2^(m_s - M) are exact and one split reproduces the one-pass result bit for bit.
 // rows is any value >= 1: the lanes past the last row of a partial wave read a clamped row (as qi
 // above) and store nothing.
@@ -821,55 +844,6 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
                                        lane, 0.f, nr);
 }
 
-// Merge of the key splits: per row M = max_s m_s, w_s = 2^(m_s - M) (exact: every m_s is an integer
-// or -inf, which weighs 0), L = sum_s w_s l_s, out = f16((sum_s w_s O_s) * (1 / L)), lse = M + log2(L):
-// the one-pass epilogue on the merged state.  One thread per 8 columns of a row.
-template <int D>
-__global__ __launch_bounds__(256) void mxfp4_split_combine_kernel(const float* __restrict__ opart,
-                                                                  const float2* __restrict__ ml,
-                                                                  _Float16* __restrict__ out,
-                                                                  float* __restrict__ lse, long rows,
-                                                                  int nsplit) {
-  constexpr int TPR = D / 8;
-  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-  const long row = gid / TPR;
-  const int c = (int)(gid % TPR);
-  if (row >= rows) return;
-  float M = -INFINITY;
-  for (int s = 0; s < nsplit; ++s) M = fmaxf(M, ml[s * rows + row].x);
-  float L = 0.f, acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int s = 0; s < nsplit; ++s) {
-    const float2 v = ml[s * rows + row];
-    const float w = v.x == -INFINITY ? 0.f : __builtin_ldexpf(1.f, (int)(v.x - M));
-    L = fmaf(w, v.y, L);
-    const v4f* a = reinterpret_cast<const v4f*>(opart + ((long)s * rows + row) * D + 8 * c);
-    const v4f a0 = a[0], a1 = a[1];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      acc[i] = fmaf(w, a0[i], acc[i]);
-      acc[4 + i] = fmaf(w, a1[i], acc[4 + i]);
-    }
-  }
-  const float inv = 1.0f / L;
-  v8h o;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) o[i] = (_Float16)(acc[i] * inv);
-  *reinterpret_cast<v8h*>(out + row * D + 8 * c) = o;
-  if (c == 0) lse[row] = M + log2_f32(L);
-}
-
-// The largest j in [0, n) with tab[j * stride + col] <= x (0 if there is none): the sequence of a
-// packed token, from the ascending first-token column of a host-built table.
-QA_DEVICE int mx_find_seq(const int* tab, int n, int stride, int col, int x) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[(long)mid * stride + col] <= x) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
 // f16 of the exact product a * b, rounded once (v_fma_mixlo_f16 with fp32 sources)
 QA_DEVICE _Float16 mul_f16_once(float a, float b) {
   unsigned r = 0;
@@ -877,31 +851,19 @@ QA_DEVICE _Float16 mul_f16_once(float a, float b) {
   return __builtin_bit_cast(_Float16, (unsigned short)r);
 }
 
-// The merge above over the compact partials of the packed step (mxfp4_attn_split_kernel VARLEN): one
-// thread per 8 columns of a packed output row (token, query head).  The thread finds its sequence j by
-// binary search over the first-token column of seq_rec, and merges that sequence's own rec[3] splits,
-// rows first + (s * Hkv + head / group) * group * sq + (head % group) * sq + token - first of opart /
-// ml, with the arithmetic above in the order above.  A row whose partial rows would pass part_rows
-// (a wrong table) is not merged.
+// Merge of the key splits of one output row, by the thread that owns its columns 8c .. 8c + 7: the row's
+// nsplit partial rows are first, first + step, .. of opart / ml.  M = max_s m_s, w_s = 2^(m_s - M) (exact:
+// every m_s is an integer or -inf, which weighs 0), L = sum_s w_s l_s, out = f16((sum_s w_s O_s) * (1 / L)),
+// lse = M + log2(L): the one-pass epilogue on the merged state.
+// The conversion to f16 is a definition, left to no heuristic of the compiler: the thread's columns 0 and 7
+// are the exact product rounded to f16 once (mul_f16_once); its columns 1 .. 6 are the fp32 product,
+// rounded, then converted (rounded twice; an empty asm keeps the product a value of its own, so it cannot
+// be contracted into the conversion).  The two forms differ by one f16 ulp about once in 10^4 elements.
+// tests/mxfp4_split_ref.py merge_bits restates this bit for bit.
 template <int D>
-__global__ __launch_bounds__(256) void mxfp4_varlen_combine_kernel(const float* __restrict__ opart,
-                                                                   const float2* __restrict__ ml,
-                                                                   _Float16* __restrict__ out,
-                                                                   float* __restrict__ lse,
-                                                                   const int* __restrict__ seq_rec, int nseq,
-                                                                   long rows, int Hq, int Hkv,
-                                                                   long part_rows) {
-  constexpr int TPR = D / 8;
-  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-  const long row = gid / TPR;
-  const int c = (int)(gid % TPR);
-  if (row >= rows) return;
-  const int token = (int)(row / Hq), head = (int)(row % Hq), G = Hq / Hkv;
-  const int* rec = seq_rec + 8L * mx_find_seq(seq_rec, nseq, 8, 1, token);
-  const int sq = max(rec[2], 1), nsplit = rec[3];
-  const long rows_j = (long)G * sq, step = (long)Hkv * rows_j;
-  const long first = rec[4] + (head / G) * rows_j + (long)(head % G) * sq + (token - rec[1]);
-  if (nsplit < 1 || first < 0 || first + (nsplit - 1) * step >= part_rows) return;
+QA_DEVICE void mx_merge_row(const float* __restrict__ opart, const float2* __restrict__ ml, long first,
+                            long step, int nsplit, int c, _Float16* __restrict__ out_row,
+                            float* __restrict__ lse_row) {
   float M = -INFINITY;
   for (int s = 0; s < nsplit; ++s) M = fmaxf(M, ml[first + s * step].x);
   float L = 0.f, acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -918,12 +880,6 @@ __global__ __launch_bounds__(256) void mxfp4_varlen_combine_kernel(const float* 
     }
   }
   const float inv = 1.0f / L;
-  // f16(acc * inv) as mxfp4_split_combine_kernel computes it.  Under the default contraction the compiler
-  // fuses that kernel's product and conversion of columns 8c and 8c + 7 into v_fma_mix (the exact product
-  // rounded to f16 once) and builds the six between them as an fp32 product converted afterwards (rounded
-  // twice); the two differ by one f16 ulp about once in 10^4 elements.  This kernel must give that
-  // kernel's bits (tests/test_gpu_mxfp4_varlen.py), so both forms are spelled out here and left to no
-  // heuristic: an empty asm keeps the fp32 product a value of its own.
   v8h o;
   o[0] = mul_f16_once(acc[0], inv);
 #pragma unroll
@@ -933,8 +889,61 @@ __global__ __launch_bounds__(256) void mxfp4_varlen_combine_kernel(const float* 
     o[i] = (_Float16)p;
   }
   o[7] = mul_f16_once(acc[7], inv);
-  *reinterpret_cast<v8h*>(out + row * D + 8 * c) = o;
-  if (c == 0) lse[row] = M + log2_f32(L);
+  *reinterpret_cast<v8h*>(out_row + 8 * c) = o;
+  if (c == 0) *lse_row = M + log2_f32(L);
+}
+
+// The merge over the padded partials (opart f32 [nsplit][rows][D], ml [nsplit][rows]): one thread per 8
+// columns of a row.
+template <int D>
+__global__ __launch_bounds__(256) void mxfp4_split_combine_kernel(const float* __restrict__ opart,
+                                                                  const float2* __restrict__ ml,
+                                                                  _Float16* __restrict__ out,
+                                                                  float* __restrict__ lse, long rows,
+                                                                  int nsplit) {
+  constexpr int TPR = D / 8;
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+  const long row = gid / TPR;
+  if (row >= rows) return;
+  mx_merge_row<D>(opart, ml, row, rows, nsplit, (int)(gid % TPR), out + row * D, lse + row);
+}
+
+// The largest j in [0, n) with tab[j * stride + col] <= x (0 if there is none): the sequence of a
+// packed token, from the ascending first-token column of a host-built table.
+QA_DEVICE int mx_find_seq(const int* tab, int n, int stride, int col, int x) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[(long)mid * stride + col] <= x) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// The merge over the compact partials of the packed step (mxfp4_attn_split_kernel VARLEN): one thread per
+// 8 columns of a packed output row (token, query head).  The thread finds its sequence j by binary search
+// over the first-token column of seq_rec, and merges that sequence's own rec[3] splits, rows first + (s *
+// Hkv + head / group) * group * sq + (head % group) * sq + token - first of opart / ml.  A row whose
+// partial rows would pass part_rows (a wrong table) is not merged.
+template <int D>
+__global__ __launch_bounds__(256) void mxfp4_varlen_combine_kernel(const float* __restrict__ opart,
+                                                                   const float2* __restrict__ ml,
+                                                                   _Float16* __restrict__ out,
+                                                                   float* __restrict__ lse,
+                                                                   const int* __restrict__ seq_rec, int nseq,
+                                                                   long rows, int Hq, int Hkv,
+                                                                   long part_rows) {
+  constexpr int TPR = D / 8;
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+  const long row = gid / TPR;
+  if (row >= rows) return;
+  const int token = (int)(row / Hq), head = (int)(row % Hq), G = Hq / Hkv;
+  const int* rec = seq_rec + 8L * mx_find_seq(seq_rec, nseq, 8, 1, token);
+  const int sq = max(rec[2], 1), nsplit = rec[3];
+  const long rows_j = (long)G * sq, step = (long)Hkv * rows_j;
+  const long first = rec[4] + (head / G) * rows_j + (long)(head % G) * sq + (token - rec[1]);
+  if (nsplit < 1 || first < 0 || first + (nsplit - 1) * step >= part_rows) return;
+  mx_merge_row<D>(opart, ml, first, step, nsplit, (int)(gid % TPR), out + row * D, lse + row);
 }
 
 // ---- packed append into the paged pool (kv_cache_mxfp4.py PagedKVFP4.append_packed)
@@ -976,21 +985,9 @@ __global__ __launch_bounds__(256) void mx_append_vt_packed_kernel(
   const int cnt = mx_packed_count(tab, lens, j, B, T, cap, slot, first, L);
   if (cnt == 0 || g < L / 64 || 64L * g >= L + cnt) return;   // L + cnt <= cap: the tile lies inside
   const long bh = (long)slot * Hkv + hd;
-  const _Float16* tail = vtail + bh * 64 * D + d;
-  const _Float16* col = v + ((long)first * Hkv + hd) * D + d;
-  float f[32];
-  float amax = 0.f;
-#pragma unroll
-  for (int jj = 0; jj < 32; ++jj) {
-    const int key = 32 * (jj >> 4) + 8 * ((jj >> 2) & 3) + 4 * h + (jj & 3);
-    const int t = 64 * g + key;
-    f[jj] = t < L ? (float)tail[(long)key * D] : t < L + cnt ? (float)col[(long)(t - L) * Hkv * D] : 0.f;
-    amax = fmaxf(amax, fabsf(f[jj]));
-  }
-  const unsigned e = e8m0_of(amax);
   const long o = (mx_paged_tile(btab, slot, hd, g, Hkv, mpp, lgt, npool) * D + d) * 2 + h;
-  reinterpret_cast<v4i*>(vt)[o] = pack_fp4x32(f, e8m0_value(e));
-  vs[o] = (uint8_t)e;
+  mx_requant_v_block<D>(vtail + bh * 64 * D + d, v + ((long)first * Hkv + hd) * D + d, Hkv, g, L, cnt,
+                        h, reinterpret_cast<v4i*>(vt) + o, vs + o);
 }
 
 // K and vtail: one thread per 32-element block of a packed row (token, head); its record is found by
@@ -1015,14 +1012,7 @@ __global__ __launch_bounds__(256) void mx_append_k_packed_kernel(
   const long bh = (long)slot * Hkv + hd;
   const v8h* mu = mean ? reinterpret_cast<const v8h*>(mean + bh * D + blk * 32) : nullptr;
   const long o = (mx_paged_tile(btab, slot, hd, t / 64, Hkv, mpp, lgt, npool) * 64 + t % 64) * NB + blk;
-  mx_quant_row_block(reinterpret_cast<const v8h*>(k + i * 32), mu, reinterpret_cast<v4i*>(k4) + o, ks + o);
-  const int end = L + cnt;
-  if (end % 64 != 0 && t / 64 == end / 64) {
-    const v8h* src = reinterpret_cast<const v8h*>(v + i * 32);
-    v8h* dst = reinterpret_cast<v8h*>(vtail + (bh * 64 + t % 64) * D + blk * 32);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) dst[c] = src[c];
-  }
+  mx_append_k_block(k + i * 32, v + i * 32, mu, k4, ks, o, vtail + (bh * 64 + t % 64) * D + blk * 32, t, L + cnt);
 }
 
 // lens[slot] += cnt, one thread per record
@@ -1110,81 +1100,63 @@ extern "C" int qattn_mxfp4_attn_fwd(const void* q4, const void* qscale, const vo
                                  head_dim, qks, stream);
 }
 
-template <bool CAUSAL>
-static int mxfp4_split_launch(const void* q4, const void* qscale, const void* k4, const void* kscale,
-                              const void* vt, const void* vscale, void* opart, void* ml, long bhv,
-                              long rows, long sq_head, long sk, int kps, float qks, void* stream) {
-  using C = MxCfg<128>;
-  const long nrb = (rows + C::QROWS - 1) / C::QROWS;
-  const long nsplit = (sk + kps - 1) / kps;
-  if (nrb * bhv > 0x7fffffffL || nsplit > 65535) return 1;
-  const int lds = C::NSLOT * C::SLOT;
-  { static LdsGrant granted_; if (!lds_grant((const void*)mxfp4_attn_split_kernel<128, CAUSAL>, lds, granted_)) return 1; }
-  hipLaunchKernelGGL((mxfp4_attn_split_kernel<128, CAUSAL>), dim3((unsigned)(nrb * bhv), (unsigned)nsplit),
-                     dim3(256), lds, (hipStream_t)stream, (const uint8_t*)q4, (const uint8_t*)qscale,
-                     (const uint8_t*)k4, (const uint8_t*)kscale, (const uint8_t*)vt,
-                     (const uint8_t*)vscale, (float*)opart, (float2*)ml, (int)bhv, (int)rows,
-                     (int)sq_head, (int)sk, kps, qks, (int)(sk - sq_head), (const int*)nullptr, 1,
-                     (const int*)nullptr, 0, 0, 0, MxVarlen{});
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+// log2(page_tokens / 64) of a page size 64 * 2^k in [64, 1024], else -1
+static int mx_page_lgt(long page_tokens) {
+  for (int k = 0; k <= 4; ++k)
+    if (page_tokens == 64L << k) return k;
+  return -1;
 }
 
-template <bool CAUSAL>
-static int mxfp4_split_len_launch(const void* q4, const void* qscale, const void* k4, const void* kscale,
-                                  const void* vt, const void* vscale, void* opart, void* ml,
-                                  const void* lens, long bhv, long hps, long rows, long sq_head, long cap,
-                                  long sk_max, int kps, float qks, void* stream) {
-  using C = MxCfg<128>;
-  const long nrb = (rows + C::QROWS - 1) / C::QROWS;
-  const long nsplit = (sk_max + kps - 1) / kps;
-  if (nrb * bhv > 0x7fffffffL || nsplit > 65535) return 1;
-  const int lds = C::NSLOT * C::SLOT;
-  { static LdsGrant granted_; if (!lds_grant((const void*)mxfp4_attn_split_kernel<128, CAUSAL, true>, lds, granted_)) return 1; }
-  hipLaunchKernelGGL((mxfp4_attn_split_kernel<128, CAUSAL, true>), dim3((unsigned)(nrb * bhv), (unsigned)nsplit),
-                     dim3(256), lds, (hipStream_t)stream, (const uint8_t*)q4, (const uint8_t*)qscale,
-                     (const uint8_t*)k4, (const uint8_t*)kscale, (const uint8_t*)vt,
-                     (const uint8_t*)vscale, (float*)opart, (float2*)ml, (int)bhv, (int)rows,
-                     (int)sq_head, (int)cap, kps, qks, 0, (const int*)lens, (int)hps, (const int*)nullptr, 0, 0, 0,
-                     MxVarlen{});
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+// the pool's limits every paged entry shares: a physical tile index below 2^31 and 32-bit token indices
+// inside a sequence
+static bool mx_pool_ok(long num_pages, long kv_heads, int lgt, long mpp) {
+  if (lgt < 0 || num_pages < 1 || kv_heads < 1 || mpp < 1 || num_pages > 0x7fffffffL) return false;
+  if (kv_heads > 0x7fffffffL || mpp > (1L << 25) || mpp * (64L << lgt) > (1L << 25)) return false;
+  return num_pages * kv_heads <= (0x7fffffffL >> lgt);
 }
 
-template <bool CAUSAL>
-static int mxfp4_split_paged_launch(const void* q4, const void* qscale, const void* k4, const void* kscale,
-                                    const void* vt, const void* vscale, void* opart, void* ml,
-                                    const void* lens, const void* btab, long bhv, long hps, long rows,
-                                    long sq_head, long npool, int lgt, long mpp, long sk_max, int kps,
-                                    float qks, void* stream) {
-  using C = MxCfg<128>;
-  const long nrb = (rows + C::QROWS - 1) / C::QROWS;
-  const long nsplit = (sk_max + kps - 1) / kps;
-  if (nrb * bhv > 0x7fffffffL || nsplit > 65535) return 1;
-  const int lds = C::NSLOT * C::SLOT;
-  { static LdsGrant granted_; if (!lds_grant((const void*)mxfp4_attn_split_kernel<128, CAUSAL, true, true>, lds, granted_)) return 1; }
-  hipLaunchKernelGGL((mxfp4_attn_split_kernel<128, CAUSAL, true, true>),
-                     dim3((unsigned)(nrb * bhv), (unsigned)nsplit), dim3(256), lds, (hipStream_t)stream,
-                     (const uint8_t*)q4, (const uint8_t*)qscale, (const uint8_t*)k4, (const uint8_t*)kscale,
-                     (const uint8_t*)vt, (const uint8_t*)vscale, (float*)opart, (float2*)ml, (int)bhv,
-                     (int)rows, (int)sq_head, (int)(mpp * (64L << lgt)), kps, qks, 0, (const int*)lens,
-                     (int)hps, (const int*)btab, (int)mpp, lgt, (int)npool, MxVarlen{});
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+// what every key-split entry asks of its head_dim and keys_per_split, and the padded ones of their rows
+static bool mx_split_ok(int head_dim, int keys_per_split) {
+  return head_dim == 128 && keys_per_split >= 64 && keys_per_split % 64 == 0;
+}
+static bool mx_rows_ok(long sq_head, long rows) { return sq_head >= 1 && rows % sq_head == 0; }
+
+// One call of mxfp4_attn_split_kernel: its arguments as the kernel takes them (Sk: the key stride of a
+// key/value head, which is the key count without lens) and its grid.
+struct MxSplitCall {
+  const void *q4, *qscale, *k4, *kscale, *vt, *vscale;
+  void *opart, *ml;
+  int bhv, rows, sq_head, Sk, kps;
+  float qks;
+  int qoff;
+  const void* lens;
+  int hps;
+  const void* btab;
+  int mpp, lgt, npool;
+  MxVarlen vl;
+  dim3 grid;
+};
+
+// the padded layouts' grid: (row blocks x key/value heads, splits of sk keys), false past the launch limits
+static bool mx_split_grid(MxSplitCall& c, long sk) {
+  const long nrb = (c.rows + MxCfg<128>::QROWS - 1) / MxCfg<128>::QROWS;
+  const long nsplit = (sk + c.kps - 1) / c.kps;
+  if (nrb * c.bhv > 0x7fffffffL || nsplit > 65535) return false;
+  c.grid = dim3((unsigned)(nrb * c.bhv), (unsigned)nsplit);
+  return true;
 }
 
-template <bool CAUSAL, bool WINDOW = false>
-static int mxfp4_varlen_paged_launch(const void* q4, const void* qscale, const void* k4, const void* kscale,
-                                     const void* vt, const void* vscale, void* opart, void* ml,
-                                     const void* lens, const void* btab, const MxVarlen& vl, long nwork,
-                                     long slots, long hps, long npool, int lgt, long mpp, int kps, float qks,
-                                     void* stream) {
+template <bool CAUSAL, bool LEN, bool PAGED, bool VARLEN, bool WINDOW>
+static int mx_split_launch(const MxSplitCall& c, void* stream) {
   using C = MxCfg<128>;
+  const auto kernel = mxfp4_attn_split_kernel<128, CAUSAL, LEN, PAGED, VARLEN, WINDOW>;
   const int lds = C::NSLOT * C::SLOT;
-  { static LdsGrant granted_; if (!lds_grant((const void*)mxfp4_attn_split_kernel<128, CAUSAL, true, true, true, WINDOW>, lds, granted_)) return 1; }
-  // rows, sq_head and qoff come from the records
-  hipLaunchKernelGGL((mxfp4_attn_split_kernel<128, CAUSAL, true, true, true, WINDOW>), dim3((unsigned)(nwork * hps)),
-                     dim3(256), lds, (hipStream_t)stream, (const uint8_t*)q4, (const uint8_t*)qscale,
-                     (const uint8_t*)k4, (const uint8_t*)kscale, (const uint8_t*)vt, (const uint8_t*)vscale,
-                     (float*)opart, (float2*)ml, (int)(slots * hps), 0, 1, (int)(mpp * (64L << lgt)), kps, qks,
-                     0, (const int*)lens, (int)hps, (const int*)btab, (int)mpp, lgt, (int)npool, vl);
+  { static LdsGrant granted_; if (!lds_grant((const void*)kernel, lds, granted_)) return 1; }
+  hipLaunchKernelGGL(kernel, c.grid, dim3(256), lds, (hipStream_t)stream, (const uint8_t*)c.q4,
+                     (const uint8_t*)c.qscale, (const uint8_t*)c.k4, (const uint8_t*)c.kscale,
+                     (const uint8_t*)c.vt, (const uint8_t*)c.vscale, (float*)c.opart, (float2*)c.ml, c.bhv,
+                     c.rows, c.sq_head, c.Sk, c.kps, c.qks, c.qoff, (const int*)c.lens, c.hps,
+                     (const int*)c.btab, c.mpp, c.lgt, c.npool, c.vl);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -1195,18 +1167,17 @@ extern "C" int qattn_mxfp4_attn_fwd_split(const void* q4, const void* qscale, co
                                           void* opart, void* ml, long bhv, long rows, long sq_head, long sk,
                                           int causal, int keys_per_split, int head_dim, float qks,
                                           void* stream) {
-  if (head_dim != 128 || bhv < 0 || rows < 0 || sk < 0 || sk % 64 != 0) return 1;
-  if (keys_per_split < 64 || keys_per_split % 64 != 0) return 1;
-  if (sq_head < 1 || rows % sq_head != 0) return 1;
+  if (!mx_split_ok(head_dim, keys_per_split) || bhv < 0 || rows < 0 || sk < 0 || sk % 64 != 0) return 1;
+  if (!mx_rows_ok(sq_head, rows)) return 1;
   if ((causal != 0 && causal != 2) || (causal == 2 && sk < sq_head)) return 1;
   if (bhv == 0 || rows == 0) return 0;
   // 32-bit row indices inside a virtual head and 32-bit byte ranges of a key/value head
   if (sk == 0 || sk > (1L << 25) || rows > (1L << 30) || bhv > 0x7fffffffL) return 1;
-  if (causal)
-    return mxfp4_split_launch<true>(q4, qscale, k4, kscale, vt, vscale, opart, ml, bhv, rows, sq_head, sk,
-                                    keys_per_split, qks, stream);
-  return mxfp4_split_launch<false>(q4, qscale, k4, kscale, vt, vscale, opart, ml, bhv, rows, sq_head, sk,
-                                   keys_per_split, qks, stream);
+  MxSplitCall c{q4, qscale, k4, kscale, vt, vscale, opart, ml, (int)bhv, (int)rows, (int)sq_head, (int)sk,
+                keys_per_split, qks, (int)(sk - sq_head), nullptr, 1, nullptr, 0, 0, 0, MxVarlen{}, dim3()};
+  if (!mx_split_grid(c, sk)) return 1;
+  return causal ? mx_split_launch<true, false, false, false, false>(c, stream)
+                : mx_split_launch<false, false, false, false, false>(c, stream);
 }
 
 // the same over a preallocated cache of cap tokens per head with one length per sequence (lens i32
@@ -1218,63 +1189,56 @@ extern "C" int qattn_mxfp4_attn_fwd_split_len(const void* q4, const void* qscale
                                               long heads_per_seq, long rows, long sq_head, long cap,
                                               long sk_max, int causal, int keys_per_split, int head_dim,
                                               float qks, void* stream) {
-  if (head_dim != 128 || bhv < 0 || rows < 0 || !lens) return 1;
+  if (!mx_split_ok(head_dim, keys_per_split) || bhv < 0 || rows < 0 || !lens) return 1;
   if (cap % 64 != 0 || sk_max % 64 != 0 || sk_max < 64 || sk_max > cap || cap > (1L << 25)) return 1;
-  if (keys_per_split < 64 || keys_per_split % 64 != 0) return 1;
-  if (sq_head < 1 || rows % sq_head != 0 || heads_per_seq < 1 || bhv % heads_per_seq != 0) return 1;
+  if (!mx_rows_ok(sq_head, rows) || heads_per_seq < 1 || bhv % heads_per_seq != 0) return 1;
   if (causal != 0 && causal != 2) return 1;
   if (bhv == 0 || rows == 0) return 0;
   if (rows > (1L << 30) || bhv > 0x7fffffffL) return 1;
-  if (causal)
-    return mxfp4_split_len_launch<true>(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, bhv,
-                                        heads_per_seq, rows, sq_head, cap, sk_max, keys_per_split, qks,
-                                        stream);
-  return mxfp4_split_len_launch<false>(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, bhv,
-                                       heads_per_seq, rows, sq_head, cap, sk_max, keys_per_split, qks,
-                                       stream);
+  MxSplitCall c{q4, qscale, k4, kscale, vt, vscale, opart, ml, (int)bhv, (int)rows, (int)sq_head, (int)cap,
+                keys_per_split, qks, 0, lens, (int)heads_per_seq, nullptr, 0, 0, 0, MxVarlen{}, dim3()};
+  if (!mx_split_grid(c, sk_max)) return 1;
+  return causal ? mx_split_launch<true, true, false, false, false>(c, stream)
+                : mx_split_launch<false, true, false, false, false>(c, stream);
 }
 
-// append n new tokens per sequence to a preallocated cache (kernels and format: "cache append" above);
-// stream-ordered, nothing is read back
-extern "C" int qattn_mxfp4_cache_append(const void* k, const void* v, const void* k_mean, void* k4,
-                                        void* kscale, void* vt, void* vscale, void* vtail, void* lens,
-                                        const void* counts, long batch, long kv_heads, long n, long cap,
-                                        int head_dim, void* stream) {
-  if (head_dim != 128 || n < 1 || cap < 0 || cap % 64 != 0 || batch < 0 || kv_heads < 0) return 1;
+// An append of n new tokens per sequence (kernels and format: "cache append" above), into the
+// preallocated cache of cap tokens per head or, PAGED, through block_table into the pool; the three
+// launches are stream-ordered, nothing is read back
+template <bool PAGED>
+static int mx_append(const void* k, const void* v, const void* k_mean, void* k4, void* kscale, void* vt,
+                     void* vscale, void* vtail, void* lens, const void* counts, const void* block_table,
+                     long batch, long kv_heads, long n, long cap, long mpp, int lgt, long npool, int head_dim,
+                     void* stream) {
+  if (head_dim != 128 || n < 1 || n > (1L << 25) || batch < 0 || batch > 0x7fffffffL) return 1;
   if (!k || !v || !k4 || !kscale || !vt || !vscale || !vtail || !lens) return 1;
-  if (cap > (1L << 25) || n > (1L << 25) || batch > 0x7fffffffL || kv_heads > 0x7fffffffL) return 1;
   const long bhv = batch * kv_heads;
   if (bhv == 0 || cap == 0) return 0;
   const long ntile = (n + 62) / 64 + 1;   // tiles n tokens can touch from any start
   const long nthr = bhv * ntile * 128 * 2, nblk = bhv * n * (128 / 32);
   if ((nthr + 255) / 256 > 0x7fffffffL || (nblk + 255) / 256 > 0x7fffffffL) return 1;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(mx_append_vt_kernel<128>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st,
+  hipLaunchKernelGGL((mx_append_vt_kernel<128, PAGED>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st,
                      (const _Float16*)v, (const _Float16*)vtail, (uint8_t*)vt, (uint8_t*)vscale,
                      (const int*)lens, (const int*)counts, nthr, (int)kv_heads, (int)n, (int)ntile, (int)cap,
-                     (const int*)nullptr, 0, 0, 0);
-  hipLaunchKernelGGL(mx_append_k_kernel<128>, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st,
+                     (const int*)block_table, (int)mpp, lgt, (int)npool);
+  hipLaunchKernelGGL((mx_append_k_kernel<128, PAGED>), dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st,
                      (const _Float16*)k, (const _Float16*)v, (const _Float16*)k_mean, (uint8_t*)k4,
                      (uint8_t*)kscale, (_Float16*)vtail, (const int*)lens, (const int*)counts, nblk,
-                     (int)kv_heads, (int)n, (int)cap, (const int*)nullptr, 0, 0, 0);
+                     (int)kv_heads, (int)n, (int)cap, (const int*)block_table, (int)mpp, lgt, (int)npool);
   hipLaunchKernelGGL(mx_append_len_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st,
                      (int*)lens, (const int*)counts, (int)batch, (int)n, (int)cap);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
-// log2(page_tokens / 64) of a page size 64 * 2^k in [64, 1024], else -1
-static int mx_page_lgt(long page_tokens) {
-  for (int k = 0; k <= 4; ++k)
-    if (page_tokens == 64L << k) return k;
-  return -1;
-}
-
-// the pool's limits both paged entries share: a physical tile index below 2^31 and 32-bit token indices
-// inside a sequence
-static bool mx_pool_ok(long num_pages, long kv_heads, int lgt, long mpp) {
-  if (lgt < 0 || num_pages < 1 || kv_heads < 1 || mpp < 1 || num_pages > 0x7fffffffL) return false;
-  if (kv_heads > 0x7fffffffL || mpp > (1L << 25) || mpp * (64L << lgt) > (1L << 25)) return false;
-  return num_pages * kv_heads <= (0x7fffffffL >> lgt);
+// append n new tokens per sequence to a preallocated cache
+extern "C" int qattn_mxfp4_cache_append(const void* k, const void* v, const void* k_mean, void* k4,
+                                        void* kscale, void* vt, void* vscale, void* vtail, void* lens,
+                                        const void* counts, long batch, long kv_heads, long n, long cap,
+                                        int head_dim, void* stream) {
+  if (cap < 0 || cap % 64 != 0 || cap > (1L << 25) || kv_heads < 0 || kv_heads > 0x7fffffffL) return 1;
+  return mx_append<false>(k, v, k_mean, k4, kscale, vt, vscale, vtail, lens, counts, nullptr, batch, kv_heads,
+                          n, cap, 0, 0, 0, head_dim, stream);
 }
 
 // qattn_mxfp4_attn_fwd_split_len over the paged pool: the operands are pages of page_tokens tokens x
@@ -1286,22 +1250,20 @@ extern "C" int qattn_mxfp4_attn_fwd_split_paged(const void* q4, const void* qsca
                                                 long rows, long sq_head, long num_pages, long page_tokens,
                                                 long max_pages_per_seq, long sk_max, int causal,
                                                 int keys_per_split, int head_dim, float qks, void* stream) {
-  if (head_dim != 128 || bhv < 0 || rows < 0 || !lens || !block_table) return 1;
+  if (!mx_split_ok(head_dim, keys_per_split) || bhv < 0 || rows < 0 || !lens || !block_table) return 1;
   const int lgt = mx_page_lgt(page_tokens);
   if (!mx_pool_ok(num_pages, heads_per_seq, lgt, max_pages_per_seq)) return 1;
   if (sk_max % 64 != 0 || sk_max < 64 || sk_max > max_pages_per_seq * page_tokens) return 1;
-  if (keys_per_split < 64 || keys_per_split % 64 != 0) return 1;
-  if (sq_head < 1 || rows % sq_head != 0 || bhv % heads_per_seq != 0) return 1;
+  if (!mx_rows_ok(sq_head, rows) || bhv % heads_per_seq != 0) return 1;
   if (causal != 0 && causal != 2) return 1;
   if (bhv == 0 || rows == 0) return 0;
   if (rows > (1L << 30) || bhv > 0x7fffffffL) return 1;
-  if (causal)
-    return mxfp4_split_paged_launch<true>(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table,
-                                          bhv, heads_per_seq, rows, sq_head, num_pages, lgt,
-                                          max_pages_per_seq, sk_max, keys_per_split, qks, stream);
-  return mxfp4_split_paged_launch<false>(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table,
-                                         bhv, heads_per_seq, rows, sq_head, num_pages, lgt,
-                                         max_pages_per_seq, sk_max, keys_per_split, qks, stream);
+  MxSplitCall c{q4, qscale, k4, kscale, vt, vscale, opart, ml, (int)bhv, (int)rows, (int)sq_head,
+                (int)(max_pages_per_seq * page_tokens), keys_per_split, qks, 0, lens, (int)heads_per_seq,
+                block_table, (int)max_pages_per_seq, lgt, (int)num_pages, MxVarlen{}, dim3()};
+  if (!mx_split_grid(c, sk_max)) return 1;
+  return causal ? mx_split_launch<true, true, true, false, false>(c, stream)
+                : mx_split_launch<false, true, true, false, false>(c, stream);
 }
 
 // qattn_mxfp4_cache_append into the paged pool: the pages the new tokens need are in block_table already
@@ -1310,32 +1272,49 @@ extern "C" int qattn_mxfp4_paged_append(const void* k, const void* v, const void
                                         const void* counts, const void* block_table, long batch,
                                         long kv_heads, long n, long num_pages, long page_tokens,
                                         long max_pages_per_seq, int head_dim, void* stream) {
-  if (head_dim != 128 || n < 1 || n > (1L << 25) || batch < 0 || batch > 0x7fffffffL) return 1;
-  if (!k || !v || !k4 || !kscale || !vt || !vscale || !vtail || !lens || !block_table) return 1;
   const int lgt = mx_page_lgt(page_tokens);
-  if (!mx_pool_ok(num_pages, kv_heads, lgt, max_pages_per_seq)) return 1;
-  const long bhv = batch * kv_heads, cap = max_pages_per_seq * page_tokens;
-  if (bhv == 0) return 0;
-  const long ntile = (n + 62) / 64 + 1;   // tiles n tokens can touch from any start
-  const long nthr = bhv * ntile * 128 * 2, nblk = bhv * n * (128 / 32);
-  if ((nthr + 255) / 256 > 0x7fffffffL || (nblk + 255) / 256 > 0x7fffffffL) return 1;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL((mx_append_vt_kernel<128, true>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st,
-                     (const _Float16*)v, (const _Float16*)vtail, (uint8_t*)vt, (uint8_t*)vscale,
-                     (const int*)lens, (const int*)counts, nthr, (int)kv_heads, (int)n, (int)ntile, (int)cap,
-                     (const int*)block_table, (int)max_pages_per_seq, lgt, (int)num_pages);
-  hipLaunchKernelGGL((mx_append_k_kernel<128, true>), dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st,
-                     (const _Float16*)k, (const _Float16*)v, (const _Float16*)k_mean, (uint8_t*)k4,
-                     (uint8_t*)kscale, (_Float16*)vtail, (const int*)lens, (const int*)counts, nblk,
-                     (int)kv_heads, (int)n, (int)cap, (const int*)block_table, (int)max_pages_per_seq, lgt,
-                     (int)num_pages);
-  hipLaunchKernelGGL(mx_append_len_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st,
-                     (int*)lens, (const int*)counts, (int)batch, (int)n, (int)cap);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+  if (!block_table || !mx_pool_ok(num_pages, kv_heads, lgt, max_pages_per_seq)) return 1;
+  return mx_append<true>(k, v, k_mean, k4, kscale, vt, vscale, vtail, lens, counts, block_table, batch,
+                         kv_heads, n, max_pages_per_seq * page_tokens, max_pages_per_seq, lgt, num_pages,
+                         head_dim, stream);
 }
 
-// the packed (varlen) step over the paged pool: nwork work records x kv_heads workgroups in one launch
-// (kernel: mxfp4_attn_split_kernel VARLEN; the tables are the host plan of kv_cache_mxfp4.plan_varlen)
+// The two packed entries below: nwork work records x kv_heads workgroups in one launch; rows, sq_head and
+// qoff come from the records.  window < 1: no window (the plain entry); else causal is 2.
+static int mx_varlen_paged(const void* q4, const void* qscale, const void* k4, const void* kscale,
+                           const void* vt, const void* vscale, void* opart, void* ml, const void* lens,
+                           const void* block_table, const void* seq_rec, const void* work, long nseq,
+                           long nwork, long tokens, long part_rows, long max_seqs, long kv_heads, long group,
+                           long num_pages, long page_tokens, long max_pages_per_seq, int causal,
+                           int keys_per_split, int head_dim, float qks, long window, long sinks,
+                           void* stream) {
+  if (!mx_split_ok(head_dim, keys_per_split) || nseq < 0 || nwork < 0 || tokens < 0 || part_rows < 0) return 1;
+  if (!lens || !block_table || !seq_rec || !work) return 1;
+  const int lgt = mx_page_lgt(page_tokens);
+  if (!mx_pool_ok(num_pages, kv_heads, lgt, max_pages_per_seq)) return 1;
+  if (max_seqs < 1 || group < 1 || group > 0x7fffffffL || (causal != 0 && causal != 2)) return 1;
+  if (nseq == 0 || nwork == 0 || tokens == 0) return 0;
+  if (nseq > max_seqs || nseq > tokens || part_rows < 1) return 1;
+  // 32-bit packed rows, partial rows, workgroups and slot heads
+  if (tokens > 0x7fffffffL / (group * kv_heads) || part_rows > 0x7fffffffL) return 1;
+  if (nwork > 0x7fffffffL / kv_heads || max_seqs > 0x7fffffffL / kv_heads) return 1;
+  // a sequence holds at most 2^25 keys (mx_pool_ok): a larger window or sink count means the same, and
+  // the kernel's 32-bit edges cannot overflow
+  const long big = 1L << 26;
+  const MxVarlen vl{(const int*)work, (const int*)seq_rec, (int)nseq, (int)group, tokens * group * kv_heads,
+                    part_rows, (int)(window < big ? window : big), (int)(sinks < big ? sinks : big)};
+  const MxSplitCall c{q4, qscale, k4, kscale, vt, vscale, opart, ml, (int)(max_seqs * kv_heads), 0, 1,
+                      (int)(max_pages_per_seq * page_tokens), keys_per_split, qks, 0, lens, (int)kv_heads,
+                      block_table, (int)max_pages_per_seq, lgt, (int)num_pages, vl,
+                      dim3((unsigned)(nwork * kv_heads))};
+  if (window < 1)
+    return causal ? mx_split_launch<true, true, true, true, false>(c, stream)
+                  : mx_split_launch<false, true, true, true, false>(c, stream);
+  return mx_split_launch<true, true, true, true, true>(c, stream);
+}
+
+// the packed (varlen) step over the paged pool (kernel: mxfp4_attn_split_kernel VARLEN; the tables are
+// the host plan of kv_cache_mxfp4.plan_varlen)
 extern "C" int qattn_mxfp4_attn_fwd_varlen_paged(const void* q4, const void* qscale, const void* k4,
                                                  const void* kscale, const void* vt, const void* vscale,
                                                  void* opart, void* ml, const void* lens,
@@ -1345,26 +1324,9 @@ extern "C" int qattn_mxfp4_attn_fwd_varlen_paged(const void* q4, const void* qsc
                                                  long num_pages, long page_tokens, long max_pages_per_seq,
                                                  int causal, int keys_per_split, int head_dim, float qks,
                                                  void* stream) {
-  if (head_dim != 128 || nseq < 0 || nwork < 0 || tokens < 0 || part_rows < 0) return 1;
-  if (!lens || !block_table || !seq_rec || !work) return 1;
-  const int lgt = mx_page_lgt(page_tokens);
-  if (!mx_pool_ok(num_pages, kv_heads, lgt, max_pages_per_seq)) return 1;
-  if (keys_per_split < 64 || keys_per_split % 64 != 0) return 1;
-  if (max_seqs < 1 || group < 1 || group > 0x7fffffffL || (causal != 0 && causal != 2)) return 1;
-  if (nseq == 0 || nwork == 0 || tokens == 0) return 0;
-  if (nseq > max_seqs || nseq > tokens || part_rows < 1) return 1;
-  // 32-bit packed rows, partial rows, workgroups and slot heads
-  if (tokens > 0x7fffffffL / (group * kv_heads) || part_rows > 0x7fffffffL) return 1;
-  if (nwork > 0x7fffffffL / kv_heads || max_seqs > 0x7fffffffL / kv_heads) return 1;
-  const MxVarlen vl{(const int*)work, (const int*)seq_rec, (int)nseq, (int)group, tokens * group * kv_heads,
-                    part_rows};
-  if (causal)
-    return mxfp4_varlen_paged_launch<true>(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table,
-                                           vl, nwork, max_seqs, kv_heads, num_pages, lgt, max_pages_per_seq,
-                                           keys_per_split, qks, stream);
-  return mxfp4_varlen_paged_launch<false>(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table,
-                                          vl, nwork, max_seqs, kv_heads, num_pages, lgt, max_pages_per_seq,
-                                          keys_per_split, qks, stream);
+  return mx_varlen_paged(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work, nseq,
+                         nwork, tokens, part_rows, max_seqs, kv_heads, group, num_pages, page_tokens,
+                         max_pages_per_seq, causal, keys_per_split, head_dim, qks, 0, 0, stream);
 }
 
 // the packed step with a sliding window and sinks (kernel: mxfp4_attn_split_kernel WINDOW): query i of
@@ -1378,24 +1340,9 @@ extern "C" int qattn_mxfp4_attn_fwd_varlen_paged_window(
     long num_pages, long page_tokens, long max_pages_per_seq, int causal, int keys_per_split, int head_dim,
     float qks, long window, long sinks, void* stream) {
   if (window < 1 || sinks < 0 || causal != 2) return 1;
-  if (head_dim != 128 || nseq < 0 || nwork < 0 || tokens < 0 || part_rows < 0) return 1;
-  if (!lens || !block_table || !seq_rec || !work) return 1;
-  const int lgt = mx_page_lgt(page_tokens);
-  if (!mx_pool_ok(num_pages, kv_heads, lgt, max_pages_per_seq)) return 1;
-  if (keys_per_split < 64 || keys_per_split % 64 != 0) return 1;
-  if (max_seqs < 1 || group < 1 || group > 0x7fffffffL) return 1;
-  if (nseq == 0 || nwork == 0 || tokens == 0) return 0;
-  if (nseq > max_seqs || nseq > tokens || part_rows < 1) return 1;
-  if (tokens > 0x7fffffffL / (group * kv_heads) || part_rows > 0x7fffffffL) return 1;
-  if (nwork > 0x7fffffffL / kv_heads || max_seqs > 0x7fffffffL / kv_heads) return 1;
-  // a sequence holds at most 2^25 keys (mx_pool_ok): a larger window or sink count means the same, and
-  // the kernel's 32-bit edges cannot overflow
-  const long big = 1L << 26;
-  const MxVarlen vl{(const int*)work, (const int*)seq_rec, (int)nseq, (int)group, tokens * group * kv_heads,
-                    part_rows, (int)(window < big ? window : big), (int)(sinks < big ? sinks : big)};
-  return mxfp4_varlen_paged_launch<true, true>(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens,
-                                               block_table, vl, nwork, max_seqs, kv_heads, num_pages, lgt,
-                                               max_pages_per_seq, keys_per_split, qks, stream);
+  return mx_varlen_paged(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work, nseq,
+                         nwork, tokens, part_rows, max_seqs, kv_heads, group, num_pages, page_tokens,
+                         max_pages_per_seq, causal, keys_per_split, head_dim, qks, window, sinks, stream);
 }
 
 // the merge of the packed step's compact partials into O f16 [tokens][q_heads][128], lse [tokens][q_heads]

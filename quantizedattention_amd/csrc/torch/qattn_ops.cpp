@@ -421,6 +421,52 @@ Tensor mxfp4_fwd_ex(const Tensor& q_in, const Tensor& k_in, const Tensor& v_in, 
 
 Tensor mxfp4_fwd(const Tensor& q, const Tensor& k, const Tensor& v) { return mxfp4_fwd_ex(q, k, v, 0); }
 
+// What the cache operators check of the four quantised operands (k4 [n0, Hkv, S, 64]; `paged`: a page pool,
+// whose vt / vs keep k4's two leading dimensions) and of lens i32 [B] (null: the operator has none).
+void check_fp4_operands(const Tensor& k4, const Tensor& ks, const Tensor& vt, const Tensor& vs,
+                        const Tensor* lens, int64_t B, bool paged) {
+  const char* what = paged ? "qattn mxfp4 paged cache: " : "qattn mxfp4 kv cache: ";
+  for (const Tensor* t : {&k4, &ks, &vt, &vs})
+    TORCH_CHECK(t->scalar_type() == at::kByte && t->is_contiguous(), what,
+                "the quantised operands must be contiguous uint8");
+  const int64_t n0 = k4.size(0), H = k4.size(1), S = k4.size(2), D = 128;
+  TORCH_CHECK(ks.sizes() == at::IntArrayRef({n0, H, S, D / 32}) &&
+                  (paged ? vt.sizes() == at::IntArrayRef({n0, H, S / 64, D, 32}) &&
+                               vs.sizes() == at::IntArrayRef({n0, H, S / 64, D, 2})
+                         : vt.sizes() == at::IntArrayRef({n0 * H, S / 64, D, 32}) &&
+                               vs.sizes() == at::IntArrayRef({n0 * H, S / 64, D, 2})),
+              what, "ks / vt / vs do not match k4");
+  if (lens)
+    TORCH_CHECK(lens->scalar_type() == at::kInt && lens->is_contiguous() && lens->dim() == 1 && lens->size(0) == B,
+                what, "lens must be contiguous int32 [B]");
+}
+
+// The tail of mxfp4_cached, mxfp4_decode and mxfp4_decode_paged after their checks: the split plan at sk
+// keys, the outputs, q quantised, the key-split entry -- split(q4, qs, opart, ml, bhv, rows, kps, stream),
+// named `name` in an error -- and the merge.
+template <class Split>
+std::tuple<Tensor, Tensor> fp4_split_and_merge(const Tensor& q_in, int64_t Hkv, int64_t sk, int64_t keys_per_split,
+                                               bool paged, const char* name, Split split) {
+  const int64_t B = q_in.size(0), Hq = q_in.size(1), Sq = q_in.size(2), D = 128;
+  const int64_t bhv = B * Hkv, rows = (Hq / Hkv) * Sq;
+  int64_t kps = keys_per_split == 0 ? qattn_split_keys(bhv, rows, sk, 64) : keys_per_split;
+  TORCH_CHECK(kps >= 64 && kps % 64 == 0, paged ? "qattn mxfp4 paged cache: " : "qattn mxfp4 kv cache: ",
+              "keys_per_split must be a multiple of 64");
+  kps = std::min(kps, sk);
+  const int64_t nsplit = (sk + kps - 1) / kps;
+  Ctx c(q_in);
+  const Tensor q = kin(q_in, at::kHalf);
+  Tensor q4 = empty({B * Hq * Sq, D / 2}, at::kByte, q), qs = empty({B * Hq * Sq, D / 32}, at::kByte, q);
+  Tensor out = empty({B, Hq, Sq, D}, at::kHalf, q), lse = empty({B * Hq, Sq}, at::kFloat, q);
+  if (out.numel() == 0) return {out, lse};
+  call(qattn_mxfp4_quant_rows(P(q), nullptr, P(q4), P(qs), B * Hq * Sq, Sq, (int)D, c.stream), "quantise q");
+  Tensor opart = empty({nsplit, bhv * rows, D}, at::kFloat, q), ml = empty({nsplit, bhv * rows, 2}, at::kFloat, q);
+  call(split(P(q4), P(qs), P(opart), P(ml), bhv, rows, (int)kps, c.stream), name);
+  call(qattn_mxfp4_split_combine(P(opart), P(ml), P(out), P(lse), bhv * rows, (int)nsplit, (int)D, c.stream),
+       "mxfp4 split merge");
+  return {out, lse};
+}
+
 // kv_cache_mxfp4.attention_mxfp4_cached: q of any Sq >= 1 against an MX-FP4 cache in the decoding
 // layout (split over the keys, then merged)
 std::tuple<Tensor, Tensor> mxfp4_cached(const Tensor& q_in, const Tensor& k4, const Tensor& ks,
@@ -429,39 +475,21 @@ std::tuple<Tensor, Tensor> mxfp4_cached(const Tensor& q_in, const Tensor& k4, co
   require_gpu({&q_in, &k4, &ks, &vt, &vs});
   TORCH_CHECK(q_in.dim() == 4 && k4.dim() == 4 && q_in.size(3) == 128 && k4.size(3) == 64,
               "qattn mxfp4 kv cache: head_dim must be 128 in q and in the cache");
-  const int64_t B = k4.size(0), Hkv = k4.size(1), Sk = k4.size(2), D = 128;
+  const int64_t B = k4.size(0), Hkv = k4.size(1), Sk = k4.size(2);
   TORCH_CHECK(q_in.size(0) == B && Hkv > 0 && q_in.size(1) % Hkv == 0,
               "qattn mxfp4 kv cache: q must be [B, G*Hkv, Sq, D] for the cache's B, Hkv");
-  const int64_t Hq = q_in.size(1), Sq = q_in.size(2);
+  const int64_t Sq = q_in.size(2);
   TORCH_CHECK(Sq >= 1 && Sk >= 64 && Sk % 64 == 0,
               "qattn mxfp4 kv cache: Sq >= 1 and a cache of 64*n tokens expected");
   TORCH_CHECK(causal == 0 || causal == 1, "qattn mxfp4 kv cache: causal must be 0 or 1");
   TORCH_CHECK(!causal || Sq <= Sk, "qattn mxfp4 kv cache: causal attention needs Sq <= the cached tokens");
-  for (const Tensor* t : {&k4, &ks, &vt, &vs})
-    TORCH_CHECK(t->scalar_type() == at::kByte && t->is_contiguous(),
-                "qattn mxfp4 kv cache: the quantised operands must be contiguous uint8");
-  TORCH_CHECK(ks.sizes() == at::IntArrayRef({B, Hkv, Sk, D / 32}) &&
-                  vt.sizes() == at::IntArrayRef({B * Hkv, Sk / 64, D, 32}) &&
-                  vs.sizes() == at::IntArrayRef({B * Hkv, Sk / 64, D, 2}),
-              "qattn mxfp4 kv cache: ks / vt / vs do not match k4");
-  const int64_t bhv = B * Hkv, rows = (Hq / Hkv) * Sq;
-  int64_t kps = keys_per_split == 0 ? qattn_split_keys(bhv, rows, Sk, 64) : keys_per_split;
-  TORCH_CHECK(kps >= 64 && kps % 64 == 0, "qattn mxfp4 kv cache: keys_per_split must be a multiple of 64");
-  kps = std::min(kps, Sk);
-  const int64_t nsplit = (Sk + kps - 1) / kps;
-  Ctx c(q_in);
-  const Tensor q = kin(q_in, at::kHalf);
-  Tensor q4 = empty({B * Hq * Sq, D / 2}, at::kByte, q), qs = empty({B * Hq * Sq, D / 32}, at::kByte, q);
-  Tensor out = empty({B, Hq, Sq, D}, at::kHalf, q), lse = empty({B * Hq, Sq}, at::kFloat, q);
-  if (out.numel() == 0) return {out, lse};
-  call(qattn_mxfp4_quant_rows(P(q), nullptr, P(q4), P(qs), B * Hq * Sq, Sq, (int)D, c.stream), "quantise q");
-  Tensor opart = empty({nsplit, bhv * rows, D}, at::kFloat, q), ml = empty({nsplit, bhv * rows, 2}, at::kFloat, q);
-  call(qattn_mxfp4_attn_fwd_split(P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), bhv, rows, Sq,
-                                  Sk, causal ? 2 : 0, (int)kps, (int)D, qk_scale(D), c.stream),
-       "mxfp4 split forward");
-  call(qattn_mxfp4_split_combine(P(opart), P(ml), P(out), P(lse), bhv * rows, (int)nsplit, (int)D, c.stream),
-       "mxfp4 split merge");
-  return {out, lse};
+  check_fp4_operands(k4, ks, vt, vs, nullptr, B, false);
+  return fp4_split_and_merge(
+      q_in, Hkv, Sk, keys_per_split, false, "mxfp4 split forward",
+      [&](void* q4, void* qs, void* opart, void* ml, int64_t bhv, int64_t rows, int kps, void* stream) {
+        return qattn_mxfp4_attn_fwd_split(q4, qs, P(k4), P(ks), P(vt), P(vs), opart, ml, bhv, rows, Sq, Sk,
+                                          causal ? 2 : 0, kps, 128, qk_scale(128), stream);
+      });
 }
 
 // kv_cache_mxfp4.attention_mxfp4_decode on a preallocated cache's operands: k4 [B, Hkv, cap, 64] with
@@ -474,44 +502,24 @@ std::tuple<Tensor, Tensor> mxfp4_decode(const Tensor& q_in, const Tensor& k4, co
   require_gpu({&q_in, &k4, &ks, &vt, &vs, &lens});
   TORCH_CHECK(q_in.dim() == 4 && k4.dim() == 4 && q_in.size(3) == 128 && k4.size(3) == 64,
               "qattn mxfp4 kv cache: head_dim must be 128 in q and in the cache");
-  const int64_t B = k4.size(0), Hkv = k4.size(1), cap = k4.size(2), D = 128;
+  const int64_t B = k4.size(0), Hkv = k4.size(1), cap = k4.size(2);
   TORCH_CHECK(q_in.size(0) == B && Hkv > 0 && q_in.size(1) % Hkv == 0,
               "qattn mxfp4 kv cache: q must be [B, G*Hkv, Sq, D] for the cache's B, Hkv");
-  const int64_t Hq = q_in.size(1), Sq = q_in.size(2);
+  const int64_t Sq = q_in.size(2);
   TORCH_CHECK(Sq >= 1 && cap >= 64 && cap % 64 == 0,
               "qattn mxfp4 kv cache: Sq >= 1 and a capacity of 64*n tokens expected");
   TORCH_CHECK(sk_max >= 64 && sk_max % 64 == 0 && sk_max <= cap,
               "qattn mxfp4 kv cache: sk_max must be a multiple of 64 in [64, capacity]");
   TORCH_CHECK(causal == 0 || causal == 1, "qattn mxfp4 kv cache: causal must be 0 or 1");
   TORCH_CHECK(!causal || Sq <= sk_max, "qattn mxfp4 kv cache: causal attention needs Sq <= the cached tokens");
-  for (const Tensor* t : {&k4, &ks, &vt, &vs})
-    TORCH_CHECK(t->scalar_type() == at::kByte && t->is_contiguous(),
-                "qattn mxfp4 kv cache: the quantised operands must be contiguous uint8");
-  TORCH_CHECK(ks.sizes() == at::IntArrayRef({B, Hkv, cap, D / 32}) &&
-                  vt.sizes() == at::IntArrayRef({B * Hkv, cap / 64, D, 32}) &&
-                  vs.sizes() == at::IntArrayRef({B * Hkv, cap / 64, D, 2}),
-              "qattn mxfp4 kv cache: ks / vt / vs do not match k4");
-  TORCH_CHECK(lens.scalar_type() == at::kInt && lens.is_contiguous() && lens.dim() == 1 && lens.size(0) == B,
-              "qattn mxfp4 kv cache: lens must be contiguous int32 [B]");
-  const int64_t bhv = B * Hkv, rows = (Hq / Hkv) * Sq;
-  int64_t kps = keys_per_split == 0 ? qattn_split_keys(bhv, rows, sk_max, 64) : keys_per_split;
-  TORCH_CHECK(kps >= 64 && kps % 64 == 0, "qattn mxfp4 kv cache: keys_per_split must be a multiple of 64");
-  kps = std::min(kps, sk_max);
-  const int64_t nsplit = (sk_max + kps - 1) / kps;
-  Ctx c(q_in);
-  const Tensor q = kin(q_in, at::kHalf);
-  Tensor q4 = empty({B * Hq * Sq, D / 2}, at::kByte, q), qs = empty({B * Hq * Sq, D / 32}, at::kByte, q);
-  Tensor out = empty({B, Hq, Sq, D}, at::kHalf, q), lse = empty({B * Hq, Sq}, at::kFloat, q);
-  if (out.numel() == 0) return {out, lse};
-  call(qattn_mxfp4_quant_rows(P(q), nullptr, P(q4), P(qs), B * Hq * Sq, Sq, (int)D, c.stream), "quantise q");
-  Tensor opart = empty({nsplit, bhv * rows, D}, at::kFloat, q), ml = empty({nsplit, bhv * rows, 2}, at::kFloat, q);
-  call(qattn_mxfp4_attn_fwd_split_len(P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens), bhv,
-                                      Hkv, rows, Sq, cap, sk_max, causal ? 2 : 0, (int)kps, (int)D,
-                                      qk_scale(D), c.stream),
-       "mxfp4 decode forward");
-  call(qattn_mxfp4_split_combine(P(opart), P(ml), P(out), P(lse), bhv * rows, (int)nsplit, (int)D, c.stream),
-       "mxfp4 split merge");
-  return {out, lse};
+  check_fp4_operands(k4, ks, vt, vs, &lens, B, false);
+  return fp4_split_and_merge(
+      q_in, Hkv, sk_max, keys_per_split, false, "mxfp4 decode forward",
+      [&](void* q4, void* qs, void* opart, void* ml, int64_t bhv, int64_t rows, int kps, void* stream) {
+        return qattn_mxfp4_attn_fwd_split_len(q4, qs, P(k4), P(ks), P(vt), P(vs), opart, ml, P(lens), bhv, Hkv,
+                                              rows, Sq, cap, sk_max, causal ? 2 : 0, kps, 128, qk_scale(128),
+                                              stream);
+      });
 }
 
 // kv_cache_mxfp4.attention_mxfp4_decode_paged on a page pool's operands: k4 [num_pages, Hkv, P, 64] with
@@ -526,7 +534,7 @@ std::tuple<Tensor, Tensor> mxfp4_decode_paged(const Tensor& q_in, const Tensor& 
   require_gpu({&q_in, &k4, &ks, &vt, &vs, &lens, &block_table});
   TORCH_CHECK(q_in.dim() == 4 && k4.dim() == 4 && q_in.size(3) == 128 && k4.size(3) == 64,
               "qattn mxfp4 paged cache: head_dim must be 128 in q and in the pool");
-  const int64_t NP = k4.size(0), Hkv = k4.size(1), PT = k4.size(2), D = 128;
+  const int64_t NP = k4.size(0), Hkv = k4.size(1), PT = k4.size(2);
   TORCH_CHECK(PT >= 64 && PT <= 1024 && (PT & (PT - 1)) == 0,
               "qattn mxfp4 paged cache: page_tokens must be 64 * 2^k in [64, 1024]");
   TORCH_CHECK(block_table.scalar_type() == at::kInt && block_table.is_contiguous() && block_table.dim() == 2 &&
@@ -535,40 +543,20 @@ std::tuple<Tensor, Tensor> mxfp4_decode_paged(const Tensor& q_in, const Tensor& 
   const int64_t B = block_table.size(0), mpp = block_table.size(1);
   TORCH_CHECK(q_in.size(0) == B && Hkv > 0 && NP > 0 && q_in.size(1) % Hkv == 0,
               "qattn mxfp4 paged cache: q must be [B, G*Hkv, Sq, D] for the table's B and the pool's Hkv");
-  const int64_t Hq = q_in.size(1), Sq = q_in.size(2);
+  const int64_t Sq = q_in.size(2);
   TORCH_CHECK(Sq >= 1, "qattn mxfp4 paged cache: Sq >= 1 expected");
   TORCH_CHECK(sk_max >= 64 && sk_max % 64 == 0 && sk_max <= mpp * PT,
               "qattn mxfp4 paged cache: sk_max must be a multiple of 64 in [64, max_pages_per_seq * page_tokens]");
   TORCH_CHECK(causal == 0 || causal == 1, "qattn mxfp4 paged cache: causal must be 0 or 1");
   TORCH_CHECK(!causal || Sq <= sk_max, "qattn mxfp4 paged cache: causal attention needs Sq <= the cached tokens");
-  for (const Tensor* t : {&k4, &ks, &vt, &vs})
-    TORCH_CHECK(t->scalar_type() == at::kByte && t->is_contiguous(),
-                "qattn mxfp4 paged cache: the quantised operands must be contiguous uint8");
-  TORCH_CHECK(ks.sizes() == at::IntArrayRef({NP, Hkv, PT, D / 32}) &&
-                  vt.sizes() == at::IntArrayRef({NP, Hkv, PT / 64, D, 32}) &&
-                  vs.sizes() == at::IntArrayRef({NP, Hkv, PT / 64, D, 2}),
-              "qattn mxfp4 paged cache: ks / vt / vs do not match k4");
-  TORCH_CHECK(lens.scalar_type() == at::kInt && lens.is_contiguous() && lens.dim() == 1 && lens.size(0) == B,
-              "qattn mxfp4 paged cache: lens must be contiguous int32 [B]");
-  const int64_t bhv = B * Hkv, rows = (Hq / Hkv) * Sq;
-  int64_t kps = keys_per_split == 0 ? qattn_split_keys(bhv, rows, sk_max, 64) : keys_per_split;
-  TORCH_CHECK(kps >= 64 && kps % 64 == 0, "qattn mxfp4 paged cache: keys_per_split must be a multiple of 64");
-  kps = std::min(kps, sk_max);
-  const int64_t nsplit = (sk_max + kps - 1) / kps;
-  Ctx c(q_in);
-  const Tensor q = kin(q_in, at::kHalf);
-  Tensor q4 = empty({B * Hq * Sq, D / 2}, at::kByte, q), qs = empty({B * Hq * Sq, D / 32}, at::kByte, q);
-  Tensor out = empty({B, Hq, Sq, D}, at::kHalf, q), lse = empty({B * Hq, Sq}, at::kFloat, q);
-  if (out.numel() == 0) return {out, lse};
-  call(qattn_mxfp4_quant_rows(P(q), nullptr, P(q4), P(qs), B * Hq * Sq, Sq, (int)D, c.stream), "quantise q");
-  Tensor opart = empty({nsplit, bhv * rows, D}, at::kFloat, q), ml = empty({nsplit, bhv * rows, 2}, at::kFloat, q);
-  call(qattn_mxfp4_attn_fwd_split_paged(P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens),
-                                        P(block_table), bhv, Hkv, rows, Sq, NP, PT, mpp, sk_max,
-                                        causal ? 2 : 0, (int)kps, (int)D, qk_scale(D), c.stream),
-       "mxfp4 paged decode forward");
-  call(qattn_mxfp4_split_combine(P(opart), P(ml), P(out), P(lse), bhv * rows, (int)nsplit, (int)D, c.stream),
-       "mxfp4 split merge");
-  return {out, lse};
+  check_fp4_operands(k4, ks, vt, vs, &lens, B, true);
+  return fp4_split_and_merge(
+      q_in, Hkv, sk_max, keys_per_split, true, "mxfp4 paged decode forward",
+      [&](void* q4, void* qs, void* opart, void* ml, int64_t bhv, int64_t rows, int kps, void* stream) {
+        return qattn_mxfp4_attn_fwd_split_paged(q4, qs, P(k4), P(ks), P(vt), P(vs), opart, ml, P(lens),
+                                                P(block_table), bhv, Hkv, rows, Sq, NP, PT, mpp, sk_max,
+                                                causal ? 2 : 0, kps, 128, qk_scale(128), stream);
+      });
 }
 
 // kv_cache_mxfp4.attention_mxfp4_varlen_paged on a page pool's operands: packed q [T, Hq, 128], lens i32
@@ -599,15 +587,7 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged_run(const Tensor& q_in, const Tens
   TORCH_CHECK(Hkv > 0 && NP > 0 && Hq > 0 && Hq % Hkv == 0,
               "qattn mxfp4 paged cache: q must have G * Hkv heads for the pool's Hkv");
   TORCH_CHECK(causal == 0 || causal == 1, "qattn mxfp4 paged cache: causal must be 0 or 1");
-  for (const Tensor* t : {&k4, &ks, &vt, &vs})
-    TORCH_CHECK(t->scalar_type() == at::kByte && t->is_contiguous(),
-                "qattn mxfp4 paged cache: the quantised operands must be contiguous uint8");
-  TORCH_CHECK(ks.sizes() == at::IntArrayRef({NP, Hkv, PT, D / 32}) &&
-                  vt.sizes() == at::IntArrayRef({NP, Hkv, PT / 64, D, 32}) &&
-                  vs.sizes() == at::IntArrayRef({NP, Hkv, PT / 64, D, 2}),
-              "qattn mxfp4 paged cache: ks / vt / vs do not match k4");
-  TORCH_CHECK(lens.scalar_type() == at::kInt && lens.is_contiguous() && lens.dim() == 1 && lens.size(0) == B,
-              "qattn mxfp4 paged cache: lens must be contiguous int32 [B]");
+  check_fp4_operands(k4, ks, vt, vs, &lens, B, true);
   TORCH_CHECK(seq_rec.scalar_type() == at::kInt && seq_rec.is_contiguous() && seq_rec.dim() == 2 &&
                   seq_rec.size(1) == 8 && seq_rec.size(0) >= 1 && seq_rec.size(0) <= B,
               "qattn mxfp4 paged cache: seq_rec must be contiguous int32 [nseq, 8], 1 <= nseq <= B");

@@ -267,6 +267,25 @@ def _split_plan_fp4(bhv: int, rows: int, sk: int) -> int:
     return _lib.load().qattn_split_keys(bhv, rows, sk, BLOCK)
 
 
+def _split_and_merge(q: torch.Tensor, kv, causal: bool, kps: int, nsplit: int, bhv: int, rows: int,
+                     entry: str, *middle):
+    """The tail the padded attention functions share, after their checks: quantise ``q`` [B, Hq, Sq, D],
+    allocate O, lse and the ``nsplit`` partials, run the key-split entry ``entry`` on the operands ``kv``
+    (``middle``: the entry's own arguments between ``ml`` and ``causal``) and merge -> (O, lse)."""
+    B, Hq, Sq, D = q.shape
+    dev, st = q.device, _lib.stream_of(q)
+    q4, qs = mxfp4_quantize_rows(q)
+    O = torch.empty((B, Hq, Sq, D), dtype=torch.float16, device=dev)
+    lse = torch.empty((B * Hq, Sq), dtype=torch.float32, device=dev)
+    opart = torch.empty((nsplit, bhv * rows, D), dtype=torch.float32, device=dev)
+    ml = torch.empty((nsplit, bhv * rows, 2), dtype=torch.float32, device=dev)
+    _lib.call(entry, _lib.ptr(q4), _lib.ptr(qs), *(_lib.ptr(t) for t in kv), _lib.ptr(opart), _lib.ptr(ml),
+              *middle, 2 if causal else 0, kps, D, _qk_scale(D), st)
+    _lib.call("qattn_mxfp4_split_combine", _lib.ptr(opart), _lib.ptr(ml), _lib.ptr(O), _lib.ptr(lse),
+              bhv * rows, nsplit, D, st)
+    return O, lse
+
+
 @torch.no_grad()
 def attention_mxfp4_cached(q: torch.Tensor, kv: QuantizedKVFP4, causal: bool = False,
                            keys_per_split: Optional[int] = None):
@@ -302,23 +321,23 @@ def attention_mxfp4_cached(q: torch.Tensor, kv: QuantizedKVFP4, causal: bool = F
         raise _lib.QAttnError("qattn mxfp4 kv cache: keys_per_split must be a multiple of 64")
     kps = min(kps, Sk)
     nsplit = -(-Sk // kps)
-    dev, st = q.device, _lib.stream_of(q)
-    q4, qs = mxfp4_quantize_rows(q)
-    O = torch.empty((B, Hq, Sq, D), dtype=torch.float16, device=dev)
-    lse = torch.empty((B * Hq, Sq), dtype=torch.float32, device=dev)
-    opart = torch.empty((nsplit, bhv * rows, D), dtype=torch.float32, device=dev)
-    ml = torch.empty((nsplit, bhv * rows, 2), dtype=torch.float32, device=dev)
-    _lib.call("qattn_mxfp4_attn_fwd_split", _lib.ptr(q4), _lib.ptr(qs), _lib.ptr(kv.k4), _lib.ptr(kv.ks),
-              _lib.ptr(kv.vt), _lib.ptr(kv.vs), _lib.ptr(opart), _lib.ptr(ml), bhv, rows, Sq, Sk,
-              2 if causal else 0, kps, D, _qk_scale(D), st)
-    _lib.call("qattn_mxfp4_split_combine", _lib.ptr(opart), _lib.ptr(ml), _lib.ptr(O), _lib.ptr(lse),
-              bhv * rows, nsplit, D, st)
-    return O, lse
+    return _split_and_merge(q, kv.kv, causal, kps, nsplit, bhv, rows, "qattn_mxfp4_attn_fwd_split",
+                            bhv, rows, Sq, Sk)
 
 
 # ------------------------------------------------------------------------------ preallocated cache
 def _ceil64(n: int) -> int:
     return -(-n // BLOCK) * BLOCK
+
+
+def _append_counts(counts, B: int, n: int, error: str) -> list:
+    """``counts`` of a padded ``append`` as B ints in [0, n] (None: n each); raises ``error`` otherwise."""
+    if counts is None:
+        return [n] * B
+    cnt = [int(c) for c in (counts.tolist() if isinstance(counts, torch.Tensor) else counts)]
+    if len(cnt) != B or any(c < 0 or c > n for c in cnt):
+        raise _lib.QAttnError(error)
+    return cnt
 
 
 class PreallocatedKVFP4:
@@ -381,12 +400,7 @@ class PreallocatedKVFP4:
                 or k.shape[2] < 1):
             raise _lib.QAttnError("qattn mxfp4 kv cache: appended tokens must be k, v [B, Hkv, n >= 1, D]")
         n = k.shape[2]
-        if counts is None:
-            cnt = [n] * B
-        else:
-            cnt = [int(c) for c in (counts.tolist() if isinstance(counts, torch.Tensor) else counts)]
-            if len(cnt) != B or any(c < 0 or c > n for c in cnt):
-                raise _lib.QAttnError("qattn mxfp4 kv cache: counts must be B values in [0, n]")
+        cnt = _append_counts(counts, B, n, "qattn mxfp4 kv cache: counts must be B values in [0, n]")
         if any(L + c > cap for L, c in zip(self.lengths, cnt)):
             raise _lib.QAttnError(f"qattn mxfp4 kv cache: append past the capacity of {cap} tokens "
                                   f"(lengths {self.lengths}, counts {cnt})")
@@ -469,21 +483,9 @@ def attention_mxfp4_decode(q: torch.Tensor, cache: PreallocatedKVFP4, causal: bo
     """
     bhv, rows, sk_max, kps, nsplit = _decode_plan(q, cache, causal, keys_per_split)
     _lib.require_gpu(q, cache.k4)
-    B, Hkv, cap, D = cache.shape
-    Hq, Sq = q.shape[1], q.shape[2]
-    dev, st = q.device, _lib.stream_of(q)
-    q4, qs = mxfp4_quantize_rows(q)
-    O = torch.empty((B, Hq, Sq, D), dtype=torch.float16, device=dev)
-    lse = torch.empty((B * Hq, Sq), dtype=torch.float32, device=dev)
-    opart = torch.empty((nsplit, bhv * rows, D), dtype=torch.float32, device=dev)
-    ml = torch.empty((nsplit, bhv * rows, 2), dtype=torch.float32, device=dev)
-    _lib.call("qattn_mxfp4_attn_fwd_split_len", _lib.ptr(q4), _lib.ptr(qs), _lib.ptr(cache.k4),
-              _lib.ptr(cache.ks), _lib.ptr(cache.vt), _lib.ptr(cache.vs), _lib.ptr(opart), _lib.ptr(ml),
-              _lib.ptr(cache.lens), bhv, Hkv, rows, Sq, cap, sk_max, 2 if causal else 0, kps, D,
-              _qk_scale(D), st)
-    _lib.call("qattn_mxfp4_split_combine", _lib.ptr(opart), _lib.ptr(ml), _lib.ptr(O), _lib.ptr(lse),
-              bhv * rows, nsplit, D, st)
-    return O, lse
+    _, Hkv, cap, _ = cache.shape
+    return _split_and_merge(q, cache.kv, causal, kps, nsplit, bhv, rows, "qattn_mxfp4_attn_fwd_split_len",
+                            _lib.ptr(cache.lens), bhv, Hkv, rows, q.shape[2], cap, sk_max)
 
 
 # ------------------------------------------------------------------------------ paged cache
@@ -722,12 +724,7 @@ class PagedKVFP4:
             raise _lib.QAttnError("qattn mxfp4 paged cache: appended tokens must be k, v [max_seqs, Hkv, "
                                   "n >= 1, D]")
         n = k.shape[2]
-        if counts is None:
-            cnt = [n] * B
-        else:
-            cnt = [int(c) for c in (counts.tolist() if isinstance(counts, torch.Tensor) else counts)]
-            if len(cnt) != B or any(c < 0 or c > n for c in cnt):
-                raise _lib.QAttnError("qattn mxfp4 paged cache: counts must be max_seqs values in [0, n]")
+        cnt = _append_counts(counts, B, n, "qattn mxfp4 paged cache: counts must be max_seqs values in [0, n]")
         _lib.require_gpu(k, v, self.k4)
         grown = self.alloc.reserve([(b, L + c) for b, (L, c) in enumerate(zip(self.lengths, cnt)) if c])
         k = _lib.kernel_input(k, torch.float16)
@@ -874,22 +871,10 @@ def attention_mxfp4_decode_paged(q: torch.Tensor, cache: PagedKVFP4, causal: boo
         for b in range(cache.alloc.max_seqs):
             cache._whole(b, "attention_mxfp4_decode_paged")
     _lib.require_gpu(q, cache.k4)
-    B, Hkv, _, D = cache.shape
-    Hq, Sq = q.shape[1], q.shape[2]
-    dev, st = q.device, _lib.stream_of(q)
-    q4, qs = mxfp4_quantize_rows(q)
-    O = torch.empty((B, Hq, Sq, D), dtype=torch.float16, device=dev)
-    lse = torch.empty((B * Hq, Sq), dtype=torch.float32, device=dev)
-    opart = torch.empty((nsplit, bhv * rows, D), dtype=torch.float32, device=dev)
-    ml = torch.empty((nsplit, bhv * rows, 2), dtype=torch.float32, device=dev)
-    _lib.call("qattn_mxfp4_attn_fwd_split_paged", _lib.ptr(q4), _lib.ptr(qs), _lib.ptr(cache.k4),
-              _lib.ptr(cache.ks), _lib.ptr(cache.vt), _lib.ptr(cache.vs), _lib.ptr(opart), _lib.ptr(ml),
-              _lib.ptr(cache.lens), _lib.ptr(cache.block_table), bhv, Hkv, rows, Sq, cache.num_pages,
-              cache.page_tokens, cache.alloc.max_pages_per_seq, sk_max, 2 if causal else 0, kps, D,
-              _qk_scale(D), st)
-    _lib.call("qattn_mxfp4_split_combine", _lib.ptr(opart), _lib.ptr(ml), _lib.ptr(O), _lib.ptr(lse),
-              bhv * rows, nsplit, D, st)
-    return O, lse
+    return _split_and_merge(q, cache.kv, causal, kps, nsplit, bhv, rows, "qattn_mxfp4_attn_fwd_split_paged",
+                            _lib.ptr(cache.lens), _lib.ptr(cache.block_table), bhv, cache.shape[1], rows,
+                            q.shape[2], cache.num_pages, cache.page_tokens, cache.alloc.max_pages_per_seq,
+                            sk_max)
 
 
 # ------------------------------------------------------------------------------ packed (varlen) step

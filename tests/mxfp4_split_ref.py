@@ -85,6 +85,60 @@ def merge(m, l, O):
     return Om.to(torch.float16), (Mx + torch.log2(L)).to(torch.float32)
 
 
+def merge_bits(opart, ml):
+    """The kernels' merge (csrc/mxfp4_attn.hip mx_merge_row) restated bit for bit on the CPU: fp32
+    ``opart`` [ns, R, D] and ``ml`` [ns, R, 2] = {m_s, l_s} -> (O fp16 [R, D], differs bool [R, D], lse fp32
+    [R]).  In fp32: M = max_s m_s; w_s = 2^(m_s - M), 0 for m_s = -inf; L = w_s * l_s + L and acc = w_s *
+    O_s + acc over the splits in order, a multiply and then an add -- w_s is a power of two, so the product
+    is exact and this is the kernel's fmaf (as long as no product is subnormal); inv = 1 / L, correctly
+    rounded.  Then the conversion as the kernel defines it: a column c with c % 8 in (0, 7) is the exact
+    product acc * inv (float64 holds it) rounded to fp16 ONCE, by numpy -- torch's float64 -> float16 goes
+    through float32 on the CPU -- and every other column is the fp32 product, rounded, then converted.
+    ``differs`` marks the elements where the two forms disagree, whichever the column takes; ``lse`` is
+    M + log2(L) in float64, for a tolerance."""
+    import numpy as np
+    opart, ml = opart.detach().float().cpu(), ml.detach().float().cpu()
+    ns, R, D = opart.shape
+    m, l = ml[..., 0], ml[..., 1]
+    Mx = m.amax(0)
+    gone = torch.isinf(m)
+    e = torch.where(gone, torch.zeros_like(m), m - Mx).to(torch.int32)
+    w = torch.where(gone, torch.zeros_like(m), torch.ldexp(torch.ones_like(m), e))
+    L = torch.zeros(R, dtype=torch.float32)
+    acc = torch.zeros((R, D), dtype=torch.float32)
+    for s in range(ns):
+        L = w[s] * l[s] + L
+        acc = w[s][:, None] * opart[s] + acc
+    inv = 1.0 / L
+    twice = (acc * inv[:, None]).to(torch.float16)
+    once = torch.from_numpy((acc.double().numpy() * inv.double().numpy()[:, None]).astype(np.float16))
+    col = torch.arange(D) % 8
+    out = torch.where(((col == 0) | (col == 7))[None, :], once, twice)
+    differs = once.view(torch.int16) != twice.view(torch.int16)
+    return out, differs, (Mx.double() + torch.log2(L.double())).to(torch.float32)
+
+
+def merge_partials(seed, nsplit, R, D=128):
+    """Random partials of R rows -> (opart fp32 [nsplit, R, D], ml fp32 [nsplit, R, 2]): O_s = 40 randn, m_s
+    integers in [-3, 3] with every seventh row of split 0 at -inf (every row keeps a finite m), l_s in
+    [1, 61)."""
+    g = torch.Generator().manual_seed(seed)
+    opart = 40 * torch.randn((nsplit, R, D), generator=g)
+    m = torch.randint(-3, 4, (nsplit, R), generator=g).float()
+    m[0, ::7] = float("-inf")
+    l = 1 + 60 * torch.rand((nsplit, R), generator=g)
+    return opart, torch.stack([m, l], -1).contiguous()
+
+
+@functools.lru_cache(maxsize=None)
+def merge_case(seed=0, nsplit=3, R=2048):
+    """``merge_partials`` on which the two conversions of :func:`merge_bits` differ in both kinds of
+    column (tests/test_mxfp4_cache_ref.py), with their merge, computed once per session; do not modify ->
+    (opart, ml, O, differs, lse)."""
+    opart, ml = merge_partials(seed, nsplit, R)
+    return (opart, ml) + merge_bits(opart, ml)
+
+
 def mxfp4_fwd_split(q, k, v, causal, kps):
     """-> (O fp16 [B,H,Sq,D], lse fp32 [B*H,Sq], operands, (m, l) of the partials)."""
     m, l, O, ops = split_partials(q, k, v, causal, kps)

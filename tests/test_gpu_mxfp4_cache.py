@@ -131,6 +131,68 @@ def test_empty_partials(lib):
     assert (lse - Rl.reshape(-1)).abs().max().item() <= 1e-4
 
 
+# ------------------------------------------------------------------ the merge, bit for bit
+def _merge(opart, ml, rec, T, Hq, Hkv):
+    """qattn_mxfp4_varlen_combine (``rec``: its seq_rec rows) or, rec None, qattn_mxfp4_split_combine of
+    the padded partials, on the GPU -> (out fp16 [T * Hq, D], lse fp32 [T * Hq]) on the CPU."""
+    from quantizedattention_amd import _lib
+    D = opart.shape[-1]
+    op_d, ml_d = opart.cuda().contiguous(), ml.cuda().contiguous()
+    out = torch.full((T * Hq, D), SENTINEL, dtype=torch.float16, device="cuda")
+    lse = torch.full((T * Hq,), SENTINEL, dtype=torch.float32, device="cuda")
+    st = _lib.stream_of(op_d)
+    if rec is None:
+        _lib.call("qattn_mxfp4_split_combine", _lib.ptr(op_d), _lib.ptr(ml_d), _lib.ptr(out), _lib.ptr(lse),
+                  T * Hq, opart.shape[0], D, st)
+    else:
+        rec_d = torch.tensor(rec, dtype=torch.int32).cuda()
+        _lib.call("qattn_mxfp4_varlen_combine", _lib.ptr(op_d), _lib.ptr(ml_d), _lib.ptr(out), _lib.ptr(lse),
+                  _lib.ptr(rec_d), len(rec), T, Hq, Hkv, ml_d.numel() // 2, D, st)
+    torch.cuda.synchronize()
+    return out.cpu(), lse.cpu()
+
+
+def test_merge_bit_for_bit(lib):
+    """Both merge kernels give the bits of the CPU restatement SR.merge_bits -- the rounding of every
+    column included: SR.merge_case has elements in both kinds of column where rounding once and rounding
+    twice differ (tests/test_mxfp4_cache_ref.py).  lse: the two kernels agree bit for bit and are within
+    test_split_vs_restatement's 1e-4 of M + log2(L).  With one key/value head, one query head and one
+    sequence the packed entry's compact layout is the padded one."""
+    opart, ml, RO, differs, Rl = SR.merge_case()
+    ns, R, D = opart.shape
+    O1, l1 = _merge(opart, ml, None, R, 1, 1)
+    O2, l2 = _merge(opart, ml, [[0, 0, R, ns, 0, 0, 0, 0]], R, 1, 1)
+    for name, O, lse in (("padded", O1, l1), ("packed", O2, l2)):
+        ne = O.view(torch.int16) != RO.view(torch.int16)
+        print(f"MXFP4-CACHE merge {name}: {int(ne.sum())} of {ne.numel()} elements differ from merge_bits "
+              f"({int((ne & differs).sum())} of them among the {int(differs.sum())} the two roundings tell "
+              f"apart), lse {(lse - Rl).abs().max().item():.3e}")
+    assert torch.equal(O1, RO)
+    assert torch.equal(O2, RO)
+    assert torch.equal(l1, l2)
+    assert (l1 - Rl).abs().max().item() <= 1e-4 and (l2 - Rl).abs().max().item() <= 1e-4
+
+    # the compact layout proper: 4 query heads over 2 key/value heads, two sequences of 37 and 50 tokens
+    # with 2 and 3 splits; sequence j's partial rows are [split][kv head][g * n_j + i] from its first one
+    Hq, Hkv, G = 4, 2, 2
+    seqs, rec, first, base = [], [], 0, 0
+    for j, (n, nsp) in enumerate(((37, 2), (50, 3))):
+        po, pm = SR.merge_partials(10 + j, nsp, n * Hq)   # in output order: row = token * Hq + head
+        tok, head = torch.arange(n * Hq) // Hq, torch.arange(n * Hq) % Hq
+        rows = (base + torch.arange(nsp)[:, None] * (Hkv * G * n) + (head // G * (G * n) + head % G * n + tok)[None])
+        seqs.append((po, pm, rows, first * Hq, n * Hq))
+        rec.append([j, first, n, nsp, base, 0, 0, 0])
+        first, base = first + n, base + nsp * Hkv * G * n
+    opart, ml = torch.zeros((base, D)), torch.zeros((base, 2))
+    for po, pm, rows, _, _ in seqs:
+        opart[rows.reshape(-1)], ml[rows.reshape(-1)] = po.reshape(-1, D), pm.reshape(-1, 2)
+    O, lse = _merge(opart, ml, rec, first, Hq, Hkv)
+    for po, pm, _, r0, nr in seqs:
+        RO, _, Rl = SR.merge_bits(po, pm)
+        assert torch.equal(O[r0:r0 + nr], RO)
+        assert (lse[r0:r0 + nr] - Rl).abs().max().item() <= 1e-4
+
+
 # ------------------------------------------------------------------ 7. row tails write nothing else
 @pytest.mark.parametrize("G,sq_head,causal", [(5, 1, 0), (1, 33, 0), (1, 33, 2), (2, 65, 2), (1, 130, 0)])
 def test_row_tails_write_nothing_else(lib, G, sq_head, causal):

@@ -40,6 +40,26 @@ def test_split_restatement_is_the_one_pass_restatement(case, qmul):
         assert not empty.any()
 
 
+def test_merge_case_tells_the_two_roundings_apart():
+    """The partials tests/test_gpu_mxfp4_cache.py merges on the GPU discriminate: the product rounded to
+    fp16 once and the one rounded twice differ in at least 4 elements of the columns that take the first
+    form (c % 8 in (0, 7)) and in at least 4 of the others, so a kernel that used one form everywhere, or
+    swapped them, would not reproduce ``merge_bits``."""
+    opart, ml, O, differs, lse = SR.merge_case()
+    assert opart.shape == (3, 2048, 128) and ml.shape == (3, 2048, 2)
+    m = ml[..., 0]
+    assert bool(torch.isinf(m[0, ::7]).all()) and bool(torch.isfinite(m).any(0).all())
+    assert torch.equal(m[torch.isfinite(m)], m[torch.isfinite(m)].round())
+    assert bool(torch.isfinite(O.float()).all()) and bool(torch.isfinite(lse).all())
+    col = torch.arange(128) % 8
+    edge = (col == 0) | (col == 7)
+    print(f"differing elements: {int(differs[:, edge].sum())} in columns 0/7, {int(differs[:, ~edge].sum())} "
+          f"in the others, of {differs.numel()}")
+    assert int(differs[:, edge].sum()) >= 4 and int(differs[:, ~edge].sum()) >= 4
+    # a second evaluation gives the same bits
+    assert torch.equal(SR.merge_bits(opart, ml)[0], O)
+
+
 # ------------------------------------------------------------------------------ wire format
 def _random_cache(B=2, H=3, S=128, D=128, smoothed=True, seed=0):
     g = torch.Generator().manual_seed(seed)
