@@ -535,6 +535,33 @@ int qattn_mxfp4_attn_fwd_varlen_paged_window(
     long num_pages, long page_tokens, long max_pages_per_seq, int causal, int keys_per_split, int head_dim,
     float qks, long window, long sinks, void* stream);
 
+/* The packed step with shared prefixes (kv_cache_mxfp4.py attention_mxfp4_varlen_paged(share_prefix=True),
+ * whose plan_varlen_shared builds the tables): the first entry above, with the key splits that lie wholly
+ * inside pages several sequences hold in common computed once for all of them.  seq_rec, the partial rows,
+ * part_rows and the merge (qattn_mxfp4_varlen_combine) are that entry's; so is every bit of opart / ml
+ * and of the merged result at the same keys_per_split.  Two more DEVICE i32 tables:
+ *   grp_rec [ngroup][4]  {first entry in members, member count >= 2, ns_g, R_g}: group g shares its
+ *                        splits [0, ns_g); R_g = group * (sum of n_j over its members) stacked rows;
+ *   members [nmember][2] {j, first stacked row of sequence j in its group}, a group's entries consecutive
+ *                        and ascending; stacked row r of a group is row r - first of its member's virtual
+ *                        head, in that member's own order g * n_j + i.
+ * and work records of two kinds: {j, 128-row block, split, 0} as in the first entry, for every split >=
+ * ns_g of a member and every split of an ungrouped sequence, and {g, 128-row block of group g's stacked
+ * rows, split < ns_g, 1}, whose workgroup fetches the split's tiles once, through the block_table row of
+ * the group's first member, and writes every row's state where the first kind would have.
+ * Preconditions the caller guarantees beyond the first entry's: the first ceil(ns_g * keys_per_split / P)
+ * block_table entries of a group's members are equal, ns_g * keys_per_split <= L_j for every member and,
+ * causal == 2, <= L_j - n_j + 1 (no shared key is masked for any row); no sequence in two groups.  Every
+ * table index is clamped or checked as in the first entry.
+ * Returns 1 as the first entry, and for a NULL grp_rec / members, ngroup < 1, nmember < 2 * ngroup or
+ * nmember > nseq; 0 without a launch for nwork or tokens == 0. */
+int qattn_mxfp4_attn_fwd_varlen_paged_shared(
+    const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt, const void* vscale,
+    void* opart, void* ml, const void* lens, const void* block_table, const void* seq_rec, const void* work,
+    long nseq, long nwork, long tokens, long part_rows, long max_seqs, long kv_heads, long group,
+    long num_pages, long page_tokens, long max_pages_per_seq, int causal, int keys_per_split, int head_dim,
+    float qks, const void* grp_rec, const void* members, long ngroup, long nmember, void* stream);
+
 /* The merge of the packed step: qattn_mxfp4_split_combine's arithmetic in its order, per packed row
  * (token, query head), over the ns_j partial rows of the token's own sequence (found by binary search
  * over seq_rec's first-token column): out f16 [tokens][q_heads][128], lse f32 [tokens][q_heads].

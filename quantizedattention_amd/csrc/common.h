@@ -623,6 +623,43 @@ QA_DEVICE void store_rows(const v16f* acc, float sc, char* lds, T* dst_row0, int
   }
 }
 
+// store_rows for a tile whose rows do not follow one another in memory (fp32, acc * sc): staged row i is
+// row rows[i] of dst, rows an LDS array of the wave's 32 destination row indices outside the staging
+// region, written by this wave before the call; an index < 0 stores nothing.  The same staging and the
+// same 16-B read-back stores, each row's chunks coalesced.
+template <int D, int NPASS>
+QA_DEVICE void store_rows_indexed(const v16f* acc, float sc, char* lds, float* dst, const int* rows, int lane) {
+  using RT = RowTile<D, float, NPASS>;
+  constexpr int NBP = D / 32 / NPASS;
+  const int h = lane >> 5, c32 = lane & 31;
+#pragma unroll
+  for (int pass = 0; pass < NPASS; ++pass) {
+#pragma unroll
+    for (int bb = 0; bb < NBP; ++bb) {
+      const int b = pass * NBP + bb;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        v4f w;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[j] = acc[b][4 * g + j] * sc;
+        *reinterpret_cast<v4f*>(lds + c32 * RT::PITCH + (32 * bb + 8 * g + 4 * h) * (int)sizeof(float)) = w;
+      }
+    }
+    constexpr int CPR = RT::DC * (int)sizeof(float) / 16;
+    constexpr int RPI = 64 / CPR;
+    const int r = lane / CPR, c = lane % CPR;
+#pragma unroll
+    for (int i = 0; i < 32 / RPI; ++i) {
+      const int row = i * RPI + r;
+      const v4u v = *reinterpret_cast<const v4u*>(lds + row * RT::PITCH + 16 * c);
+      const int d = rows[row];
+      if (d >= 0)
+        *reinterpret_cast<v4u*>(reinterpret_cast<char*>(dst) + (long)d * D * (long)sizeof(float) +
+                                pass * RT::DC * (int)sizeof(float) + 16 * c) = v;
+    }
+  }
+}
+
 // Causal grids: the work of a workgroup grows with its query block (forward, dQ) or shrinks with
 // its key block (dK/dV).  Dispatch the heaviest block of every head first -- longest-processing-
 // time order, so the light blocks fill the tail -- with every head still on XCD bh & 7.

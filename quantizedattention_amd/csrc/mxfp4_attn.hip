@@ -685,9 +685,106 @@ struct MxVarlen {
   long qrows;           // T * group * hps packed query rows
   long part_rows;
   int window, sinks;    // WINDOW: W >= 1 keys a query looks back (itself included), S >= 0 sink keys
+  // SHARED (at the end: the arguments of the other instantiations keep their places)
+  const int* grp_rec;   // i32 [ngroup][4]
+  const int* members;   // i32 [nmember][2]
+  int ngroup, nmember;
 };
 
-template <int D, bool CAUSAL, bool LEN = false, bool PAGED = false, bool VARLEN = false, bool WINDOW = false>
+// SHARED (with VARLEN; the shared-prefix step of kv_cache_mxfp4.py): one workgroup of a group record {g,
+// 128-row block of the group's stacked rows, split, 1}.  grp_rec[g] = {first entry in members, member
+// count, ns_g shared splits, R_g stacked rows}, members[e] = {j, first stacked row of sequence j}: stacked
+// row r belongs to the last member whose first row is <= r and is virtual row r' = r - first of that
+// sequence, in its own order g * sq_j + i.  The workgroup runs the split's kps / 64 tiles ONCE for all of
+// its rows, through the table row of the group's first member (the host has found the pages equal in
+// every member's row), and every lane writes its state where the VARLEN workgroup of its own sequence
+// would have: partial row pbase_j + (split * hps + hd) * G * sq_j + r'.  The host shares only splits that
+// lie wholly inside the common pages and below every member's first diagonal, so every key of every tile
+// is visible to every row: no length is read and the tile body is mx_tile<D, false>, the statements the
+// CAUSAL and LEN instantiations execute on such a tile (diag == false).  The ring is given npages =
+// ceil(ns_g * kps / P), so its one-page-ahead table read stays inside the shared run.
+// Every index is clamped (group, member slice, j, slot, row block, first tile, packed row) or checked
+// (partial row): a wrong table gives a wrong answer, never an address outside q, the tables or the
+// partials.  A wave's 32 rows may lie in several members, so the epilogue stores row by row
+// (store_rows_indexed) from the 32 partial-row indices the lanes leave in LDS behind the ring; the state a
+// lane keeps across the tile loop for this is that one index.
+template <int D>
+QA_DEVICE void mx_group_split(const uint8_t* __restrict__ q4, const uint8_t* __restrict__ qs,
+                              const uint8_t* __restrict__ k4, const uint8_t* __restrict__ ks,
+                              const uint8_t* __restrict__ vt, const uint8_t* __restrict__ vs,
+                              float* __restrict__ opart, float2* __restrict__ ml, int nslot, int kps, float qks,
+                              int hps, const int* __restrict__ btab, int mpp, int lgt, int npool,
+                              const MxVarlen& vl, int g, int qt, int split, int hd, char* smem) {
+  using C = MxCfg<D>;
+  typedef const __attribute__((address_space(4))) int* table_ptr;
+  const table_ptr grp = (table_ptr)(unsigned long)(vl.grp_rec + 4L * min(max(g, 0), vl.ngroup - 1));
+  const int mfirst = min(max(grp[0], 0), vl.nmember - 1);
+  const int mcnt = min(max(grp[1], 1), vl.nmember - mfirst);
+  const int rows = max(grp[3], 1);
+  const table_ptr mem = (table_ptr)(unsigned long)(vl.members + 2L * mfirst);
+  const table_ptr recs = (table_ptr)(unsigned long)vl.seq_rec;
+  // the shared run: gt >= 1 tiles from key 0 that the first member's table row can hold; this workgroup's
+  // tiles [t0, t0 + ntw) of it, ntw >= 1
+  const long gt = min((long)max(grp[2], 1) * (kps / C::KT), (long)mpp << lgt);
+  const int t0 = (int)min((long)split * (kps / C::KT), gt - 1);
+  const int ntw = (int)min((long)(kps / C::KT), gt - t0);
+  const int slot0 = min(max(recs[8L * min(max(mem[0], 0), vl.nseq - 1)], 0), nslot - 1);
+
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = tid & 63, h = lane >> 5, c32 = lane & 31;
+  const int q0 = min(qt, (rows - 1) / C::QROWS) * C::QROWS + wave * 32;
+  const int qi = min(q0 + c32, rows - 1);
+  const bool active = q0 < rows;
+
+  // the member of the lane's row: the last entry of the group's slice whose first row is <= qi
+  int lo = 0, hi = mcnt - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (mem[2 * mid + 1] <= qi) lo = mid;
+    else hi = mid - 1;
+  }
+  const table_ptr rec = recs + 8L * min(max(mem[2 * lo], 0), vl.nseq - 1);
+  const int sq = max(rec[2], 1);
+  const int rr = min(max(qi - mem[2 * lo + 1], 0), vl.group * sq - 1);   // virtual row of the member
+  const long qrow = min(max(((long)rec[1] + rr % sq) * (vl.group * hps) + hd * vl.group + rr / sq, 0L),
+                        vl.qrows - 1);
+  const long prow = rec[4] + ((long)split * hps + hd) * ((long)vl.group * sq) + rr;
+  // the lane's partial row, -1 for a lane without a row of its own or with one outside the partials
+  const int dst = q0 + c32 < rows && prow >= 0 && prow < vl.part_rows ? (int)prow : -1;
+
+  MxPagedRing<D> ring(k4, ks, vt, vs, btab + (long)slot0 * mpp, (int)((gt + (1 << lgt) - 1) >> lgt), lgt, hps,
+                      hd, npool, t0, smem, wave, lane);
+  ring.prologue(ntw);
+
+  v4i qf[C::NKS];
+  const unsigned qsw = mx_load_q<D>(q4, qs, qrow, h, qf);
+
+  v16f o[C::NDB];
+#pragma unroll
+  for (int b = 0; b < C::NDB; ++b) o[b] = v16f{};
+  float m = -INFINITY, l = 0.f;
+
+  vmem_drain();
+  __syncthreads();
+  for (int t = 0; t < ntw; ++t) {
+    ring_wait_barrier<2 * C::IPW>();
+    ring.issue(t + 3, ntw);
+    if (!active) continue;   // a wave without rows keeps its share of the DMA and the barrier
+    mx_tile<D, false>(smem + (t & 3) * C::SLOT, qf, qsw, o, m, l, false, 0, qks, lane, h, c32);
+  }
+  vmcnt_wait_all();
+  __syncthreads();
+  if (!active) return;
+  if (h == 0 && dst >= 0) ml[dst] = make_float2(m, l);
+  int* rowidx = reinterpret_cast<int*>(smem + C::NSLOT * C::SLOT) + wave * 32;
+  if (h == 0) rowidx[c32] = dst;
+  store_rows_indexed<D, 2>(o, 1.0f, smem + wave * RowTile<D, float, 2>::BYTES, opart, rowidx, lane);
+}
+constexpr int MX_GROUP_LDS = MxCfg<128>::WAVES * 32 * (int)sizeof(int);   // rowidx, behind the ring
+
+template <int D, bool CAUSAL, bool LEN = false, bool PAGED = false, bool VARLEN = false, bool WINDOW = false,
+          bool SHARED = false>
 __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
     const uint8_t* __restrict__ q4, const uint8_t* __restrict__ qs, const uint8_t* __restrict__ k4,
     const uint8_t* __restrict__ ks, const uint8_t* __restrict__ vt, const uint8_t* __restrict__ vs,
@@ -699,6 +796,7 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
   static_assert(LEN || !PAGED, "the paged pool has a length per sequence");
   static_assert(PAGED || !VARLEN, "the packed step runs over the paged pool");
   static_assert(!WINDOW || (VARLEN && CAUSAL), "the window is the packed step's, and causal");
+  static_assert(!SHARED || (VARLEN && !WINDOW), "shared prefixes are the packed step's, without a window");
   static_assert(sizeof(float) == 4 && D == 128, "fp32 staging in two passes fills the ring exactly");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int bh, qt, split = (int)blockIdx.y;
@@ -708,7 +806,14 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
     typedef const __attribute__((address_space(4))) int* table_ptr;
     const int hd = (int)(blockIdx.x % (unsigned)hps);
     const table_ptr w = (table_ptr)(unsigned long)(vl.work + 4L * (blockIdx.x / (unsigned)hps));
-    const table_ptr rec = (table_ptr)(unsigned long)(vl.seq_rec + 8L * min(max(w[0], 0), vl.nseq - 1));
+    if constexpr (SHARED) {
+      if (w[3] == 1) {   // a group record (workgroup-uniform); every other record is the VARLEN path below
+        mx_group_split<D>(q4, qs, k4, ks, vt, vs, opart, ml, BHV / hps, kps, qks, hps, btab, mpp, lgt, npool, vl,
+                          w[0], max(w[1], 0), max(w[2], 0), hd, smem);
+        return;
+      }
+    }
+    const table_ptr rec =(table_ptr)(unsigned long)(vl.seq_rec + 8L * min(max(w[0], 0), vl.nseq - 1));
     qt = max(w[1], 0);
     split = max(w[2], 0);
     bh = min(max(rec[0], 0), BHV / hps - 1) * hps + hd;
@@ -1146,11 +1251,11 @@ static bool mx_split_grid(MxSplitCall& c, long sk) {
   return true;
 }
 
-template <bool CAUSAL, bool LEN, bool PAGED, bool VARLEN, bool WINDOW>
+template <bool CAUSAL, bool LEN, bool PAGED, bool VARLEN, bool WINDOW, bool SHARED = false>
 static int mx_split_launch(const MxSplitCall& c, void* stream) {
   using C = MxCfg<128>;
-  const auto kernel = mxfp4_attn_split_kernel<128, CAUSAL, LEN, PAGED, VARLEN, WINDOW>;
-  const int lds = C::NSLOT * C::SLOT;
+  const auto kernel = mxfp4_attn_split_kernel<128, CAUSAL, LEN, PAGED, VARLEN, WINDOW, SHARED>;
+  const int lds = C::NSLOT * C::SLOT + (SHARED ? MX_GROUP_LDS : 0);
   { static LdsGrant granted_; if (!lds_grant((const void*)kernel, lds, granted_)) return 1; }
   hipLaunchKernelGGL(kernel, c.grid, dim3(256), lds, (hipStream_t)stream, (const uint8_t*)c.q4,
                      (const uint8_t*)c.qscale, (const uint8_t*)c.k4, (const uint8_t*)c.kscale,
@@ -1408,4 +1513,39 @@ extern "C" int qattn_mxfp4_split_combine(const void* opart, const void* ml, void
                      (hipStream_t)stream, (const float*)opart, (const float2*)ml, (_Float16*)out,
                      (float*)lse, rows_total, nsplit);
   return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// The packed step with shared prefixes (kernel: mxfp4_attn_split_kernel SHARED; the tables are the host
+// plan of kv_cache_mxfp4.plan_varlen_shared): qattn_mxfp4_attn_fwd_varlen_paged with work records of two
+// kinds, [j, row block, split, 0] as there and [g, row block of group g's stacked rows, split, 1], which
+// one workgroup runs once for every member of the group (grp_rec i32 [ngroup][4], members i32
+// [nmember][2] on the device).  Partials and merge are the plain entry's.  It stands last: its kernels
+// are emitted after every other one of this file.
+extern "C" int qattn_mxfp4_attn_fwd_varlen_paged_shared(
+    const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt, const void* vscale,
+    void* opart, void* ml, const void* lens, const void* block_table, const void* seq_rec, const void* work,
+    long nseq, long nwork, long tokens, long part_rows, long max_seqs, long kv_heads, long group,
+    long num_pages, long page_tokens, long max_pages_per_seq, int causal, int keys_per_split, int head_dim,
+    float qks, const void* grp_rec, const void* members, long ngroup, long nmember, void* stream) {
+  if (!mx_split_ok(head_dim, keys_per_split) || nseq < 0 || nwork < 0 || tokens < 0 || part_rows < 0) return 1;
+  if (!lens || !block_table || !seq_rec || !work || !grp_rec || !members) return 1;
+  const int lgt = mx_page_lgt(page_tokens);
+  if (!mx_pool_ok(num_pages, kv_heads, lgt, max_pages_per_seq)) return 1;
+  if (max_seqs < 1 || group < 1 || group > 0x7fffffffL || (causal != 0 && causal != 2)) return 1;
+  // at least one group, every group of at least two members, no sequence in two groups
+  if (ngroup < 1 || nmember < 2 * ngroup || nmember > nseq) return 1;
+  if (nwork == 0 || tokens == 0) return 0;
+  if (nseq > max_seqs || nseq > tokens || part_rows < 1) return 1;
+  // 32-bit packed rows, partial rows, workgroups and slot heads; a group's stacked rows are among the
+  // packed rows
+  if (tokens > 0x7fffffffL / (group * kv_heads) || part_rows > 0x7fffffffL) return 1;
+  if (nwork > 0x7fffffffL / kv_heads || max_seqs > 0x7fffffffL / kv_heads) return 1;
+  const MxVarlen vl{(const int*)work, (const int*)seq_rec, (int)nseq, (int)group, tokens * group * kv_heads,
+                    part_rows, 0, 0, (const int*)grp_rec, (const int*)members, (int)ngroup, (int)nmember};
+  const MxSplitCall c{q4, qscale, k4, kscale, vt, vscale, opart, ml, (int)(max_seqs * kv_heads), 0, 1,
+                      (int)(max_pages_per_seq * page_tokens), keys_per_split, qks, 0, lens, (int)kv_heads,
+                      block_table, (int)max_pages_per_seq, lgt, (int)num_pages, vl,
+                      dim3((unsigned)(nwork * kv_heads))};
+  return causal ? mx_split_launch<true, true, true, true, false, true>(c, stream)
+                : mx_split_launch<false, true, true, true, false, true>(c, stream);
 }

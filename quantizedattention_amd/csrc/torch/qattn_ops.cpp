@@ -33,6 +33,9 @@
 //   mxfp4_varlen_paged(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal,
 //                      keys_per_split) -> (O, lse)
 //       kv_cache_mxfp4.attention_mxfp4_varlen_paged: packed q [T, Hq, 128] and the two plan tables
+//   mxfp4_varlen_paged_shared(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, grp_rec, members,
+//                             part_rows, causal, keys_per_split) -> (O, lse)
+//       the same with shared prefixes: the four tables of kv_cache_mxfp4.plan_varlen_shared
 // Workspaces, head chunks and key splits are planned by the library (csrc/plan.hip), as in the drop-ins.
 // Errors: TORCH_CHECK (c10::Error, RuntimeError in Python) with the drop-ins' messages; int8_quant's
 // argument checks raise ValueError (TORCH_CHECK_VALUE) as its Python predecessor did.
@@ -572,8 +575,20 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged_run(const Tensor& q_in, const Tens
                                                   const Tensor& block_table, const Tensor& seq_rec,
                                                   const Tensor& work, int64_t part_rows, int64_t causal,
                                                   int64_t keys_per_split, bool windowed, int64_t window,
-                                                  int64_t sinks) {
+                                                  int64_t sinks, const Tensor* grp_rec = nullptr,
+                                                  const Tensor* members = nullptr) {
   require_gpu({&q_in, &k4, &ks, &vt, &vs, &lens, &block_table, &seq_rec, &work});
+  if (grp_rec) {   // the shared-prefix plan's two further tables
+    require_gpu({grp_rec, members});
+    TORCH_CHECK(grp_rec->scalar_type() == at::kInt && grp_rec->is_contiguous() && grp_rec->dim() == 2 &&
+                    grp_rec->size(1) == 4 && grp_rec->size(0) >= 1,
+                "qattn mxfp4 paged cache: grp_rec must be contiguous int32 [ngroup >= 1, 4]");
+    TORCH_CHECK(members->scalar_type() == at::kInt && members->is_contiguous() && members->dim() == 2 &&
+                    members->size(1) == 2 && members->size(0) >= 2 * grp_rec->size(0) &&
+                    members->size(0) <= seq_rec.size(0),
+                "qattn mxfp4 paged cache: members must be contiguous int32 [nmember, 2], 2 * ngroup <= nmember "
+                "<= nseq");
+  }
   TORCH_CHECK(q_in.dim() == 3 && k4.dim() == 4 && q_in.size(2) == 128 && k4.size(3) == 64,
               "qattn mxfp4 paged cache: packed queries must be q [T, Hq, 128], head_dim 128 in the pool");
   const int64_t NP = k4.size(0), Hkv = k4.size(1), PT = k4.size(2), D = 128;
@@ -603,7 +618,14 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged_run(const Tensor& q_in, const Tens
   Tensor out = empty({T, Hq, D}, at::kHalf, q), lse = empty({T, Hq}, at::kFloat, q);
   call(qattn_mxfp4_quant_rows(P(q), nullptr, P(q4), P(qs), T * Hq, Hq, (int)D, c.stream), "quantise q");
   Tensor opart = empty({part_rows, D}, at::kFloat, q), ml = empty({part_rows, 2}, at::kFloat, q);
-  if (windowed)
+  if (grp_rec)
+    call(qattn_mxfp4_attn_fwd_varlen_paged_shared(
+             P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens), P(block_table), P(seq_rec),
+             P(work), seq_rec.size(0), work.size(0), T, part_rows, B, Hkv, Hq / Hkv, NP, PT, mpp, causal ? 2 : 0,
+             (int)keys_per_split, (int)D, qk_scale(D), P(*grp_rec), P(*members), grp_rec->size(0),
+             members->size(0), c.stream),
+         "mxfp4 shared-prefix varlen forward");
+  else if (windowed)
     call(qattn_mxfp4_attn_fwd_varlen_paged_window(
              P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens), P(block_table), P(seq_rec),
              P(work), seq_rec.size(0), work.size(0), T, part_rows, B, Hkv, Hq / Hkv, NP, PT, mpp, causal ? 2 : 0,
@@ -643,6 +665,18 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged_window(const Tensor& q, const Tens
                                 keys_per_split, true, window, sinks);
 }
 
+// the same with shared prefixes (kv_cache_mxfp4.attention_mxfp4_varlen_paged(share_prefix=True)): the
+// tables are plan_varlen_shared's, grp_rec i32 [ngroup, 4] and members i32 [nmember, 2] among them
+std::tuple<Tensor, Tensor> mxfp4_varlen_paged_shared(const Tensor& q, const Tensor& k4, const Tensor& ks,
+                                                     const Tensor& vt, const Tensor& vs, const Tensor& lens,
+                                                     const Tensor& block_table, const Tensor& seq_rec,
+                                                     const Tensor& work, const Tensor& grp_rec,
+                                                     const Tensor& members, int64_t part_rows, int64_t causal,
+                                                     int64_t keys_per_split) {
+  return mxfp4_varlen_paged_run(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal,
+                                keys_per_split, false, 0, 0, &grp_rec, &members);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(qattn, m) {
@@ -668,6 +702,9 @@ TORCH_LIBRARY(qattn, m) {
   m.def("mxfp4_varlen_paged_window(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, "
         "Tensor block_table, Tensor seq_rec, Tensor work, int part_rows, int causal, int keys_per_split, "
         "int window, int sinks) -> (Tensor, Tensor)");
+  m.def("mxfp4_varlen_paged_shared(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, "
+        "Tensor block_table, Tensor seq_rec, Tensor work, Tensor grp_rec, Tensor members, int part_rows, "
+        "int causal, int keys_per_split) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
@@ -684,4 +721,5 @@ TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
   m.impl("mxfp4_decode_paged", &mxfp4_decode_paged);
   m.impl("mxfp4_varlen_paged", &mxfp4_varlen_paged);
   m.impl("mxfp4_varlen_paged_window", &mxfp4_varlen_paged_window);
+  m.impl("mxfp4_varlen_paged_shared", &mxfp4_varlen_paged_shared);
 }

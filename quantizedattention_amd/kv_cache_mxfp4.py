@@ -100,6 +100,25 @@ without a window, with a larger window or more sinks, ``attention_mxfp4_decode_p
 ``snapshot``, ``fork`` from that sequence -- raises :class:`QAttnError` naming "trimmed" before any
 launch; ``free`` works.
 
+Shared prefixes (``share_prefix=True``, not together with a window): sequences that ``fork`` made of one
+prompt hold the same physical pages, and the packed call above fetches them once per sequence.  The
+shared call keeps that call's splits exactly and changes only who computes them:
+:meth:`PagedKVFP4.prefix_groups` finds the listed sequences whose leading pages are the same physical
+pages, :func:`plan_varlen_shared` gives group g its first ns_g = min(common pages * P, min_j vis_j) //
+kps splits (vis_j = L_j - n_j + 1 causal, L_j otherwise: wholly inside the common pages, no key masked for
+any member row) as work records of a second kind, [g, 128-row block of the group's stacked rows, split,
+1], and adds two tables::
+
+    grp_rec  int32 [ngroup][4]   {first entry in members, member count, ns_g, R_g = G * sum of n_j}
+    members  int32 [nmember][2]  {j, first stacked row of sequence j in its group}
+
+A group workgroup (``qattn_mxfp4_attn_fwd_varlen_paged_shared``) runs the split's tiles once, through
+the table row of the group's first member, for up to 128 rows of several sequences, and writes each row's
+state into its own sequence's partial row at that split, the row the plain workgroup would have written;
+``seq_rec``, the partial rows and the merge are unchanged, and the result is the plain call's bit for bit
+at the same keys per split.  One level of sharing per call: a sub-group with a longer common prefix (a
+fork of a fork) still shares only its group's common pages.
+
 Wire format (little-endian), the container of kv_cache.py with a magic of its own::
 
     offset 0   8 B   magic  b"QATTNKF4"
@@ -118,6 +137,7 @@ keeps the keys <= Sk - Sq + i), Sq <= Sk.
 """
 from __future__ import annotations
 
+import itertools
 import json
 from dataclasses import dataclass
 from typing import Optional
@@ -134,7 +154,7 @@ _DTYPES = {"uint8": torch.uint8, "float16": torch.float16}
 
 __all__ = ["QuantizedKVFP4", "quantize_kv_fp4", "attention_mxfp4_cached", "PreallocatedKVFP4",
            "attention_mxfp4_decode", "PageAllocator", "PagedKVFP4", "attention_mxfp4_decode_paged",
-           "plan_varlen", "attention_mxfp4_varlen_paged"]
+           "plan_varlen", "plan_varlen_shared", "attention_mxfp4_varlen_paged"]
 
 
 @dataclass
@@ -630,6 +650,31 @@ class PageAllocator:
             self.pages[dst].append(p)
         return self._take(dst, fresh)
 
+    def prefix_groups(self, seq_ids) -> list:
+        """The listed sequences that hold the same leading physical pages -> ``[(members, common_pages),
+        ...]``: ``members`` are indices into ``seq_ids``, ascending, of the sequences whose page 0 is the
+        same physical page, and ``common_pages`` the number of leading positions at which every member
+        holds the same physical page.  Groups of one member or without a common page are not returned, a
+        sequence with holes (``drop``) or without pages is never grouped, and the slots that are not
+        listed are not looked at.  One level of sharing: members of a group that share a longer prefix
+        among themselves (a fork of a fork) still get only the whole group's common pages.  Host only."""
+        ids = [self._seq(b) for b in seq_ids]
+        by_first = {}
+        for i, b in enumerate(ids):
+            if self.pages[b] and not self.nholes[b]:
+                by_first.setdefault(self.pages[b][0], []).append(i)
+        out = []
+        for idxs in by_first.values():
+            if len(idxs) < 2:
+                continue
+            lists = [self.pages[ids[i]] for i in idxs]
+            head = lists[0][:min(len(x) for x in lists)]
+            for x in lists[1:]:   # whole-slice compares: the lists of forks are equal up to their own pages
+                if x[:len(head)] != head:
+                    head = head[:next(i for i, p in enumerate(head) if x[i] != p)]
+            out.append((idxs, len(head)))
+        return out
+
 
 class PagedKVFP4:
     """MX-FP4 keys/values of up to ``max_seqs`` sequences x ``kv_heads`` heads in a pool of
@@ -836,6 +881,13 @@ class PagedKVFP4:
         self.lengths[dst] = L
         self._upload(table=True)
 
+    def prefix_groups(self, seq_ids) -> list:
+        """:meth:`PageAllocator.prefix_groups` of the pool: which of the listed sequences hold the same
+        leading pages (after :meth:`fork`), as ``[(members, common_pages), ...]`` with ``members`` indices
+        into ``seq_ids``.  One level of sharing per call: a sub-group that shares a longer prefix still
+        gets only its group's common pages.  Host only, no tensor."""
+        return self.alloc.prefix_groups(seq_ids)
+
     def gather(self, b: int):
         """Copies of sequence ``b``'s pages in order, per head: (k4 [Hkv, n*P, D/2], ks [Hkv, n*P, D/32],
         vt [Hkv, n*P/64, D, 32], vs [Hkv, n*P/64, D, 2]) for its n pages.  A trimmed sequence is refused."""
@@ -929,6 +981,22 @@ def _window_pages(L: int, n: int, W: int, S: int, P: int) -> list:
     return sorted(pages | set(range(wt0 // tpp, -(-nt // tpp))))
 
 
+def _varlen_lists(lengths, seq_ids, q_lens, Hq: int, Hkv: int, causal: bool):
+    """What every packed plan checks first -> (slots, q_lens, lengths of the listed slots) as ints."""
+    lengths = [int(x) for x in lengths]
+    ids, sq = _packed_lists(len(lengths), seq_ids, q_lens, "q_lens")
+    if Hkv < 1 or Hq < 1 or Hq % Hkv:
+        raise _lib.QAttnError("qattn mxfp4 paged cache: q must have G * Hkv heads for the cache's Hkv")
+    Ls = [lengths[b] for b in ids]
+    if min(Ls) < 1:
+        raise _lib.QAttnError("qattn mxfp4 paged cache: every listed sequence needs at least one cached "
+                              f"token (slots {ids}, lengths {Ls})")
+    if causal and any(n > L for n, L in zip(sq, Ls)):
+        raise _lib.QAttnError("qattn mxfp4 paged cache: causal attention needs q_lens[j] <= the cached "
+                              f"tokens of every listed sequence (q_lens {sq}, lengths {Ls})")
+    return ids, sq, Ls
+
+
 def plan_varlen(lengths, seq_ids, q_lens, Hq: int, Hkv: int, keys_per_split: Optional[int] = None,
                 causal: bool = False, window: Optional[int] = None, sinks: int = 0):
     """The host plan of :func:`attention_mxfp4_varlen_paged` -> (kps, seq_rec, work, part_rows); pure
@@ -977,17 +1045,7 @@ def plan_varlen(lengths, seq_ids, q_lens, Hq: int, Hkv: int, keys_per_split: Opt
     W, S = _window_args(window, sinks)
     if W is not None and not causal:
         raise _lib.QAttnError("qattn mxfp4 paged cache: a window implies causal attention; pass causal=True")
-    lengths = [int(x) for x in lengths]
-    ids, sq = _packed_lists(len(lengths), seq_ids, q_lens, "q_lens")
-    if Hkv < 1 or Hq < 1 or Hq % Hkv:
-        raise _lib.QAttnError("qattn mxfp4 paged cache: q must have G * Hkv heads for the cache's Hkv")
-    Ls = [lengths[b] for b in ids]
-    if min(Ls) < 1:
-        raise _lib.QAttnError("qattn mxfp4 paged cache: every listed sequence needs at least one cached "
-                              f"token (slots {ids}, lengths {Ls})")
-    if causal and any(n > L for n, L in zip(sq, Ls)):
-        raise _lib.QAttnError("qattn mxfp4 paged cache: causal attention needs q_lens[j] <= the cached "
-                              f"tokens of every listed sequence (q_lens {sq}, lengths {Ls})")
+    ids, sq, Ls = _varlen_lists(lengths, seq_ids, q_lens, Hq, Hkv, causal)
     G = Hq // Hkv
     nrb = [-(-G * n // QROWS) for n in sq]
     sk_max = _ceil64(max(Ls))
@@ -1028,6 +1086,131 @@ def plan_varlen(lengths, seq_ids, q_lens, Hq: int, Hkv: int, keys_per_split: Opt
     return kps, seq_rec, [w for _, w in work], base
 
 
+def plan_varlen_shared(lengths, seq_ids, q_lens, Hq: int, Hkv: int, groups, keys_per_split: Optional[int] = None,
+                       causal: bool = False, *, page_tokens: int):
+    """The host plan of :func:`attention_mxfp4_varlen_paged` with ``share_prefix=True`` -> (kps, seq_rec,
+    work, part_rows, grp_rec, members); pure Python like :func:`plan_varlen`.  ``groups`` is what
+    :meth:`PagedKVFP4.prefix_groups` gives for ``seq_ids``, ``[(members, common_pages), ...]`` with
+    ``members`` ascending indices into ``seq_ids``, and ``page_tokens`` the pool's P.
+
+    The shared call keeps the plain call's splits and changes only who computes them.  Sequence j has
+    the splits [s * kps, (s + 1) * kps) of :func:`plan_varlen`; group g shares the first ``ns_g = min(
+    common_pages * P, min_j vis_j) // kps`` of them, vis_j = L_j - n_j + 1 causal and L_j otherwise: the
+    splits that lie wholly inside the common pages and on which no row of any member masks a key.  A
+    group with ns_g == 0 dissolves into plain sequences.  ``seq_rec`` and ``part_rows`` are
+    :func:`plan_varlen`'s for the same ``kps``.  ``work`` [nwork][4] holds [j, 128-row block, split, 0] for
+    every split >= ns_g of a member (every split of an ungrouped sequence) and [g, 128-row block of the
+    group's stacked rows, split, 1] for every split < ns_g, by descending tile count.  ``grp_rec``
+    [ngroup][4] = [first entry in members, member count, ns_g, R_g], R_g = G * sum of the members' q_lens;
+    ``members`` [nmember][2] = [j, first stacked row of sequence j in its group], ascending inside a
+    group; stacked row r is row r - first of its member's virtual head, in that member's own order g *
+    n_j + i.  The group workgroup writes each row's state into the member's own partial rows at split s,
+    where the plain workgroup would have, so the merge is unchanged.
+
+    ``kps`` when ``keys_per_split`` is None: ``qattn_split_keys`` at the shared call's own workgroup count,
+    Hkv * (sum_g ceil(R_g / 128) + sum over ungrouped j of ceil(G * n_j / 128)), then lowered to the
+    largest multiple of 64 that is <= the smallest group's shareable key count min(common_pages * P, min_j
+    vis_j) when it exceeds that, so that every group shares at least one split (a group that cannot
+    share 64 keys is left out of this minimum: it dissolves whatever kps is).  An explicit
+    ``keys_per_split`` is used as given (a multiple of 64, clamped to sk_max as in :func:`plan_varlen`).
+    This default began as a guess from byte counts.  What one MI355X gave (tools/time_decode_shared.py,
+    2026-10-20, one new token per sequence, 32 / 8 heads, P = 256, causal, median us of 3 x 20 alternating
+    calls, whole call | kernel alone, against the plain call at its own rule in the same run; pass
+    medians within 0.2 to 3 % except the first shape's shared whole calls, 10 %): 64 forks of a 32768-key
+    prompt + 256 own keys, plain 539.8 | 522.7, shared at the rule (1088 keys) 267.3 | 32.6, at 512 keys
+    287.1 | 34.6, at 1024 keys 272.9 | 29.5; 8 forks of it, plain 114.7 | 67.7, shared at the rule (1088)
+    110.7 | 22.2, at 512 118.6 | 15.2, at 1024 110.3 | 21.2; 64 forks of a 2048-key prompt, plain 171.6 |
+    34.9, shared at the rule (1152) 209.1 | 27.0, at 576 210.0 | 16.6, at 1024 209.8 | 19.1; 16 forks of an
+    8192-key prompt beside 16 unrelated decodes, plain 140.5 | 70.4, shared at the rule (2112) 161.2 |
+    44.5, at 1024 177.5 | 25.9.  The kernel wins on all four; the whole call wins on the first (2.0 x) and
+    barely on the second, and LOSES on the last two (host-bound: the groups and the longer plan are
+    Python before the launch).  On the kernel alone the rule loses to a swept value by more than the
+    spread on every shape (1024, 512, 576, 1024 keys); on the whole call it is level or ahead on all
+    four, so it is left as it is.
+
+    Raises as :func:`plan_varlen` (same messages, same 2^31 limits), and for a group with fewer than two
+    members or no common page, a member out of range or not ascending, and a sequence in two groups.
+    """
+    ids, sq, Ls = _varlen_lists(lengths, seq_ids, q_lens, Hq, Hkv, causal)
+    P, G, nseq = int(page_tokens), Hq // Hkv, len(ids)
+    if P not in PAGE_TOKENS:
+        raise _lib.QAttnError(f"qattn mxfp4 paged cache: page_tokens must be 64 * 2^k in [64, 1024], got {P}")
+    glist, grouped = [], set()
+    for mem, common in groups:
+        mem, common = [int(x) for x in mem], int(common)
+        if len(mem) < 2 or common < 1:
+            raise _lib.QAttnError("qattn mxfp4 paged cache: a prefix group needs at least two members and one "
+                                  f"common page, got {mem}, {common}")
+        if any(not 0 <= j < nseq for j in mem) or any(a >= b for a, b in zip(mem, mem[1:])):
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: group members must be ascending indices into the "
+                                  f"{nseq} listed sequences, got {mem}")
+        if grouped.intersection(mem):
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: sequences {sorted(grouped.intersection(mem))} are "
+                                  "in two prefix groups")
+        grouped.update(mem)
+        vis = min(Ls[j] - sq[j] + 1 if causal else Ls[j] for j in mem)
+        glist.append((mem, min(common * P, vis)))   # (members, keys the group can share)
+    nrb = [-(-G * n // QROWS) for n in sq]
+    sk_max = _ceil64(max(Ls))
+    if keys_per_split is None:
+        wgs = sum(-(-G * sum(sq[j] for j in mem) // QROWS) for mem, _ in glist)
+        wgs += sum(r for j, r in enumerate(nrb) if j not in grouped)
+        kps = _lib.load().qattn_split_keys(Hkv * wgs, 1, sk_max, BLOCK)
+        least = min((keys for _, keys in glist if keys >= BLOCK), default=kps)
+        if kps > least:
+            kps = least // BLOCK * BLOCK
+    else:
+        kps = int(keys_per_split)
+    if kps < BLOCK or kps % BLOCK:
+        raise _lib.QAttnError("qattn mxfp4 paged cache: keys_per_split must be a multiple of 64")
+    kps = min(kps, sk_max)
+    tps = kps // BLOCK
+    nsp = [-(-_ceil64(L) // kps) for L in Ls]
+    if (sum(sq) * Hq >= 1 << 31 or sum(ns * Hkv * G * n for ns, n in zip(nsp, sq)) >= 1 << 31
+            or sum(ns * r for ns, r in zip(nsp, nrb)) * Hkv >= 1 << 31):
+        raise _lib.QAttnError("qattn mxfp4 paged cache: a packed call of 2^31 or more query rows, partial "
+                              "rows or workgroups")
+    shared = [0] * nseq   # ns_g of the sequence's group, 0 for a plain sequence
+    grp_rec, members, work = [], [], []
+    for mem, keys in glist:
+        ns_g = keys // kps
+        if not ns_g:   # nothing to share at this kps: plain sequences
+            continue
+        rows = 0
+        grp_rec.append([len(members), len(mem), ns_g, G * sum(sq[j] for j in mem)])
+        for j in mem:
+            shared[j] = ns_g
+            members.append([j, rows])
+            rows += G * sq[j]
+        g = len(grp_rec) - 1
+        work += [(tps, [g, rb, s, 1]) for s in range(ns_g) for rb in range(-(-rows // QROWS))]
+    seq_rec, first, base = [], 0, 0
+    for j, (b, n, L, ns) in enumerate(zip(ids, sq, Ls, nsp)):
+        seq_rec.append([b, first, n, ns, base, 0, 0, 0])
+        nt = -(-L // BLOCK)
+        for s in range(shared[j], ns):
+            work += [(min(nt, (s + 1) * tps) - s * tps, [j, rb, s, 0]) for rb in range(nrb[j])]
+        first += n
+        base += ns * Hkv * G * n
+    work.sort(key=lambda w: -w[0])   # stable: group records first among the full splits
+    return kps, seq_rec, [w for _, w in work], base, grp_rec, members
+
+
+def _shared_plan(cache: "PagedKVFP4", ids, sq, Hq: int, keys_per_split, causal: bool, window):
+    """The plan of a ``share_prefix=True`` call over the listed slots, or None when nothing is shared
+    (no two listed sequences hold a common page, or no whole split fits the common pages): the caller
+    then makes the plain call.  Raises for a window."""
+    if window is not None:
+        raise _lib.QAttnError("qattn mxfp4 paged cache: share_prefix with a window is not supported (a "
+                              "window's lower edge masks keys of the shared prefix row by row)")
+    groups = cache.prefix_groups(ids)
+    if not groups:
+        return None
+    plan = plan_varlen_shared(cache.lengths, ids, sq, Hq, cache.shape[1], groups, keys_per_split, causal,
+                              page_tokens=cache.page_tokens)
+    return plan if plan[4] else None
+
+
 def _check_trimmed(cache: "PagedKVFP4", ids, sq, W, S) -> None:
     """Raise when a packed call over ``ids`` with ``sq`` queries each and window ``(W, S)`` (W None: no
     window) would read a page that :meth:`PagedKVFP4.trim` gave back."""
@@ -1049,7 +1232,7 @@ def _check_trimmed(cache: "PagedKVFP4", ids, sq, W, S) -> None:
 @torch.no_grad()
 def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_lens, causal: bool = False,
                                  keys_per_split: Optional[int] = None, window: Optional[int] = None,
-                                 sinks: int = 0):
+                                 sinks: int = 0, share_prefix: bool = False):
     """A ragged batch against a paged cache in one attention launch and one merge: packed fp16 queries
     ``q`` [T, Hq, D], token-major, the ``q_lens[0]`` tokens of sequence ``seq_ids[0]`` first, then
     those of ``seq_ids[1]``, ... (nseq >= 1 distinct slots, every q_lens[j] >= 1, T = sum(q_lens)) ->
@@ -1064,7 +1247,17 @@ def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_
     causal call's bits.  Raises before any launch (and before any tensor is made) as
     :func:`plan_varlen` does, for sum(q_lens) != T, and when a listed sequence has had a page trimmed
     that this call would read.  Stream-ordered: the plan comes from the host mirror, its two
-    tables are uploaded without a synchronisation, nothing is read back."""
+    tables are uploaded without a synchronisation, nothing is read back.
+
+    ``share_prefix=True`` reads the pages that listed sequences hold in common (after
+    :meth:`PagedKVFP4.fork`: parallel sampling, beam search, a shared system prompt) once per group
+    instead of once per sequence: :meth:`PagedKVFP4.prefix_groups` finds the groups on the host,
+    :func:`plan_varlen_shared` gives the key splits inside the common pages to group workgroups whose 128
+    rows come from several sequences (``qattn_mxfp4_attn_fwd_varlen_paged_shared``), and everything else
+    runs as above.  The result is, bit for bit, that of the same call without ``share_prefix`` at the
+    same ``keys_per_split`` (the default ``keys_per_split`` differs: :func:`plan_varlen_shared`); when
+    nothing is shared the plain call is made.  One level of sharing per call, and no ``window``: the
+    combination raises :class:`QAttnError` before any launch."""
     if not isinstance(cache, PagedKVFP4):
         raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PagedKVFP4")
     _, Hkv, _, D = cache.shape
@@ -1076,15 +1269,25 @@ def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_
     ids, sq = _packed_lists(cache.alloc.max_seqs, seq_ids, q_lens, "q_lens")
     if sum(sq) != T:
         raise _lib.QAttnError(f"qattn mxfp4 paged cache: q holds {T} tokens, q_lens sum to {sum(sq)}")
-    kps, seq_rec, work, part_rows = plan_varlen(cache.lengths, ids, sq, Hq, Hkv, keys_per_split, causal,
-                                                window, sinks)
+    shared = _shared_plan(cache, ids, sq, Hq, keys_per_split, causal, window) if share_prefix else None
+    if shared is not None:
+        kps, seq_rec, work, part_rows, grp_rec, members = shared
+    else:
+        kps, seq_rec, work, part_rows = plan_varlen(cache.lengths, ids, sq, Hq, Hkv, keys_per_split, causal,
+                                                    window, sinks)
     W, S = _window_args(window, sinks)
     _check_trimmed(cache, ids, sq, W, S)
     _lib.require_gpu(q, cache.k4)
     dev, st = q.device, _lib.stream_of(q)
     # from fresh pageable host tensors, as PagedKVFP4._upload: staged before the copies return
-    rec_d = torch.tensor(seq_rec, dtype=torch.int32).to(dev, non_blocking=True)
-    work_d = torch.tensor(work, dtype=torch.int32).to(dev, non_blocking=True)
+    if shared is None:
+        rec_d = torch.tensor(seq_rec, dtype=torch.int32).to(dev, non_blocking=True)
+        work_d = torch.tensor(work, dtype=torch.int32).to(dev, non_blocking=True)
+    else:   # one upload of the four tables, the longest records first
+        flat = list(itertools.chain.from_iterable(seq_rec + work + grp_rec + members))
+        rec_d = torch.tensor(flat, dtype=torch.int32).to(dev, non_blocking=True)
+        work_d = rec_d[8 * len(seq_rec):]
+        grp_d = work_d[4 * len(work):]
     q4, qs = mxfp4_quantize_rows(q)
     O = torch.empty((T, Hq, D), dtype=torch.float16, device=dev)
     lse = torch.empty((T, Hq), dtype=torch.float32, device=dev)
@@ -1095,7 +1298,10 @@ def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_
             _lib.ptr(cache.lens), _lib.ptr(cache.block_table), _lib.ptr(rec_d), _lib.ptr(work_d), len(ids),
             len(work), T, part_rows, cache.alloc.max_seqs, Hkv, Hq // Hkv, cache.num_pages,
             cache.page_tokens, cache.alloc.max_pages_per_seq, 2 if causal else 0, kps, D, _qk_scale(D))
-    if W is None:
+    if shared is not None:
+        _lib.call("qattn_mxfp4_attn_fwd_varlen_paged_shared", *args, _lib.ptr(grp_d),
+                  _lib.ptr(grp_d[4 * len(grp_rec):]), len(grp_rec), len(members), st)
+    elif W is None:
         _lib.call("qattn_mxfp4_attn_fwd_varlen_paged", *args, st)
     else:   # no sequence holds 2^25 keys or more: a larger window or sink count means the same
         _lib.call("qattn_mxfp4_attn_fwd_varlen_paged_window", *args, min(W, 1 << 26), min(S, 1 << 26), st)

@@ -24,6 +24,8 @@ the autograd rules of ``int8_fwd`` and ``bf16_fwd`` (their backward operators).
                                        causal, keys_per_split) -> (O, lse)
     torch.ops.qattn.mxfp4_varlen_paged_window(q, k4, ks, vt, vs, lens, block_table, seq_rec, work,
                                               part_rows, causal, keys_per_split, window, sinks) -> (O, lse)
+    torch.ops.qattn.mxfp4_varlen_paged_shared(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, grp_rec,
+                                              members, part_rows, causal, keys_per_split) -> (O, lse)
 
 Shapes follow the drop-in functions (attention_int8.py:259-262 for the int8 outputs) except that
 k_i8 is returned row-major [B*Hkv*Sk, D] (the drop-in's k_i8T is its transposed view: an operator
@@ -32,6 +34,8 @@ raises NotImplementedError from the dispatcher.  The Python wrappers below only 
 ``torch.ops.qattn`` (the names existing callers import).
 """
 from __future__ import annotations
+
+import itertools
 
 import torch
 
@@ -130,6 +134,12 @@ def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal, ke
 
 @torch.library.register_fake("qattn::mxfp4_varlen_paged_window")
 def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal, keys_per_split, window, sinks):
+    T, H, D = q.shape
+    return (q.new_empty((T, H, D), dtype=torch.float16), q.new_empty((T, H), dtype=torch.float32))
+
+
+@torch.library.register_fake("qattn::mxfp4_varlen_paged_shared")
+def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, grp_rec, members, part_rows, causal, keys_per_split):
     T, H, D = q.shape
     return (q.new_empty((T, H, D), dtype=torch.float16), q.new_empty((T, H), dtype=torch.float32))
 
@@ -256,15 +266,20 @@ def mxfp4_decode_paged(q, cache, causal=False, keys_per_split=None):
                                    sk_max, int(bool(causal)), 0 if keys_per_split is None else int(keys_per_split))
 
 
-def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=None, window=None, sinks=0):
+def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=None, window=None, sinks=0,
+                       share_prefix=False):
     """``kv_cache_mxfp4.attention_mxfp4_varlen_paged`` as one operator: packed q [T, Hq, 128] against
     a ``PagedKVFP4``, the ``q_lens[j]`` tokens of slot ``seq_ids[j]`` over that sequence's own length
     and pages -> (O fp16 [T, Hq, 128], lse fp32 [T, Hq]).  The plan (``plan_varlen``) is made and checked
     here, on the cache's host mirror, and its two tables are uploaded without a synchronisation; the
     operator reads only ``lens``, ``block_table`` and the tables on the device.  ``window`` (with
     ``sinks``) routes to ``torch.ops.qattn.mxfp4_varlen_paged_window``: a sliding window with sinks, as the
-    Python call's."""
-    from .kv_cache_mxfp4 import PagedKVFP4, _check_trimmed, _packed_lists, _window_args, plan_varlen
+    Python call's.  ``share_prefix=True`` (without a window) routes to
+    ``torch.ops.qattn.mxfp4_varlen_paged_shared`` with the tables of ``plan_varlen_shared`` when the listed
+    sequences hold leading pages in common (``PagedKVFP4.prefix_groups``), and to the plain operator when
+    they do not: the same bits either way."""
+    from .kv_cache_mxfp4 import (PagedKVFP4, _check_trimmed, _packed_lists, _shared_plan, _window_args,
+                                 plan_varlen)
     if not isinstance(cache, PagedKVFP4):
         raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PagedKVFP4")
     if q.dim() != 3:
@@ -272,6 +287,20 @@ def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=N
     ids, sq = _packed_lists(cache.alloc.max_seqs, seq_ids, q_lens, "q_lens")
     if sum(sq) != q.shape[0]:
         raise _lib.QAttnError(f"qattn mxfp4 paged cache: q holds {q.shape[0]} tokens, q_lens sum to {sum(sq)}")
+    shared = _shared_plan(cache, ids, sq, q.shape[1], keys_per_split, causal, window) if share_prefix else None
+    if shared is not None:
+        kps, seq_rec, work, part_rows, grp_rec, members = shared
+        _check_trimmed(cache, ids, sq, None, 0)
+        _lib.require_gpu(q, cache.k4)
+        # one upload of the four tables, cut into views
+        flat = torch.tensor(list(itertools.chain.from_iterable(seq_rec + work + grp_rec + members)),
+                            dtype=torch.int32).to(q.device, non_blocking=True)
+        cut = itertools.accumulate((0, 8 * len(seq_rec), 4 * len(work), 4 * len(grp_rec), 2 * len(members)))
+        cut = list(cut)
+        rec_d, work_d, grp_d, mem_d = (flat[a:b].view(-1, w) for a, b, w in zip(cut, cut[1:], (8, 4, 4, 2)))
+        return _ops.mxfp4_varlen_paged_shared(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens,
+                                              cache.block_table, rec_d, work_d, grp_d, mem_d, part_rows,
+                                              int(bool(causal)), kps)
     kps, seq_rec, work, part_rows = plan_varlen(cache.lengths, ids, sq, q.shape[1], cache.k4.shape[1],
                                                 keys_per_split, causal, window, sinks)
     W, S = _window_args(window, sinks)
