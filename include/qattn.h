@@ -562,6 +562,44 @@ int qattn_mxfp4_attn_fwd_varlen_paged_shared(
     long num_pages, long page_tokens, long max_pages_per_seq, int causal, int keys_per_split, int head_dim,
     float qks, const void* grp_rec, const void* members, long ngroup, long nmember, void* stream);
 
+/* The packed step with a tree mask, the verify step of speculative decoding (kv_cache_mxfp4.py
+ * attention_mxfp4_varlen_paged(tree=)): the first entry above at causal == 2, with seq_rec[j][7] = nd_j, 0 <=
+ * nd_j <= min(n_j, 64), and tree_masks, DEVICE u64 [tokens], one word per packed token (0 outside a tree).
+ * The last nd_j packed tokens of sequence j are the nodes of a draft tree (or forest) in topological order,
+ * appended already at keys base_j = L_j - nd_j ..; with t = i - (n_j - nd_j), packed token i of j
+ *   t <  0: sees keys <= L_j - n_j + i, as in the first entry;
+ *   t >= 0: sees key k iff k < base_j, or k = base_j + b with bit b of its word set.
+ * The word holds the node's ancestors and the node itself; the kernel uses (word & bits <= t) | bit t, so
+ * every mask is a subset of the causal row that holds the token itself (a wrong word gives a wrong answer,
+ * never an empty row), and a chain (bits 0 .. t) gives the first entry's bits.  lse is over the visible
+ * keys.  Splits, work records, partial rows, clamping and the merge (qattn_mxfp4_varlen_combine) are the
+ * first entry's; nd_j is clamped to [0, min(n_j, 64)].  A draft token at tree depth d stands for position
+ * L_j - nd_j + d of its path: the caller position-encodes draft keys and queries by depth.
+ * Returns 1 without a launch for causal != 2 and a NULL tree_masks, and as the first entry. */
+int qattn_mxfp4_attn_fwd_varlen_paged_tree(
+    const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt, const void* vscale,
+    void* opart, void* ml, const void* lens, const void* block_table, const void* seq_rec, const void* work,
+    long nseq, long nwork, long tokens, long part_rows, long max_seqs, long kv_heads, long group,
+    long num_pages, long page_tokens, long max_pages_per_seq, int causal, int keys_per_split, int head_dim,
+    float qks, const void* tree_masks, void* stream);
+
+/* Taking tokens back from the pool (kv_cache_mxfp4.py PagedKVFP4.checkpoint / rollback).  saved f16
+ * [nsaved][kv_heads][64][128] is a copy of vtail rows taken when the sequences stood at their lengths L0;
+ * recs, DEVICE i32 [nrec][4] = {slot, L0, row of that slot in saved, 0}, distinct slots.  For every record,
+ * in one launch: vtail rows [0, L0 % 64) of the slot are restored from saved; when L0 % 64 != 0, V tile
+ * L0 / 64 of every head is quantised again FROM THE SAVED ROWS with the keys at or past L0 zero (vt / vscale,
+ * through block_table, whose entry L0 / page_tokens is still the sequence's); lens[slot] = L0.  K rows at or
+ * past L0 are left as they are (unspecified by the pool's invariant).  Afterwards rows [0, L0) of k4 /
+ * kscale, tiles [0, ceil(L0 / 64)) of vt / vscale, the live vtail rows and lens hold, bit for bit, what
+ * they held when saved was taken, provided only appends happened in between.  A record whose slot, L0 or
+ * row lies outside [0, max_seqs), [0, max_pages_per_seq * page_tokens] or [0, nsaved) writes nothing.
+ * Returns 1 for head_dim != 128, a NULL pointer, the pool's limits above, nrec > max_seqs, nsaved < 1; 0
+ * without a launch for nrec == 0.  Allocates nothing. */
+int qattn_mxfp4_paged_rollback(const void* saved, void* vtail, void* vt, void* vscale, void* lens,
+                               const void* block_table, const void* recs, long nrec, long nsaved,
+                               long max_seqs, long kv_heads, long num_pages, long page_tokens,
+                               long max_pages_per_seq, int head_dim, void* stream);
+
 /* The merge of the packed step: qattn_mxfp4_split_combine's arithmetic in its order, per packed row
  * (token, query head), over the ns_j partial rows of the token's own sequence (found by binary search
  * over seq_rec's first-token column): out f16 [tokens][q_heads][128], lse f32 [tokens][q_heads].

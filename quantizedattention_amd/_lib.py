@@ -97,6 +97,9 @@ SIGNATURES = {
                                                                                _c_long, _c_long, _vp],
     "qattn_mxfp4_attn_fwd_varlen_paged_shared": [_vp] * 12 + [_c_long] * 10 + [_c_int, _c_int, _c_int, _c_float,
                                                                                _vp, _vp, _c_long, _c_long, _vp],
+    "qattn_mxfp4_attn_fwd_varlen_paged_tree": [_vp] * 12 + [_c_long] * 10 + [_c_int, _c_int, _c_int, _c_float,
+                                                                             _vp, _vp],
+    "qattn_mxfp4_paged_rollback": [_vp] * 7 + [_c_long] * 7 + [_c_int, _vp],
     "qattn_mxfp4_varlen_combine": [_vp] * 5 + [_c_long] * 5 + [_c_int, _vp],
     "qattn_mxfp4_paged_append_packed": [_vp] * 12 + [_c_long] * 8 + [_c_int, _vp],
     "qattn_split_keys": [_c_long, _c_long, _c_long, _c_int],

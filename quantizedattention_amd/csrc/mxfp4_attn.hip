@@ -42,9 +42,9 @@
 // tests/mxfp4_split_ref.py merge_bits restates it bit for bit); mx_requant_v_block and mx_append_k_block
 // (the bodies of the padded, paged and packed append kernels, which differ in how a thread finds its
 // sequence, head and source row); and on the host MxSplitCall + mx_split_launch (every key-split entry:
-// its own argument checks, the call filled in, a dispatch on `causal`), mx_varlen_paged (the two packed
-// entries) and mx_append (the padded and the paged append).  The two rings, MxRing and MxPagedRing, keep
-// a piece plan each: holding one in common changed the paged kernels' instruction streams.  The C entries
+// its own argument checks, the call filled in, a dispatch on `causal`), mx_varlen_call (the checks and the
+// call of the three packed entries without groups), mx_varlen_paged (the plain and the windowed one) and
+// mx_append (the padded and the paged append).  The two rings, MxRing and MxPagedRing, keep a piece plan each: holding one in common changed the paged kernels' instruction streams.  The C entries
 // stand in the order in which they first use their kernels, which is the order the kernels are emitted
 // in; tools/asm_compare.py compares branch labels too, and those carry the function's number.
 #include "common.h"
@@ -457,13 +457,21 @@ QA_DEVICE unsigned mx_load_q(const uint8_t* q4, const uint8_t* qs, long r, int h
 // visible iff e <= lim && (e >= lo || e <= slim), lo the first element of the lane's window and slim
 // the last sink element, both relative to the tile and the lane half as lim is.  The three limits are
 // all a lane carries; every compare is against a constant e and feeds its select at once.
-template <int D, bool CAUSAL, bool WINDOW = false>
+// TREE (with CAUSAL; the tree-masked verify step): the mask is a set, not an edge.  The lane brings the
+// tile's visibility word, bit e of (vis1:vis0) set iff it sees element e (the word is shifted down by 4h
+// already, so e is the constant of the other paths); every test is of a constant bit of one of the two
+// registers and feeds its select at once.
+template <int D, bool CAUSAL, bool WINDOW = false, bool TREE = false>
 QA_DEVICE void mx_tile(const char* sl, const v4i (&qf)[MxCfg<D>::NKS], unsigned qsw,
                        v16f (&o)[MxCfg<D>::NDB], float& m, float& l, bool diag, int lim, float qks, int lane,
-                       int h, int c32, int lo = 0, int slim = 0) {
+                       int h, int c32, int lo = 0, int slim = 0, unsigned vis0 = 0, unsigned vis1 = 0) {
   static_assert(CAUSAL || !WINDOW, "a window is causal");
-  // WINDOW: element e of the lane is visible
-  const auto seen = [&](int e) { return e <= lim && (e >= lo || e <= slim); };
+  static_assert(!TREE || (CAUSAL && !WINDOW), "a tree mask is causal, without a window");
+  // WINDOW, TREE: element e of the lane is visible
+  const auto seen = [&](int e) {
+    if constexpr (TREE) return (((e < 32 ? vis0 : vis1) >> (e & 31)) & 1u) != 0;
+    else return e <= lim && (e >= lo || e <= slim);
+  };
   using C = MxCfg<D>;
   // S^T for the two 32-key halves u: A = K rows 32u + c32, k = 64s + 32h .. +32
   v16f acc[2];
@@ -486,7 +494,7 @@ QA_DEVICE void mx_tile(const char* sl, const v4i (&qf)[MxCfg<D>::NKS], unsigned 
   // integer (log2 units) raised only when the row max exceeds it by more than MSLACK, so every
   // rescale is an exact power of two and, between raises, P <= 2^MSLACK needs no rescale at all.
   float amx;
-  if (WINDOW && diag) {
+  if ((WINDOW || TREE) && diag) {
     amx = -INFINITY;
 #pragma unroll
     for (int u = 0; u < 2; ++u)
@@ -525,7 +533,7 @@ QA_DEVICE void mx_tile(const char* sl, const v4i (&qf)[MxCfg<D>::NKS], unsigned 
   for (int u = 0; u < 2; ++u)
 #pragma unroll
     for (int r = 0; r < 16; ++r) x[16 * u + r] = exp2_f32(__builtin_fmaf(acc[u][r], qks, nm));
-  if (WINDOW && diag) {
+  if ((WINDOW || TREE) && diag) {
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -678,6 +686,19 @@ __global__ __launch_bounds__(256, CAUSAL ? QA_MX_OCC_CAUSAL : QA_MX_OCC) void mx
 // may have given those back: PagedKVFP4.trim).  Both numbers are clamped; a first tile past the
 // sequence is the empty state.  tests/mxfp4_window_ref.py restates it, tests/test_gpu_mxfp4_window.py
 // checks it.
+// TREE (with VARLEN and CAUSAL, no window; the verify step of speculative decoding): rec[7] = nd, clamped
+// to [0, min(sq, 64)], says that the sequence's last nd queries are the nodes of a draft tree, already
+// appended at keys base = len - nd .. len - 1 in topological order.  Query i with t = i - (sq - nd) >= 0
+// sees key k iff k < base or k = base + b with bit b of its word vl.tree[first packed token + i] set (the
+// node's ancestors and itself); the lane loads the word once and clamps it to (word & bits <= t) | bit t,
+// so the mask is a subset of the causal row that holds the query itself: a wrong word gives a wrong answer,
+// never an empty row.  Queries with t < 0 and sequences with nd = 0 are plain causal.  Tiles, splits, the
+// wave's causal skip, partial rows and the merge are the VARLEN instantiation's.  Its own: on a tile that
+// crosses a causal diagonal of the wave or holds a key >= base (`diag`; at most two tiles of a sequence do
+// the latter) every lane builds the tile's visibility word -- ones below base - k0 and the node's word
+// shifted there, or the causal prefix for t < 0 -- shifted down by 4h, and mx_tile TREE tests its bits.
+// The lane carries the word (two registers), t and the wave base.  tests/mxfp4_tree_ref.py restates it,
+// tests/test_gpu_mxfp4_tree.py checks it.
 struct MxVarlen {
   const int* work;      // i32 [nwork][4]
   const int* seq_rec;   // i32 [nseq][8]
@@ -689,6 +710,9 @@ struct MxVarlen {
   const int* grp_rec;   // i32 [ngroup][4]
   const int* members;   // i32 [nmember][2]
   int ngroup, nmember;
+  // TREE (after them, for the same reason)
+  const unsigned long* tree;   // u64 [tokens]: the ancestor word of every packed token, 0 outside a tree
+  long tokens;
 };
 
 // SHARED (with VARLEN; the shared-prefix step of kv_cache_mxfp4.py): one workgroup of a group record {g,
@@ -784,7 +808,7 @@ QA_DEVICE void mx_group_split(const uint8_t* __restrict__ q4, const uint8_t* __r
 constexpr int MX_GROUP_LDS = MxCfg<128>::WAVES * 32 * (int)sizeof(int);   // rowidx, behind the ring
 
 template <int D, bool CAUSAL, bool LEN = false, bool PAGED = false, bool VARLEN = false, bool WINDOW = false,
-          bool SHARED = false>
+          bool SHARED = false, bool TREE = false>
 __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
     const uint8_t* __restrict__ q4, const uint8_t* __restrict__ qs, const uint8_t* __restrict__ k4,
     const uint8_t* __restrict__ ks, const uint8_t* __restrict__ vt, const uint8_t* __restrict__ vs,
@@ -797,11 +821,13 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
   static_assert(PAGED || !VARLEN, "the packed step runs over the paged pool");
   static_assert(!WINDOW || (VARLEN && CAUSAL), "the window is the packed step's, and causal");
   static_assert(!SHARED || (VARLEN && !WINDOW), "shared prefixes are the packed step's, without a window");
+  static_assert(!TREE || (VARLEN && CAUSAL && !WINDOW && !SHARED), "tree masks are the causal packed step's");
   static_assert(sizeof(float) == 4 && D == 128, "fp32 staging in two passes fills the ring exactly");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int bh, qt, split = (int)blockIdx.y;
   long qbase = 0, pbase = 0;   // VARLEN: the sequence's first packed token and first partial row
   int wt0 = 0, nsink = 0;      // WINDOW: first tile of the window run; sink tiles when there is a gap, else 0
+  [[maybe_unused]] int nd = 0; // TREE: the sequence's last nd queries are tree nodes
   if constexpr (VARLEN) {
     typedef const __attribute__((address_space(4))) int* table_ptr;
     const int hd = (int)(blockIdx.x % (unsigned)hps);
@@ -825,6 +851,7 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
       wt0 = max(rec[5], 0);
       nsink = max(rec[6], 0);
     }
+    if constexpr (TREE) nd = min(max(rec[7], 0), min(sq_head, 64));
   } else {
     const int nrb = (rows + C::QROWS - 1) / C::QROWS;
     xcd_remap(blockIdx.x, nrb, BHV, bh, qt);
@@ -880,6 +907,17 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
     wmax = wraps ? sq_head - 1 : p0 + nr - 1;
     pos = qi % sq_head;
   }
+  // TREE: the node of the lane's row (tnode < 0: a plain causal row), its cleaned word, the first tree key
+  [[maybe_unused]] int tnode = -1, tbase = 0;
+  [[maybe_unused]] unsigned long tword = 0;
+  if constexpr (TREE) {
+    tnode = nd > 0 ? pos - (sq_head - nd) : -1;
+    tbase = max(len - nd, 0);
+    if (tnode >= 0) {
+      const unsigned long self = 1ul << tnode;
+      tword = (vl.tree[min(max(qbase + pos, 0L), vl.tokens - 1)] & (self | (self - 1))) | self;
+    }
+  }
 
   // the ring over the split's own byte range: the buffer bounds end at its last tile
   const long kvh = bh;
@@ -915,6 +953,7 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
     bool diag = false;
     int lim = 0;
     [[maybe_unused]] int lo = 0, slim = 0;
+    [[maybe_unused]] unsigned vis0 = 0, vis1 = 0;
     if constexpr (CAUSAL) {
       const int k0 = C::KT * (t0 + t);
       if (k0 > wmax + qoff) continue;           // no row of the wave sees the tile: m, l, O unchanged
@@ -928,6 +967,21 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
         lo = pos + qoff - vl.window + 1 - k0 - 4 * h;
         slim = vl.sinks - 1 - k0 - 4 * h;
       }
+      if constexpr (TREE) {
+        // the tile holds a tree key: masked too.  d keys of the tile lie below the first tree key; the
+        // tile starts below len <= tbase + 64, so a word is shifted by less than 64 either way
+        const int d = tbase - k0;
+        diag = diag || (nd > 0 && d < C::KT);
+        if (diag) {
+          const int c = pos + qoff - k0;   // the last element a causal row sees
+          unsigned long vis = c >= C::KT - 1 ? ~0ul : c < 0 ? 0ul : (2ul << c) - 1;
+          if (tnode >= 0)
+            vis = d >= C::KT ? ~0ul : d >= 0 ? (tword << d) | ((1ul << d) - 1) : tword >> min(-d, C::KT - 1);
+          vis >>= 4 * h;
+          vis0 = (unsigned)vis;
+          vis1 = (unsigned)(vis >> 32);
+        }
+      }
     } else if constexpr (LEN) {   // every row sees the keys <= len - 1
       const int k0 = C::KT * (t0 + t);
       diag = k0 + C::KT > len;
@@ -935,6 +989,9 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
     }
     if constexpr (WINDOW)
       mx_tile<D, MASK, true>(smem + (t & 3) * C::SLOT, qf, qsw, o, m, l, diag, lim, qks, lane, h, c32, lo, slim);
+    else if constexpr (TREE)
+      mx_tile<D, MASK, false, true>(smem + (t & 3) * C::SLOT, qf, qsw, o, m, l, diag, lim, qks, lane, h, c32, 0, 0,
+                                    vis0, vis1);
     else
       mx_tile<D, MASK>(smem + (t & 3) * C::SLOT, qf, qsw, o, m, l, diag, lim, qks, lane, h, c32);
   }
@@ -1251,10 +1308,10 @@ static bool mx_split_grid(MxSplitCall& c, long sk) {
   return true;
 }
 
-template <bool CAUSAL, bool LEN, bool PAGED, bool VARLEN, bool WINDOW, bool SHARED = false>
+template <bool CAUSAL, bool LEN, bool PAGED, bool VARLEN, bool WINDOW, bool SHARED = false, bool TREE = false>
 static int mx_split_launch(const MxSplitCall& c, void* stream) {
   using C = MxCfg<128>;
-  const auto kernel = mxfp4_attn_split_kernel<128, CAUSAL, LEN, PAGED, VARLEN, WINDOW, SHARED>;
+  const auto kernel = mxfp4_attn_split_kernel<128, CAUSAL, LEN, PAGED, VARLEN, WINDOW, SHARED, TREE>;
   const int lds = C::NSLOT * C::SLOT + (SHARED ? MX_GROUP_LDS : 0);
   { static LdsGrant granted_; if (!lds_grant((const void*)kernel, lds, granted_)) return 1; }
   hipLaunchKernelGGL(kernel, c.grid, dim3(256), lds, (hipStream_t)stream, (const uint8_t*)c.q4,
@@ -1384,15 +1441,17 @@ extern "C" int qattn_mxfp4_paged_append(const void* k, const void* v, const void
                          head_dim, stream);
 }
 
-// The two packed entries below: nwork work records x kv_heads workgroups in one launch; rows, sq_head and
-// qoff come from the records.  window < 1: no window (the plain entry); else causal is 2.
-static int mx_varlen_paged(const void* q4, const void* qscale, const void* k4, const void* kscale,
-                           const void* vt, const void* vscale, void* opart, void* ml, const void* lens,
-                           const void* block_table, const void* seq_rec, const void* work, long nseq,
-                           long nwork, long tokens, long part_rows, long max_seqs, long kv_heads, long group,
-                           long num_pages, long page_tokens, long max_pages_per_seq, int causal,
-                           int keys_per_split, int head_dim, float qks, long window, long sinks,
-                           void* stream) {
+// What the packed entries without groups share: their argument checks and the call filled in (nwork work
+// records x kv_heads workgroups in one launch; rows, sq_head and qoff come from the records).  Returns the
+// entry's status when there is nothing to launch, -1 when `c` is to be launched.  tree: the ancestor words
+// of the tree entry, else null.
+static int mx_varlen_call(MxSplitCall& c, const void* q4, const void* qscale, const void* k4,
+                          const void* kscale, const void* vt, const void* vscale, void* opart, void* ml,
+                          const void* lens, const void* block_table, const void* seq_rec, const void* work,
+                          long nseq, long nwork, long tokens, long part_rows, long max_seqs, long kv_heads,
+                          long group, long num_pages, long page_tokens, long max_pages_per_seq, int causal,
+                          int keys_per_split, int head_dim, float qks, long window, long sinks,
+                          const void* tree) {
   if (!mx_split_ok(head_dim, keys_per_split) || nseq < 0 || nwork < 0 || tokens < 0 || part_rows < 0) return 1;
   if (!lens || !block_table || !seq_rec || !work) return 1;
   const int lgt = mx_page_lgt(page_tokens);
@@ -1407,11 +1466,29 @@ static int mx_varlen_paged(const void* q4, const void* qscale, const void* k4, c
   // the kernel's 32-bit edges cannot overflow
   const long big = 1L << 26;
   const MxVarlen vl{(const int*)work, (const int*)seq_rec, (int)nseq, (int)group, tokens * group * kv_heads,
-                    part_rows, (int)(window < big ? window : big), (int)(sinks < big ? sinks : big)};
-  const MxSplitCall c{q4, qscale, k4, kscale, vt, vscale, opart, ml, (int)(max_seqs * kv_heads), 0, 1,
-                      (int)(max_pages_per_seq * page_tokens), keys_per_split, qks, 0, lens, (int)kv_heads,
-                      block_table, (int)max_pages_per_seq, lgt, (int)num_pages, vl,
-                      dim3((unsigned)(nwork * kv_heads))};
+                    part_rows, (int)(window < big ? window : big), (int)(sinks < big ? sinks : big),
+                    nullptr, nullptr, 0, 0, (const unsigned long*)tree, tokens};
+  c = MxSplitCall{q4, qscale, k4, kscale, vt, vscale, opart, ml, (int)(max_seqs * kv_heads), 0, 1,
+                  (int)(max_pages_per_seq * page_tokens), keys_per_split, qks, 0, lens, (int)kv_heads,
+                  block_table, (int)max_pages_per_seq, lgt, (int)num_pages, vl,
+                  dim3((unsigned)(nwork * kv_heads))};
+  return -1;
+}
+
+// The two packed entries below.  window < 1: no window (the plain entry); else causal is 2.
+static int mx_varlen_paged(const void* q4, const void* qscale, const void* k4, const void* kscale,
+                           const void* vt, const void* vscale, void* opart, void* ml, const void* lens,
+                           const void* block_table, const void* seq_rec, const void* work, long nseq,
+                           long nwork, long tokens, long part_rows, long max_seqs, long kv_heads, long group,
+                           long num_pages, long page_tokens, long max_pages_per_seq, int causal,
+                           int keys_per_split, int head_dim, float qks, long window, long sinks,
+                           void* stream) {
+  MxSplitCall c;
+  const int rc = mx_varlen_call(c, q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec,
+                                work, nseq, nwork, tokens, part_rows, max_seqs, kv_heads, group, num_pages,
+                                page_tokens, max_pages_per_seq, causal, keys_per_split, head_dim, qks, window,
+                                sinks, nullptr);
+  if (rc >= 0) return rc;
   if (window < 1)
     return causal ? mx_split_launch<true, true, true, true, false>(c, stream)
                   : mx_split_launch<false, true, true, true, false>(c, stream);
@@ -1548,4 +1625,88 @@ extern "C" int qattn_mxfp4_attn_fwd_varlen_paged_shared(
                       dim3((unsigned)(nwork * kv_heads))};
   return causal ? mx_split_launch<true, true, true, true, false, true>(c, stream)
                 : mx_split_launch<false, true, true, true, false, true>(c, stream);
+}
+
+// The packed step with a tree mask on every sequence's last queries (kernel: mxfp4_attn_split_kernel TREE;
+// kv_cache_mxfp4.attention_mxfp4_varlen_paged(tree=)): qattn_mxfp4_attn_fwd_varlen_paged at causal == 2
+// with seq_rec[j][7] = nd_j tree nodes and tree_masks u64 [tokens] on the device, the ancestor word of
+// every packed token (0 outside a tree).  Partials and merge are the plain entry's.  It stands behind
+// every older entry, as its kernel is emitted behind theirs.
+extern "C" int qattn_mxfp4_attn_fwd_varlen_paged_tree(
+    const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt, const void* vscale,
+    void* opart, void* ml, const void* lens, const void* block_table, const void* seq_rec, const void* work,
+    long nseq, long nwork, long tokens, long part_rows, long max_seqs, long kv_heads, long group,
+    long num_pages, long page_tokens, long max_pages_per_seq, int causal, int keys_per_split, int head_dim,
+    float qks, const void* tree_masks, void* stream) {
+  if (causal != 2 || !tree_masks) return 1;
+  MxSplitCall c;
+  const int rc = mx_varlen_call(c, q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec,
+                                work, nseq, nwork, tokens, part_rows, max_seqs, kv_heads, group, num_pages,
+                                page_tokens, max_pages_per_seq, causal, keys_per_split, head_dim, qks, 0, 0,
+                                tree_masks);
+  if (rc >= 0) return rc;
+  return mx_split_launch<true, true, true, true, false, false, true>(c, stream);
+}
+
+// ---- rollback of the paged pool (kv_cache_mxfp4.py PagedKVFP4.rollback)
+// recs i32 [nrec][4] = {slot, L0, row in saved, 0} (distinct slots); saved f16 [nsaved][Hkv][64][D] is the
+// copy of the listed slots' vtail rows that PagedKVFP4.checkpoint took when sequence slot held L0 tokens.
+// One thread per (record, head, column d, half h), in mx_append_vt_kernel's order: it puts the column's
+// elements of vtail rows [0, L0 % 64) of its half's keys back, quantises its block of V tile L0 / 64 again
+// FROM THE SAVED ROWS when L0 % 64 != 0 (mx_requant_v_block with no new token: the keys at or past L0 are
+// zero, as after the appends that made L0), and thread (head 0, d 0, h 0) writes lens[slot] = L0.  The
+// tile is written where the block table puts it; page L0 / P of the slot is still the sequence's.  A
+// record whose slot, L0 or row lies outside [0, B), [0, cap] or [0, nsaved) writes nothing.
+namespace qattn {
+template <int D>
+__global__ __launch_bounds__(256) void mx_rollback_kernel(const _Float16* __restrict__ saved,
+                                                          _Float16* __restrict__ vtail,
+                                                          uint8_t* __restrict__ vt, uint8_t* __restrict__ vs,
+                                                          int* __restrict__ lens, const int* __restrict__ recs,
+                                                          long nthr, int nsaved, int B, int Hkv, int cap,
+                                                          const int* __restrict__ btab, int mpp, int lgt,
+                                                          int npool) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nthr) return;
+  const int h = (int)(i & 1);
+  const int d = (int)((i >> 1) % D);
+  const long rh = (i >> 1) / D;                 // record * Hkv + head
+  const int hd = (int)(rh % Hkv);
+  const int* rec = recs + 4 * (rh / Hkv);
+  const int slot = rec[0], L0 = rec[1], row = rec[2];
+  if (slot < 0 || slot >= B || L0 < 0 || L0 > cap || row < 0 || row >= nsaved) return;
+  const _Float16* src = saved + (((long)row * Hkv + hd) * 64) * D + d;
+  _Float16* dst = vtail + (((long)slot * Hkv + hd) * 64) * D + d;
+  const int live = L0 % 64;
+#pragma unroll 4
+  for (int j = 0; j < 32; ++j) {
+    const int key = 32 * (j >> 4) + 8 * ((j >> 2) & 3) + 4 * h + (j & 3);
+    if (key < live) dst[(long)key * D] = src[(long)key * D];
+  }
+  if (live) {
+    const long o = (mx_paged_tile(btab, slot, hd, L0 / 64, Hkv, mpp, lgt, npool) * D + d) * 2 + h;
+    mx_requant_v_block<D>(src, src, 1, L0 / 64, L0, 0, h, reinterpret_cast<v4i*>(vt) + o, vs + o);
+  }
+  if (hd == 0 && d == 0 && h == 0) lens[slot] = L0;
+}
+}  // namespace qattn
+
+extern "C" int qattn_mxfp4_paged_rollback(const void* saved, void* vtail, void* vt, void* vscale, void* lens,
+                                          const void* block_table, const void* recs, long nrec, long nsaved,
+                                          long max_seqs, long kv_heads, long num_pages, long page_tokens,
+                                          long max_pages_per_seq, int head_dim, void* stream) {
+  if (head_dim != 128 || nrec < 0 || nsaved < 0 || max_seqs < 1) return 1;
+  if (!saved || !vtail || !vt || !vscale || !lens || !block_table || !recs) return 1;
+  const int lgt = mx_page_lgt(page_tokens);
+  if (!mx_pool_ok(num_pages, kv_heads, lgt, max_pages_per_seq)) return 1;
+  if (nrec == 0) return 0;
+  if (nrec > max_seqs || nsaved < 1 || nsaved > 0x7fffffffL || max_seqs > 0x7fffffffL / kv_heads) return 1;
+  const long nthr = nrec * kv_heads * 128 * 2;
+  if ((nthr + 255) / 256 > 0x7fffffffL) return 1;
+  hipLaunchKernelGGL(mx_rollback_kernel<128>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, (const _Float16*)saved, (_Float16*)vtail, (uint8_t*)vt,
+                     (uint8_t*)vscale, (int*)lens, (const int*)recs, nthr, (int)nsaved, (int)max_seqs,
+                     (int)kv_heads, (int)(max_pages_per_seq * page_tokens), (const int*)block_table,
+                     (int)max_pages_per_seq, lgt, (int)num_pages);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
 }

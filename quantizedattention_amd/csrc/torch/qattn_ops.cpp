@@ -33,6 +33,8 @@
 //   mxfp4_varlen_paged(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal,
 //                      keys_per_split) -> (O, lse)
 //       kv_cache_mxfp4.attention_mxfp4_varlen_paged: packed q [T, Hq, 128] and the two plan tables
+//   mxfp4_varlen_paged_tree(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, tree_masks, part_rows,
+//                           causal, keys_per_split) -> (O, lse)      the same with a tree mask (verify step)
 //   mxfp4_varlen_paged_shared(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, grp_rec, members,
 //                             part_rows, causal, keys_per_split) -> (O, lse)
 //       the same with shared prefixes: the four tables of kv_cache_mxfp4.plan_varlen_shared
@@ -576,8 +578,15 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged_run(const Tensor& q_in, const Tens
                                                   const Tensor& work, int64_t part_rows, int64_t causal,
                                                   int64_t keys_per_split, bool windowed, int64_t window,
                                                   int64_t sinks, const Tensor* grp_rec = nullptr,
-                                                  const Tensor* members = nullptr) {
+                                                  const Tensor* members = nullptr,
+                                                  const Tensor* tree = nullptr) {
   require_gpu({&q_in, &k4, &ks, &vt, &vs, &lens, &block_table, &seq_rec, &work});
+  if (tree) {   // the tree entry's ancestor words, one per packed token
+    require_gpu({tree});
+    TORCH_CHECK(tree->scalar_type() == at::kLong && tree->is_contiguous() && tree->dim() == 1 &&
+                    q_in.dim() == 3 && tree->size(0) == q_in.size(0),
+                "qattn mxfp4 paged cache: tree_masks must be contiguous int64 [T], one word per packed token");
+  }
   if (grp_rec) {   // the shared-prefix plan's two further tables
     require_gpu({grp_rec, members});
     TORCH_CHECK(grp_rec->scalar_type() == at::kInt && grp_rec->is_contiguous() && grp_rec->dim() == 2 &&
@@ -625,6 +634,12 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged_run(const Tensor& q_in, const Tens
              (int)keys_per_split, (int)D, qk_scale(D), P(*grp_rec), P(*members), grp_rec->size(0),
              members->size(0), c.stream),
          "mxfp4 shared-prefix varlen forward");
+  else if (tree)
+    call(qattn_mxfp4_attn_fwd_varlen_paged_tree(
+             P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens), P(block_table), P(seq_rec),
+             P(work), seq_rec.size(0), work.size(0), T, part_rows, B, Hkv, Hq / Hkv, NP, PT, mpp, causal ? 2 : 0,
+             (int)keys_per_split, (int)D, qk_scale(D), P(*tree), c.stream),
+         "mxfp4 tree-masked varlen forward");
   else if (windowed)
     call(qattn_mxfp4_attn_fwd_varlen_paged_window(
              P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens), P(block_table), P(seq_rec),
@@ -677,6 +692,19 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged_shared(const Tensor& q, const Tens
                                 keys_per_split, false, 0, 0, &grp_rec, &members);
 }
 
+// the same with a tree mask on every sequence's last queries (kv_cache_mxfp4.attention_mxfp4_varlen_paged(
+// tree=)): causal only; seq_rec is plan_varlen's with the tree lengths, tree_masks i64 [T] the ancestor word
+// of every packed token (0 outside a tree)
+std::tuple<Tensor, Tensor> mxfp4_varlen_paged_tree(const Tensor& q, const Tensor& k4, const Tensor& ks,
+                                                   const Tensor& vt, const Tensor& vs, const Tensor& lens,
+                                                   const Tensor& block_table, const Tensor& seq_rec,
+                                                   const Tensor& work, const Tensor& tree_masks,
+                                                   int64_t part_rows, int64_t causal, int64_t keys_per_split) {
+  TORCH_CHECK(causal == 1, "qattn mxfp4 paged cache: a tree mask implies causal attention (causal must be 1)");
+  return mxfp4_varlen_paged_run(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal,
+                                keys_per_split, false, 0, 0, nullptr, nullptr, &tree_masks);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(qattn, m) {
@@ -705,6 +733,9 @@ TORCH_LIBRARY(qattn, m) {
   m.def("mxfp4_varlen_paged_shared(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, "
         "Tensor block_table, Tensor seq_rec, Tensor work, Tensor grp_rec, Tensor members, int part_rows, "
         "int causal, int keys_per_split) -> (Tensor, Tensor)");
+  m.def("mxfp4_varlen_paged_tree(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, "
+        "Tensor block_table, Tensor seq_rec, Tensor work, Tensor tree_masks, int part_rows, int causal, "
+        "int keys_per_split) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
@@ -722,4 +753,5 @@ TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
   m.impl("mxfp4_varlen_paged", &mxfp4_varlen_paged);
   m.impl("mxfp4_varlen_paged_window", &mxfp4_varlen_paged_window);
   m.impl("mxfp4_varlen_paged_shared", &mxfp4_varlen_paged_shared);
+  m.impl("mxfp4_varlen_paged_tree", &mxfp4_varlen_paged_tree);
 }

@@ -119,6 +119,28 @@ state into its own sequence's partial row at that split, the row the plain workg
 at the same keys per split.  One level of sharing per call: a sub-group with a longer common prefix (a
 fork of a fork) still shares only its group's common pages.
 
+Speculative decoding: a step that verifies a draft (a chain from a small model, or a Medusa / EAGLE-style
+token tree) appends the draft tokens and queries them in one packed step, as a prefill chunk, and then
+keeps one root-to-leaf path.  Two things serve it.  The tree mask (``tree=``, causal only, not with a
+window or ``share_prefix``): the last nd_j <= min(n_j, 64) query tokens of sequence j are the nodes of a
+tree (or forest) in topological order, already appended at keys base_j = L_j - nd_j ..; node t sees key
+k iff ``k < base_j`` or ``k = base_j + b`` with bit b of its 64-bit word set, the word holding the node's
+ancestors and itself (:func:`tree_ancestor_masks`); the queries before the tree are plain causal,
+``lse`` is over the visible keys, and a chain is the causal call bit for bit
+(``qattn_mxfp4_attn_fwd_varlen_paged_tree``; ``seq_rec[j][7]`` = nd_j, the words travel as one int64 [T]
+tensor behind the two tables, in their upload).  A draft token at tree depth d sits on a path whose
+accepted form lands at position L0 + d, whatever its index in the packed step: callers position-encode
+draft keys (and queries) by DEPTH, not by their place in the append.  Taking tokens back:
+:meth:`PagedKVFP4.checkpoint` notes the listed sequences' lengths and pages and copies their ``vtail``
+rows; :meth:`PagedKVFP4.rollback` restores those rows, quantises V tile L0 // 64 again from them (an
+append that crossed the tile boundary overwrote ``vtail``, and the tile holds the drafts' scales),
+writes the lengths back (``qattn_mxfp4_paged_rollback``) and returns the pages past ceil(L0 / P)
+(:meth:`PageAllocator.shrink`).  Afterwards the pool holds, byte for byte, what it held at the
+checkpoint -- rows [0, L0) of ``k4`` / ``ks``, tiles [0, ceil(L0 / 64)) of ``vt`` / ``vs``, ``vtail``
+rows [0, L0 % 64), ``lens``, the page lists below ceil(L0 / P) and the free-page count -- so every later
+``append`` gives the bytes of a pool that never saw the drafts.  :meth:`PagedKVFP4.accept` is that
+followed by one ``append_packed`` of the surviving draft rows.
+
 Wire format (little-endian), the container of kv_cache.py with a magic of its own::
 
     offset 0   8 B   magic  b"QATTNKF4"
@@ -154,7 +176,8 @@ _DTYPES = {"uint8": torch.uint8, "float16": torch.float16}
 
 __all__ = ["QuantizedKVFP4", "quantize_kv_fp4", "attention_mxfp4_cached", "PreallocatedKVFP4",
            "attention_mxfp4_decode", "PageAllocator", "PagedKVFP4", "attention_mxfp4_decode_paged",
-           "plan_varlen", "plan_varlen_shared", "attention_mxfp4_varlen_paged"]
+           "plan_varlen", "plan_varlen_shared", "attention_mxfp4_varlen_paged", "tree_ancestor_masks",
+           "tree_path", "Checkpoint"]
 
 
 @dataclass
@@ -621,6 +644,28 @@ class PageAllocator:
                 freed += 1
         return freed
 
+    def shrink(self, b, pages: int) -> int:
+        """Cut sequence ``b``'s page list to its first ``pages`` logical pages -> the pages that returned to
+        the free list.  Each page past the cut loses one reference (a page shared by ``share`` just loses
+        that one); a hole past the cut only stops being counted, the holes below it stay.  ``table[b]``
+        keeps what it held past the cut and means nothing there.  All or nothing: ``pages`` outside [0,
+        len(pages[b])] raises."""
+        b, pages = self._seq(b), int(pages)
+        if not 0 <= pages <= len(self.pages[b]):
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: sequence {b} cannot shrink to {pages} pages "
+                                  f"(it has {len(self.pages[b])})")
+        freed = 0
+        for p in reversed(self.pages[b][pages:]):   # last taken, first back: the free list as it was
+            if p is None:
+                self.nholes[b] -= 1
+                continue
+            self.refcount[p] -= 1
+            if self.refcount[p] == 0:
+                self._free.append(p)
+                freed += 1
+        del self.pages[b][pages:]
+        return freed
+
     def holes(self, b, first_page: int = 0, last_page: Optional[int] = None) -> list:
         """The indices in ``[first_page, last_page)`` (default: all) of sequence ``b``'s pages that are
         holes."""
@@ -676,6 +721,22 @@ class PageAllocator:
         return out
 
 
+@dataclass
+class Checkpoint:
+    """What :meth:`PagedKVFP4.checkpoint` notes of the sequences ``seq_ids`` (slots) of ``cache``: per
+    sequence its length L0, its logical page count, its hole count and the slot's epoch, all host lists
+    in the order of ``seq_ids``, and ``saved`` f16 [len(seq_ids), Hkv, 64, D], the copy of the slots'
+    ``vtail`` rows on the device.  :meth:`PagedKVFP4.rollback` stamps ``epochs`` again."""
+
+    cache: "PagedKVFP4"
+    seq_ids: list
+    lengths: list
+    pages: list
+    holes: list
+    epochs: list
+    saved: torch.Tensor
+
+
 class PagedKVFP4:
     """MX-FP4 keys/values of up to ``max_seqs`` sequences x ``kv_heads`` heads in a pool of
     ``num_pages`` pages of ``page_tokens`` tokens; layout and invariant: the module docstring.
@@ -693,6 +754,7 @@ class PagedKVFP4:
         self.k4, self.ks, self.vt, self.vs = k4, ks, vt, vs
         self.vtail, self.lens, self.block_table, self.alloc, self.k_mean = vtail, lens, block_table, alloc, k_mean
         self.lengths = [0] * alloc.max_seqs
+        self.epoch = [0] * alloc.max_seqs   # bumped by free, trim and rollback: what a Checkpoint is held to
 
     @classmethod
     def allocate(cls, num_pages: int, page_tokens: int, max_seqs: int, kv_heads: int, max_pages_per_seq: int,
@@ -828,6 +890,7 @@ class PagedKVFP4:
         for b in seqs:
             self.lengths[b] = 0
             self.alloc.release(b)
+            self.epoch[b] += 1
         self._upload(table=False)
 
     def _whole(self, b: int, what: str) -> None:
@@ -857,7 +920,110 @@ class PagedKVFP4:
             first, last = -(-S // P), (self.lengths[b] - W + 1) // P
             if last > first:
                 freed += self.alloc.drop(b, first, last)
+            self.epoch[b] += 1
         return freed
+
+    # ------------------------------------------------------------------------------ speculative decoding
+    def checkpoint(self, seq_ids) -> "Checkpoint":
+        """Note where the listed sequences (distinct slots; a length of 0 is allowed) stand, so that
+        :meth:`rollback` can take back what is appended after this: per sequence the slot, its length
+        L0, its logical page count, its hole count and the slot's epoch on the host, and on the device a
+        copy of the slots' ``vtail`` rows (rows [0, L0 % 64) are what matters: a later append that crosses
+        a tile boundary overwrites them).  Stream-ordered, no synchronisation, nothing read back."""
+        ids = [self.alloc._seq(b) for b in seq_ids]
+        if not ids or len(set(ids)) != len(ids):
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: checkpoint needs distinct slots, got {ids}")
+        dev = self.vtail.device
+        saved = self.vtail.index_select(0, torch.tensor(ids, dtype=torch.long).to(dev, non_blocking=True))
+        a = self.alloc
+        return Checkpoint(self, ids, [self.lengths[b] for b in ids], [len(a.pages[b]) for b in ids],
+                          [a.nholes[b] for b in ids], [self.epoch[b] for b in ids], saved)
+
+    def _rollback_check(self, ckpt: "Checkpoint", seq_ids) -> list:
+        """The refusals of :meth:`rollback` -> the checkpoint's rows of the listed sequences."""
+        if not isinstance(ckpt, Checkpoint) or ckpt.cache is not self:
+            raise _lib.QAttnError("qattn mxfp4 paged cache: rollback needs a checkpoint of this pool")
+        ids = ckpt.seq_ids if seq_ids is None else [self.alloc._seq(b) for b in seq_ids]
+        if len(set(ids)) != len(ids) or any(b not in ckpt.seq_ids for b in ids):
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: rollback of {ids}: distinct sequences of the "
+                                  f"checkpoint ({ckpt.seq_ids}) expected")
+        rows = [ckpt.seq_ids.index(b) for b in ids]
+        a, P = self.alloc, self.page_tokens
+        for r in rows:
+            b, L0 = ckpt.seq_ids[r], ckpt.lengths[r]
+            if self.epoch[b] != ckpt.epochs[r]:
+                raise _lib.QAttnError(f"qattn mxfp4 paged cache: stale checkpoint of sequence {b}: it was "
+                                      "freed, trimmed or rolled back through another checkpoint since")
+            if self.lengths[b] < L0:
+                raise _lib.QAttnError(f"qattn mxfp4 paged cache: sequence {b} is shorter ({self.lengths[b]} "
+                                      f"tokens) than its checkpoint ({L0})")
+            page = a.pages[b][L0 // P] if L0 % P else None
+            if page is not None and a.refcount[page] > 1:
+                raise _lib.QAttnError(f"qattn mxfp4 paged cache: the page that holds position {L0} of sequence "
+                                      f"{b} is shared (a fork after the checkpoint): rolling back would let "
+                                      "later appends write into a page another sequence reads")
+        return rows
+
+    def rollback(self, ckpt: "Checkpoint", seq_ids=None) -> "PagedKVFP4":
+        """Take the listed sequences (default: all of the checkpoint) back to their lengths L0 at
+        ``ckpt``.  One launch (``qattn_mxfp4_paged_rollback``) restores ``vtail`` rows [0, L0 % 64),
+        quantises V tile L0 // 64 again from the saved rows when L0 % 64 != 0 (the rows at or past L0 are
+        zero) and writes ``lens``; the host gives the pages past ceil(L0 / P) back
+        (:meth:`PageAllocator.shrink`) and mirrors the lengths.  K rows at or past L0 are left alone
+        (unspecified by the invariant).  Afterwards the pool holds, byte for byte, what it held at the
+        checkpoint (module docstring).  The checkpoint is stamped again, so it can serve the next draft
+        round.  Raises before any launch or change, naming the reason: "stale" (the slot was freed, trimmed
+        or rolled back through another checkpoint since), "shorter" (its length is below L0 now), "shared"
+        (L0 % P != 0 and the page holding position L0 has a reference count above 1).  Stream-ordered, no
+        synchronisation; returns ``self``.  Not for :class:`PreallocatedKVFP4`."""
+        rows = self._rollback_check(ckpt, seq_ids)
+        self._rollback(ckpt, rows)
+        return self
+
+    def _rollback(self, ckpt: "Checkpoint", rows) -> None:
+        _, H, _, D = self.shape
+        recs = [x for r in rows for x in (ckpt.seq_ids[r], ckpt.lengths[r], r, 0)]
+        dev = torch.tensor(recs, dtype=torch.int32).to(self.vtail.device, non_blocking=True)
+        _lib.call("qattn_mxfp4_paged_rollback", _lib.ptr(ckpt.saved), _lib.ptr(self.vtail), _lib.ptr(self.vt),
+                  _lib.ptr(self.vs), _lib.ptr(self.lens), _lib.ptr(self.block_table), _lib.ptr(dev), len(rows),
+                  len(ckpt.seq_ids), self.alloc.max_seqs, H, self.num_pages, self.page_tokens,
+                  self.alloc.max_pages_per_seq, D, _lib.stream_of(self.vtail))
+        for r in rows:
+            b = ckpt.seq_ids[r]
+            self.alloc.shrink(b, ckpt.pages[r])
+            self.lengths[b] = ckpt.lengths[r]
+            self.epoch[b] += 1
+            ckpt.epochs[r] = self.epoch[b]
+
+    def accept(self, ckpt: "Checkpoint", k: torch.Tensor, v: torch.Tensor, seq_ids, counts, accepted) -> "PagedKVFP4":
+        """:meth:`rollback` of ``seq_ids`` followed by one :meth:`append_packed` of the draft rows that
+        survive.  ``k``, ``v``, ``seq_ids`` and ``counts`` are those of the draft step's ``append_packed``;
+        ``accepted[j]`` lists distinct token indices into sequence j's ``counts[j]`` tokens, in the order
+        in which they are kept (a :func:`tree_path`, say); it may be empty, and a sequence that keeps
+        nothing is only rolled back.  The kept rows are gathered from ``k``, ``v`` on the device with
+        uploaded indices.  Every argument is checked before anything changes; the pages the kept tokens
+        need were the drafts' a moment ago, so the append finds them unless another sequence took them
+        in between.  Stream-ordered; returns ``self``."""
+        _, H, _, D = self.shape
+        ids, cnt = _packed_lists(self.alloc.max_seqs, seq_ids, counts, "counts")
+        if (k.dim() != 3 or tuple(k.shape[1:]) != (H, D) or k.shape != v.shape or k.shape[0] != sum(cnt)):
+            raise _lib.QAttnError("qattn mxfp4 paged cache: packed tokens must be k, v [sum(counts), Hkv, D]")
+        acc = [[int(i) for i in a] for a in accepted]
+        if len(acc) != len(ids) or any(len(set(a)) != len(a) or any(not 0 <= i < c for i in a)
+                                       for a, c in zip(acc, cnt)):
+            raise _lib.QAttnError("qattn mxfp4 paged cache: accepted must list, per sequence, distinct token "
+                                  f"indices below its count (counts {cnt}, accepted {acc})")
+        rows = self._rollback_check(ckpt, ids)
+        _lib.require_gpu(k, v, self.k4)
+        self._rollback(ckpt, rows)
+        first = list(itertools.accumulate([0] + cnt[:-1]))
+        keep = [f + i for f, a in zip(first, acc) for i in a]
+        if keep:
+            idx = torch.tensor(keep, dtype=torch.long).to(k.device, non_blocking=True)
+            kept = [(b, len(a)) for b, a in zip(ids, acc) if a]
+            self.append_packed(k.index_select(0, idx), v.index_select(0, idx), [b for b, _ in kept],
+                               [n for _, n in kept])
+        return self
 
     def fork(self, src: int, dst: int) -> None:
         """Make the empty sequence ``dst`` a copy of ``src`` that shares its memory: the ``L // P``
@@ -997,8 +1163,48 @@ def _varlen_lists(lengths, seq_ids, q_lens, Hq: int, Hkv: int, causal: bool):
     return ids, sq, Ls
 
 
+TREE_NODES = 64   # nodes of one sequence's draft tree: the bits of its ancestor words
+
+
+def _tree_parents(parents) -> list:
+    par = [int(p) for p in (parents.tolist() if isinstance(parents, torch.Tensor) else parents)]
+    if len(par) > TREE_NODES:
+        raise _lib.QAttnError(f"qattn mxfp4 paged cache: a draft tree of {len(par)} nodes; at most {TREE_NODES} "
+                              "(one bit of the ancestor word each)")
+    bad = [t for t, p in enumerate(par) if not -1 <= p < t]
+    if bad:
+        raise _lib.QAttnError(f"qattn mxfp4 paged cache: draft tree nodes {bad} have a parent outside [-1, t): "
+                              "nodes come in topological order (parent < child, -1 marks a root)")
+    return par
+
+
+def tree_ancestor_masks(parents) -> list:
+    """The 64-bit ancestor words of a draft tree (or forest) given as ``parents``: ``parents[t]`` in [-1, t)
+    is the parent of node t, -1 marks a root, so the nodes are in topological order -> ``anc`` with bit b of
+    ``anc[t]`` set iff node b is an ancestor of node t or t itself.  Every word is a subset of bits <= t
+    that holds bit t.  Pure Python, no device.  Raises :class:`QAttnError` for a parent >= t (or < -1) and
+    for more than 64 nodes."""
+    anc = []
+    for t, p in enumerate(_tree_parents(parents)):
+        anc.append((anc[p] if p >= 0 else 0) | 1 << t)
+    return anc
+
+
+def tree_path(parents, leaf: int) -> list:
+    """The node indices from the root to ``leaf`` (both included), ascending: the ``accepted`` list of
+    :meth:`PagedKVFP4.accept` for the path that ends at ``leaf``."""
+    par, leaf = _tree_parents(parents), int(leaf)
+    if not 0 <= leaf < len(par):
+        raise _lib.QAttnError(f"qattn mxfp4 paged cache: no node {leaf} in a draft tree of {len(par)} nodes")
+    path = []
+    while leaf >= 0:
+        path.append(leaf)
+        leaf = par[leaf]
+    return path[::-1]
+
+
 def plan_varlen(lengths, seq_ids, q_lens, Hq: int, Hkv: int, keys_per_split: Optional[int] = None,
-                causal: bool = False, window: Optional[int] = None, sinks: int = 0):
+                causal: bool = False, window: Optional[int] = None, sinks: int = 0, tree_lens=None):
     """The host plan of :func:`attention_mxfp4_varlen_paged` -> (kps, seq_rec, work, part_rows); pure
     Python on the host mirror ``lengths`` (one entry per slot), no device and no tensor.
 
@@ -1037,6 +1243,11 @@ def plan_varlen(lengths, seq_ids, q_lens, Hq: int, Hkv: int, keys_per_split: Opt
     sink split costs 0.9 us, the rest of the 6.5 us is the windowed instantiation.
     ``free_pages`` before and after ``trim`` of that batch: 0 -> 7104 of 8192.
 
+    ``tree_lens`` (None: no trees): one int per listed sequence, nd_j tree tokens among its q_lens[j] (module
+    docstring); ``seq_rec[j][7]`` = nd_j and everything else -- splits, work records, partial rows -- is the
+    causal plan's.  Raises, naming "tree", without ``causal``, with a window, and for nd_j outside [0,
+    min(q_lens[j], 64)].
+
     Raises :class:`QAttnError` for an empty, duplicate or out-of-range slot list, a q_lens entry < 1, a
     listed slot of length 0, ``causal`` with q_lens[j] > L_j, Hq % Hkv != 0, a ``keys_per_split`` that
     is not a multiple of 64, and when T * Hq, part_rows or nwork * Hkv reach 2^31.  The slots that are
@@ -1046,6 +1257,15 @@ def plan_varlen(lengths, seq_ids, q_lens, Hq: int, Hkv: int, keys_per_split: Opt
     if W is not None and not causal:
         raise _lib.QAttnError("qattn mxfp4 paged cache: a window implies causal attention; pass causal=True")
     ids, sq, Ls = _varlen_lists(lengths, seq_ids, q_lens, Hq, Hkv, causal)
+    nds = [0] * len(ids)
+    if tree_lens is not None:
+        nds = [int(x) for x in tree_lens]
+        if not causal or W is not None:
+            raise _lib.QAttnError("qattn mxfp4 paged cache: a tree mask needs causal=True and no window (every "
+                                  "tree node sees the cached keys and its ancestors)")
+        if len(nds) != len(ids) or any(not 0 <= nd <= min(n, TREE_NODES) for nd, n in zip(nds, sq)):
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: tree lengths {nds} must be one per sequence, each "
+                                  f"in [0, min(q_lens[j], {TREE_NODES})] (q_lens {sq})")
     G = Hq // Hkv
     nrb = [-(-G * n // QROWS) for n in sq]
     sk_max = _ceil64(max(Ls))
@@ -1069,7 +1289,7 @@ def plan_varlen(lengths, seq_ids, q_lens, Hq: int, Hkv: int, keys_per_split: Opt
     seq_rec, work, first, base = [], [], 0, 0
     for j, (b, n, L, ns) in enumerate(zip(ids, sq, Ls, nsp)):
         wt0, nst = wt[j][:2] if W is not None else (0, 0)
-        seq_rec.append([b, first, n, ns, base, wt0, nst, 0])
+        seq_rec.append([b, first, n, ns, base, wt0, nst, nds[j]])
         nt = -(-L // BLOCK)
         for s in range(ns):
             if nst and s == 0:   # a gap: the sink split, then the window splits from wt0
@@ -1229,10 +1449,41 @@ def _check_trimmed(cache: "PagedKVFP4", ids, sq, W, S) -> None:
                                   "window or fewer sinks)")
 
 
+def _tree_args(tree, sq, causal: bool, window, share_prefix: bool):
+    """``tree`` of a packed call over sequences of ``sq`` queries, checked -> (tree lengths, the int64
+    ancestor word of every packed token as a host int32 tensor [2 T], low half first), or None when no
+    sequence has a tree (the plain causal call is then made).  Every refusal names "tree"."""
+    if not causal or window is not None or share_prefix:
+        raise _lib.QAttnError("qattn mxfp4 paged cache: tree needs causal=True and cannot be combined with a "
+                              "window or share_prefix")
+    tree = list(tree)
+    if len(tree) != len(sq):
+        raise _lib.QAttnError(f"qattn mxfp4 paged cache: tree must have one entry (None or a parents list) per "
+                              f"listed sequence, got {len(tree)} for {len(sq)}")
+    # one host tensor of words per distinct parents list (a batch usually drafts one tree shape): the host
+    # work per sequence is a dictionary look-up and, at the end, one concatenation
+    seen, parts, nds = {}, [], []
+    for p, n in zip(tree, sq):
+        w = seen.get(id(p))
+        if w is None:
+            anc = [] if p is None else tree_ancestor_masks(p)
+            w = seen[id(p)] = torch.tensor([x - (1 << 64) if x >> 63 else x for x in anc], dtype=torch.int64)
+        nds.append(w.numel())
+        if w.numel() > n:
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: a tree of {w.numel()} nodes on a sequence of {n} "
+                                  "query tokens")
+        if n > w.numel():
+            parts.append(torch.zeros(n - w.numel(), dtype=torch.int64))
+        parts.append(w)
+    if not any(nds):
+        return None
+    return nds, torch.cat(parts).view(torch.int32)
+
+
 @torch.no_grad()
 def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_lens, causal: bool = False,
                                  keys_per_split: Optional[int] = None, window: Optional[int] = None,
-                                 sinks: int = 0, share_prefix: bool = False):
+                                 sinks: int = 0, share_prefix: bool = False, tree=None):
     """A ragged batch against a paged cache in one attention launch and one merge: packed fp16 queries
     ``q`` [T, Hq, D], token-major, the ``q_lens[0]`` tokens of sequence ``seq_ids[0]`` first, then
     those of ``seq_ids[1]``, ... (nseq >= 1 distinct slots, every q_lens[j] >= 1, T = sum(q_lens)) ->
@@ -1257,7 +1508,21 @@ def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_
     runs as above.  The result is, bit for bit, that of the same call without ``share_prefix`` at the
     same ``keys_per_split`` (the default ``keys_per_split`` differs: :func:`plan_varlen_shared`); when
     nothing is shared the plain call is made.  One level of sharing per call, and no ``window``: the
-    combination raises :class:`QAttnError` before any launch."""
+    combination raises :class:`QAttnError` before any launch.
+
+    ``tree`` (causal only) is the verify step of speculative decoding: a list with one entry per listed
+    sequence, None or that sequence's ``parents`` list (:func:`tree_ancestor_masks`), whose length is
+    nd_j: the last nd_j <= min(q_lens[j], 64) query tokens of the sequence are the nodes of a draft tree
+    in topological order, appended already like a prefill chunk.  With base_j = L_j - nd_j, node t sees
+    key k iff ``k < base_j`` or ``k = base_j + b`` for an ancestor b of t or b = t; the queries before
+    the tree and the sequences with None are plain causal; ``lse`` is over the visible keys
+    (``qattn_mxfp4_attn_fwd_varlen_paged_tree``; the words are uploaded with the two tables, in one
+    upload).  A chain gives the causal call's bits, and with every entry None the plain causal call is
+    made.  A draft token at tree depth d sits on a path whose accepted form lands at position L0 + d (L0
+    the length before the drafts): position-encode draft keys and queries by their depth, not by their
+    index in the packed step.  Raises before any launch, naming "tree": without ``causal``, together
+    with ``window`` or ``share_prefix=True``, for more nodes than min(q_lens[j], 64), and for a parent
+    that is not in [-1, t)."""
     if not isinstance(cache, PagedKVFP4):
         raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PagedKVFP4")
     _, Hkv, _, D = cache.shape
@@ -1269,18 +1534,24 @@ def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_
     ids, sq = _packed_lists(cache.alloc.max_seqs, seq_ids, q_lens, "q_lens")
     if sum(sq) != T:
         raise _lib.QAttnError(f"qattn mxfp4 paged cache: q holds {T} tokens, q_lens sum to {sum(sq)}")
+    trees = None if tree is None else _tree_args(tree, sq, causal, window, share_prefix)
     shared = _shared_plan(cache, ids, sq, Hq, keys_per_split, causal, window) if share_prefix else None
     if shared is not None:
         kps, seq_rec, work, part_rows, grp_rec, members = shared
     else:
         kps, seq_rec, work, part_rows = plan_varlen(cache.lengths, ids, sq, Hq, Hkv, keys_per_split, causal,
-                                                    window, sinks)
+                                                    window, sinks, None if trees is None else trees[0])
     W, S = _window_args(window, sinks)
     _check_trimmed(cache, ids, sq, W, S)
     _lib.require_gpu(q, cache.k4)
     dev, st = q.device, _lib.stream_of(q)
     # from fresh pageable host tensors, as PagedKVFP4._upload: staged before the copies return
-    if shared is None:
+    if trees is not None:   # one upload: the two tables, then the words (at a multiple of 16 bytes)
+        flat = torch.tensor(list(itertools.chain.from_iterable(seq_rec + work)), dtype=torch.int32)
+        rec_d = torch.cat([flat, trees[1]]).to(dev, non_blocking=True)
+        work_d = rec_d[8 * len(seq_rec):]
+        tree_d = work_d[4 * len(work):].view(torch.int64)
+    elif shared is None:
         rec_d = torch.tensor(seq_rec, dtype=torch.int32).to(dev, non_blocking=True)
         work_d = torch.tensor(work, dtype=torch.int32).to(dev, non_blocking=True)
     else:   # one upload of the four tables, the longest records first
@@ -1301,6 +1572,8 @@ def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_
     if shared is not None:
         _lib.call("qattn_mxfp4_attn_fwd_varlen_paged_shared", *args, _lib.ptr(grp_d),
                   _lib.ptr(grp_d[4 * len(grp_rec):]), len(grp_rec), len(members), st)
+    elif trees is not None:
+        _lib.call("qattn_mxfp4_attn_fwd_varlen_paged_tree", *args, _lib.ptr(tree_d), st)
     elif W is None:
         _lib.call("qattn_mxfp4_attn_fwd_varlen_paged", *args, st)
     else:   # no sequence holds 2^25 keys or more: a larger window or sink count means the same

@@ -26,6 +26,8 @@ the autograd rules of ``int8_fwd`` and ``bf16_fwd`` (their backward operators).
                                               part_rows, causal, keys_per_split, window, sinks) -> (O, lse)
     torch.ops.qattn.mxfp4_varlen_paged_shared(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, grp_rec,
                                               members, part_rows, causal, keys_per_split) -> (O, lse)
+    torch.ops.qattn.mxfp4_varlen_paged_tree(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, tree_masks,
+                                            part_rows, causal, keys_per_split) -> (O, lse)
 
 Shapes follow the drop-in functions (attention_int8.py:259-262 for the int8 outputs) except that
 k_i8 is returned row-major [B*Hkv*Sk, D] (the drop-in's k_i8T is its transposed view: an operator
@@ -140,6 +142,12 @@ def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal, ke
 
 @torch.library.register_fake("qattn::mxfp4_varlen_paged_shared")
 def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, grp_rec, members, part_rows, causal, keys_per_split):
+    T, H, D = q.shape
+    return (q.new_empty((T, H, D), dtype=torch.float16), q.new_empty((T, H), dtype=torch.float32))
+
+
+@torch.library.register_fake("qattn::mxfp4_varlen_paged_tree")
+def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, tree_masks, part_rows, causal, keys_per_split):
     T, H, D = q.shape
     return (q.new_empty((T, H, D), dtype=torch.float16), q.new_empty((T, H), dtype=torch.float32))
 
@@ -267,7 +275,7 @@ def mxfp4_decode_paged(q, cache, causal=False, keys_per_split=None):
 
 
 def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=None, window=None, sinks=0,
-                       share_prefix=False):
+                       share_prefix=False, tree=None):
     """``kv_cache_mxfp4.attention_mxfp4_varlen_paged`` as one operator: packed q [T, Hq, 128] against
     a ``PagedKVFP4``, the ``q_lens[j]`` tokens of slot ``seq_ids[j]`` over that sequence's own length
     and pages -> (O fp16 [T, Hq, 128], lse fp32 [T, Hq]).  The plan (``plan_varlen``) is made and checked
@@ -277,9 +285,11 @@ def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=N
     Python call's.  ``share_prefix=True`` (without a window) routes to
     ``torch.ops.qattn.mxfp4_varlen_paged_shared`` with the tables of ``plan_varlen_shared`` when the listed
     sequences hold leading pages in common (``PagedKVFP4.prefix_groups``), and to the plain operator when
-    they do not: the same bits either way."""
-    from .kv_cache_mxfp4 import (PagedKVFP4, _check_trimmed, _packed_lists, _shared_plan, _window_args,
-                                 plan_varlen)
+    they do not: the same bits either way.  ``tree`` (causal only, without a window or ``share_prefix``; one
+    entry per sequence, None or a ``parents`` list) routes to ``torch.ops.qattn.mxfp4_varlen_paged_tree``, the
+    tree-masked verify step of the Python call, and to the plain operator when every entry is None."""
+    from .kv_cache_mxfp4 import (PagedKVFP4, _check_trimmed, _packed_lists, _shared_plan, _tree_args,
+                                 _window_args, plan_varlen)
     if not isinstance(cache, PagedKVFP4):
         raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PagedKVFP4")
     if q.dim() != 3:
@@ -287,6 +297,19 @@ def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=N
     ids, sq = _packed_lists(cache.alloc.max_seqs, seq_ids, q_lens, "q_lens")
     if sum(sq) != q.shape[0]:
         raise _lib.QAttnError(f"qattn mxfp4 paged cache: q holds {q.shape[0]} tokens, q_lens sum to {sum(sq)}")
+    trees = None if tree is None else _tree_args(tree, sq, causal, window, share_prefix)
+    if trees is not None:
+        kps, seq_rec, work, part_rows = plan_varlen(cache.lengths, ids, sq, q.shape[1], cache.k4.shape[1],
+                                                    keys_per_split, causal, None, 0, trees[0])
+        _check_trimmed(cache, ids, sq, None, 0)
+        _lib.require_gpu(q, cache.k4)
+        # one upload: the two tables, then the ancestor words
+        flat = torch.tensor(list(itertools.chain.from_iterable(seq_rec + work)), dtype=torch.int32)
+        flat = torch.cat([flat, trees[1]]).to(q.device, non_blocking=True)
+        a, b = 8 * len(seq_rec), 8 * len(seq_rec) + 4 * len(work)
+        return _ops.mxfp4_varlen_paged_tree(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens,
+                                            cache.block_table, flat[:a].view(-1, 8), flat[a:b].view(-1, 4),
+                                            flat[b:].view(torch.int64), part_rows, 1, kps)
     shared = _shared_plan(cache, ids, sq, q.shape[1], keys_per_split, causal, window) if share_prefix else None
     if shared is not None:
         kps, seq_rec, work, part_rows, grp_rec, members = shared
