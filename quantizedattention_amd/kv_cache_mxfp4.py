@@ -995,15 +995,40 @@ class PagedKVFP4:
             self.epoch[b] += 1
             ckpt.epochs[r] = self.epoch[b]
 
+    def _accept_pages(self, ckpt: "Checkpoint", rows, ids, acc) -> None:
+        """Raise unless the append that follows the rollback of :meth:`accept` will find its pages, so that
+        a refused accept changes nothing.  The rollback returns a page past a sequence's cut only when the
+        listed sequences hold all its references: a fork made after the drafts keeps it.  Those pages are
+        counted only when the free ones do not suffice."""
+        a = self.alloc
+        full = [a.pages_for(ckpt.lengths[r] + len(kept)) for r, kept in zip(rows, acc)]
+        if max(full) > a.max_pages_per_seq:
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: sequences {ids} would pass max_pages_per_seq = "
+                                  f"{a.max_pages_per_seq} pages with their accepted tokens")
+        need = sum(max(0, n - ckpt.pages[r]) for n, r in zip(full, rows))
+        if need <= a.free_pages:
+            return
+        past = {}
+        for r, b in zip(rows, ids):
+            for p in a.pages[b][ckpt.pages[r]:]:
+                if p is not None:
+                    past[p] = past.get(p, 0) + 1
+        back = sum(1 for p, n in past.items() if a.refcount[p] == n)
+        if need > a.free_pages + back:
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: out of pages ({need} needed for the accepted tokens, "
+                                  f"{a.free_pages} of {self.num_pages} free and {back} returned by the rollback: "
+                                  "a fork made after the drafts still holds their pages)")
+
     def accept(self, ckpt: "Checkpoint", k: torch.Tensor, v: torch.Tensor, seq_ids, counts, accepted) -> "PagedKVFP4":
         """:meth:`rollback` of ``seq_ids`` followed by one :meth:`append_packed` of the draft rows that
         survive.  ``k``, ``v``, ``seq_ids`` and ``counts`` are those of the draft step's ``append_packed``;
         ``accepted[j]`` lists distinct token indices into sequence j's ``counts[j]`` tokens, in the order
         in which they are kept (a :func:`tree_path`, say); it may be empty, and a sequence that keeps
         nothing is only rolled back.  The kept rows are gathered from ``k``, ``v`` on the device with
-        uploaded indices.  Every argument is checked before anything changes; the pages the kept tokens
-        need were the drafts' a moment ago, so the append finds them unless another sequence took them
-        in between.  Stream-ordered; returns ``self``."""
+        uploaded indices.  Every argument is checked before anything changes, the pages included: the
+        kept tokens take the pages the rollback returns, and when a fork made after the drafts still
+        holds those and the pool has no others, the call raises, naming "out of pages", before the
+        rollback.  Stream-ordered; returns ``self``."""
         _, H, _, D = self.shape
         ids, cnt = _packed_lists(self.alloc.max_seqs, seq_ids, counts, "counts")
         if (k.dim() != 3 or tuple(k.shape[1:]) != (H, D) or k.shape != v.shape or k.shape[0] != sum(cnt)):
@@ -1015,6 +1040,7 @@ class PagedKVFP4:
                                   f"indices below its count (counts {cnt}, accepted {acc})")
         rows = self._rollback_check(ckpt, ids)
         _lib.require_gpu(k, v, self.k4)
+        self._accept_pages(ckpt, rows, ids, acc)
         self._rollback(ckpt, rows)
         first = list(itertools.accumulate([0] + cnt[:-1]))
         keep = [f + i for f, a in zip(first, acc) for i in a]
