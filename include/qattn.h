@@ -36,7 +36,7 @@ extern "C" {
  * qattn_source_hash() is the sha256 (hex) of the kernel sources and compile flags the library was
  * built from (quantizedattention_amd/_srchash.py); the Python binding refuses a library whose hash
  * differs from the sources beside it (a stale prebuilt library). */
-#define QATTN_ABI_VERSION 7
+#define QATTN_ABI_VERSION 8
 int qattn_abi_version(void);
 const char* qattn_source_hash(void);
 
@@ -574,7 +574,7 @@ int qattn_mxfp4_attn_fwd_varlen_paged_shared(
  * never an empty row), and a chain (bits 0 .. t) gives the first entry's bits.  lse is over the visible
  * keys.  Splits, work records, partial rows, clamping and the merge (qattn_mxfp4_varlen_combine) are the
  * first entry's; nd_j is clamped to [0, min(n_j, 64)].  A draft token at tree depth d stands for position
- * L_j - nd_j + d of its path: the caller position-encodes draft keys and queries by depth.
+ * L_j - nd_j + d of its path: the rotary entries below are given those positions for draft keys and queries.
  * Returns 1 without a launch for causal != 2 and a NULL tree_masks, and as the first entry. */
 int qattn_mxfp4_attn_fwd_varlen_paged_tree(
     const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt, const void* vscale,
@@ -623,6 +623,36 @@ int qattn_mxfp4_paged_append_packed(const void* k, const void* v, const void* k_
                                     long nseq, long ntiles, long tokens, long max_seqs, long kv_heads,
                                     long num_pages, long page_tokens, long max_pages_per_seq, int head_dim,
                                     void* stream);
+
+/* Rotary position embedding fused into the quantisers of the packed step (kv_cache_mxfp4.py Rope).
+ * cos_sin f32 [max_pos][128], contiguous: row p holds cos theta(p, i) at column i and sin theta(p, i) at
+ * column 64 + i for pair i in [0, 64) (the cos_sin_cache convention; a table scaled by YaRN, llama3 or NTK
+ * is passed as it is).  interleaved 0 (NeoX, rotate half) pairs elements (i, i + 64) of a row, 1 (GPT-J)
+ * elements (2i, 2i + 1).  With c, s from the row of the token's position, a pair (a, b) of f16 inputs
+ * becomes first = f16(f32(a c) - f32(b s)), second = f16(f32(b c) + f32(a s)): two rounded fp32 products,
+ * one rounded fp32 sum, round-to-nearest-even to f16, no fused multiply-add; the rotated f16 row then
+ * goes through the quantiser unchanged (keys: f16(x - k_mean) first, as without).  pos i32 [tokens] on
+ * the device holds one position per packed token and is clamped to [0, max_pos - 1]: a wrong position
+ * gives a wrong answer, never an address outside the table.
+ *
+ * qattn_mxfp4_quant_rows_rope: qattn_mxfp4_quant_rows without a mean on x f16 [tokens][heads][128], token-
+ * major (the packed q of qattn_mxfp4_attn_fwd_varlen_paged), each row rotated first.  Returns 1 for head_dim
+ * != 128, a NULL cos_sin or pos, max_pos < 1 or >= 2^31, interleaved outside {0, 1}, tokens * heads >= 2^31;
+ * 0 without a launch for tokens or heads == 0. */
+int qattn_mxfp4_quant_rows_rope(const void* x, void* q4, void* scale, const void* cos_sin, const void* pos,
+                                long tokens, long heads, long max_pos, int interleaved, int head_dim,
+                                void* stream);
+
+/* qattn_mxfp4_paged_append_packed with the new keys rotated first (pos[t]: the position of packed token t);
+ * V, vtail and the lengths are that entry's.  Returns 1 as that entry does and as the entry above does for
+ * cos_sin, pos, max_pos and interleaved. */
+int qattn_mxfp4_paged_append_packed_rope(const void* k, const void* v, const void* k_mean, void* k4,
+                                         void* kscale, void* vt, void* vscale, void* vtail, void* lens,
+                                         const void* block_table, const void* seq_tab, const void* tiles,
+                                         long nseq, long ntiles, long tokens, long max_seqs, long kv_heads,
+                                         long num_pages, long page_tokens, long max_pages_per_seq,
+                                         int head_dim, const void* cos_sin, const void* pos, long max_pos,
+                                         int interleaved, void* stream);
 
 /* Merge of the splits, per row of rows_total = bhv*rows: M = max_s m_s, w_s = 2^(m_s - M) (exact; 0
  * for m_s = -inf), L = sum_s w_s l_s, out f16 [rows_total, 128] = (sum_s w_s O_s) * (1 / L), lse f32

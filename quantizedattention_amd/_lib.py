@@ -102,6 +102,8 @@ SIGNATURES = {
     "qattn_mxfp4_paged_rollback": [_vp] * 7 + [_c_long] * 7 + [_c_int, _vp],
     "qattn_mxfp4_varlen_combine": [_vp] * 5 + [_c_long] * 5 + [_c_int, _vp],
     "qattn_mxfp4_paged_append_packed": [_vp] * 12 + [_c_long] * 8 + [_c_int, _vp],
+    "qattn_mxfp4_quant_rows_rope": [_vp] * 5 + [_c_long] * 3 + [_c_int, _c_int, _vp],
+    "qattn_mxfp4_paged_append_packed_rope": [_vp] * 12 + [_c_long] * 8 + [_c_int, _vp, _vp, _c_long, _c_int, _vp],
     "qattn_split_keys": [_c_long, _c_long, _c_long, _c_int],
     "qattn_int8_bwd_plan": [_c_long, _c_int, _c_long, _c_long, _c_int, _c_long, _c_long, _vp],
     "qattn_bf16_bwd_plan": [_c_long, _c_long, _c_long, _c_int, _c_int, _c_long],
@@ -129,7 +131,7 @@ RESTYPES = {"qattn_abi_version": ctypes.c_int, "qattn_source_hash": ctypes.c_cha
             "qattn_int8_bwd_plan": ctypes.c_long, "qattn_bf16_bwd_plan": ctypes.c_long}
 
 # include/qattn.h QATTN_ABI_VERSION: the argument lists SIGNATURES describes
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 _lib = None
 _dev = None

@@ -21,12 +21,14 @@ outputs carry no autograd graph.
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
+
 import torch
 
 from . import _lib
 
 __all__ = ["mxfp4_quantize_rows", "mxfp4_quantize_v", "mxfp4_attn_fwd", "mxfp4_attn_fwd_kv",
-           "sage_attention_3_fp4"]
+           "sage_attention_3_fp4", "Rope", "rope_table", "mxfp4_quantize_rows_rope"]
 
 
 _qk_scale = _lib.qk_scale
@@ -52,6 +54,98 @@ def mxfp4_quantize_rows(x: torch.Tensor, mean: torch.Tensor | None = None):
     sc = torch.empty((rows, D // 32), dtype=torch.uint8, device=x.device)
     _lib.call("qattn_mxfp4_quant_rows", _lib.ptr(x), _lib.ptr(mean) if mean is not None else None,
               _lib.ptr(q4), _lib.ptr(sc), rows, seq, D, _lib.stream_of(x))
+    return q4, sc
+
+
+ROPE_DIM = 128   # the head_dim of every rotary entry
+
+
+@dataclass(frozen=True)
+class Rope:
+    """A rotary table for the ``rope=`` arguments of the packed MX-FP4 cache path.
+
+    ``table`` fp32 [max_pos, 128], contiguous, on the GPU: row p holds cos theta(p, i) in column i and
+    sin theta(p, i) in column 64 + i for pair i in [0, 64) (the ``cos_sin_cache`` convention, so a table
+    scaled by YaRN, llama3 or NTK is passed as it is; :func:`rope_table` makes the plain one).
+    ``interleaved=False`` (NeoX, rotate half) pairs elements (i, i + 64) of a head's row, ``True`` (GPT-J)
+    elements (2i, 2i + 1).  The rotation itself is defined bit for bit (include/qattn.h): per pair (a, b),
+    ``f16(f32(a c) - f32(b s))`` and ``f16(f32(b c) + f32(a s))``, what ``(a.float() * c - b.float() *
+    s).half()`` gives in torch."""
+
+    table: torch.Tensor
+    interleaved: bool = False
+
+    def __post_init__(self):
+        t = self.table
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2
+                or t.shape[1] != ROPE_DIM or t.shape[0] < 1 or not t.is_contiguous()):
+            raise _lib.QAttnError("qattn mxfp4 rope: the table must be a contiguous fp32 tensor [max_pos >= 1, 128] "
+                                  "(cos in columns [0, 64), sin in [64, 128))")
+        _lib.require_gpu(t)
+        if not isinstance(self.interleaved, bool):
+            raise _lib.QAttnError(f"qattn mxfp4 rope: interleaved must be a bool, got {self.interleaved!r}")
+
+    @property
+    def max_pos(self) -> int:
+        return self.table.shape[0]
+
+
+def rope_table(max_pos: int, base: float = 10000.0, device=None) -> torch.Tensor:
+    """The plain rotary table fp32 [max_pos, 128] of :class:`Rope`: the angles ``p * base ** (-2 i / 128)``
+    are computed in float64 on the host, their cos (columns [0, 64)) and sin (columns [64, 128)) rounded
+    once to fp32, then moved to ``device`` (None: left on the host)."""
+    if int(max_pos) < 1 or not base > 0:
+        raise _lib.QAttnError(f"qattn mxfp4 rope: max_pos >= 1 and base > 0 expected, got {max_pos}, {base}")
+    i = torch.arange(ROPE_DIM // 2, dtype=torch.float64)
+    inv_freq = torch.pow(torch.tensor(float(base), dtype=torch.float64), -2.0 * i / ROPE_DIM)
+    ang = torch.arange(int(max_pos), dtype=torch.float64)[:, None] * inv_freq[None, :]
+    table = torch.cat([ang.cos(), ang.sin()], 1).to(torch.float32).contiguous()
+    return table if device is None else table.to(device)
+
+
+def _host_positions(positions, tokens: int, max_pos: int) -> torch.Tensor:
+    """Host ``positions`` (a list or a host tensor) of a rotary call as a host int32 tensor of ``tokens``
+    values in [0, max_pos); raises :class:`QAttnError` otherwise.  No device."""
+    pos = torch.as_tensor(positions, dtype=torch.int64).reshape(-1)
+    if pos.numel() != tokens:
+        raise _lib.QAttnError(f"qattn mxfp4 rope: {pos.numel()} positions for {tokens} packed tokens")
+    if tokens and (int(pos.min()) < 0 or int(pos.max()) >= max_pos):
+        bad = pos[(pos < 0) | (pos >= max_pos)][:8].tolist()
+        raise _lib.QAttnError(f"qattn mxfp4 rope: positions {bad} outside the table's [0, {max_pos})")
+    return pos.to(torch.int32)
+
+
+def _device_positions(positions, tokens: int) -> bool:
+    """Whether ``positions`` is a device tensor, which is then held to int32 [tokens], contiguous; it is
+    used as given and never read back (the kernels clamp it to the table)."""
+    if not (isinstance(positions, torch.Tensor) and positions.is_cuda):
+        return False
+    if positions.dtype != torch.int32 or tuple(positions.shape) != (tokens,) or not positions.is_contiguous():
+        raise _lib.QAttnError(f"qattn mxfp4 rope: device positions must be a contiguous int32 tensor [{tokens}]")
+    return True
+
+
+def mxfp4_quantize_rows_rope(x: torch.Tensor, rope: Rope, positions):
+    """Packed x [T, H, 128] (fp16, token-major), each row rotated by its token's position first (:class:`Rope`)
+    -> (packed uint8 [T*H, 64], scales uint8 [T*H, 4]), bit for bit ``mxfp4_quantize_rows`` of the rotated
+    fp16 rows.  ``positions``: T ints in [0, rope.max_pos) as a list or a host tensor (checked, uploaded
+    without a synchronisation), or a device int32 tensor [T], used as given."""
+    if not isinstance(rope, Rope):
+        raise _lib.QAttnError("qattn mxfp4 rope: rope must be a Rope")
+    if x.dim() != 3 or x.shape[2] != ROPE_DIM:
+        raise _lib.QAttnError("qattn mxfp4 rope: packed rows must be x [T, H, 128]")
+    T, H, D = x.shape
+    if T * H >= 1 << 31:
+        raise _lib.QAttnError("qattn mxfp4 rope: fewer than 2^31 packed rows expected")
+    if not _device_positions(positions, T):
+        positions = _host_positions(positions, T, rope.max_pos)
+    _lib.require_gpu(x, rope.table)
+    x = _lib.kernel_input(x, torch.float16)
+    pos = _lib.kernel_input(positions.to(x.device, non_blocking=True))
+    q4 = torch.empty((T * H, D // 2), dtype=torch.uint8, device=x.device)
+    sc = torch.empty((T * H, D // 32), dtype=torch.uint8, device=x.device)
+    _lib.call("qattn_mxfp4_quant_rows_rope", _lib.ptr(x), _lib.ptr(q4), _lib.ptr(sc), _lib.ptr(rope.table),
+              _lib.ptr(pos), T, H, rope.max_pos, int(rope.interleaved), D, _lib.stream_of(x))
     return q4, sc
 
 

@@ -43,8 +43,10 @@
 // (the bodies of the padded, paged and packed append kernels, which differ in how a thread finds its
 // sequence, head and source row); and on the host MxSplitCall + mx_split_launch (every key-split entry:
 // its own argument checks, the call filled in, a dispatch on `causal`), mx_varlen_call (the checks and the
-// call of the three packed entries without groups), mx_varlen_paged (the plain and the windowed one) and
-// mx_append (the padded and the paged append).  The two rings, MxRing and MxPagedRing, keep a piece plan each: holding one in common changed the paged kernels' instruction streams.  The C entries
+// call of the three packed entries without groups), mx_varlen_paged (the plain and the windowed one),
+// mx_append (the padded and the paged append) and mx_append_packed (the packed append with and without rotary
+// positions; mx_rope_block, the rotation both rope kernels put in front of the one quantiser body, is
+// restated by tests/mxfp4_rope_ref.py and held bit for bit by tests/test_gpu_mxfp4_rope.py).  The two rings, MxRing and MxPagedRing, keep a piece plan each: holding one in common changed the paged kernels' instruction streams.  The C entries
 // stand in the order in which they first use their kernels, which is the order the kernels are emitted
 // in; tools/asm_compare.py compares branch labels too, and those carry the function's number.
 #include "common.h"
@@ -1188,6 +1190,110 @@ __global__ __launch_bounds__(256) void mx_append_len_packed_kernel(int* __restri
   if (cnt) lens[slot] = L + cnt;
 }
 
+// ---- rotary positions (kv_cache_mxfp4.py Rope): q on quantise, new keys on the packed append
+// cos_sin f32 [max_pos][D]: row p holds cos theta(p, i) at [i] and sin theta(p, i) at [D/2 + i], pair i <
+// D/2.  NeoX (IL false) pairs elements (i, i + D/2), interleaved (IL true) elements (2i, 2i + 1).  A pair
+// (a, b) of f16 inputs becomes first = f16(f32(a c) - f32(b s)), second = f16(f32(b c) + f32(a s)): two
+// rounded fp32 products, one rounded fp32 sum, one round-to-nearest-even to f16 and NO fused multiply-add,
+// which is what separate fp32 tensor operations give (tests/mxfp4_rope_ref.py), so the rotated row is
+// defined bit for bit and the quantisers take it unchanged.  The position is clamped to [0, max_pos): a
+// wrong position gives a wrong answer, never an address outside the table.
+
+// Block blk of the rotated row: row's own block and, NeoX, its partner blk ^ (D/64) -> out[4].
+template <int D, bool IL>
+QA_DEVICE void mx_rope_block(const _Float16* row, const float* cs, int blk, v8h* out) {
+#pragma clang fp contract(off)
+  constexpr int HALF = D / 2;
+  const v8h* own = reinterpret_cast<const v8h*>(row + blk * 32);
+  if constexpr (IL) {
+    const v4f* co = reinterpret_cast<const v4f*>(cs + blk * 16);
+    const v4f* si = reinterpret_cast<const v4f*>(cs + HALF + blk * 16);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const v8h v = own[c];
+      const v4f cc = co[c], ss = si[c];
+      v8h r;
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+        const float a = (float)v[2 * m], b = (float)v[2 * m + 1];
+        const float ac = a * cc[m], bs = b * ss[m], bc = b * cc[m], as = a * ss[m];
+        r[2 * m] = (_Float16)(ac - bs);
+        r[2 * m + 1] = (_Float16)(bc + as);
+      }
+      out[c] = r;
+    }
+  } else {
+    const bool second = blk * 32 >= HALF;             // the block holds the pairs' second elements
+    const int pb = blk * 32 - (second ? HALF : 0);    // its first pair
+    const v8h* par = reinterpret_cast<const v8h*>(row + (second ? pb : pb + HALF));
+    const v4f* co = reinterpret_cast<const v4f*>(cs + pb);
+    const v4f* si = reinterpret_cast<const v4f*>(cs + HALF + pb);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const v8h v = own[c], w = par[c];
+      v8h r;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const v4f cc = co[2 * c + h], ss = si[2 * c + h];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {   // own c - partner s for a first element, own c + partner s for a second
+          const float oc = (float)v[4 * h + m] * cc[m], ps = (float)w[4 * h + m] * ss[m];
+          r[4 * h + m] = (_Float16)(second ? oc + ps : oc - ps);
+        }
+      }
+      out[c] = r;
+    }
+  }
+}
+
+// Q: mx_quant_rows_kernel without a mean on packed rows x f16 [T][H][D], rotated first by pos[token]; one
+// thread per 32-element block, the heads of a token adjacent (they read the same table row).
+template <int D, bool IL>
+__global__ __launch_bounds__(256) void mx_quant_rows_rope_kernel(const _Float16* __restrict__ x,
+                                                                 uint8_t* __restrict__ q4,
+                                                                 uint8_t* __restrict__ sc,
+                                                                 const float* __restrict__ cos_sin,
+                                                                 const int* __restrict__ pos, long nblk, int H,
+                                                                 int max_pos) {
+  constexpr int NB = D / 32;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nblk) return;
+  const long row = i / NB;
+  const int p = min(max(pos[row / H], 0), max_pos - 1);
+  v8h r[4];
+  mx_rope_block<D, IL>(x + row * D, cos_sin + (long)p * D, (int)(i % NB), r);
+  mx_quant_row_block(r, nullptr, reinterpret_cast<v4i*>(q4) + i, sc + i);
+}
+
+// K and vtail: mx_append_k_packed_kernel with the K block rotated first by pos[packed token]; V is not rotated.
+template <int D, bool IL>
+__global__ __launch_bounds__(256) void mx_append_k_packed_rope_kernel(
+    const _Float16* __restrict__ k, const _Float16* __restrict__ v, const _Float16* __restrict__ mean,
+    uint8_t* __restrict__ k4, uint8_t* __restrict__ ks, _Float16* __restrict__ vtail,
+    const int* __restrict__ lens, const int* __restrict__ tab, long nblk, int nseq, int B, int Hkv, long T,
+    int cap, const int* __restrict__ btab, int mpp, int lgt, int npool, const float* __restrict__ cos_sin,
+    const int* __restrict__ pos, int max_pos) {
+  constexpr int NB = D / 32;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nblk) return;
+  const int blk = (int)(i % NB);
+  const int hd = (int)(i / NB % Hkv);
+  const int token = (int)(i / NB / Hkv);
+  int slot, first, L;
+  const int cnt = mx_packed_count(tab, lens, mx_find_seq(tab, nseq, 4, 2, token), B, T, cap, slot, first, L);
+  const int tok = token - first;
+  if (tok < 0 || tok >= cnt) return;   // t < L + cnt <= cap
+  const int t = L + tok;
+  const long bh = (long)slot * Hkv + hd;
+  const v8h* mu = mean ? reinterpret_cast<const v8h*>(mean + bh * D + blk * 32) : nullptr;
+  const long o = (mx_paged_tile(btab, slot, hd, t / 64, Hkv, mpp, lgt, npool) * 64 + t % 64) * NB + blk;
+  const int p = min(max(pos[token], 0), max_pos - 1);
+  v8h r[4];
+  mx_rope_block<D, IL>(k + (i / NB) * D, cos_sin + (long)p * D, blk, r);
+  mx_append_k_block(reinterpret_cast<const _Float16*>(r), v + i * 32, mu, k4, ks, o,
+                    vtail + (bh * 64 + t % 64) * D + blk * 32, t, L + cnt);
+}
+
 }  // namespace qattn
 
 using namespace qattn;
@@ -1544,16 +1650,23 @@ extern "C" int qattn_mxfp4_varlen_combine(const void* opart, const void* ml, voi
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
+// what the rotary entries hold their table to ("rotary positions" above)
+static bool mx_rope_ok(const void* cos_sin, const void* pos, long max_pos, int interleaved) {
+  return cos_sin && pos && max_pos >= 1 && max_pos <= 0x7fffffffL && (interleaved == 0 || interleaved == 1);
+}
+
 // a packed append into the paged pool ("packed append" above): seq_tab i32 [nseq][4] and tiles i32
-// [ntiles][2] on the device, the pages the new tokens need in block_table already
-extern "C" int qattn_mxfp4_paged_append_packed(const void* k, const void* v, const void* k_mean, void* k4,
-                                               void* kscale, void* vt, void* vscale, void* vtail,
-                                               void* lens, const void* block_table, const void* seq_tab,
-                                               const void* tiles, long nseq, long ntiles, long tokens,
-                                               long max_seqs, long kv_heads, long num_pages,
-                                               long page_tokens, long max_pages_per_seq, int head_dim,
-                                               void* stream) {
+// [ntiles][2] on the device, the pages the new tokens need in block_table already.  ROPE: the keys are
+// rotated first (interleaved picks the pairing), V and the lengths as without.
+template <bool ROPE>
+static int mx_append_packed(const void* k, const void* v, const void* k_mean, void* k4, void* kscale, void* vt,
+                            void* vscale, void* vtail, void* lens, const void* block_table,
+                            const void* seq_tab, const void* tiles, long nseq, long ntiles, long tokens,
+                            long max_seqs, long kv_heads, long num_pages, long page_tokens,
+                            long max_pages_per_seq, int head_dim, const void* cos_sin, const void* pos,
+                            long max_pos, int interleaved, void* stream) {
   if (head_dim != 128 || nseq < 0 || ntiles < 0 || tokens < 0 || max_seqs < 1) return 1;
+  if (ROPE && !mx_rope_ok(cos_sin, pos, max_pos, interleaved)) return 1;
   if (!k || !v || !k4 || !kscale || !vt || !vscale || !vtail || !lens || !block_table || !seq_tab || !tiles)
     return 1;
   const int lgt = mx_page_lgt(page_tokens);
@@ -1570,14 +1683,36 @@ extern "C" int qattn_mxfp4_paged_append_packed(const void* k, const void* v, con
                      (const int*)lens, (const int*)seq_tab, (const int*)tiles, nthr, (int)nseq, (int)max_seqs,
                      (int)kv_heads, tokens, (int)cap, (const int*)block_table, (int)max_pages_per_seq, lgt,
                      (int)num_pages);
-  hipLaunchKernelGGL(mx_append_k_packed_kernel<128>, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st,
-                     (const _Float16*)k, (const _Float16*)v, (const _Float16*)k_mean, (uint8_t*)k4,
-                     (uint8_t*)kscale, (_Float16*)vtail, (const int*)lens, (const int*)seq_tab, nblk,
-                     (int)nseq, (int)max_seqs, (int)kv_heads, tokens, (int)cap, (const int*)block_table,
-                     (int)max_pages_per_seq, lgt, (int)num_pages);
+  const dim3 kgrid((unsigned)((nblk + 255) / 256));
+  if constexpr (ROPE) {
+    auto kern = interleaved ? mx_append_k_packed_rope_kernel<128, true> : mx_append_k_packed_rope_kernel<128, false>;
+    hipLaunchKernelGGL(kern, kgrid, dim3(256), 0, st, (const _Float16*)k, (const _Float16*)v,
+                       (const _Float16*)k_mean, (uint8_t*)k4, (uint8_t*)kscale, (_Float16*)vtail,
+                       (const int*)lens, (const int*)seq_tab, nblk, (int)nseq, (int)max_seqs, (int)kv_heads,
+                       tokens, (int)cap, (const int*)block_table, (int)max_pages_per_seq, lgt, (int)num_pages,
+                       (const float*)cos_sin, (const int*)pos, (int)max_pos);
+  } else {
+    hipLaunchKernelGGL(mx_append_k_packed_kernel<128>, kgrid, dim3(256), 0, st,
+                       (const _Float16*)k, (const _Float16*)v, (const _Float16*)k_mean, (uint8_t*)k4,
+                       (uint8_t*)kscale, (_Float16*)vtail, (const int*)lens, (const int*)seq_tab, nblk,
+                       (int)nseq, (int)max_seqs, (int)kv_heads, tokens, (int)cap, (const int*)block_table,
+                       (int)max_pages_per_seq, lgt, (int)num_pages);
+  }
   hipLaunchKernelGGL(mx_append_len_packed_kernel, dim3((unsigned)((nseq + 255) / 256)), dim3(256), 0, st,
                      (int*)lens, (const int*)seq_tab, (int)nseq, (int)max_seqs, tokens, (int)cap);
   return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+extern "C" int qattn_mxfp4_paged_append_packed(const void* k, const void* v, const void* k_mean, void* k4,
+                                               void* kscale, void* vt, void* vscale, void* vtail,
+                                               void* lens, const void* block_table, const void* seq_tab,
+                                               const void* tiles, long nseq, long ntiles, long tokens,
+                                               long max_seqs, long kv_heads, long num_pages,
+                                               long page_tokens, long max_pages_per_seq, int head_dim,
+                                               void* stream) {
+  return mx_append_packed<false>(k, v, k_mean, k4, kscale, vt, vscale, vtail, lens, block_table, seq_tab, tiles,
+                                 nseq, ntiles, tokens, max_seqs, kv_heads, num_pages, page_tokens,
+                                 max_pages_per_seq, head_dim, nullptr, nullptr, 0, 0, stream);
 }
 
 extern "C" int qattn_mxfp4_split_combine(const void* opart, const void* ml, void* out, void* lse,
@@ -1709,4 +1844,32 @@ extern "C" int qattn_mxfp4_paged_rollback(const void* saved, void* vtail, void* 
                      (int)kv_heads, (int)(max_pages_per_seq * page_tokens), (const int*)block_table,
                      (int)max_pages_per_seq, lgt, (int)num_pages);
   return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// ------------------------------------------------------------------------------ rotary positions
+// ("rotary positions" above) q quantised for the packed step with its rotation, and the packed append that
+// rotates the new keys
+extern "C" int qattn_mxfp4_quant_rows_rope(const void* x, void* q4, void* scale, const void* cos_sin,
+                                           const void* pos, long tokens, long heads, long max_pos,
+                                           int interleaved, int head_dim, void* stream) {
+  if (head_dim != 128 || tokens < 0 || heads < 0 || !mx_rope_ok(cos_sin, pos, max_pos, interleaved)) return 1;
+  if (tokens == 0 || heads == 0) return 0;
+  if (!x || !q4 || !scale || tokens > 0x7fffffffL / heads) return 1;
+  const long nblk = tokens * heads * (128 / 32);
+  auto kern = interleaved ? mx_quant_rows_rope_kernel<128, true> : mx_quant_rows_rope_kernel<128, false>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const _Float16*)x, (uint8_t*)q4, (uint8_t*)scale, (const float*)cos_sin, (const int*)pos,
+                     nblk, (int)heads, (int)max_pos);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+extern "C" int qattn_mxfp4_paged_append_packed_rope(
+    const void* k, const void* v, const void* k_mean, void* k4, void* kscale, void* vt, void* vscale,
+    void* vtail, void* lens, const void* block_table, const void* seq_tab, const void* tiles, long nseq,
+    long ntiles, long tokens, long max_seqs, long kv_heads, long num_pages, long page_tokens,
+    long max_pages_per_seq, int head_dim, const void* cos_sin, const void* pos, long max_pos, int interleaved,
+    void* stream) {
+  return mx_append_packed<true>(k, v, k_mean, k4, kscale, vt, vscale, vtail, lens, block_table, seq_tab, tiles,
+                                nseq, ntiles, tokens, max_seqs, kv_heads, num_pages, page_tokens,
+                                max_pages_per_seq, head_dim, cos_sin, pos, max_pos, interleaved, stream);
 }

@@ -38,6 +38,11 @@
 //   mxfp4_varlen_paged_shared(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, grp_rec, members,
 //                             part_rows, causal, keys_per_split) -> (O, lse)
 //       the same with shared prefixes: the four tables of kv_cache_mxfp4.plan_varlen_shared
+//   mxfp4_quant_rows_rope(x, cos_sin, pos, interleaved) -> (q4, qs)
+//       attention_mxfp4.mxfp4_quantize_rows_rope: packed x [T, H, 128] rotated by pos i32 [T] through the
+//       table cos_sin f32 [max_pos, 128], then quantised
+//   mxfp4_varlen_paged_rope(.. the arguments of mxfp4_varlen_paged .., cos_sin, pos, interleaved) -> (O, lse)
+//       the same with q rotated inside its quantiser (attention_mxfp4_varlen_paged(rope=))
 // Workspaces, head chunks and key splits are planned by the library (csrc/plan.hip), as in the drop-ins.
 // Errors: TORCH_CHECK (c10::Error, RuntimeError in Python) with the drop-ins' messages; int8_quant's
 // argument checks raise ValueError (TORCH_CHECK_VALUE) as its Python predecessor did.
@@ -564,6 +569,39 @@ std::tuple<Tensor, Tensor> mxfp4_decode_paged(const Tensor& q_in, const Tensor& 
       });
 }
 
+// The rotary arguments of an operator (attention_mxfp4.Rope and device positions), checked
+struct RopeArgs {
+  const Tensor& cos_sin;
+  const Tensor& pos;
+  bool interleaved;
+};
+void check_rope(const RopeArgs& r, int64_t tokens) {
+  require_gpu({&r.cos_sin, &r.pos});
+  TORCH_CHECK(r.cos_sin.scalar_type() == at::kFloat && r.cos_sin.is_contiguous() && r.cos_sin.dim() == 2 &&
+                  r.cos_sin.size(1) == 128 && r.cos_sin.size(0) >= 1,
+              "qattn mxfp4 rope: the table must be a contiguous fp32 tensor [max_pos >= 1, 128]");
+  TORCH_CHECK(r.pos.scalar_type() == at::kInt && r.pos.is_contiguous() && r.pos.dim() == 1 &&
+                  r.pos.size(0) == tokens,
+              "qattn mxfp4 rope: positions must be a contiguous int32 tensor [T], one per packed token");
+}
+
+// attention_mxfp4.mxfp4_quantize_rows_rope: packed x [T, H, 128], each row rotated by pos[token] first
+std::tuple<Tensor, Tensor> mxfp4_quant_rows_rope(const Tensor& x_in, const Tensor& cos_sin, const Tensor& pos,
+                                                 bool interleaved) {
+  require_gpu({&x_in});
+  TORCH_CHECK(x_in.dim() == 3 && x_in.size(2) == 128, "qattn mxfp4 rope: packed rows must be x [T, H, 128]");
+  const int64_t T = x_in.size(0), H = x_in.size(1), D = 128;
+  const RopeArgs rope{cos_sin, pos, interleaved};
+  check_rope(rope, T);
+  Ctx c(x_in);
+  const Tensor x = kin(x_in, at::kHalf), p = kin(pos);
+  Tensor q4 = empty({T * H, D / 2}, at::kByte, x), qs = empty({T * H, D / 32}, at::kByte, x);
+  call(qattn_mxfp4_quant_rows_rope(P(x), P(q4), P(qs), P(cos_sin), P(p), T, H, cos_sin.size(0), interleaved,
+                                   (int)D, c.stream),
+       "quantise rotated rows");
+  return {q4, qs};
+}
+
 // kv_cache_mxfp4.attention_mxfp4_varlen_paged on a page pool's operands: packed q [T, Hq, 128], lens i32
 // [B] and block_table i32 [B, max_pages_per_seq] on the device, and the two tables of
 // kv_cache_mxfp4.plan_varlen as device tensors, seq_rec i32 [nseq, 8] and work i32 [nwork, 4], with the
@@ -571,7 +609,7 @@ std::tuple<Tensor, Tensor> mxfp4_decode_paged(const Tensor& q_in, const Tensor& 
 // the caller guarantees that they are a plan of the pool's lengths (the Python wrapper
 // ops.mxfp4_varlen_paged builds them from the cache's host mirror); the kernels keep every address a
 // wrong table names inside the buffers.  With `windowed` the plan is plan_varlen's for (window, sinks) and
-// the forward is qattn_mxfp4_attn_fwd_varlen_paged_window.
+// the forward is qattn_mxfp4_attn_fwd_varlen_paged_window.  With `rope` q is rotated inside its quantiser.
 std::tuple<Tensor, Tensor> mxfp4_varlen_paged_run(const Tensor& q_in, const Tensor& k4, const Tensor& ks,
                                                   const Tensor& vt, const Tensor& vs, const Tensor& lens,
                                                   const Tensor& block_table, const Tensor& seq_rec,
@@ -579,8 +617,10 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged_run(const Tensor& q_in, const Tens
                                                   int64_t keys_per_split, bool windowed, int64_t window,
                                                   int64_t sinks, const Tensor* grp_rec = nullptr,
                                                   const Tensor* members = nullptr,
-                                                  const Tensor* tree = nullptr) {
+                                                  const Tensor* tree = nullptr,
+                                                  const RopeArgs* rope = nullptr) {
   require_gpu({&q_in, &k4, &ks, &vt, &vs, &lens, &block_table, &seq_rec, &work});
+  if (rope) check_rope(*rope, q_in.dim() == 3 ? q_in.size(0) : -1);
   if (tree) {   // the tree entry's ancestor words, one per packed token
     require_gpu({tree});
     TORCH_CHECK(tree->scalar_type() == at::kLong && tree->is_contiguous() && tree->dim() == 1 &&
@@ -625,7 +665,14 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged_run(const Tensor& q_in, const Tens
   const Tensor q = kin(q_in, at::kHalf);
   Tensor q4 = empty({T * Hq, D / 2}, at::kByte, q), qs = empty({T * Hq, D / 32}, at::kByte, q);
   Tensor out = empty({T, Hq, D}, at::kHalf, q), lse = empty({T, Hq}, at::kFloat, q);
-  call(qattn_mxfp4_quant_rows(P(q), nullptr, P(q4), P(qs), T * Hq, Hq, (int)D, c.stream), "quantise q");
+  if (rope) {
+    const Tensor p = kin(rope->pos);
+    call(qattn_mxfp4_quant_rows_rope(P(q), P(q4), P(qs), P(rope->cos_sin), P(p), T, Hq, rope->cos_sin.size(0),
+                                     rope->interleaved, (int)D, c.stream),
+         "quantise rotated q");
+  } else {
+    call(qattn_mxfp4_quant_rows(P(q), nullptr, P(q4), P(qs), T * Hq, Hq, (int)D, c.stream), "quantise q");
+  }
   Tensor opart = empty({part_rows, D}, at::kFloat, q), ml = empty({part_rows, 2}, at::kFloat, q);
   if (grp_rec)
     call(qattn_mxfp4_attn_fwd_varlen_paged_shared(
@@ -665,6 +712,19 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged(const Tensor& q, const Tensor& k4,
                                               int64_t keys_per_split) {
   return mxfp4_varlen_paged_run(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal,
                                 keys_per_split, false, 0, 0);
+}
+
+// the same with q rotated inside its quantiser (kv_cache_mxfp4.attention_mxfp4_varlen_paged(rope=)): cos_sin
+// f32 [max_pos, 128] and pos i32 [T] on the device
+std::tuple<Tensor, Tensor> mxfp4_varlen_paged_rope(const Tensor& q, const Tensor& k4, const Tensor& ks,
+                                                   const Tensor& vt, const Tensor& vs, const Tensor& lens,
+                                                   const Tensor& block_table, const Tensor& seq_rec,
+                                                   const Tensor& work, int64_t part_rows, int64_t causal,
+                                                   int64_t keys_per_split, const Tensor& cos_sin,
+                                                   const Tensor& pos, bool interleaved) {
+  const RopeArgs rope{cos_sin, pos, interleaved};
+  return mxfp4_varlen_paged_run(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal,
+                                keys_per_split, false, 0, 0, nullptr, nullptr, nullptr, &rope);
 }
 
 // the same with a sliding window and sinks (kv_cache_mxfp4.attention_mxfp4_varlen_paged(window=, sinks=)):
@@ -736,6 +796,10 @@ TORCH_LIBRARY(qattn, m) {
   m.def("mxfp4_varlen_paged_tree(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, "
         "Tensor block_table, Tensor seq_rec, Tensor work, Tensor tree_masks, int part_rows, int causal, "
         "int keys_per_split) -> (Tensor, Tensor)");
+  m.def("mxfp4_quant_rows_rope(Tensor x, Tensor cos_sin, Tensor pos, bool interleaved) -> (Tensor, Tensor)");
+  m.def("mxfp4_varlen_paged_rope(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, "
+        "Tensor block_table, Tensor seq_rec, Tensor work, int part_rows, int causal, int keys_per_split, "
+        "Tensor cos_sin, Tensor pos, bool interleaved) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
@@ -754,4 +818,6 @@ TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
   m.impl("mxfp4_varlen_paged_window", &mxfp4_varlen_paged_window);
   m.impl("mxfp4_varlen_paged_shared", &mxfp4_varlen_paged_shared);
   m.impl("mxfp4_varlen_paged_tree", &mxfp4_varlen_paged_tree);
+  m.impl("mxfp4_quant_rows_rope", &mxfp4_quant_rows_rope);
+  m.impl("mxfp4_varlen_paged_rope", &mxfp4_varlen_paged_rope);
 }

@@ -129,8 +129,8 @@ ancestors and itself (:func:`tree_ancestor_masks`); the queries before the tree 
 ``lse`` is over the visible keys, and a chain is the causal call bit for bit
 (``qattn_mxfp4_attn_fwd_varlen_paged_tree``; ``seq_rec[j][7]`` = nd_j, the words travel as one int64 [T]
 tensor behind the two tables, in their upload).  A draft token at tree depth d sits on a path whose
-accepted form lands at position L0 + d, whatever its index in the packed step: callers position-encode
-draft keys (and queries) by DEPTH, not by their place in the append.  Taking tokens back:
+accepted form lands at position L0 + d, whatever its index in the packed step: ``rope=`` (below) places
+draft keys and queries by depth itself.  Taking tokens back:
 :meth:`PagedKVFP4.checkpoint` notes the listed sequences' lengths and pages and copies their ``vtail``
 rows; :meth:`PagedKVFP4.rollback` restores those rows, quantises V tile L0 // 64 again from them (an
 append that crossed the tile boundary overwrote ``vtail``, and the tile holds the drafts' scales),
@@ -140,6 +140,19 @@ checkpoint -- rows [0, L0) of ``k4`` / ``ks``, tiles [0, ceil(L0 / 64)) of ``vt`
 rows [0, L0 % 64), ``lens``, the page lists below ceil(L0 / P) and the free-page count -- so every later
 ``append`` gives the bytes of a pool that never saw the drafts.  :meth:`PagedKVFP4.accept` is that
 followed by one ``append_packed`` of the surviving draft rows.
+
+Rotary positions (``rope=``, a :class:`Rope`: an fp32 table [max_pos, 128] of cos and sin and the pairing,
+NeoX or interleaved): the packed path rotates q and the new k inside its quantisers, which read every
+element once anyway, so no rotated fp16 copy is written.  :meth:`PagedKVFP4.append_packed` rotates the new
+keys (``qattn_mxfp4_paged_append_packed_rope``; V is never rotated), :func:`attention_mxfp4_varlen_paged`
+the queries (``qattn_mxfp4_quant_rows_rope``), :meth:`PagedKVFP4.accept` the kept rows at their final
+places.  The positions default to what the pool knows (:func:`rope_positions`): token i of an append to a
+sequence of length L sits at L + i, a draft tree's node at (its first node's position) + depth, a kept row
+of ``accept`` at L0, L0 + 1, ...; explicit ``positions`` (host, checked against the table; or a device
+int32 tensor, used as given and clamped by the kernel) override them.  The rotation is defined bit for bit
+-- per pair (a, b), ``f16(f32(a c) - f32(b s))`` and ``f16(f32(b c) + f32(a s))``, no fused multiply-add
+-- so every ``rope=`` call gives exactly the bytes of the same call on rows rotated that way in torch.
+Cached keys are never rotated again, and the padded entries take no ``rope``.
 
 Wire format (little-endian), the container of kv_cache.py with a magic of its own::
 
@@ -167,7 +180,8 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .attention_mxfp4 import _qk_scale, mxfp4_quantize_rows, mxfp4_quantize_v
+from .attention_mxfp4 import (Rope, _device_positions, _host_positions, _qk_scale, mxfp4_quantize_rows,
+                              mxfp4_quantize_rows_rope, mxfp4_quantize_v, rope_table)
 
 MAGIC = b"QATTNKF4"
 BLOCK = 64
@@ -177,7 +191,7 @@ _DTYPES = {"uint8": torch.uint8, "float16": torch.float16}
 __all__ = ["QuantizedKVFP4", "quantize_kv_fp4", "attention_mxfp4_cached", "PreallocatedKVFP4",
            "attention_mxfp4_decode", "PageAllocator", "PagedKVFP4", "attention_mxfp4_decode_paged",
            "plan_varlen", "plan_varlen_shared", "attention_mxfp4_varlen_paged", "tree_ancestor_masks",
-           "tree_path", "Checkpoint"]
+           "tree_path", "Checkpoint", "Rope", "rope_table", "rope_positions"]
 
 
 @dataclass
@@ -846,7 +860,8 @@ class PagedKVFP4:
         self.lengths = [L + c for L, c in zip(self.lengths, cnt)]
         return self
 
-    def append_packed(self, k: torch.Tensor, v: torch.Tensor, seq_ids, counts) -> "PagedKVFP4":
+    def append_packed(self, k: torch.Tensor, v: torch.Tensor, seq_ids, counts, rope: Optional[Rope] = None,
+                      positions=None, tree=None) -> "PagedKVFP4":
         """Append packed fp16 ``k, v`` [T, Hkv, D], token-major as a model produces them: the first
         ``counts[0]`` tokens go to sequence ``seq_ids[0]``, the next ``counts[1]`` to ``seq_ids[1]``,
         ... (distinct slots, every count >= 1, T = sum(counts)); the slots that are not listed are
@@ -854,13 +869,23 @@ class PagedKVFP4:
         raises before anything is launched or changed), the changed table is uploaded in stream
         order and ``qattn_mxfp4_paged_append_packed`` writes in place, over exactly the V tiles the
         appends touch (listed here from the host mirror).  No host synchronisation, nothing is read
-        back; returns ``self``."""
+        back; returns ``self``.
+
+        ``rope`` (a :class:`Rope`; None: no rotation, the bits of the call without these arguments) rotates
+        the new keys inside the K quantiser (``qattn_mxfp4_paged_append_packed_rope``; V is not rotated): ``k`` is the UNROTATED
+        key.  ``positions`` defaults to ``rope_positions(self.lengths, seq_ids, counts, tree)``: token i of
+        sequence j at L_j + i, and with ``tree`` (entries as in :func:`attention_mxfp4_varlen_paged`) a
+        draft node at its depth.  A list or a host tensor is checked against [0, rope.max_pos) -- the call
+        raises before any page is reserved -- and travels in the upload of the records; a device int32
+        tensor [T] is used as given, never read back, and clamped to the table by the kernel.
+        ``positions`` or ``tree`` without ``rope``, and ``positions`` together with ``tree``, raise."""
         _, H, _, D = self.shape
         ids, cnt = _packed_lists(self.alloc.max_seqs, seq_ids, counts, "counts")
         if (k.dim() != 3 or tuple(k.shape[1:]) != (H, D) or k.shape != v.shape or k.shape[0] != sum(cnt)):
             raise _lib.QAttnError("qattn mxfp4 paged cache: packed tokens must be k, v [sum(counts), Hkv, D]")
         if k.shape[0] * H >= 1 << 31:
             raise _lib.QAttnError("qattn mxfp4 paged cache: fewer than 2^31 packed rows expected")
+        pos = _rope_args(rope, positions, tree, k.shape[0], lambda: (self.lengths, ids, cnt, tree))
         _lib.require_gpu(k, v, self.k4)
         grown = self.alloc.reserve([(b, self.lengths[b] + c) for b, c in zip(ids, cnt)])
         k = _lib.kernel_input(k, torch.float16)
@@ -873,13 +898,24 @@ class PagedKVFP4:
             tab += [b, c, first, 0]
             tiles += [x for g in range(L // BLOCK, (L + c - 1) // BLOCK + 1) for x in (j, g)]
             first += c
-        # one upload: the records, then the tile list (the record block is a multiple of 16 bytes)
-        dev = torch.tensor(tab + tiles, dtype=torch.int32).to(k.device, non_blocking=True)
-        _lib.call("qattn_mxfp4_paged_append_packed", _lib.ptr(k), _lib.ptr(v), _lib.ptr(self.k_mean),
-                  _lib.ptr(self.k4), _lib.ptr(self.ks), _lib.ptr(self.vt), _lib.ptr(self.vs),
-                  _lib.ptr(self.vtail), _lib.ptr(self.lens), _lib.ptr(self.block_table), _lib.ptr(dev),
-                  _lib.ptr(dev[len(tab):]), len(ids), len(tiles) // 2, k.shape[0], self.alloc.max_seqs, H,
-                  self.num_pages, self.page_tokens, self.alloc.max_pages_per_seq, D, _lib.stream_of(k))
+        # one upload: the records, then the tile list (the record block is a multiple of 16 bytes), then,
+        # at the next multiple of 16 bytes, host positions
+        if pos is None or pos.is_cuda:
+            flat = torch.tensor(tab + tiles, dtype=torch.int32)
+        else:
+            flat = torch.cat([torch.tensor(tab + tiles + [0] * (-len(tiles) % 4), dtype=torch.int32), pos])
+        dev = flat.to(k.device, non_blocking=True)
+        args = (_lib.ptr(k), _lib.ptr(v), _lib.ptr(self.k_mean),
+                _lib.ptr(self.k4), _lib.ptr(self.ks), _lib.ptr(self.vt), _lib.ptr(self.vs),
+                _lib.ptr(self.vtail), _lib.ptr(self.lens), _lib.ptr(self.block_table), _lib.ptr(dev),
+                _lib.ptr(dev[len(tab):]), len(ids), len(tiles) // 2, k.shape[0], self.alloc.max_seqs, H,
+                self.num_pages, self.page_tokens, self.alloc.max_pages_per_seq, D)
+        if rope is None:
+            _lib.call("qattn_mxfp4_paged_append_packed", *args, _lib.stream_of(k))
+        else:
+            pos_d = _lib.kernel_input(pos) if pos.is_cuda else dev[len(dev) - k.shape[0]:]
+            _lib.call("qattn_mxfp4_paged_append_packed_rope", *args, _lib.ptr(rope.table), _lib.ptr(pos_d),
+                      rope.max_pos, int(rope.interleaved), _lib.stream_of(k))
         for b, c in zip(ids, cnt):
             self.lengths[b] += c
         return self
@@ -1019,7 +1055,8 @@ class PagedKVFP4:
                                   f"{a.free_pages} of {self.num_pages} free and {back} returned by the rollback: "
                                   "a fork made after the drafts still holds their pages)")
 
-    def accept(self, ckpt: "Checkpoint", k: torch.Tensor, v: torch.Tensor, seq_ids, counts, accepted) -> "PagedKVFP4":
+    def accept(self, ckpt: "Checkpoint", k: torch.Tensor, v: torch.Tensor, seq_ids, counts, accepted,
+               rope: Optional[Rope] = None) -> "PagedKVFP4":
         """:meth:`rollback` of ``seq_ids`` followed by one :meth:`append_packed` of the draft rows that
         survive.  ``k``, ``v``, ``seq_ids`` and ``counts`` are those of the draft step's ``append_packed``;
         ``accepted[j]`` lists distinct token indices into sequence j's ``counts[j]`` tokens, in the order
@@ -1028,8 +1065,15 @@ class PagedKVFP4:
         uploaded indices.  Every argument is checked before anything changes, the pages included: the
         kept tokens take the pages the rollback returns, and when a fork made after the drafts still
         holds those and the pool has no others, the call raises, naming "out of pages", before the
-        rollback.  Stream-ordered; returns ``self``."""
+        rollback.  Stream-ordered; returns ``self``.
+
+        ``rope`` goes to the inner ``append_packed`` with its default positions, so the kept rows of
+        sequence j are rotated to L0_j, L0_j + 1, ...: for a :func:`tree_path` exactly where their depths
+        put them in the draft step.  ``k`` is then the UNROTATED key of the draft step, the tensor that
+        step's ``append_packed(..., rope=)`` was given."""
         _, H, _, D = self.shape
+        if rope is not None and not isinstance(rope, Rope):
+            raise _lib.QAttnError("qattn mxfp4 rope: rope must be a Rope")
         ids, cnt = _packed_lists(self.alloc.max_seqs, seq_ids, counts, "counts")
         if (k.dim() != 3 or tuple(k.shape[1:]) != (H, D) or k.shape != v.shape or k.shape[0] != sum(cnt)):
             raise _lib.QAttnError("qattn mxfp4 paged cache: packed tokens must be k, v [sum(counts), Hkv, D]")
@@ -1048,7 +1092,7 @@ class PagedKVFP4:
             idx = torch.tensor(keep, dtype=torch.long).to(k.device, non_blocking=True)
             kept = [(b, len(a)) for b, a in zip(ids, acc) if a]
             self.append_packed(k.index_select(0, idx), v.index_select(0, idx), [b for b, _ in kept],
-                               [n for _, n in kept])
+                               [n for _, n in kept], rope=rope)
         return self
 
     def fork(self, src: int, dst: int) -> None:
@@ -1227,6 +1271,80 @@ def tree_path(parents, leaf: int) -> list:
         path.append(leaf)
         leaf = par[leaf]
     return path[::-1]
+
+
+ARANGE_TOKENS = 32   # a run of more default positions than this is a torch.arange, not a Python list
+
+
+def _default_positions(lengths_before, seq_ids, counts, tree=None):
+    """:func:`rope_positions` as (host int32 tensor [T], lowest value, highest value): long runs are ranges,
+    so a prefill chunk costs no Python per token."""
+    lengths = [int(x) for x in lengths_before]
+    ids, cnt = _packed_lists(len(lengths), seq_ids, counts, "counts")
+    trees = [None] * len(ids) if tree is None else list(tree)
+    if len(trees) != len(ids):
+        raise _lib.QAttnError(f"qattn mxfp4 paged cache: tree must have one entry (None or a parents list) per "
+                              f"listed sequence, got {len(trees)} for {len(ids)}")
+    parts, run, hi = [], [], -1
+
+    def flush():
+        if run:
+            parts.append(torch.tensor(run, dtype=torch.int32))
+            run.clear()
+
+    for b, c, p in zip(ids, cnt, trees):
+        depth = []
+        for q in ([] if p is None else _tree_parents(p)):
+            depth.append(depth[q] + 1 if q >= 0 else 0)
+        if len(depth) > c:
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: a tree of {len(depth)} nodes on a sequence of {c} "
+                                  "tokens")
+        L, plain = lengths[b], c - len(depth)
+        if plain > ARANGE_TOKENS:
+            flush()
+            parts.append(torch.arange(L, L + plain, dtype=torch.int32))
+        else:
+            run.extend(range(L, L + plain))
+        run.extend(L + plain + d for d in depth)
+        hi = max(hi, L + plain - 1, L + plain + max(depth, default=-1))
+    flush()
+    lo = min(lengths[b] for b in ids)
+    return (parts[0] if len(parts) == 1 else torch.cat(parts)), lo, hi
+
+
+def rope_positions(lengths_before, seq_ids, counts, tree=None) -> list:
+    """The default rotary positions of a packed step -> one int per packed token, from the host mirror
+    alone (no device).  ``lengths_before`` holds one length per slot BEFORE the step's append; token i of
+    the ``counts[j]`` tokens of slot ``seq_ids[j]`` gets L_j + i.  With ``tree`` (one entry per listed
+    sequence, None or a ``parents`` list of nd_j <= counts[j] nodes, as in
+    :func:`attention_mxfp4_varlen_paged`) the last nd_j tokens are draft nodes and get L_j + (counts[j] -
+    nd_j) + depth, a root at depth 0: where the node lands when its path is accepted.  Raises
+    :class:`QAttnError` as ``append_packed`` does for its lists and :func:`tree_ancestor_masks` for a tree,
+    and for a tree list of another length or a tree of more nodes than the sequence has tokens."""
+    return _default_positions(lengths_before, seq_ids, counts, tree)[0].tolist()
+
+
+def _rope_args(rope, positions, tree, tokens: int, default):
+    """The rotary arguments of a packed call, checked before anything is reserved or launched -> None
+    without ``rope``, else an int32 tensor [tokens]: the device tensor given as ``positions``, or host
+    positions inside the table (``positions``, else ``default()``, the arguments of
+    :func:`_default_positions`)."""
+    if rope is None:
+        if positions is not None or tree is not None:
+            raise _lib.QAttnError("qattn mxfp4 rope: positions or tree without rope (they place the rotation)")
+        return None
+    if not isinstance(rope, Rope):
+        raise _lib.QAttnError("qattn mxfp4 rope: rope must be a Rope")
+    if positions is None:
+        pos, lo, hi = _default_positions(*default())
+        if lo < 0 or hi >= rope.max_pos:
+            raise _lib.QAttnError(f"qattn mxfp4 rope: the default positions [{lo}, {hi}] lie outside the table's "
+                                  f"[0, {rope.max_pos})")
+        return pos
+    if tree is not None:
+        raise _lib.QAttnError("qattn mxfp4 rope: explicit positions together with tree (tree only places the "
+                              "default positions)")
+    return positions if _device_positions(positions, tokens) else _host_positions(positions, tokens, rope.max_pos)
 
 
 def plan_varlen(lengths, seq_ids, q_lens, Hq: int, Hkv: int, keys_per_split: Optional[int] = None,
@@ -1506,10 +1624,23 @@ def _tree_args(tree, sq, causal: bool, window, share_prefix: bool):
     return nds, torch.cat(parts).view(torch.int32)
 
 
+def _query_positions(cache: "PagedKVFP4", ids, sq, tree, rope, positions):
+    """``_rope_args`` of a packed attention call: the default positions are those of the append that made
+    the queries the sequences' last tokens (``tree`` is the call's mask, so explicit positions may come
+    with it)."""
+    def default():
+        before = list(cache.lengths)
+        for b, n in zip(ids, sq):
+            before[b] -= n
+        return before, ids, sq, tree
+    return _rope_args(rope, positions, None, sum(sq), default)
+
+
 @torch.no_grad()
 def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_lens, causal: bool = False,
                                  keys_per_split: Optional[int] = None, window: Optional[int] = None,
-                                 sinks: int = 0, share_prefix: bool = False, tree=None):
+                                 sinks: int = 0, share_prefix: bool = False, tree=None,
+                                 rope: Optional[Rope] = None, positions=None):
     """A ragged batch against a paged cache in one attention launch and one merge: packed fp16 queries
     ``q`` [T, Hq, D], token-major, the ``q_lens[0]`` tokens of sequence ``seq_ids[0]`` first, then
     those of ``seq_ids[1]``, ... (nseq >= 1 distinct slots, every q_lens[j] >= 1, T = sum(q_lens)) ->
@@ -1545,10 +1676,19 @@ def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_
     (``qattn_mxfp4_attn_fwd_varlen_paged_tree``; the words are uploaded with the two tables, in one
     upload).  A chain gives the causal call's bits, and with every entry None the plain causal call is
     made.  A draft token at tree depth d sits on a path whose accepted form lands at position L0 + d (L0
-    the length before the drafts): position-encode draft keys and queries by their depth, not by their
-    index in the packed step.  Raises before any launch, naming "tree": without ``causal``, together
+    the length before the drafts): ``rope=`` (below, and in :meth:`PagedKVFP4.append_packed`) places draft
+    keys and queries by depth.  Raises before any launch, naming "tree": without ``causal``, together
     with ``window`` or ``share_prefix=True``, for more nodes than min(q_lens[j], 64), and for a parent
-    that is not in [-1, t)."""
+    that is not in [-1, t).
+
+    ``rope`` (a :class:`Rope`; None: no rotation, the bits of the call without these arguments) rotates
+    ``q``, given UNROTATED, inside its quantiser (``qattn_mxfp4_quant_rows_rope`` in place of ``qattn_mxfp4_quant_rows``); everything after
+    that is unchanged, so ``window``, ``share_prefix`` and ``tree`` work with it.  ``positions`` defaults to
+    L_j - q_lens[j] + i for query i of sequence j, and under ``tree=`` the nodes are placed by depth: the
+    numbers :func:`rope_positions` gives for the ``append_packed`` that preceded this call (the queries
+    are the sequence's last q_lens[j] tokens).  Explicit ``positions`` are as in ``append_packed``: a list
+    or a host tensor, checked against the table before any launch, or a device int32 tensor [T], used as
+    given.  ``positions`` without ``rope`` raises."""
     if not isinstance(cache, PagedKVFP4):
         raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PagedKVFP4")
     _, Hkv, _, D = cache.shape
@@ -1569,6 +1709,7 @@ def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_
                                                     window, sinks, None if trees is None else trees[0])
     W, S = _window_args(window, sinks)
     _check_trimmed(cache, ids, sq, W, S)
+    pos = _query_positions(cache, ids, sq, tree, rope, positions)
     _lib.require_gpu(q, cache.k4)
     dev, st = q.device, _lib.stream_of(q)
     # from fresh pageable host tensors, as PagedKVFP4._upload: staged before the copies return
@@ -1585,7 +1726,7 @@ def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_
         rec_d = torch.tensor(flat, dtype=torch.int32).to(dev, non_blocking=True)
         work_d = rec_d[8 * len(seq_rec):]
         grp_d = work_d[4 * len(work):]
-    q4, qs = mxfp4_quantize_rows(q)
+    q4, qs = mxfp4_quantize_rows(q) if rope is None else mxfp4_quantize_rows_rope(q, rope, pos)
     O = torch.empty((T, Hq, D), dtype=torch.float16, device=dev)
     lse = torch.empty((T, Hq), dtype=torch.float32, device=dev)
     opart = torch.empty((part_rows, D), dtype=torch.float32, device=dev)

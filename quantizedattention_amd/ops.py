@@ -28,6 +28,9 @@ the autograd rules of ``int8_fwd`` and ``bf16_fwd`` (their backward operators).
                                               members, part_rows, causal, keys_per_split) -> (O, lse)
     torch.ops.qattn.mxfp4_varlen_paged_tree(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, tree_masks,
                                             part_rows, causal, keys_per_split) -> (O, lse)
+    torch.ops.qattn.mxfp4_quant_rows_rope(x, cos_sin, pos, interleaved) -> (q4, qs)
+    torch.ops.qattn.mxfp4_varlen_paged_rope(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows,
+                                            causal, keys_per_split, cos_sin, pos, interleaved) -> (O, lse)
 
 Shapes follow the drop-in functions (attention_int8.py:259-262 for the int8 outputs) except that
 k_i8 is returned row-major [B*Hkv*Sk, D] (the drop-in's k_i8T is its transposed view: an operator
@@ -44,7 +47,8 @@ import torch
 from . import _lib
 
 __all__ = ["int8_quant", "int8_fwd", "int8_bwd", "bf16_fwd", "bf16_bwd", "jvp_fwd", "mxfp4_fwd",
-           "mxfp4_fwd_ex", "mxfp4_cached", "mxfp4_decode", "mxfp4_decode_paged", "mxfp4_varlen_paged"]
+           "mxfp4_fwd_ex", "mxfp4_cached", "mxfp4_decode", "mxfp4_decode_paged", "mxfp4_varlen_paged",
+           "mxfp4_quant_rows_rope"]
 
 _lib.load_ops()
 _ops = torch.ops.qattn
@@ -148,6 +152,19 @@ def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, grp_rec, members, par
 
 @torch.library.register_fake("qattn::mxfp4_varlen_paged_tree")
 def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, tree_masks, part_rows, causal, keys_per_split):
+    T, H, D = q.shape
+    return (q.new_empty((T, H, D), dtype=torch.float16), q.new_empty((T, H), dtype=torch.float32))
+
+
+@torch.library.register_fake("qattn::mxfp4_quant_rows_rope")
+def _(x, cos_sin, pos, interleaved):
+    T, H, D = x.shape
+    return (x.new_empty((T * H, D // 2), dtype=torch.uint8), x.new_empty((T * H, D // 32), dtype=torch.uint8))
+
+
+@torch.library.register_fake("qattn::mxfp4_varlen_paged_rope")
+def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal, keys_per_split, cos_sin, pos,
+      interleaved):
     T, H, D = q.shape
     return (q.new_empty((T, H, D), dtype=torch.float16), q.new_empty((T, H), dtype=torch.float32))
 
@@ -274,8 +291,22 @@ def mxfp4_decode_paged(q, cache, causal=False, keys_per_split=None):
                                    sk_max, int(bool(causal)), 0 if keys_per_split is None else int(keys_per_split))
 
 
+def mxfp4_quant_rows_rope(x, rope, positions):
+    """``attention_mxfp4.mxfp4_quantize_rows_rope`` as one operator: packed x [T, H, 128] rotated by its
+    tokens' positions through ``rope`` (a ``Rope``), then quantised -> (q4 u8 [T*H, 64], qs u8 [T*H, 4]).
+    Host ``positions`` are checked against the table and uploaded here; a device int32 tensor is passed on."""
+    from .attention_mxfp4 import Rope, _device_positions, _host_positions
+    if not isinstance(rope, Rope):
+        raise _lib.QAttnError("qattn mxfp4 rope: rope must be a Rope")
+    if x.dim() != 3:
+        raise _lib.QAttnError("qattn mxfp4 rope: packed rows must be x [T, H, 128]")
+    if not _device_positions(positions, x.shape[0]):
+        positions = _host_positions(positions, x.shape[0], rope.max_pos).to(x.device, non_blocking=True)
+    return _ops.mxfp4_quant_rows_rope(x, rope.table, positions, rope.interleaved)
+
+
 def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=None, window=None, sinks=0,
-                       share_prefix=False, tree=None):
+                       share_prefix=False, tree=None, rope=None, positions=None):
     """``kv_cache_mxfp4.attention_mxfp4_varlen_paged`` as one operator: packed q [T, Hq, 128] against
     a ``PagedKVFP4``, the ``q_lens[j]`` tokens of slot ``seq_ids[j]`` over that sequence's own length
     and pages -> (O fp16 [T, Hq, 128], lse fp32 [T, Hq]).  The plan (``plan_varlen``) is made and checked
@@ -287,9 +318,11 @@ def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=N
     sequences hold leading pages in common (``PagedKVFP4.prefix_groups``), and to the plain operator when
     they do not: the same bits either way.  ``tree`` (causal only, without a window or ``share_prefix``; one
     entry per sequence, None or a ``parents`` list) routes to ``torch.ops.qattn.mxfp4_varlen_paged_tree``, the
-    tree-masked verify step of the Python call, and to the plain operator when every entry is None."""
-    from .kv_cache_mxfp4 import (PagedKVFP4, _check_trimmed, _packed_lists, _shared_plan, _tree_args,
-                                 _window_args, plan_varlen)
+    tree-masked verify step of the Python call, and to the plain operator when every entry is None.  ``rope``
+    (with ``positions``, as the Python call's; without a window, ``share_prefix`` or ``tree``: those
+    combinations are the Python call's alone) routes to ``torch.ops.qattn.mxfp4_varlen_paged_rope``."""
+    from .kv_cache_mxfp4 import (PagedKVFP4, _check_trimmed, _packed_lists, _query_positions, _shared_plan,
+                                 _tree_args, _window_args, plan_varlen)
     if not isinstance(cache, PagedKVFP4):
         raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PagedKVFP4")
     if q.dim() != 3:
@@ -297,6 +330,9 @@ def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=N
     ids, sq = _packed_lists(cache.alloc.max_seqs, seq_ids, q_lens, "q_lens")
     if sum(sq) != q.shape[0]:
         raise _lib.QAttnError(f"qattn mxfp4 paged cache: q holds {q.shape[0]} tokens, q_lens sum to {sum(sq)}")
+    if (rope is not None or positions is not None) and (window is not None or share_prefix or tree is not None):
+        raise _lib.QAttnError("qattn mxfp4 rope: the rope operator takes no window, share_prefix or tree; "
+                              "kv_cache_mxfp4.attention_mxfp4_varlen_paged serves those with rope=")
     trees = None if tree is None else _tree_args(tree, sq, causal, window, share_prefix)
     if trees is not None:
         kps, seq_rec, work, part_rows = plan_varlen(cache.lengths, ids, sq, q.shape[1], cache.k4.shape[1],
@@ -328,9 +364,14 @@ def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=N
                                                 keys_per_split, causal, window, sinks)
     W, S = _window_args(window, sinks)
     _check_trimmed(cache, ids, sq, W, S)
+    pos = _query_positions(cache, ids, sq, None, rope, positions)
     _lib.require_gpu(q, cache.k4)
     rec_d = torch.tensor(seq_rec, dtype=torch.int32).to(q.device, non_blocking=True)
     work_d = torch.tensor(work, dtype=torch.int32).to(q.device, non_blocking=True)
+    if rope is not None:
+        return _ops.mxfp4_varlen_paged_rope(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens,
+                                            cache.block_table, rec_d, work_d, part_rows, int(bool(causal)), kps,
+                                            rope.table, pos.to(q.device, non_blocking=True), rope.interleaved)
     if W is not None:
         return _ops.mxfp4_varlen_paged_window(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens,
                                               cache.block_table, rec_d, work_d, part_rows, int(bool(causal)),
