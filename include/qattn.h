@@ -654,6 +654,50 @@ int qattn_mxfp4_paged_append_packed_rope(const void* k, const void* v, const voi
                                          int head_dim, const void* cos_sin, const void* pos, long max_pos,
                                          int interleaved, void* stream);
 
+/* The device-planned decode step (kv_cache_mxfp4.py DecodeStep): one new token for each of up to n listed
+ * sequences of the pool, with no argument below that a host computed from the lengths, so the launches can
+ * be captured in a graph once and replayed while the sequences grow.  n, splits, keys_per_split, window and
+ * sinks (window 0: none, sinks then 0) are fixed when the step is made; capacity = max_pages_per_seq *
+ * page_tokens.  The host still owns the pages: before a step, block_table holds the page that position
+ * lens[slot] of every listed slot needs.
+ *
+ * qattn_mxfp4_decode_step_plan, one launch, reads slots i32 [n] (a slot per entry; any other value marks
+ * padding) and lens, the lengths BEFORE the append, and writes four device tables of n rows, with b =
+ * slots[i] and L = lens[b]:
+ *   seq_tab i32 [n][4] = {b, 1, i, 0} and tiles i32 [n][2] = {i, L / 64}: the arguments of
+ *     qattn_mxfp4_paged_append_packed(_rope) at nseq = ntiles = tokens = n;
+ *   pos i32 [n] = L: the rotary position of the new key and query;
+ *   seq_rec i32 [n][8] = {b, i, 1, ns, i * splits * kv_heads * group, wt0, nst, 0} for the length L + 1, with
+ *     ns, wt0, nst what the host plan of the packed step gives one query over L + 1 keys (the first packed
+ *     entries above; ns held to splits).
+ * An entry with b outside [0, max_seqs) or L outside [0, capacity) is padding: seq_tab {-1, 0, i, 0} and tiles
+ * {-1, 0}, which the append skips, pos 0 and ns = 0.  No content of slots or lens makes the kernel read or
+ * write outside its tables.  Returns 1 for a NULL pointer, a keys_per_split that is no multiple of 64, max_seqs,
+ * kv_heads, group or splits < 1, splits > 65535, a capacity that is no multiple of 64 in [64, 2^25], window or
+ * sinks < 0, sinks without a window, n * splits * kv_heads * group >= 2^31; 0 without a launch for n == 0.
+ *
+ * qattn_mxfp4_attn_fwd_decode_step is the causal packed forward (with the window's mask for window >= 1) of
+ * those n one-token sequences over a grid fixed by n, splits and kv_heads: work i32 [n * splits][4] holds
+ * {i, 0, s, 0} for every entry i and split s < splits once, in any order, and a workgroup whose s is >= ns of
+ * its entry returns at once without a store.  q4 / qscale: the n * kv_heads * group quantised query rows,
+ * token-major; opart f32 [n * splits * kv_heads * group][128] and ml f32 x 2 of as many rows.  Every entry gets,
+ * bit for bit, what the first packed entry (or the windowed one) gives it at the same keys_per_split.
+ * Returns 1 as those entries do for their pool, and for the limits of the plan entry.
+ *
+ * qattn_mxfp4_decode_step_combine merges entry i's ns splits from its rows [i * splits * q_heads, ..) with
+ * qattn_mxfp4_varlen_combine's arithmetic into out f16 [n][q_heads][128] and lse f32 [n][q_heads]; a padding
+ * entry (ns < 1) gets out = 0 and lse = -inf.  Nothing allocates. */
+int qattn_mxfp4_decode_step_plan(const void* slots, const void* lens, void* seq_tab, void* tiles, void* seq_rec,
+                                 void* pos, long n, long max_seqs, long capacity, long kv_heads, long group,
+                                 int keys_per_split, long splits, long window, long sinks, void* stream);
+int qattn_mxfp4_attn_fwd_decode_step(
+    const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt, const void* vscale,
+    void* opart, void* ml, const void* lens, const void* block_table, const void* seq_rec, const void* work, long n,
+    long splits, long max_seqs, long kv_heads, long group, long num_pages, long page_tokens,
+    long max_pages_per_seq, int keys_per_split, int head_dim, float qks, long window, long sinks, void* stream);
+int qattn_mxfp4_decode_step_combine(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
+                                    long n, long splits, long q_heads, long kv_heads, int head_dim, void* stream);
+
 /* Merge of the splits, per row of rows_total = bhv*rows: M = max_s m_s, w_s = 2^(m_s - M) (exact; 0
  * for m_s = -inf), L = sum_s w_s l_s, out f16 [rows_total, 128] = (sum_s w_s O_s) * (1 / L), lse f32
  * [rows_total] = M + log2(L).  With nsplit == 1 this is the one-pass forward's epilogue bit for bit. */

@@ -104,6 +104,10 @@ SIGNATURES = {
     "qattn_mxfp4_paged_append_packed": [_vp] * 12 + [_c_long] * 8 + [_c_int, _vp],
     "qattn_mxfp4_quant_rows_rope": [_vp] * 5 + [_c_long] * 3 + [_c_int, _c_int, _vp],
     "qattn_mxfp4_paged_append_packed_rope": [_vp] * 12 + [_c_long] * 8 + [_c_int, _vp, _vp, _c_long, _c_int, _vp],
+    "qattn_mxfp4_decode_step_plan": [_vp] * 6 + [_c_long] * 5 + [_c_int] + [_c_long] * 3 + [_vp],
+    "qattn_mxfp4_attn_fwd_decode_step": [_vp] * 12 + [_c_long] * 8 + [_c_int, _c_int, _c_float, _c_long, _c_long,
+                                                                       _vp],
+    "qattn_mxfp4_decode_step_combine": [_vp] * 5 + [_c_long] * 4 + [_c_int, _vp],
     "qattn_split_keys": [_c_long, _c_long, _c_long, _c_int],
     "qattn_int8_bwd_plan": [_c_long, _c_int, _c_long, _c_long, _c_int, _c_long, _c_long, _vp],
     "qattn_bf16_bwd_plan": [_c_long, _c_long, _c_long, _c_int, _c_int, _c_long],

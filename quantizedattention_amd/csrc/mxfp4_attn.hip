@@ -701,6 +701,12 @@ __global__ __launch_bounds__(256, CAUSAL ? QA_MX_OCC_CAUSAL : QA_MX_OCC) void mx
 // shifted there, or the causal prefix for t < 0 -- shifted down by 4h, and mx_tile TREE tests its bits.
 // The lane carries the word (two registers), t and the wave base.  tests/mxfp4_tree_ref.py restates it,
 // tests/test_gpu_mxfp4_tree.py checks it.
+// STEP (with VARLEN and CAUSAL, with or without WINDOW; the device-planned decode step at the end of this
+// file): the grid is fixed when the step is made, `splits` work records {i, 0, s, 0} per entry i, and the
+// records seq_rec[i] are written by mx_decode_plan_kernel from the device lengths.  A workgroup whose split
+// s is >= rec[3] = ns_i -- a padding entry (ns = 0) or a sequence that needs fewer splits than the longest
+// one could -- returns before it reads anything else and stores nothing; every other workgroup is the
+// VARLEN (WINDOW) instantiation's statement for statement.
 struct MxVarlen {
   const int* work;      // i32 [nwork][4]
   const int* seq_rec;   // i32 [nseq][8]
@@ -810,7 +816,7 @@ QA_DEVICE void mx_group_split(const uint8_t* __restrict__ q4, const uint8_t* __r
 constexpr int MX_GROUP_LDS = MxCfg<128>::WAVES * 32 * (int)sizeof(int);   // rowidx, behind the ring
 
 template <int D, bool CAUSAL, bool LEN = false, bool PAGED = false, bool VARLEN = false, bool WINDOW = false,
-          bool SHARED = false, bool TREE = false>
+          bool SHARED = false, bool TREE = false, bool STEP = false>
 __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
     const uint8_t* __restrict__ q4, const uint8_t* __restrict__ qs, const uint8_t* __restrict__ k4,
     const uint8_t* __restrict__ ks, const uint8_t* __restrict__ vt, const uint8_t* __restrict__ vs,
@@ -824,6 +830,7 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
   static_assert(!WINDOW || (VARLEN && CAUSAL), "the window is the packed step's, and causal");
   static_assert(!SHARED || (VARLEN && !WINDOW), "shared prefixes are the packed step's, without a window");
   static_assert(!TREE || (VARLEN && CAUSAL && !WINDOW && !SHARED), "tree masks are the causal packed step's");
+  static_assert(!STEP || (VARLEN && CAUSAL && !SHARED && !TREE), "the fixed grid is the causal packed step's");
   static_assert(sizeof(float) == 4 && D == 128, "fp32 staging in two passes fills the ring exactly");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int bh, qt, split = (int)blockIdx.y;
@@ -842,6 +849,9 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
       }
     }
     const table_ptr rec =(table_ptr)(unsigned long)(vl.seq_rec + 8L * min(max(w[0], 0), vl.nseq - 1));
+    if constexpr (STEP) {   // a surplus workgroup of the fixed grid: nothing fetched, nothing stored
+      if (max(w[2], 0) >= rec[3]) return;
+    }
     qt = max(w[1], 0);
     split = max(w[2], 0);
     bh = min(max(rec[0], 0), BHV / hps - 1) * hps + hd;
@@ -1414,10 +1424,11 @@ static bool mx_split_grid(MxSplitCall& c, long sk) {
   return true;
 }
 
-template <bool CAUSAL, bool LEN, bool PAGED, bool VARLEN, bool WINDOW, bool SHARED = false, bool TREE = false>
+template <bool CAUSAL, bool LEN, bool PAGED, bool VARLEN, bool WINDOW, bool SHARED = false, bool TREE = false,
+          bool STEP = false>
 static int mx_split_launch(const MxSplitCall& c, void* stream) {
   using C = MxCfg<128>;
-  const auto kernel = mxfp4_attn_split_kernel<128, CAUSAL, LEN, PAGED, VARLEN, WINDOW, SHARED, TREE>;
+  const auto kernel = mxfp4_attn_split_kernel<128, CAUSAL, LEN, PAGED, VARLEN, WINDOW, SHARED, TREE, STEP>;
   const int lds = C::NSLOT * C::SLOT + (SHARED ? MX_GROUP_LDS : 0);
   { static LdsGrant granted_; if (!lds_grant((const void*)kernel, lds, granted_)) return 1; }
   hipLaunchKernelGGL(kernel, c.grid, dim3(256), lds, (hipStream_t)stream, (const uint8_t*)c.q4,
@@ -1872,4 +1883,142 @@ extern "C" int qattn_mxfp4_paged_append_packed_rope(
   return mx_append_packed<true>(k, v, k_mean, k4, kscale, vt, vscale, vtail, lens, block_table, seq_tab, tiles,
                                 nseq, ntiles, tokens, max_seqs, kv_heads, num_pages, page_tokens,
                                 max_pages_per_seq, head_dim, cos_sin, pos, max_pos, interleaved, stream);
+}
+
+// ------------------------------------------------------------------------------ device-planned decode step
+// (kv_cache_mxfp4.py DecodeStep) One new token for each of up to n listed sequences, with nothing in the
+// launches that a host computed from the lengths: shapes, grids and pointers are fixed when the step is made,
+// so the append and the attention can be captured once and replayed while the lengths move.
+// mx_decode_plan_kernel, one thread per entry i < n, reads b = slots[i] and L = lens[b], the length BEFORE the
+// append, and writes what the host plan would have uploaded (kv_cache_mxfp4.plan_decode_step restates it):
+//   tab[i]     = {b, 1, i, 0}      the record of mx_append_*_packed_kernel: packed token i goes to slot b
+//   tiles[i]   = {i, L / 64}       the one V tile that append touches
+//   pos[i]     = L                 the rotary position of the new token, key and query
+//   seq_rec[i] = {b, i, 1, ns, i * splits * hq, wt0, nst, 0} for the length L + 1: plan_varlen's expressions at
+//                one query, nt = ceil((L + 1) / 64), ns = ceil(nt * 64 / kps) without a window; with one, wt0 =
+//                max(0, L + 1 - W) / 64 and nst = ceil(min(S, L + 1) / 64) when wt0 > nst (a gap), else 0, 0,
+//                and ns = (nst > 0) + ceil((nt - wt0) * 64 / kps); ns is held to `splits`, the grid's.
+// An entry whose b lies outside [0, B) or whose L lies outside [0, cap) is padding: tab {-1, 0, i, 0}, which
+// the append kernels skip, tiles {-1, 0}, pos 0 and ns = 0, so no workgroup runs for it and the merge writes
+// O = 0, lse = -inf.  lens is read only at a checked b; every store goes to row i < n of a table of n rows.
+// (A template over the tile's keys, so that it is emitted where it is first used, behind every older kernel.)
+namespace qattn {
+template <int KT>
+__global__ __launch_bounds__(256) void mx_decode_plan_kernel(const int* __restrict__ slots,
+                                                             const int* __restrict__ lens, int* __restrict__ tab,
+                                                             int* __restrict__ tiles, int* __restrict__ seq_rec,
+                                                             int* __restrict__ pos, int n, int B, int cap, int kt,
+                                                             int splits, int hq, int window, int sinks) {
+  const int i = (int)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int b = slots[i];
+  int L = -1;
+  if (b >= 0 && b < B) L = lens[b];
+  const bool ok = L >= 0 && L < cap;
+  int ns = 0, wt0 = 0, nst = 0;
+  if (ok) {
+    const int L1 = L + 1, nt = (L1 + KT - 1) / KT;
+    if (window > 0) {
+      const int w0 = max(0, L1 - window) / KT, s0 = (min(sinks, L1) + KT - 1) / KT;
+      if (w0 > s0) {
+        wt0 = w0;
+        nst = s0;
+      }
+    }
+    ns = min((nst > 0) + (nt - wt0 + kt - 1) / kt, splits);
+  }
+  reinterpret_cast<v4i*>(tab)[i] = v4i{ok ? b : -1, ok ? 1 : 0, i, 0};
+  reinterpret_cast<int2*>(tiles)[i] = make_int2(ok ? i : -1, ok ? L / KT : 0);
+  pos[i] = ok ? L : 0;
+  reinterpret_cast<v4i*>(seq_rec)[2 * i] = v4i{ok ? b : -1, i, 1, ns};
+  reinterpret_cast<v4i*>(seq_rec)[2 * i + 1] = v4i{i * splits * hq, wt0, nst, 0};
+}
+
+// The merge of the step: entry i owns the partial rows [i * splits * Hq, (i + 1) * splits * Hq), laid out
+// [split][query head] (one query: the virtual head order is the head order), so nothing but ns is read from
+// the record and every address lies inside the partials.  mx_merge_row over the entry's ns splits, the
+// arithmetic of mxfp4_varlen_combine_kernel in its order; an entry with ns < 1 (padding) gets O = 0 and lse =
+// -inf.
+template <int D>
+__global__ __launch_bounds__(256) void mxfp4_decode_step_combine_kernel(const float* __restrict__ opart,
+                                                                        const float2* __restrict__ ml,
+                                                                        _Float16* __restrict__ out,
+                                                                        float* __restrict__ lse,
+                                                                        const int* __restrict__ seq_rec, long rows,
+                                                                        int Hq, int splits) {
+  constexpr int TPR = D / 8;
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+  const long row = gid / TPR;
+  if (row >= rows) return;
+  const int c = (int)(gid % TPR);
+  const long token = row / Hq;
+  const int ns = min(seq_rec[8 * token + 3], splits);
+  if (ns < 1) {
+    *reinterpret_cast<v8h*>(out + row * D + 8 * c) = v8h{};
+    if (c == 0) lse[row] = -INFINITY;
+    return;
+  }
+  mx_merge_row<D>(opart, ml, token * splits * Hq + row % Hq, Hq, ns, c, out + row * D, lse + row);
+}
+}  // namespace qattn
+
+// window 0: none (then sinks must be 0); the kernels' 32-bit edges as in mx_varlen_call
+static bool mx_step_window_ok(long window, long sinks) {
+  return window >= 0 && sinks >= 0 && (window > 0 || sinks == 0);
+}
+
+extern "C" int qattn_mxfp4_decode_step_plan(const void* slots, const void* lens, void* seq_tab, void* tiles,
+                                            void* seq_rec, void* pos, long n, long max_seqs, long capacity,
+                                            long kv_heads, long group, int keys_per_split, long splits,
+                                            long window, long sinks, void* stream) {
+  if (!mx_split_ok(128, keys_per_split) || n < 0 || max_seqs < 1 || max_seqs > 0x7fffffffL) return 1;
+  if (capacity < 64 || capacity % 64 || capacity > (1L << 25) || !mx_step_window_ok(window, sinks)) return 1;
+  if (kv_heads < 1 || group < 1 || splits < 1 || splits > 65535) return 1;
+  if (kv_heads > 0x7fffffffL / group || n > 0x7fffffffL / (splits * kv_heads * group)) return 1;
+  if (n == 0) return 0;
+  if (!slots || !lens || !seq_tab || !tiles || !seq_rec || !pos) return 1;
+  const long big = 1L << 26;
+  hipLaunchKernelGGL(mx_decode_plan_kernel<64>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const int*)slots, (const int*)lens, (int*)seq_tab, (int*)tiles, (int*)seq_rec, (int*)pos,
+                     (int)n, (int)max_seqs, (int)capacity, keys_per_split / 64, (int)splits,
+                     (int)(kv_heads * group), (int)(window < big ? window : big), (int)(sinks < big ? sinks : big));
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// The attention of the step over its fixed grid (kernel: mxfp4_attn_split_kernel STEP): n entries x splits
+// work records x kv_heads workgroups, causal, with the window's instantiation for window >= 1.  seq_rec is
+// mx_decode_plan_kernel's, work i32 [n * splits][4] = {i, 0, s, 0} in any order; the partials hold n * splits
+// * kv_heads * group rows.  It stands behind every older entry, as its kernels are emitted behind theirs.
+extern "C" int qattn_mxfp4_attn_fwd_decode_step(
+    const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt, const void* vscale,
+    void* opart, void* ml, const void* lens, const void* block_table, const void* seq_rec, const void* work, long n,
+    long splits, long max_seqs, long kv_heads, long group, long num_pages, long page_tokens,
+    long max_pages_per_seq, int keys_per_split, int head_dim, float qks, long window, long sinks, void* stream) {
+  if (n < 0 || splits < 1 || splits > 65535 || kv_heads < 1 || group < 1 || !mx_step_window_ok(window, sinks))
+    return 1;
+  if (kv_heads > 0x7fffffffL / group || n > 0x7fffffffL / (splits * kv_heads * group)) return 1;
+  if (n > 0 && (!q4 || !qscale || !k4 || !kscale || !vt || !vscale || !opart || !ml)) return 1;
+  MxSplitCall c;
+  const int rc = mx_varlen_call(c, q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work,
+                                n, n * splits, n, n * splits * kv_heads * group, max_seqs, kv_heads, group,
+                                num_pages, page_tokens, max_pages_per_seq, 2, keys_per_split, head_dim, qks,
+                                window, sinks, nullptr);
+  if (rc >= 0) return rc;
+  return window < 1 ? mx_split_launch<true, true, true, true, false, false, false, true>(c, stream)
+                    : mx_split_launch<true, true, true, true, true, false, false, true>(c, stream);
+}
+
+extern "C" int qattn_mxfp4_decode_step_combine(const void* opart, const void* ml, void* out, void* lse,
+                                               const void* seq_rec, long n, long splits, long q_heads,
+                                               long kv_heads, int head_dim, void* stream) {
+  if (head_dim != 128 || n < 0 || splits < 1 || splits > 65535) return 1;
+  if (kv_heads < 1 || q_heads < 1 || q_heads % kv_heads != 0 || q_heads > 0x7fffffffL) return 1;
+  if (n > 0x7fffffffL / (splits * q_heads)) return 1;
+  if (n == 0) return 0;
+  if (!opart || !ml || !out || !lse || !seq_rec) return 1;
+  const long rows = n * q_heads, nthr = rows * (128 / 8);
+  hipLaunchKernelGGL(mxfp4_decode_step_combine_kernel<128>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)opart, (const float2*)ml, (_Float16*)out, (float*)lse,
+                     (const int*)seq_rec, rows, (int)q_heads, (int)splits);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
 }

@@ -43,6 +43,10 @@
 //       table cos_sin f32 [max_pos, 128], then quantised
 //   mxfp4_varlen_paged_rope(.. the arguments of mxfp4_varlen_paged .., cos_sin, pos, interleaved) -> (O, lse)
 //       the same with q rotated inside its quantiser (attention_mxfp4_varlen_paged(rope=))
+//   mxfp4_decode_step_plan(slots, lens, capacity, kv_heads, group, keys_per_split, splits, window, sinks)
+//       -> (seq_tab, tiles, pos, seq_rec): kv_cache_mxfp4.DecodeStep's tables, derived on the device
+//   mxfp4_decode_step(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, splits, keys_per_split, window,
+//       sinks) -> (O, lse): kv_cache_mxfp4.DecodeStep.attend over its fixed grid
 // Workspaces, head chunks and key splits are planned by the library (csrc/plan.hip), as in the drop-ins.
 // Errors: TORCH_CHECK (c10::Error, RuntimeError in Python) with the drop-ins' messages; int8_quant's
 // argument checks raise ValueError (TORCH_CHECK_VALUE) as its Python predecessor did.
@@ -765,6 +769,78 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged_tree(const Tensor& q, const Tensor
                                 keys_per_split, false, 0, 0, nullptr, nullptr, &tree_masks);
 }
 
+// kv_cache_mxfp4.DecodeStep's plan as an operator: from slots i32 [n] and the pool's lens i32 [B] (the lengths
+// BEFORE the step's append) the four device tables of qattn_mxfp4_decode_step_plan, seq_tab i32 [n, 4], tiles
+// i32 [n, 2], pos i32 [n] and seq_rec i32 [n, 8].  Nothing is read back; window 0: none.
+std::tuple<Tensor, Tensor, Tensor, Tensor> mxfp4_decode_step_plan(const Tensor& slots, const Tensor& lens,
+                                                                  int64_t capacity, int64_t kv_heads,
+                                                                  int64_t group, int64_t keys_per_split,
+                                                                  int64_t splits, int64_t window, int64_t sinks) {
+  require_gpu({&slots, &lens});
+  TORCH_CHECK(slots.scalar_type() == at::kInt && slots.is_contiguous() && slots.dim() == 1 && slots.size(0) >= 1,
+              "qattn mxfp4 decode step: slots must be contiguous int32 [n >= 1]");
+  TORCH_CHECK(lens.scalar_type() == at::kInt && lens.is_contiguous() && lens.dim() == 1 && lens.size(0) >= 1,
+              "qattn mxfp4 decode step: lens must be contiguous int32 [max_seqs]");
+  TORCH_CHECK(keys_per_split >= 64 && keys_per_split % 64 == 0,
+              "qattn mxfp4 decode step: keys_per_split must be a multiple of 64");
+  const int64_t n = slots.size(0);
+  Ctx c(slots);
+  Tensor seq_tab = empty({n, 4}, at::kInt, slots), tiles = empty({n, 2}, at::kInt, slots);
+  Tensor pos = empty({n}, at::kInt, slots), seq_rec = empty({n, 8}, at::kInt, slots);
+  call(qattn_mxfp4_decode_step_plan(P(slots), P(lens), P(seq_tab), P(tiles), P(seq_rec), P(pos), n, lens.size(0),
+                                    capacity, kv_heads, group, (int)keys_per_split, splits, window, sinks,
+                                    c.stream),
+       "mxfp4 decode step plan");
+  return {seq_tab, tiles, pos, seq_rec};
+}
+
+// kv_cache_mxfp4.DecodeStep.attend as an operator: q [n, Hq, 128], the pool's operands, lens (AFTER the step's
+// append) and block table, seq_rec i32 [n, 8] of the plan above and work i32 [n * splits, 4] = {i, 0, s, 0}.
+std::tuple<Tensor, Tensor> mxfp4_decode_step(const Tensor& q_in, const Tensor& k4, const Tensor& ks,
+                                             const Tensor& vt, const Tensor& vs, const Tensor& lens,
+                                             const Tensor& block_table, const Tensor& seq_rec, const Tensor& work,
+                                             int64_t splits, int64_t keys_per_split, int64_t window,
+                                             int64_t sinks) {
+  require_gpu({&q_in, &k4, &ks, &vt, &vs, &lens, &block_table, &seq_rec, &work});
+  TORCH_CHECK(q_in.dim() == 3 && k4.dim() == 4 && q_in.size(2) == 128 && k4.size(3) == 64,
+              "qattn mxfp4 decode step: q must be [n, Hq, 128], head_dim 128 in the pool");
+  const int64_t NP = k4.size(0), Hkv = k4.size(1), PT = k4.size(2), D = 128;
+  TORCH_CHECK(PT >= 64 && PT <= 1024 && (PT & (PT - 1)) == 0,
+              "qattn mxfp4 paged cache: page_tokens must be 64 * 2^k in [64, 1024]");
+  TORCH_CHECK(block_table.scalar_type() == at::kInt && block_table.is_contiguous() && block_table.dim() == 2 &&
+                  block_table.size(1) >= 1,
+              "qattn mxfp4 paged cache: block_table must be contiguous int32 [B, max_pages_per_seq]");
+  const int64_t B = block_table.size(0), mpp = block_table.size(1);
+  const int64_t n = q_in.size(0), Hq = q_in.size(1);
+  TORCH_CHECK(Hkv > 0 && NP > 0 && Hq > 0 && Hq % Hkv == 0 && n >= 1 && n <= B,
+              "qattn mxfp4 decode step: q must have G * Hkv heads for the pool's Hkv and 1 <= n <= B rows");
+  check_fp4_operands(k4, ks, vt, vs, &lens, B, true);
+  TORCH_CHECK(splits >= 1 && splits <= 65535 && n * splits * Hq < (int64_t(1) << 31),
+              "qattn mxfp4 decode step: splits in [1, 65535] and fewer than 2^31 partial rows expected");
+  TORCH_CHECK(seq_rec.scalar_type() == at::kInt && seq_rec.is_contiguous() && seq_rec.dim() == 2 &&
+                  seq_rec.size(1) == 8 && seq_rec.size(0) == n,
+              "qattn mxfp4 decode step: seq_rec must be contiguous int32 [n, 8]");
+  TORCH_CHECK(work.scalar_type() == at::kInt && work.is_contiguous() && work.dim() == 2 && work.size(1) == 4 &&
+                  work.size(0) == n * splits,
+              "qattn mxfp4 decode step: work must be contiguous int32 [n * splits, 4]");
+  TORCH_CHECK(keys_per_split >= 64 && keys_per_split % 64 == 0,
+              "qattn mxfp4 decode step: keys_per_split must be a multiple of 64");
+  Ctx c(q_in);
+  const Tensor q = kin(q_in, at::kHalf);
+  Tensor q4 = empty({n * Hq, D / 2}, at::kByte, q), qs = empty({n * Hq, D / 32}, at::kByte, q);
+  Tensor out = empty({n, Hq, D}, at::kHalf, q), lse = empty({n, Hq}, at::kFloat, q);
+  Tensor opart = empty({n * splits * Hq, D}, at::kFloat, q), ml = empty({n * splits * Hq, 2}, at::kFloat, q);
+  call(qattn_mxfp4_quant_rows(P(q), nullptr, P(q4), P(qs), n * Hq, Hq, (int)D, c.stream), "quantise q");
+  call(qattn_mxfp4_attn_fwd_decode_step(P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens),
+                                        P(block_table), P(seq_rec), P(work), n, splits, B, Hkv, Hq / Hkv, NP, PT,
+                                        mpp, (int)keys_per_split, (int)D, qk_scale(D), window, sinks, c.stream),
+       "mxfp4 decode step forward");
+  call(qattn_mxfp4_decode_step_combine(P(opart), P(ml), P(out), P(lse), P(seq_rec), n, splits, Hq, Hkv, (int)D,
+                                       c.stream),
+       "mxfp4 decode step merge");
+  return {out, lse};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(qattn, m) {
@@ -800,6 +876,10 @@ TORCH_LIBRARY(qattn, m) {
   m.def("mxfp4_varlen_paged_rope(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, "
         "Tensor block_table, Tensor seq_rec, Tensor work, int part_rows, int causal, int keys_per_split, "
         "Tensor cos_sin, Tensor pos, bool interleaved) -> (Tensor, Tensor)");
+  m.def("mxfp4_decode_step_plan(Tensor slots, Tensor lens, int capacity, int kv_heads, int group, "
+        "int keys_per_split, int splits, int window, int sinks) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("mxfp4_decode_step(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, Tensor block_table, "
+        "Tensor seq_rec, Tensor work, int splits, int keys_per_split, int window, int sinks) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
@@ -820,4 +900,6 @@ TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
   m.impl("mxfp4_varlen_paged_tree", &mxfp4_varlen_paged_tree);
   m.impl("mxfp4_quant_rows_rope", &mxfp4_quant_rows_rope);
   m.impl("mxfp4_varlen_paged_rope", &mxfp4_varlen_paged_rope);
+  m.impl("mxfp4_decode_step_plan", &mxfp4_decode_step_plan);
+  m.impl("mxfp4_decode_step", &mxfp4_decode_step);
 }

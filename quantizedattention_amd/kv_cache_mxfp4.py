@@ -154,6 +154,17 @@ int32 tensor, used as given and clamped by the kernel) override them.  The rotat
 -- so every ``rope=`` call gives exactly the bytes of the same call on rows rotated that way in torch.
 Cached keys are never rotated again, and the padded entries take no ``rope``.
 
+The device-planned decode step (:class:`DecodeStep`): the commonest step, one new token for each of N running
+sequences, is bound by the host plan and its uploads, not by its kernels, and a plan made from the host mirror
+cannot be captured in a graph (a replay would run stale lengths).  A ``DecodeStep`` fixes every shape, grid and
+pointer when it is made; ``qattn_mxfp4_decode_step_plan`` derives the append record, the V tile, the rotary
+position and ``seq_rec`` of every entry from ``slots`` and ``lens`` on the device (:func:`plan_decode_step`
+restates it), the attention runs ``splits`` (:func:`decode_step_splits`) work records per entry whatever the
+lengths are, and a workgroup whose split its sequence does not have exits at once.  The host keeps what only it
+can do, in ``prepare``: the checks, the page reservation, the table upload when a page was added and the upload
+of ``slots``.  Results are the host-planned pair's bit for bit at the same keys per split.  ``share_prefix``,
+trees, ``trim``, prefill chunks and more than one new token per sequence stay on the host-planned path.
+
 Wire format (little-endian), the container of kv_cache.py with a magic of its own::
 
     offset 0   8 B   magic  b"QATTNKF4"
@@ -191,7 +202,8 @@ _DTYPES = {"uint8": torch.uint8, "float16": torch.float16}
 __all__ = ["QuantizedKVFP4", "quantize_kv_fp4", "attention_mxfp4_cached", "PreallocatedKVFP4",
            "attention_mxfp4_decode", "PageAllocator", "PagedKVFP4", "attention_mxfp4_decode_paged",
            "plan_varlen", "plan_varlen_shared", "attention_mxfp4_varlen_paged", "tree_ancestor_masks",
-           "tree_path", "Checkpoint", "Rope", "rope_table", "rope_positions"]
+           "tree_path", "Checkpoint", "Rope", "rope_table", "rope_positions", "DecodeStep",
+           "decode_step_splits", "plan_decode_step"]
 
 
 @dataclass
@@ -1748,3 +1760,254 @@ def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_
     _lib.call("qattn_mxfp4_varlen_combine", _lib.ptr(opart), _lib.ptr(ml), _lib.ptr(O), _lib.ptr(lse),
               _lib.ptr(rec_d), len(ids), T, Hq, Hkv, part_rows, D, st)
     return O, lse
+
+
+# ------------------------------------------------------------------------------ device-planned decode step
+def _step_plan(L1: int, kps: int, W, S: int):
+    """(ns, wt0, nst) of one query over ``L1`` >= 1 keys at ``kps`` keys per split under window ``(W, S)`` (W
+    None: no window): :func:`plan_varlen`'s expressions at q_len 1."""
+    wt0, nst, nt = (0, 0, -(-L1 // BLOCK)) if W is None else _window_tiles(L1, 1, W, S)
+    return (1 if nst else 0) + -(-(nt - wt0) * BLOCK // kps), wt0, nst
+
+
+def _step_split_order(splits: int, W, S: int) -> list:
+    """The order of the splits in a step's ``work`` table (results do not depend on it): ascending, except that
+    under a window with sinks split 0 comes last.  With a gap it is the short sink run, and the host plan starts
+    the longest workgroups first; measured on the 64-decode window case of DESIGN.md section 5."""
+    return list(range(splits)) if W is None or not S or splits < 2 else list(range(1, splits)) + [0]
+
+
+def decode_step_splits(max_keys: int, kps: int, window: Optional[int] = None, sinks: int = 0) -> int:
+    """The largest number of key splits one query needs over any length in [1, ``max_keys``] at ``kps`` keys per
+    split under ``(window, sinks)``: the ``splits`` of a :class:`DecodeStep`, whose grid is sized for it.  Pure
+    Python.  Without a window it is ceil(ceil64(max_keys) / kps).  With one it does not grow with ``max_keys``:
+    while the sink tiles and the window's first tile touch, the sequence is shorter than W + 64 * (ceil(S / 64)
+    + 1) keys and runs every tile; beyond that (a gap) the window run holds at most ceil(W / 64) + 1 tiles
+    whatever the length, so the count is at most 1 + the splits of the W-key run and repeats with period 64."""
+    W, S = _window_args(window, sinks)
+    max_keys, kps = int(max_keys), int(kps)
+    if max_keys < 1 or kps < BLOCK or kps % BLOCK:
+        raise _lib.QAttnError("qattn mxfp4 decode step: max_keys >= 1 and keys_per_split a multiple of 64 expected")
+    if W is None:
+        return _step_plan(max_keys, kps, None, 0)[0]
+    gap = W + BLOCK * (-(-S // BLOCK) + 1)   # the first length with a gap; every longer one has it too
+    best = _step_plan(min(max_keys, gap - 1), kps, W, S)[0]   # no gap: the count grows with the length
+    return max([best] + [_step_plan(L1, kps, W, S)[0] for L1 in range(gap, min(max_keys, gap + BLOCK - 1) + 1)])
+
+
+def plan_decode_step(lengths_before, slots, kps: int, splits: int, kv_heads: int, group: int,
+                     window: Optional[int] = None, sinks: int = 0, capacity: Optional[int] = None):
+    """The tables of one device-planned decode step -> (seq_tab, tiles, pos, seq_rec, work) as lists: the pure-
+    Python statement of what ``qattn_mxfp4_decode_step_plan`` writes (and of ``work``, which a :class:`DecodeStep`
+    writes once when it is made).  No device.  ``lengths_before`` holds one length per slot BEFORE the step's
+    append and ``slots`` one slot per entry of the step, any value outside [0, len(lengths_before)) marking
+    padding.  For entry i with b = slots[i] and L = lengths_before[b]:
+
+        seq_tab[i] = [b, 1, i, 0]          the record of ``append_packed``: packed token i goes to slot b
+        tiles[i]   = [i, L // 64]          the V tile that append touches
+        pos[i]     = L                     the rotary position of the new key and of the query
+        seq_rec[i] = [b, i, 1, ns, i * splits * kv_heads * group, wt0, nst, 0]
+
+    with ns, wt0 and nst those of :func:`plan_varlen` for one sequence of L + 1 keys and one query at ``kps``
+    under ``(window, sinks)`` (ns held to ``splits``, which :func:`decode_step_splits` makes large enough).  A
+    padding entry -- b out of range, or L outside [0, ``capacity``) -- is seq_tab [-1, 0, i, 0], tiles [-1, 0],
+    pos 0 and seq_rec [-1, i, 1, 0, i * splits * kv_heads * group, 0, 0, 0]: the append skips it, no workgroup
+    runs for it and the merge writes O = 0, lse = -inf.  ``work`` = [i, 0, s, 0] for every s < ``splits`` and
+    every entry, split by split (under a window with sinks split 0 last: the sink run is the short one)."""
+    W, S = _window_args(window, sinks)
+    lengths = [int(x) for x in lengths_before]
+    slots = [int(b) for b in slots]
+    kps, splits, hq = int(kps), int(splits), int(kv_heads) * int(group)
+    if kps < BLOCK or kps % BLOCK or splits < 1 or hq < 1:
+        raise _lib.QAttnError("qattn mxfp4 decode step: keys_per_split must be a multiple of 64, splits, kv_heads "
+                              "and group >= 1")
+    seq_tab, tiles, pos, seq_rec = [], [], [], []
+    for i, b in enumerate(slots):
+        L = lengths[b] if 0 <= b < len(lengths) else -1
+        if L < 0 or (capacity is not None and L >= capacity):
+            seq_tab.append([-1, 0, i, 0])
+            tiles.append([-1, 0])
+            pos.append(0)
+            seq_rec.append([-1, i, 1, 0, i * splits * hq, 0, 0, 0])
+            continue
+        ns, wt0, nst = _step_plan(L + 1, kps, W, S)
+        seq_tab.append([b, 1, i, 0])
+        tiles.append([i, L // BLOCK])
+        pos.append(L)
+        seq_rec.append([b, i, 1, min(ns, splits), i * splits * hq, wt0, nst, 0])
+    work = [[i, 0, s, 0] for s in _step_split_order(splits, W, S) for i in range(len(slots))]
+    return seq_tab, tiles, pos, seq_rec, work
+
+
+class DecodeStep:
+    """One decode step -- one new token for each of up to ``max_batch`` running sequences of a
+    :class:`PagedKVFP4` -- whose launches depend on nothing the host computed from the lengths, so ``append`` and
+    ``attend`` can be captured in a graph once and replayed while the sequences grow, leave and join.
+
+    Everything is allocated here, once, and nothing at call time: ``slots`` i32 [N] (the listed slots, -1 for
+    padding), the append table ``seq_tab`` i32 [N, 4] and tile list ``tiles`` i32 [N, 2], ``seq_rec`` i32 [N, 8],
+    ``pos`` i32 [N], ``work`` i32 [N * splits, 4] (written here and never again), the quantised queries ``q4`` /
+    ``qs``, the partials ``opart`` f32 [N * splits * Hq, 128] / ``ml``, and the results ``O`` f16 [N, Hq, 128] /
+    ``lse`` f32 [N, Hq], which ``attend`` returns and the next ``attend`` overwrites.  ``kps`` is fixed here:
+    ``keys_per_split``, or ``qattn_split_keys(kv_heads * N, 1, ceil64(max_keys), 64)``; ``splits`` =
+    :func:`decode_step_splits`, so the attention grid is N * splits * kv_heads workgroups whatever the lengths
+    are.  ``window`` / ``sinks`` as in :func:`attention_mxfp4_varlen_paged`; under a window ``splits`` does not
+    grow with ``max_keys``.
+
+    ``prepare`` is the host's part, before every step or replay: the checks, the pages, ``slots``.  ``append``
+    derives the step's tables from the device lengths (``qattn_mxfp4_decode_step_plan``) and appends;
+    ``attend`` quantises ``q`` and runs the fixed grid (``qattn_mxfp4_attn_fwd_decode_step``), whose surplus
+    workgroups exit, and the merge (``qattn_mxfp4_decode_step_combine``).  Every listed entry gets, bit for bit,
+    what ``append_packed(k, v, ids, [1] * n)`` followed by ``attention_mxfp4_varlen_paged(q, cache, ids, [1] * n,
+    causal=True, keys_per_split=step.kps[, window, sinks][, rope])`` gives.  One step object serves any number of
+    pools, layer after layer, on one stream: each pool's ``append`` rewrites the tables from that pool's own
+    ``lens``."""
+
+    def __init__(self, max_batch: int, max_keys: int, q_heads: int, kv_heads: int, device,
+                 keys_per_split: Optional[int] = None, window: Optional[int] = None, sinks: int = 0):
+        N, max_keys, Hq, Hkv, D = int(max_batch), int(max_keys), int(q_heads), int(kv_heads), 128
+        self.window, self.sinks = _window_args(window, sinks)
+        if N < 1 or Hkv < 1 or Hq < 1 or Hq % Hkv or not 1 <= max_keys <= 1 << 25:
+            raise _lib.QAttnError("qattn mxfp4 decode step: max_batch >= 1, q_heads = G * kv_heads and max_keys in "
+                                  "[1, 2^25] expected")
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.QAttnError(f"qattn kernels run on the GPU only; got device {dev} "
+                                  "(no CPU fallback by design)")
+        if keys_per_split is None:
+            kps = _lib.load().qattn_split_keys(Hkv * N, 1, _ceil64(max_keys), BLOCK)
+        else:
+            kps = int(keys_per_split)
+        if kps < BLOCK or kps % BLOCK:
+            raise _lib.QAttnError("qattn mxfp4 decode step: keys_per_split must be a multiple of 64")
+        self.N, self.max_keys, self.q_heads, self.kv_heads, self.kps = N, max_keys, Hq, Hkv, kps
+        self.splits = decode_step_splits(max_keys, kps, self.window, self.sinks)
+        if self.splits > 65535 or N * self.splits * Hq >= 1 << 31:
+            raise _lib.QAttnError("qattn mxfp4 decode step: more than 65535 splits or 2^31 partial rows; raise "
+                                  "keys_per_split")
+        z = lambda *shape, dt=torch.int32: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        self.slots = torch.full((N,), -1, dtype=torch.int32, device=dev)
+        self.seq_tab, self.tiles, self.seq_rec, self.pos = z(N, 4), z(N, 2), z(N, 8), z(N)
+        self.work = torch.tensor([[i, 0, s, 0] for s in _step_split_order(self.splits, self.window, self.sinks)
+                                  for i in range(N)], dtype=torch.int32).to(dev)
+        rows = N * self.splits * Hq
+        self.opart, self.ml = z(rows, D, dt=torch.float32), z(rows, 2, dt=torch.float32)
+        self.q4, self.qs = z(N * Hq, D // 2, dt=torch.uint8), z(N * Hq, D // 32, dt=torch.uint8)
+        self.O, self.lse = z(N, Hq, D, dt=torch.float16), z(N, Hq, dt=torch.float32)
+        self.listed = []   # the slots of the last prepare
+
+    def _pool(self, cache: "PagedKVFP4") -> None:
+        if not isinstance(cache, PagedKVFP4):
+            raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PagedKVFP4")
+        if cache.shape[1] != self.kv_heads or cache.k4.device != self.slots.device:
+            raise _lib.QAttnError(f"qattn mxfp4 decode step: a pool of {self.kv_heads} key/value heads on "
+                                  f"{self.slots.device} expected")
+        if self.N > cache.alloc.max_seqs:
+            raise _lib.QAttnError(f"qattn mxfp4 decode step: a step of {self.N} entries on a pool of "
+                                  f"{cache.alloc.max_seqs} sequence slots")
+
+    def prepare(self, cache: "PagedKVFP4", seq_ids) -> "DecodeStep":
+        """The host's part of a step over the slots ``seq_ids`` of ``cache`` (at most N, distinct, none empty),
+        before ``append`` / ``attend`` or a replay of their graph; not capturable.  Raises :class:`QAttnError`
+        before anything changes for duplicate or out-of-range slots, more than N of them, a listed slot of length
+        0, a sequence whose length + 1 would pass ``max_keys`` or what its table row can hold, and a trimmed page
+        the step would read.  Then it reserves the pages the lengths + 1 need (all or nothing: out of pages
+        raises with nothing changed), uploads the table if it grew and ``seq_ids``, padded with -1, into
+        ``slots``, and adds 1 to the listed ``cache.lengths``.  It builds no plan and no per-tile list;
+        stream-ordered, nothing read back."""
+        self._pool(cache)
+        ids = [int(b) for b in (seq_ids.tolist() if isinstance(seq_ids, torch.Tensor) else seq_ids)]
+        a = cache.alloc
+        if len(ids) > self.N or len(set(ids)) != len(ids) or any(not 0 <= b < a.max_seqs for b in ids):
+            raise _lib.QAttnError(f"qattn mxfp4 decode step: seq_ids must be at most {self.N} distinct slots in "
+                                  f"[0, {a.max_seqs}), got {ids}")
+        Ls = [cache.lengths[b] for b in ids]
+        if any(L < 1 for L in Ls):
+            raise _lib.QAttnError("qattn mxfp4 decode step: every listed sequence needs at least one cached token "
+                                  f"(slots {ids}, lengths {Ls})")
+        cap = min(self.max_keys, a.max_pages_per_seq * a.page_tokens)
+        if any(L + 1 > cap for L in Ls):
+            raise _lib.QAttnError(f"qattn mxfp4 decode step: a sequence would pass {cap} keys (the step's max_keys "
+                                  f"{self.max_keys}, the pool's {a.max_pages_per_seq} pages of {a.page_tokens}; "
+                                  f"slots {ids}, lengths {Ls})")
+        for b in ids:   # the lengths the step attends at; taken back if it is refused
+            cache.lengths[b] += 1
+        try:
+            _check_trimmed(cache, ids, [1] * len(ids), self.window, self.sinks)
+            grown = a.reserve([(b, cache.lengths[b]) for b in ids])
+        except _lib.QAttnError:
+            for b in ids:
+                cache.lengths[b] -= 1
+            raise
+        if grown:
+            cache.block_table.copy_(torch.tensor(a.table, dtype=torch.int32), non_blocking=True)
+        self.slots.copy_(torch.tensor(ids + [-1] * (self.N - len(ids)), dtype=torch.int32), non_blocking=True)
+        self.listed = ids
+        return self
+
+    def _rope(self, cache: "PagedKVFP4", rope) -> None:
+        if not isinstance(rope, Rope):
+            raise _lib.QAttnError("qattn mxfp4 rope: rope must be a Rope")
+        hi = max((cache.lengths[b] - 1 for b in self.listed), default=0)
+        if hi >= rope.max_pos:   # (the mirror after prepare: a check only, no launch depends on it)
+            raise _lib.QAttnError(f"qattn mxfp4 rope: the step's positions reach {hi}, outside the table's "
+                                  f"[0, {rope.max_pos})")
+
+    def append(self, cache: "PagedKVFP4", k: torch.Tensor, v: torch.Tensor, rope: Optional[Rope] = None):
+        """Append ``k, v`` fp16 [N, Hkv, 128], row i the new token of entry i (rows of padding entries are not
+        read), to the sequences ``slots`` names; capturable.  One launch derives the tables from ``cache.lens``
+        (``qattn_mxfp4_decode_step_plan``), then ``qattn_mxfp4_paged_append_packed`` (``_rope`` with ``rope``:
+        the keys rotated to ``pos``, their lengths before the append) runs on them as it is."""
+        self._pool(cache)
+        N, H, D = self.N, self.kv_heads, 128
+        if tuple(k.shape) != (N, H, D) or k.shape != v.shape:
+            raise _lib.QAttnError(f"qattn mxfp4 decode step: k, v must be [{N}, {H}, 128]")
+        if rope is not None:
+            self._rope(cache, rope)
+        _lib.require_gpu(k, v, cache.k4)
+        k = _lib.kernel_input(k, torch.float16)
+        v = _lib.kernel_input(v, torch.float16)
+        a, st = cache.alloc, _lib.stream_of(k)
+        _lib.call("qattn_mxfp4_decode_step_plan", _lib.ptr(self.slots), _lib.ptr(cache.lens), _lib.ptr(self.seq_tab),
+                  _lib.ptr(self.tiles), _lib.ptr(self.seq_rec), _lib.ptr(self.pos), N, a.max_seqs,
+                  a.max_pages_per_seq * a.page_tokens, H, self.q_heads // H, self.kps, self.splits,
+                  self.window or 0, self.sinks, st)
+        args = (_lib.ptr(k), _lib.ptr(v), _lib.ptr(cache.k_mean), _lib.ptr(cache.k4), _lib.ptr(cache.ks),
+                _lib.ptr(cache.vt), _lib.ptr(cache.vs), _lib.ptr(cache.vtail), _lib.ptr(cache.lens),
+                _lib.ptr(cache.block_table), _lib.ptr(self.seq_tab), _lib.ptr(self.tiles), N, N, N, a.max_seqs, H,
+                a.num_pages, a.page_tokens, a.max_pages_per_seq, D)
+        if rope is None:
+            _lib.call("qattn_mxfp4_paged_append_packed", *args, st)
+        else:
+            _lib.call("qattn_mxfp4_paged_append_packed_rope", *args, _lib.ptr(rope.table), _lib.ptr(self.pos),
+                      rope.max_pos, int(rope.interleaved), st)
+        return self
+
+    def attend(self, cache: "PagedKVFP4", q: torch.Tensor, rope: Optional[Rope] = None):
+        """Attention of ``q`` fp16 [N, Hq, 128], row i the query of entry i's new token, over the sequences after
+        this step's ``append`` -> (``O`` fp16 [N, Hq, 128], ``lse`` fp32 [N, Hq] base 2), the step's own buffers;
+        capturable.  ``q`` is quantised (rotated to ``pos`` first with ``rope``), one attention launch runs the
+        fixed grid and one merge follows; the rows of padding entries come back as O = 0, lse = -inf."""
+        self._pool(cache)
+        N, Hq, H, D = self.N, self.q_heads, self.kv_heads, 128
+        if tuple(q.shape) != (N, Hq, D):
+            raise _lib.QAttnError(f"qattn mxfp4 decode step: q must be [{N}, {Hq}, 128]")
+        if rope is not None:
+            self._rope(cache, rope)
+        _lib.require_gpu(q, cache.k4)
+        q = _lib.kernel_input(q, torch.float16)
+        a, st = cache.alloc, _lib.stream_of(q)
+        if rope is None:
+            _lib.call("qattn_mxfp4_quant_rows", _lib.ptr(q), None, _lib.ptr(self.q4), _lib.ptr(self.qs), N * Hq, Hq,
+                      D, st)
+        else:
+            _lib.call("qattn_mxfp4_quant_rows_rope", _lib.ptr(q), _lib.ptr(self.q4), _lib.ptr(self.qs),
+                      _lib.ptr(rope.table), _lib.ptr(self.pos), N, Hq, rope.max_pos, int(rope.interleaved), D, st)
+        _lib.call("qattn_mxfp4_attn_fwd_decode_step", _lib.ptr(self.q4), _lib.ptr(self.qs), _lib.ptr(cache.k4),
+                  _lib.ptr(cache.ks), _lib.ptr(cache.vt), _lib.ptr(cache.vs), _lib.ptr(self.opart),
+                  _lib.ptr(self.ml), _lib.ptr(cache.lens), _lib.ptr(cache.block_table), _lib.ptr(self.seq_rec),
+                  _lib.ptr(self.work), N, self.splits, a.max_seqs, H, Hq // H, a.num_pages, a.page_tokens,
+                  a.max_pages_per_seq, self.kps, D, _qk_scale(D), self.window or 0, self.sinks, st)
+        _lib.call("qattn_mxfp4_decode_step_combine", _lib.ptr(self.opart), _lib.ptr(self.ml), _lib.ptr(self.O),
+                  _lib.ptr(self.lse), _lib.ptr(self.seq_rec), N, self.splits, Hq, H, D, st)
+        return self.O, self.lse

@@ -31,6 +31,10 @@ the autograd rules of ``int8_fwd`` and ``bf16_fwd`` (their backward operators).
     torch.ops.qattn.mxfp4_quant_rows_rope(x, cos_sin, pos, interleaved) -> (q4, qs)
     torch.ops.qattn.mxfp4_varlen_paged_rope(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows,
                                             causal, keys_per_split, cos_sin, pos, interleaved) -> (O, lse)
+    torch.ops.qattn.mxfp4_decode_step_plan(slots, lens, capacity, kv_heads, group, keys_per_split, splits,
+                                           window, sinks) -> (seq_tab, tiles, pos, seq_rec)
+    torch.ops.qattn.mxfp4_decode_step(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, splits,
+                                      keys_per_split, window, sinks) -> (O, lse)
 
 Shapes follow the drop-in functions (attention_int8.py:259-262 for the int8 outputs) except that
 k_i8 is returned row-major [B*Hkv*Sk, D] (the drop-in's k_i8T is its transposed view: an operator
@@ -48,7 +52,7 @@ from . import _lib
 
 __all__ = ["int8_quant", "int8_fwd", "int8_bwd", "bf16_fwd", "bf16_bwd", "jvp_fwd", "mxfp4_fwd",
            "mxfp4_fwd_ex", "mxfp4_cached", "mxfp4_decode", "mxfp4_decode_paged", "mxfp4_varlen_paged",
-           "mxfp4_quant_rows_rope"]
+           "mxfp4_quant_rows_rope", "mxfp4_decode_step_plan", "mxfp4_decode_step"]
 
 _lib.load_ops()
 _ops = torch.ops.qattn
@@ -165,6 +169,19 @@ def _(x, cos_sin, pos, interleaved):
 @torch.library.register_fake("qattn::mxfp4_varlen_paged_rope")
 def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal, keys_per_split, cos_sin, pos,
       interleaved):
+    T, H, D = q.shape
+    return (q.new_empty((T, H, D), dtype=torch.float16), q.new_empty((T, H), dtype=torch.float32))
+
+
+@torch.library.register_fake("qattn::mxfp4_decode_step_plan")
+def _(slots, lens, capacity, kv_heads, group, keys_per_split, splits, window, sinks):
+    n = slots.shape[0]
+    e = lambda *s: slots.new_empty(s, dtype=torch.int32)  # noqa: E731
+    return e(n, 4), e(n, 2), e(n), e(n, 8)
+
+
+@torch.library.register_fake("qattn::mxfp4_decode_step")
+def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, splits, keys_per_split, window, sinks):
     T, H, D = q.shape
     return (q.new_empty((T, H, D), dtype=torch.float16), q.new_empty((T, H), dtype=torch.float32))
 
@@ -378,3 +395,23 @@ def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=N
                                               kps, min(W, 1 << 26), min(S, 1 << 26))
     return _ops.mxfp4_varlen_paged(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens, cache.block_table,
                                    rec_d, work_d, part_rows, int(bool(causal)), kps)
+
+
+def mxfp4_decode_step_plan(step, cache):
+    """The tables of ``kv_cache_mxfp4.DecodeStep.append`` as one operator: from ``step.slots`` (what
+    ``step.prepare`` uploaded) and ``cache.lens``, the lengths BEFORE the step's append -> new device tensors
+    (seq_tab [N, 4], tiles [N, 2], pos [N], seq_rec [N, 8]), what ``qattn_mxfp4_decode_step_plan`` writes into
+    the step's own tables."""
+    a = cache.alloc
+    return _ops.mxfp4_decode_step_plan(step.slots, cache.lens, a.max_pages_per_seq * a.page_tokens, step.kv_heads,
+                                       step.q_heads // step.kv_heads, step.kps, step.splits, step.window or 0,
+                                       step.sinks)
+
+
+def mxfp4_decode_step(q, step, cache, seq_rec=None):
+    """``kv_cache_mxfp4.DecodeStep.attend`` (without ``rope``) as one operator that allocates its outputs: q [N,
+    Hq, 128] against ``cache`` after the step's append, over ``seq_rec`` (default: the step's own, which its
+    ``append`` wrote) and the step's ``work`` -> (O, lse), the Python call's bits."""
+    return _ops.mxfp4_decode_step(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens, cache.block_table,
+                                  step.seq_rec if seq_rec is None else seq_rec, step.work, step.splits, step.kps,
+                                  step.window or 0, step.sinks)
