@@ -20,6 +20,13 @@ against ``oracle.mxfp4``), "a refusal changes nothing" after every refusal, and 
 operation and for the slots an operation touched: bit for bit against a fresh twin pool built from the model's
 rows by one padded append, and against the float64 restatements at the bars of
 ``test_trees_against_the_restatement``.  A failure raises :class:`CheckFailed`, which names the check.
+
+With ``Spec.steps`` on (``STEP_SCHEDULES``) the generator also draws decode steps (``DecodeStep``): a ``step``
+operation lists slots, one of the schedule's two configurations (``step_cfgs``: plain, and windowed at a
+``(W, S)`` of TRIMS), "eager" or "graph", ``rope`` or not.  In the model it is ``append_packed(ids, [1] * n)``
+(a rope step stores the key rotated to the length before the step) and one causal query per slot; the
+refusals are ``prepare``'s, in its order.  ``Harness.stepped`` sends the listed rows through ``attended`` as mode
+"step" and holds the padding rows to O = 0, lse = -inf.
 """
 from __future__ import annotations
 
@@ -29,6 +36,7 @@ import random
 import torch
 
 import mxfp4_ragged_ref as RR
+import mxfp4_rope_ref as ROPE
 import mxfp4_tree_ref as TR
 import mxfp4_varlen_helpers as VH
 import mxfp4_window_ref as WR
@@ -37,16 +45,25 @@ from oracle import mxfp4 as M
 D, HQ, HKV = 128, 4, 2
 MAX_TOKENS = {64: 384, 256: 768}        # max_pages_per_seq * P
 N_OPS = 40
+STEP_N_OPS = 48                         # of a schedule with steps
 BARS = (2e-2, 1e-4, 2e-3)               # max|dO|, max|dlse|, relL2: test_trees_against_the_restatement's
 KPS = (64, 128, None)
 TRIMS = {64: ((16, 0), (16, 4), (70, 64), (130, 4), (40, 70)), 256: ((16, 0), (70, 4), (130, 0), (16, 256))}
 
-Spec = collections.namedtuple("Spec", "seed P slots pages smoothed n_ops")
+ROPE_MAX = 800                          # rows of the rotary table of the rope steps (> MAX_TOKENS + 1)
+
+# ``steps``: the schedule also draws decode steps (kv_cache_mxfp4.DecodeStep); off, _Gen draws what it always drew
+Spec = collections.namedtuple("Spec", "seed P slots pages smoothed n_ops steps", defaults=(False,))
 
 # (seed, P, smoothed): the schedules both test files replay; one per page size runs a smoothed pool
 SCHEDULES = ((5, 64, False), (29, 64, True), (89, 64, False), (94, 64, False), (126, 64, False),
              (141, 64, False), (9, 256, False), (33, 256, True), (37, 256, False), (76, 256, False),
              (78, 256, False), (115, 256, False))
+
+# (seed, P, smoothed) with ``steps`` on: the schedules that hold the decode step, eager and graph-replayed
+# (tests/test_mxfp4_lifecycle_model.py::STEP_COVERAGE)
+STEP_SCHEDULES = ((7, 64, True), (9, 64, False), (72, 64, False), (103, 64, False), (26, 256, False),
+                  (43, 256, True), (99, 256, False), (108, 256, False))
 
 # what a refusal of each kind must name
 WORD = {"out_of_pages_append": "out of pages", "out_of_pages_packed": "out of pages",
@@ -54,13 +71,55 @@ WORD = {"out_of_pages_append": "out of pages", "out_of_pages_packed": "out of pa
         "max_pages": "max_pages_per_seq", "fork_nonempty": "not empty",
         "fork_trimmed": "trimmed", "gather_trimmed": "trimmed", "plain_trimmed": "trimmed",
         "window_too_large": "trimmed", "stale_free": "stale", "stale_trim": "stale", "stale_rollback": "stale",
-        "rollback_shared": "shared", "tree_window": "tree", "shared_window": "share_prefix"}
+        "rollback_shared": "shared", "tree_window": "tree", "shared_window": "share_prefix",
+        # DecodeStep.prepare, in the order of its checks
+        "step_slots": "distinct", "step_empty": "at least one cached token", "step_full": "would pass",
+        "step_plain_trimmed": "trimmed", "step_window_trimmed": "trimmed", "step_out_of_pages": "out of pages"}
 
 
-def spec(seed: int, P: int, n_ops: int = N_OPS, smoothed: bool = False) -> Spec:
+def spec(seed: int, P: int, n_ops: int = N_OPS, smoothed: bool = False, steps: bool = False) -> Spec:
     """The pool of schedule ``(seed, P)``: 5 or 6 slots and a pool small enough to run out by itself."""
     pages = 14 + (5 * seed) % 11 if P == 64 else 6 + seed % 3
-    return Spec(seed, P, 5 + seed % 2, pages, smoothed, n_ops)
+    return Spec(seed, P, 5 + seed % 2, pages, smoothed, n_ops, steps)
+
+
+def step_spec(seed: int, P: int, smoothed: bool = False) -> Spec:
+    """The pool of the step schedule ``(seed, P)``."""
+    return spec(seed, P, STEP_N_OPS, smoothed, steps=True)
+
+
+def step_cfgs(sp: Spec) -> tuple:
+    """The two step configurations ``(kps, window, sinks)`` of a schedule: plain at one ``kps``, windowed at a
+    ``(W, S)`` of TRIMS[P] at another."""
+    rng = random.Random(7919 * sp.seed + sp.P)
+    k0, k1 = rng.sample(KPS, 2)
+    return (k0, None, 0), (k1, *rng.choice(TRIMS[sp.P]))
+
+
+def step_rows(seed: int, n: int):
+    """The fp16 (k, v [n, Hkv, 128], q [n, Hq, 128]) of a step of n entries; the rows of padding entries hold
+    values too."""
+    g = torch.Generator().manual_seed(seed + 29)
+    r = lambda h: torch.randn((n, h, D), generator=g).half()  # noqa: E731
+    return r(HKV), r(HKV), r(HQ)
+
+
+_ROPE = []
+
+
+def rope_of(sp: Spec) -> tuple:
+    """(table fp32 [ROPE_MAX, 128] on the CPU, interleaved) of the rope steps of a schedule; odd seeds pair
+    elements (2i, 2i + 1)."""
+    if not _ROPE:
+        _ROPE.append(ROPE.table(ROPE_MAX))
+    return _ROPE[0], bool(sp.seed % 2)
+
+
+def rotated(sp: Spec, x, pos):
+    """x fp16 [n, H, 128] rotated to ``pos`` as include/qattn.h defines it bit for bit (mxfp4_rope_ref.rope_ref),
+    so that the rows are what the pool must quantise."""
+    tab, interleaved = rope_of(sp)
+    return ROPE.rope_ref(x, tab, list(pos), interleaved)
 
 
 def rows(seed: int, n: int):
@@ -112,6 +171,8 @@ class Seq:
         self.trim_shared = self.holds_trimmed = False
         self.family = None
         self.exp = None             # the expected bytes (Model.expected)
+        self.parent = None          # the Seq this one was forked from
+        self.after = None           # "rollback" / "accept" until the next step
 
     @property
     def holes(self) -> set:
@@ -128,6 +189,8 @@ class Model:
         self.ckpts, self.next_id, self.families, self.tick = [], 0, 0, 0
         self.cov = collections.Counter()
         self.pending_reuse = None   # the slot whose shared-source free released unshared pages
+        self.frees = [0] * sp.slots  # how often each slot was freed
+        self.stepped = {}           # per step configuration, its last step: {"ids", "frees"}
 
     def _bump(self, s) -> None:
         self.tick += 1
@@ -182,6 +245,8 @@ class Model:
         o = op["op"]
         if o == "append_packed":
             return self._grow_refusal(zip(op["ids"], op["counts"]), "out_of_pages_packed")
+        if o == "step":
+            return self._step_refusal(op)
         if o == "draft":
             return self._grow_refusal(zip(op["ids"], [len(t) for t in op["trees"]]), "out_of_pages_packed")
         if o == "append":
@@ -215,6 +280,24 @@ class Model:
                 elif window_pages(s.L, n, op["window"], op["sinks"], self.P) & s.holes:
                     return "window_too_large"
         return None
+
+    def _step_refusal(self, op):
+        """DecodeStep.prepare's checks, in its order."""
+        ids, W, S = op["ids"], op["window"], op["sinks"]
+        if len(ids) > self.nslots or len(set(ids)) != len(ids) or any(not 0 <= b < self.nslots for b in ids):
+            return "step_slots"
+        seqs = [self.seqs[b] for b in ids]
+        if any(not s.L for s in seqs):
+            return "step_empty"
+        if any(s.L + 1 > MAX_TOKENS[self.P] for s in seqs):
+            return "step_full"
+        for s in seqs:      # the lengths the step attends at
+            if W is None:
+                if s.holes:
+                    return "step_plain_trimmed"
+            elif window_pages(s.L + 1, 1, W, S, self.P) & s.holes:
+                return "step_window_trimmed"
+        return self._grow_refusal([(b, 1) for b in ids], "step_out_of_pages")
 
     def note_refusal(self, kind: str, op=None) -> None:
         self.cov["refused " + kind] += 1
@@ -281,7 +364,10 @@ class Model:
                 self.cov["fork after the checkpoint, L0 % P == 0: rollback allowed"] += 1
             if s.holes:
                 self.cov["trim before the checkpoint, then rollback"] += 1
+            if b in ck["stepped"]:
+                self.cov["step between a checkpoint and its rollback"] += 1
         self._cut(b, L0)
+        ck["stepped"].discard(b)
         s.draft, s.mutated = None, True
         self.epoch[b] += 1
         self.why[b] = "rollback"
@@ -311,6 +397,7 @@ class Model:
             d.k, d.v, d.L = s.k, s.v, L
             self._bump(d)
             d.is_fork, d.family, s.has_forks, s.mutated = True, s.family, True, False
+            d.parent = s
             if self.mean is not None:
                 self.mean[op["dst"]] = self.mean[op["src"]]
             for ck in self.ckpts:
@@ -325,6 +412,7 @@ class Model:
                     if any(held[i] == 1 for i in s.ids if i is not None):
                         self.pending_reuse = b
                 self.seqs[b] = Seq(was_freed=s.L > 0 or s.was_freed)
+                self.frees[b] += 1
                 self._bump(self.seqs[b])
                 self.epoch[b] += 1
                 self.why[b] = "free"
@@ -351,7 +439,8 @@ class Model:
             self.ckpts.append({"slots": list(op["slots"]), "L0": {b: self.seqs[b].L for b in op["slots"]},
                                "npages": {b: len(self.seqs[b].ids) for b in op["slots"]},
                                "epochs": {b: self.epoch[b] for b in op["slots"]},
-                               "rounds": collections.Counter(), "forked_after": set(), "draft": None})
+                               "rounds": collections.Counter(), "forked_after": set(), "draft": None,
+                               "stepped": set()})
             return []
         if o == "draft":
             ck = self.ckpts[op["ckpt"]]
@@ -371,6 +460,7 @@ class Model:
             slots = self.ckpts[op["ckpt"]]["slots"] if op["slots"] is None else op["slots"]
             for b in slots:
                 self._rollback(op["ckpt"], b)
+                self.seqs[b].after = "rollback"
             return list(slots)
         if o == "accept":
             d = self.ckpts[op["ckpt"]]["draft"]
@@ -385,10 +475,53 @@ class Model:
                     idx = torch.tensor([first + i for i in acc])
                     self._grow(b, len(acc), *((k[idx], v[idx]) if self.data else ()))
                 first += c
+                self.seqs[b].after = "accept"
             return list(d["ids"])
+        if o == "step":
+            return self._step(op)
         if o == "attend":
             self._cover_attend(op)
         return []
+
+    def _step(self, op) -> list:
+        """One decode step: ``append_packed(ids, [1] * n)`` of the first n rows of the step's k, v (with ``rope``
+        the key of slot b rotated to L_b, its length before the step); the attend that follows changes nothing."""
+        ids, cfg, P, cov = op["ids"], op["cfg"], self.P, self.cov
+        prev, n = self.stepped.get(cfg), len(ids)
+        replayed = op["how"] == "graph" and prev is not None    # the first step of a configuration warms up
+        cov["step replayed" if replayed else "step eager"] += 1
+        cov["step with padding entries" if n < self.nslots else "step listing every slot"] += 1
+        if replayed and prev["ids"] != ids:
+            cov["replay whose listed slots or their order differ from the configuration's previous step"] += 1
+        if op["rope"]:
+            cov["rope step"] += 1
+        live = lambda a, b: any(t is a for t in self.seqs) and set(a.ids) & set(b.ids) - {None}  # noqa: E731
+        for b in ids:
+            s, L = self.seqs[b], self.seqs[b].L
+            cov["step at L % 64 == 63 (fills a tile)"] += L % 64 == 63
+            cov["step at L % 64 == 0 (opens a tile)"] += L % 64 == 0
+            cov["step at L % P == 0 (opens a page)"] += L % P == 0
+            cov["step on a fork while its source lives"] += bool(s.parent is not None and live(s.parent, s))
+            cov["step on a source while its fork lives"] += any(t.parent is s and live(t, s) for t in self.seqs)
+            cov["step on a slot freed and filled again since the configuration's previous step"] += \
+                prev is not None and self.frees[b] > prev["frees"][b]
+            if op["window"] is not None:    # window_pages: the sink run and the window run, apart or touching
+                gap = (L + 1 - op["window"]) // 64 > ceil_div(min(op["sinks"], L + 1), 64)
+                cov["windowed step on a slot with holes (a gap)"] += bool(gap and s.holes)
+                cov["windowed step without a gap"] += not gap
+            if s.after:
+                cov["step after " + ("a rollback" if s.after == "rollback" else "an accept")] += 1
+                s.after = None
+            for ck in self.ckpts:
+                if b in ck["slots"] and ck["epochs"][b] == self.epoch[b]:
+                    ck["stepped"].add(b)
+        if self.data:
+            k, v, _ = step_rows(op["seed"], self.nslots)
+            k = rotated(self.sp, k[:n], [self.seqs[b].L for b in ids]) if op["rope"] else k
+        for j, b in enumerate(ids):
+            self._grow(b, 1, *((k[j:j + 1], v[j:j + 1]) if self.data else ()))
+        self.stepped[cfg] = {"ids": list(ids), "frees": list(self.frees)}
+        return list(ids)
 
     def _cover_attend(self, op) -> None:
         mode = op["mode"]
@@ -487,6 +620,9 @@ class _Gen:
     def __init__(self, sp: Spec):
         self.sp, self.rng, self.m = sp, random.Random(1000 * sp.seed + sp.P), Model(sp, data=False)
         self.n, self.refused = 0, 0
+        # with steps on: the step move (set until STEP_COVERAGE occurs over STEP_SCHEDULES) and its configurations
+        self.weights = self.WEIGHTS + ((("step", 12),) if sp.steps else ())
+        self.cfgs = step_cfgs(sp) if sp.steps else ()
 
     # -- helpers
     def live(self, whole=False):
@@ -579,6 +715,8 @@ class _Gen:
                 if (m.seqs[b].L - W + 1) // P > ceil_div(S, P) and m.seqs[b].trim in (None, (W, S))]
         if not opts:
             return None
+        if self.sp.steps and rng.random() < .7:   # the trim the windowed steps can follow
+            opts = [o for o in opts if o[1:] == self.cfgs[1][1:]] or opts
         shared = [o for o in opts if m.shares(o[0])]
         b, W, S = rng.choice(shared if shared and rng.random() < .7 else opts)
         return {"op": "trim", "slots": [b], "window": W, "sinks": S}
@@ -620,6 +758,11 @@ class _Gen:
         cand = [(c, b) for c, ck in enumerate(m.ckpts) for b in ck["slots"]
                 if ck["epochs"][b] == m.epoch[b] and m.seqs[b].L >= ck["L0"][b]]
         drafted = [(c, b) for c, b in cand if m.seqs[b].draft and m.seqs[b].draft["ckpt"] == c]
+        stepped = [(c, b) for c, b in cand if b in m.ckpts[c]["stepped"] and not m.seqs[b].draft] \
+            if self.sp.steps else []
+        if stepped and rng.random() < .6:     # a rollback that takes decode steps back
+            c, b = rng.choice(stepped)
+            return {"op": "rollback", "ckpt": c, "slots": [b]}
         if not cand or not drafted and rng.random() < .75:
             return None
         c, b = rng.choice(drafted if drafted and rng.random() < .85 else cand)
@@ -718,6 +861,53 @@ class _Gen:
         op["q_lens"] = [self._q_len(m.seqs[b].L) for b in op["ids"]]
         return op
 
+    def _steppable(self, cfg: int) -> list:
+        """The slots a step of configuration ``cfg`` may list: not empty, not full, no outstanding draft (as for
+        ``append_packed``) and no hole the step would read."""
+        m, P, (_, W, S) = self.m, self.sp.P, self.cfgs[cfg]
+        return [b for b, s in enumerate(m.seqs) if s.L and not s.draft and s.L < MAX_TOKENS[P]
+                and not (s.holes if W is None else window_pages(s.L + 1, 1, W, S, P) & s.holes)]
+
+    def _step_op(self, cfg: int, ids) -> dict:
+        kps, W, S = self.cfgs[cfg]
+        return {"op": "step", "ids": list(ids), "cfg": cfg, "kps": kps, "window": W, "sinks": S,
+                "how": self.rng.choice(("eager", "graph", "graph")), "rope": self.rng.random() < .4,
+                "seed": self.seed()}
+
+    def step(self):
+        rng, m = self.rng, self.m
+        cfg = rng.randrange(2)
+        cand = self._steppable(cfg)
+        if not cand:
+            return None
+        ids = rng.sample(cand, len(cand) if rng.random() < .35 else rng.randint(1, len(cand)))
+        holed = [b for b in cand if m.seqs[b].holes]
+        if holed and rng.random() < .7 and not set(holed) & set(ids):
+            ids[0] = rng.choice(holed)
+        return self._step_op(cfg, ids)
+
+    def _illegal_steps(self, cheap: bool = True) -> list:
+        """Steps DecodeStep.prepare must refuse, of the kinds the state offers."""
+        rng, m, P = self.rng, self.m, self.sp.P
+        cfg = rng.randrange(2)
+        good = self._steppable(cfg)
+        base = rng.sample(good, min(len(good), 2))
+        offers = []
+        if cheap and rng.random() < .3:     # the refusals every state offers
+            empty = [b for b, s in enumerate(m.seqs) if not s.L]
+            offers += [self._step_op(cfg, base + [b]) for b in empty[:1]]
+            if base:
+                offers.append(self._step_op(cfg, base + [rng.choice((base[0], m.nslots, -1))]))
+        for b, s in enumerate(m.seqs):
+            if s.L == MAX_TOKENS[P]:
+                offers += [self._step_op(cfg, base + [b])] * 3
+            if s.holes and not s.draft and s.L < MAX_TOKENS[P]:
+                offers += [self._step_op(c, [x for x in base if x in self._steppable(c)] + [b]) for c in (0, 1)]
+        opening = [b for b in good if m.seqs[b].L % P == 0]
+        if len(opening) > m.free:
+            offers += [self._step_op(cfg, rng.sample(opening, len(opening)))] * 3
+        return offers
+
     def illegal(self):
         """An operation the pool must refuse, of a kind the state offers (the rarest kinds first)."""
         rng, m = self.rng, self.m
@@ -772,6 +962,8 @@ class _Gen:
                 else:
                     a.update(mode="tree+window", window=64, trees=[[-1]] * len(a["ids"]))
                 offers.append(a)
+        if self.sp.steps:
+            offers += self._illegal_steps()
         offers = [o for o in offers if m.refusal(o)]
         if not offers:
             return None
@@ -784,7 +976,18 @@ class _Gen:
             ids = rng.sample(range(m.nslots), 3)
             return {"op": "append_packed", "ids": ids, "counts": [rng.randint(40, 70) for _ in ids],
                     "seed": self.seed()}
-        names, weights = zip(*self.WEIGHTS)
+        names, weights = zip(*self.weights)
+        if self.sp.steps and rng.random() < .4 and self.refused <= .25 * (self.n + 4):
+            # a step refusal of a kind this schedule has not had yet, whenever the state offers one
+            new = [o for o in self._illegal_steps(cheap=False) if m.refusal(o) and not m.cov["refused " + m.refusal(o)]]
+            if new:
+                return rng.choice(new)
+            fill = [b for b in self._steppable(0) if m.seqs[b].L % self.sp.P]
+            if not m.free and fill and not m.cov["refused step_out_of_pages"]:
+                # the pool is empty: fill a page to its end, so that a step on that slot needs a page
+                b = rng.choice(fill)
+                return {"op": "append_packed", "ids": [b], "counts": [self.sp.P - m.seqs[b].L % self.sp.P],
+                        "seed": self.seed()}
         for _ in range(200):
             name = rng.choices(names, weights)[0]
             if name == "free" and m.free > 3 and rng.random() < .5 and not any(
@@ -814,9 +1017,14 @@ class _Gen:
         return out
 
 
-def schedule(seed: int, P: int, n_ops: int = N_OPS, smoothed: bool = False) -> list:
+def schedule(seed: int, P: int, n_ops: int = N_OPS, smoothed: bool = False, steps: bool = False) -> list:
     """The operations of schedule ``(seed, P)``; each carries the refusal the model predicts ("refuse")."""
-    return _Gen(spec(seed, P, n_ops, smoothed)).run()
+    return _Gen(spec(seed, P, n_ops, smoothed, steps)).run()
+
+
+def step_schedule(seed: int, P: int, smoothed: bool = False) -> list:
+    """The operations of the step schedule ``(seed, P)``: STEP_N_OPS of them, decode steps among them."""
+    return _Gen(step_spec(seed, P, smoothed)).run()
 
 
 def scripted(sp: Spec, ops) -> list:
@@ -825,6 +1033,8 @@ def scripted(sp: Spec, ops) -> list:
     for i, op in enumerate(ops):
         if op["op"] == "attend":
             op = ops[i] = {"kps": 64, "causal": True, "window": None, "sinks": 0, "share": False, "trees": None, **op}
+        if op["op"] == "step":
+            op = ops[i] = {"cfg": 0, "kps": 64, "window": None, "sinks": 0, "how": "eager", "rope": False, **op}
         op.setdefault("seed", 900001 + 101 * i)
         op["refuse"] = m.refusal(op)
         m.note_refusal(op["refuse"], op) if op["refuse"] else m.apply(op)
@@ -877,6 +1087,8 @@ def name_of(op) -> str:
         extra = f"ckpt{op['ckpt']}{[len(a) for a in op['accepted']]}"
     if o == "rollback":
         extra = f"ckpt{op['ckpt']}{op['slots']}"
+    if o == "step":
+        extra = f"{op['ids']}cfg{op['cfg']}:{op['how']}" + ("+rope" if op["rope"] else "")
     return f"{o}{extra}" + (f"!{op['refuse']}" if op.get("refuse") else "")
 
 
@@ -911,7 +1123,10 @@ class Harness:
 
     ``backend`` has ``device``, ``allocate(num_pages, P, slots, Hkv, max_pages, k_mean, free_order)``,
     ``varlen(q, pool, ids, q_lens, **kw)``, ``decode(q, pool, causal, keys_per_split)``, ``sync()`` and
-    ``ops_varlen`` (the operator form of ``varlen``, or None)."""
+    ``ops_varlen`` (the operator form of ``varlen``, or None); for a schedule with steps also ``step(pool, cfg,
+    ids, k, v, q, rope, how) -> (O [N, Hq, 128], lse [N, Hq])`` -- one decode step of configuration ``cfg`` =
+    ``(kps, window, sinks)`` over the slots ``ids``, ``rope`` None or ``rope_of(sp)``, ``how`` "eager" or "graph"
+    --, ``step_kps(cfg)``, the keys per split that configuration runs at, and ``ops_step`` (below, or None)."""
 
     def __init__(self, backend, sp: Spec, log=print):
         self.be, self.sp, self.m, self.log = backend, sp, Model(sp), log
@@ -953,10 +1168,20 @@ class Harness:
             pool.accept(self.ckpts[op["ckpt"]], self.dev(k), self.dev(v), d["ids"], d["counts"], op["accepted"])
         elif o == "attend":
             return self.call(pool, op)
+        elif o == "step":
+            k, v, q = (self.dev(t) for t in step_rows(op["seed"], self.sp.slots))
+            O, lse = self.be.step(pool, (op["kps"], op["window"], op["sinks"]), op["ids"], k, v, q,
+                                  rope_of(self.sp) if op["rope"] else None, op["how"])
+            return O.cpu(), lse.cpu()
+
+    @staticmethod
+    def q_of(op):
+        """The packed queries of an attend operation: those of its seed, or the ones it carries (a step's)."""
+        return op["q"] if "q" in op else queries(op["seed"], sum(op["q_lens"]))
 
     def call(self, pool, op, share=None, fn=None):
         """The attention call of ``op`` on ``pool`` -> (O, lse) on the CPU, packed [T, Hq, ..]."""
-        q = self.dev(queries(op["seed"], sum(op["q_lens"])))
+        q = self.dev(self.q_of(op))
         if op["mode"] == "decode":
             n = op["q_lens"][0]
             O, lse = self.be.decode(q.view(self.sp.slots, n, HQ, D).transpose(1, 2).contiguous(), pool, op["causal"],
@@ -1008,10 +1233,29 @@ class Harness:
         self.check(what)
         if op["op"] == "attend" and not kind:
             self.attended(op, out, what)
+        if op["op"] == "step" and not kind:
+            self.stepped(op, out, what)
+            touched = []    # (the step attended on exactly the slots it touched)
         for b in touched:
             if self.m.seqs[b].L:
                 self.attended(self.touch(b), None, what)
         self.n += 1
+
+    def stepped(self, op, out, what=""):
+        """The (O, lse) [N, ..] of a step: the listed entries are an attend operation of mode "step" (one causal
+        query per slot at the step's keys per split and window; for a rope step the queries rotated to the
+        lengths before the step, and no ``rope=``), the padding entries O = 0 and lse = -inf."""
+        (O, lse), ids, n = out, op["ids"], len(op["ids"])
+        need(not bool(O[n:].any()) and bool((lse[n:] == float("-inf")).all()), "padding rows",
+             lambda: f"{what}: O {O[n:].abs().max():.3e}, lse {lse[n:].tolist()}")
+        q = step_rows(op["seed"], self.sp.slots)[2][:n]
+        if op["rope"]:
+            q = rotated(self.sp, q, [self.m.seqs[b].L - 1 for b in ids])
+        cfg = (op["kps"], op["window"], op["sinks"])
+        att = {"op": "attend", "mode": "step", "ids": ids, "q_lens": [1] * n, "kps": self.be.step_kps(cfg),
+               "causal": True, "window": op["window"], "sinks": op["sinks"], "share": False, "trees": None,
+               "seed": op["seed"], "q": q}
+        self.attended(att, (O[:n].contiguous(), lse[:n].contiguous()), f"{what} {name_of(op)}")
 
     def touch(self, b: int):
         """A small causal call on slot b (under its window when it is trimmed), or None where the holes allow
@@ -1103,7 +1347,7 @@ class Harness:
         first, worst = 0, [0.0, 0.0, 0.0]
         for j, (b, n) in enumerate(zip(op["ids"], op["q_lens"])):
             s = self.m.seqs[b]
-            q = queries(op["seed"], sum(op["q_lens"]))[first:first + n]
+            q = self.q_of(op)[first:first + n]
             par = None if op["trees"] is None else op["trees"][j]
             RO, Rl = restated(mode, q, s.k, s.v, op["causal"], op["kps"], op["window"], op["sinks"], par)
             Oj, lj = O[first:first + n].float(), lse[first:first + n]
@@ -1135,6 +1379,18 @@ class Harness:
                          f"seed={self.sp.seed} P={self.sp.P} {name_of(op)}")
                     done.append(mode)
                     break
+        for cfg in range(2 if self.sp.steps and self.be.ops_step else 0):
+            ids = g._steppable(cfg)
+            if not ids or self.m.refusal(g._step_op(cfg, ids)):     # (the pool may be out of pages)
+                continue
+            op = {**g._step_op(cfg, ids), "how": "eager", "rope": False}
+            k, v, q = (self.dev(t) for t in step_rows(op["seed"], self.sp.slots))
+            pairs = self.be.ops_step(self.pool, (op["kps"], op["window"], op["sinks"]), ids, k, v, q)
+            need(all(x.dtype == y.dtype and torch.equal(x, y) for x, y in pairs),
+                 "the operator equals the Python call", f"seed={self.sp.seed} P={self.sp.P} {name_of(op)}")
+            self.m.apply(op)
+            self.check(f"seed={self.sp.seed} P={self.sp.P} operators {name_of(op)}")
+            done.append(f"step cfg{cfg}")
         return done
 
     def run(self, ops):

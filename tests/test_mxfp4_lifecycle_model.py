@@ -7,13 +7,19 @@
    harness calls -- the real ``PageAllocator``, fp16 rows per physical page, a ``vtail``, epochs, the oracle's
    quantisers behind ``kv`` and the float64 restatements as its attention.  The clean fake passes every schedule;
    each planted fault (a one-line variant) fails the harness on the schedule and the check FAULTS names.
+3. The decode step: the old schedules are, by digest, what they were before the generator learnt the ``step``
+   operation; over STEP_SCHEDULES every situation of STEP_COVERAGE occurs at least twice and the old operations
+   still happen around the steps; ``FakeBackend.step`` (``prepare``'s checks in its order, one row through
+   ``_write``, the float64 restatement; no graph) passes every step schedule and five planted faults on it fail.
 """
 import collections
+import hashlib
 
 import pytest
 import torch
 
 import mxfp4_lifecycle as LC
+import mxfp4_rope_ref as R
 from mxfp4_lifecycle import D, HKV, ceil_div
 from oracle import mxfp4 as M
 from quantizedattention_amd._lib import QAttnError
@@ -42,8 +48,83 @@ COVERAGE = (
     "attend causal", "attend noncausal", "attend window", "attend shared", "attend tree", "attend decode")
 
 
+# every situation must occur at least twice over STEP_SCHEDULES
+STEP_COVERAGE = (
+    "step eager", "step replayed", "step with padding entries", "step listing every slot",
+    "replay whose listed slots or their order differ from the configuration's previous step",
+    "step at L % 64 == 63 (fills a tile)", "step at L % 64 == 0 (opens a tile)", "step at L % P == 0 (opens a page)",
+    "step on a fork while its source lives", "step on a source while its fork lives",
+    "step on a slot freed and filled again since the configuration's previous step",
+    "windowed step on a slot with holes (a gap)", "windowed step without a gap",
+    "step between a checkpoint and its rollback", "step after a rollback", "step after an accept", "rope step",
+    "refused step_slots", "refused step_empty", "refused step_full", "refused step_plain_trimmed",
+    "refused step_window_trimmed", "refused step_out_of_pages")
+
+# sha256(repr(schedule))[:16] of every entry of SCHEDULES, recorded before the generator learnt the step
+# operation: with ``steps`` off it draws what it drew then
+DIGESTS = {
+    (5, 64, False): "a3f8778adada5fb7", (29, 64, True): "005bb15be9b49719", (89, 64, False): "c91f4dd3461a94b3",
+    (94, 64, False): "9d0fbc3421478c8d", (126, 64, False): "c2f84ae876f665f1", (141, 64, False): "f59c38305d467eff",
+    (9, 256, False): "43a425529775e0ee", (33, 256, True): "0d26b49690f72961", (37, 256, False): "8a5e65a6f4dc4db9",
+    (76, 256, False): "4d1542d679446d9b", (78, 256, False): "1c3959ef1b430b64", (115, 256, False): "a14a1b1bfa9f6d9c"}
+
+
 def _ops(seed, P, smoothed):
+    if (seed, P, smoothed) in LC.STEP_SCHEDULES:
+        return LC.step_spec(seed, P, smoothed), LC.step_schedule(seed, P, smoothed)
     return LC.spec(seed, P, smoothed=smoothed), LC.schedule(seed, P, smoothed=smoothed)
+
+
+def test_the_old_schedules_are_what_they_were():
+    assert set(DIGESTS) == set(SCHEDULES) and len(SCHEDULES) == 12 and not set(SCHEDULES) & set(LC.STEP_SCHEDULES)
+    for (seed, P, smoothed), digest in DIGESTS.items():
+        ops = LC.schedule(seed, P, smoothed=smoothed)
+        assert hashlib.sha256(repr(ops).encode()).hexdigest()[:16] == digest, (seed, P)
+        assert not any(op["op"] == "step" for op in ops)
+
+
+def test_step_schedules_cover_the_situations():
+    total = collections.Counter()
+    per_size = collections.Counter()
+    for seed, P, smoothed in LC.STEP_SCHEDULES:
+        sp, ops = _ops(seed, P, smoothed)
+        assert sp.steps and len(ops) == LC.STEP_N_OPS and ops == LC.step_schedule(seed, P, smoothed)     # seeded
+        per_size[P, smoothed] += 1
+        cfgs = LC.step_cfgs(sp)
+        assert cfgs[0][1] is None and cfgs[1][1:] in LC.TRIMS[P] and cfgs[0][0] != cfgs[1][0]
+        assert {c[0] for c in cfgs} <= set(LC.KPS)
+        for op in ops:
+            if op["op"] == "step":
+                assert (op["kps"], op["window"], op["sinks"]) == cfgs[op["cfg"]] and op["how"] in ("eager", "graph")
+        total += LC.coverage(sp, ops)
+        # the old operations still happen around the steps
+        done = collections.Counter(op["op"] for op in ops if not op["refuse"])
+        assert all(done[o] for o in ("fork", "free", "trim", "rollback", "step")), (seed, P, done)
+        assert any(op["op"] == "attend" and not op["refuse"] and (op["share"] or op["trees"] is not None)
+                   for op in ops), (seed, P)
+    for P in (64, 256):
+        assert per_size[P, False] + per_size[P, True] >= 3 and per_size[P, True] >= 1
+    for what in STEP_COVERAGE:
+        print(f"MXFP4-LIFE-COVERAGE {total[what]:3d}  {what}")
+    assert not [w for w in STEP_COVERAGE if total[w] < 2], {w: total[w] for w in STEP_COVERAGE if total[w] < 2}
+
+
+def test_the_rope_rows_of_the_steps_are_the_exact_rotation():
+    """The rows the model stores for a rope step (mxfp4_rope_ref.rope_ref, the bit-for-bit contract) against the
+    float64 rotation ``rope_exact``: the two differ by the roundings of the contract alone -- two fp32 products
+    and their fp32 sum, 1.5 * 2^-24 of |a c| + |b s|, then half an fp16 ulp of the result."""
+    seed, P, smoothed = LC.STEP_SCHEDULES[0]
+    sp, n = LC.step_spec(seed, P, smoothed), 0
+    for op in LC.step_schedule(seed, P, smoothed):
+        if op["op"] == "step" and op["rope"] and not op["refuse"]:
+            k = LC.step_rows(op["seed"], sp.slots)[0]
+            pos = [(37 * i + op["seed"]) % LC.MAX_TOKENS[P] for i in range(sp.slots)]
+            exact, mag = R.rope_exact(k, LC.rope_of(sp)[0], pos, LC.rope_of(sp)[1])
+            got = LC.rotated(sp, k, pos).double()
+            ulp = 2.0 ** (torch.floor(torch.log2(exact.abs().clamp_min(2.0 ** -14))) - 10)
+            assert bool(((got - exact).abs() <= 0.5 * ulp + 1.5 * 2.0 ** -24 * mag + 2.0 ** -25).all())
+            n += 1
+    assert n >= 2
 
 
 def test_schedules_cover_the_situations():
@@ -57,7 +138,8 @@ def test_schedules_cover_the_situations():
         print(f"MXFP4-LIFE-COVERAGE {total[what]:3d}  {what}")
     assert not [w for w in COVERAGE if total[w] < 2], {w: total[w] for w in COVERAGE if total[w] < 2}
     # (every refusal but that of an accept whose pages a later fork holds, which has a schedule of its own)
-    assert set(LC.WORD) - {"out_of_pages_accept"} <= {w[len("refused "):] for w in COVERAGE if w.startswith("refused ")}
+    assert set(LC.WORD) - {"out_of_pages_accept"} <= {w[len("refused "):] for w in COVERAGE + STEP_COVERAGE
+                                                     if w.startswith("refused ")}
 
 
 # ------------------------------------------------------------------------------------------------ the fake pool
@@ -273,10 +355,60 @@ class FakePool:
 
 
 class FakeBackend:
-    device, ops_varlen = "cpu", None
+    device, ops_varlen, ops_step = "cpu", None, None
 
     def __init__(self, fault=None):
         self.fault = fault
+
+    @staticmethod
+    def step_kps(cfg):
+        return cfg[0]
+
+    def step(self, pool, cfg, ids, k, v, q, rope, how):
+        """``DecodeStep`` without a device and without a graph ("graph" and "eager" are one): ``prepare``'s checks
+        in ``prepare``'s order against the real allocator, then one row per listed slot through ``_write`` and
+        the float64 restatement of one causal query per slot."""
+        (kps, W, S), a, P, N, n, fault = cfg, pool.alloc, pool.P, k.shape[0], len(ids), self.fault
+        if n > N or len(set(ids)) != n or any(not 0 <= b < a.max_seqs for b in ids):
+            raise QAttnError(f"fake step: seq_ids must be at most {N} distinct slots")
+        Ls = [pool.lengths[b] for b in ids]
+        if any(L < 1 for L in Ls):
+            raise QAttnError("fake step: every listed sequence needs at least one cached token")
+        if any(L + 1 > LC.MAX_TOKENS[P] for L in Ls):
+            raise QAttnError(f"fake step: a sequence would pass {LC.MAX_TOKENS[P]} keys")
+        for b in ids:
+            pool.lengths[b] += 1
+        try:
+            for b in ids:
+                holes = set(a.holes(b))
+                if holes and (W is None or LC.window_pages(pool.lengths[b], 1, W, S, P) & holes):
+                    raise QAttnError(f"fake step: the step would read trimmed pages of sequence {b}")
+            grown = a.reserve([(b, pool.lengths[b]) for b in ids])
+        except QAttnError:
+            for b in ids:
+                pool.lengths[b] -= 0 if fault == "a refused prepare keeps the lengths it added" else 1
+            raise
+        for b in ids:       # (_write adds it again)
+            pool.lengths[b] -= 1
+        tab, il = rope if rope is not None else (None, False)
+        at = [L + 1 for L in Ls] if fault == "the new key is rotated to L + 1" else Ls
+        kr = R.rope_ref(k[:n], tab, at, il) if rope is not None else k
+        for j, b in enumerate(ids):
+            pool._write(b, kr[j:j + 1], v[j:j + 1])
+        if fault == "a padding entry's row is appended to the slot its index names":
+            for i in range(n, N):
+                if i not in ids and pool.lengths[i] % 64:     # (room in its tile, so in its page)
+                    pool._write(i, k[i:i + 1], v[i:i + 1])
+        pool._upload(bool(grown))
+        qr = R.rope_ref(q[:n], tab, Ls, il) if rope is not None else q
+        O, lse = torch.zeros((N, LC.HQ, D), dtype=torch.float16), torch.full((N, LC.HQ), float("-inf"))
+        for j, b in enumerate(ids):
+            kb, vb = pool.rows(b)
+            if fault == "the step attends over L keys, not L + 1":
+                kb, vb = kb[:, :Ls[j]], vb[:, :Ls[j]]
+            O[j], lse[j] = (t[0] for t in LC.restated(
+                "fake", qr[j:j + 1], kb, vb, True, kps, W, 0 if fault == "a windowed step ignores its sinks" else S))
+        return O, lse
 
     def allocate(self, *args):
         return FakePool(*args, fault=self.fault)
@@ -334,11 +466,12 @@ def test_the_named_regressions_on_the_clean_fake():
     assert e.value.check == "a refusal changes nothing", str(e.value)
 
 
-@pytest.mark.parametrize("seed,P,smoothed", SCHEDULES)
+@pytest.mark.parametrize("seed,P,smoothed", SCHEDULES + LC.STEP_SCHEDULES)
 def test_the_clean_fake_passes(seed, P, smoothed):
     h = _run(seed, P, smoothed)
     assert h.m.cov == LC.coverage(*_ops(seed, P, smoothed))
     assert all(w == [0.0, 0.0, 0.0] for w in h.worst.values()) and h.worst
+    assert ("step" in h.worst) == ((seed, P, smoothed) in LC.STEP_SCHEDULES)
 
 
 # fault -> ((seed, P, smoothed) of a schedule of SCHEDULES that catches it, the check that fails)
@@ -354,13 +487,20 @@ FAULTS = {
     "free does not bump the epoch": ((78, 256, False), "refusal"),            # the stale rollback is not refused
     # "a refusal changes nothing" itself: the first sequences keep the pages they took before the pool ran out
     "append_packed reserves sequence by sequence": ((78, 256, False), "a refusal changes nothing"),
+    # the fake step (FakeBackend.step), on schedules of STEP_SCHEDULES
+    "a refused prepare keeps the lengths it added": ((26, 256, False), "a refusal changes nothing"),
+    "the new key is rotated to L + 1": ((7, 64, True), "K bytes"),
+    "the step attends over L keys, not L + 1": ((108, 256, False), "attention equals the twin pool's"),
+    "a windowed step ignores its sinks": ((43, 256, True), "attention equals the twin pool's"),
+    "a padding entry's row is appended to the slot its index names": ((72, 64, False), "lengths"),
 }
+STEP_FAULTS = tuple(f for f in FAULTS if "step" in f or "prepare" in f or "new key" in f or "padding" in f)
 
 
 @pytest.mark.parametrize("fault", sorted(FAULTS))
 def test_a_planted_fault_is_caught(fault):
     where, check = FAULTS[fault]
-    assert where in SCHEDULES
+    assert where in (LC.STEP_SCHEDULES if fault in STEP_FAULTS else SCHEDULES) and len(STEP_FAULTS) == 5
     with pytest.raises(LC.CheckFailed) as e:
         _run(*where, fault=fault)
     assert e.value.check == check, str(e.value)

@@ -3,6 +3,7 @@ schedules than the suite replays: every schedule ``(seed, P)`` for seed in [firs
 third one on a smoothed pool, on the real ``PagedKVFP4`` with the model's check after every operation.
 
     python tools/fuzz_lifecycle.py 200 500 --ops 80
+    python tools/fuzz_lifecycle.py 200 500 --ops 80 --steps     (decode steps among the operations)
 
 A failed check is logged with the operations up to it and the run goes on with the next schedule; any other
 error (a failed launch, the device) ends the run at once.  Prints the failures, the worst distances to the
@@ -26,6 +27,7 @@ def main():
     ap.add_argument("first", type=int)
     ap.add_argument("last", type=int)
     ap.add_argument("--ops", type=int, default=80, help="operations per schedule")
+    ap.add_argument("--steps", action="store_true", help="draw decode steps too, eager and graph-replayed")
     ap.add_argument("--seconds", type=float, default=400.0, help="start no schedule after this long")
     args = ap.parse_args()
     _lib.load()
@@ -34,9 +36,9 @@ def main():
         if time.time() - t0 > args.seconds:
             break
         for P in (64, 256):
-            sp = LC.spec(seed, P, args.ops, seed % 3 == 0)
-            ops = LC.schedule(seed, P, args.ops, sp.smoothed)
-            h = LC.Harness(Backend, sp, log=lambda *_: None)
+            sp = LC.spec(seed, P, args.ops, seed % 3 == 0, args.steps)
+            ops = LC.schedule(seed, P, args.ops, sp.smoothed, args.steps)
+            h = LC.Harness(Backend(), sp, log=lambda *_: None)
             ran += 1
             try:
                 h.run(ops)
