@@ -698,6 +698,54 @@ int qattn_mxfp4_attn_fwd_decode_step(
 int qattn_mxfp4_decode_step_combine(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
                                     long n, long splits, long q_heads, long kv_heads, int head_dim, void* stream);
 
+/* The device-planned verify step (kv_cache_mxfp4.py VerifyStep): draft_tokens = K new tokens, 1 <= K <= 64, a
+ * chain or a draft tree in topological order, for each of up to n listed sequences, appended and then attended
+ * under the tree mask.  As in the decode step above no argument is computed by a host from the lengths: n, K,
+ * splits and keys_per_split are fixed when the step is made, capacity = max_pages_per_seq * page_tokens, and the
+ * host owns the pages (block_table holds the pages of positions lens[slot] .. lens[slot] + K - 1 of every listed
+ * slot).  tree u64 [n * K] holds the ancestor word of every packed token: bit b of word t of an entry set iff
+ * node b is an ancestor of node t or t itself.  Every reader cleans a word to (word & bits <= t) | bit t.
+ *
+ * qattn_mxfp4_verify_step_plan, one launch, reads slots i32 [n] (a slot per entry; any other value marks
+ * padding), lens (the lengths BEFORE the append) and tree, and writes, with b = slots[i] and L = lens[b]:
+ *   seq_tab i32 [n][4] = {b, K, i * K, 0} and tiles i32 [2 n][2], rows 2 i = {i, L / 64} and 2 i + 1 = {i,
+ *     (L + K - 1) / 64} when that is another tile, else {-1, 0}: the arguments of
+ *     qattn_mxfp4_paged_append_packed(_rope) at nseq = n, ntiles = 2 n, tokens = n * K;
+ *   pos i32 [n * K]: L + popcount(cleaned word) - 1, the node's depth behind the cached keys (its rotary
+ *     position, key and query);
+ *   seq_rec i32 [n][8] = {b, i * K, K, ns, i * splits * kv_heads * group * K, 0, 0, K} for the length L + K, ns =
+ *     ceil(ceil((L + K) / 64) * 64 / keys_per_split) held to splits: the host plan's record of K tree queries.
+ * An entry with b outside [0, max_seqs), L < 0 or L + K > capacity is padding: seq_tab {-1, 0, i * K, 0}, both
+ * tiles {-1, 0}, pos 0 and ns = 0.  No content of slots, lens or tree makes the kernel read or write outside its
+ * tables.  Returns 1 for a NULL pointer, a keys_per_split that is no multiple of 64, K outside [1, 64], max_seqs,
+ * kv_heads, group or splits < 1, splits > 65535, a capacity that is no multiple of 64 in [64, 2^25], n * splits *
+ * kv_heads * group * K >= 2^31; 0 without a launch for n == 0.
+ *
+ * qattn_mxfp4_attn_fwd_verify_step is qattn_mxfp4_attn_fwd_varlen_paged_tree for those n sequences of K tree
+ * queries over a grid fixed by n, K, group, splits and kv_heads: work i32 [n * nrb * splits][4], nrb = ceil(group
+ * * K / 128), holds {i, row block, s, 0} for every entry, row block and split s < splits once, in any order, and a
+ * workgroup whose s is >= ns of its entry returns at once without a store.  q4 / qscale: the n * K * kv_heads *
+ * group quantised query rows, token-major; opart f32 [n * splits * kv_heads * group * K][128], ml as many rows;
+ * entry i's rows are [split][kv head][g * K + t] from i * splits * kv_heads * group * K.  Every entry gets, bit
+ * for bit, what the tree entry gives it at the same keys_per_split.  Returns 1 as that entry does for its pool,
+ * and for the limits of the plan entry.
+ *
+ * qattn_mxfp4_verify_step_combine merges entry i's ns splits with qattn_mxfp4_varlen_combine's arithmetic into
+ * out f16 [n * K][q_heads][128] and lse f32 [n * K][q_heads]; a padding entry (ns < 1) gets out = 0 and lse = -inf
+ * in its K rows.  Only ns is read from seq_rec.  Nothing allocates. */
+int qattn_mxfp4_verify_step_plan(const void* slots, const void* lens, const void* tree, void* seq_tab, void* tiles,
+                                 void* seq_rec, void* pos, long n, long draft_tokens, long max_seqs, long capacity,
+                                 long kv_heads, long group, int keys_per_split, long splits, void* stream);
+int qattn_mxfp4_attn_fwd_verify_step(
+    const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt, const void* vscale,
+    void* opart, void* ml, const void* lens, const void* block_table, const void* seq_rec, const void* work,
+    const void* tree_masks, long n, long draft_tokens, long splits, long max_seqs, long kv_heads, long group,
+    long num_pages, long page_tokens, long max_pages_per_seq, int keys_per_split, int head_dim, float qks,
+    void* stream);
+int qattn_mxfp4_verify_step_combine(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
+                                    long n, long draft_tokens, long splits, long q_heads, long kv_heads,
+                                    int head_dim, void* stream);
+
 /* Merge of the splits, per row of rows_total = bhv*rows: M = max_s m_s, w_s = 2^(m_s - M) (exact; 0
  * for m_s = -inf), L = sum_s w_s l_s, out f16 [rows_total, 128] = (sum_s w_s O_s) * (1 / L), lse f32
  * [rows_total] = M + log2(L).  With nsplit == 1 this is the one-pass forward's epilogue bit for bit. */

@@ -108,6 +108,9 @@ SIGNATURES = {
     "qattn_mxfp4_attn_fwd_decode_step": [_vp] * 12 + [_c_long] * 8 + [_c_int, _c_int, _c_float, _c_long, _c_long,
                                                                        _vp],
     "qattn_mxfp4_decode_step_combine": [_vp] * 5 + [_c_long] * 4 + [_c_int, _vp],
+    "qattn_mxfp4_verify_step_plan": [_vp] * 7 + [_c_long] * 6 + [_c_int, _c_long, _vp],
+    "qattn_mxfp4_attn_fwd_verify_step": [_vp] * 13 + [_c_long] * 9 + [_c_int, _c_int, _c_float, _vp],
+    "qattn_mxfp4_verify_step_combine": [_vp] * 5 + [_c_long] * 5 + [_c_int, _vp],
     "qattn_split_keys": [_c_long, _c_long, _c_long, _c_int],
     "qattn_int8_bwd_plan": [_c_long, _c_int, _c_long, _c_long, _c_int, _c_long, _c_long, _vp],
     "qattn_bf16_bwd_plan": [_c_long, _c_long, _c_long, _c_int, _c_int, _c_long],

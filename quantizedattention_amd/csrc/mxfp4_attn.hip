@@ -706,7 +706,10 @@ __global__ __launch_bounds__(256, CAUSAL ? QA_MX_OCC_CAUSAL : QA_MX_OCC) void mx
 // records seq_rec[i] are written by mx_decode_plan_kernel from the device lengths.  A workgroup whose split
 // s is >= rec[3] = ns_i -- a padding entry (ns = 0) or a sequence that needs fewer splits than the longest
 // one could -- returns before it reads anything else and stores nothing; every other workgroup is the
-// VARLEN (WINDOW) instantiation's statement for statement.
+// VARLEN (WINDOW) instantiation's statement for statement.  STEP with TREE (the device-planned verify step at
+// the end of this file) is the same exit in front of the TREE instantiation: mx_verify_plan_kernel writes the
+// records, rec[7] = K draft nodes of K queries, and the work records {i, row block, s, 0} cover ceil(G * K /
+// 128) row blocks per entry.
 struct MxVarlen {
   const int* work;      // i32 [nwork][4]
   const int* seq_rec;   // i32 [nseq][8]
@@ -830,7 +833,7 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
   static_assert(!WINDOW || (VARLEN && CAUSAL), "the window is the packed step's, and causal");
   static_assert(!SHARED || (VARLEN && !WINDOW), "shared prefixes are the packed step's, without a window");
   static_assert(!TREE || (VARLEN && CAUSAL && !WINDOW && !SHARED), "tree masks are the causal packed step's");
-  static_assert(!STEP || (VARLEN && CAUSAL && !SHARED && !TREE), "the fixed grid is the causal packed step's");
+  static_assert(!STEP || (VARLEN && CAUSAL && !SHARED), "the fixed grid is the causal packed step's");
   static_assert(sizeof(float) == 4 && D == 128, "fp32 staging in two passes fills the ring exactly");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int bh, qt, split = (int)blockIdx.y;
@@ -2020,5 +2023,148 @@ extern "C" int qattn_mxfp4_decode_step_combine(const void* opart, const void* ml
   hipLaunchKernelGGL(mxfp4_decode_step_combine_kernel<128>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0,
                      (hipStream_t)stream, (const float*)opart, (const float2*)ml, (_Float16*)out, (float*)lse,
                      (const int*)seq_rec, rows, (int)q_heads, (int)splits);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// ------------------------------------------------------------------------------ device-planned verify step
+// (kv_cache_mxfp4.py VerifyStep) K draft tokens -- a chain or a tree, 1 <= K <= 64 -- for each of up to n listed
+// sequences, appended and attended under the tree mask with launches fixed when the step is made, as the decode
+// step above.  mx_verify_plan_kernel, one thread per packed token i * K + t, reads b = slots[i] and L = lens[b],
+// the length BEFORE the append, and the token's ancestor word, cleaned as the TREE kernel cleans it: (word & (self
+// | (self - 1))) | self with self = 1 << t.  It writes (kv_cache_mxfp4.plan_verify_step restates it):
+//   pos[i * K + t] = L + popcount(cleaned word) - 1     the node's depth behind the cached keys
+// and, the thread of t = 0,
+//   tab[i]           = {b, K, i * K, 0}                 the record of mx_append_*_packed_kernel
+//   tiles[2 i]       = {i, L / 64}                      the V tiles the K tokens touch: at most two, as K <= 64;
+//   tiles[2 i + 1]   = {i, (L + K - 1) / 64} if that is another tile, else {-1, 0}, which the append skips
+//   seq_rec[i]       = {b, i * K, K, ns, i * splits * hq * K, 0, 0, K} for the length L + K: plan_varlen's record
+//                      of K queries that are all tree nodes, ns = ceil(ceil((L + K) / 64) * 64 / kps) held to
+//                      `splits`; only the partial base differs, a fixed stride instead of compact.
+// An entry whose b lies outside [0, B), whose L is negative or whose L + K passes cap is padding: tab {-1, 0, i *
+// K, 0}, both tiles {-1, 0}, pos 0 and ns = 0 (slot -1 in the record).  lens is read only at a checked b, tree
+// only at i * K + t < n * K; every store goes to row i of a table of n rows (2 i, 2 i + 1 of 2 n; i * K + t of n
+// * K).
+namespace qattn {
+template <int KT>
+__global__ __launch_bounds__(256) void mx_verify_plan_kernel(const int* __restrict__ slots,
+                                                             const int* __restrict__ lens,
+                                                             const unsigned long* __restrict__ tree,
+                                                             int* __restrict__ tab, int* __restrict__ tiles,
+                                                             int* __restrict__ seq_rec, int* __restrict__ pos, int n,
+                                                             int K, int B, int cap, int kt, int splits, int hq) {
+  const int tok = (int)blockIdx.x * 256 + threadIdx.x;
+  if (tok >= n * K) return;
+  const int i = tok / K, t = tok % K;
+  const int b = slots[i];
+  int L = -1;
+  if (b >= 0 && b < B) L = lens[b];
+  const bool ok = L >= 0 && L <= cap - K;
+  const unsigned long self = 1ul << t;
+  const unsigned long word = (tree[tok] & (self | (self - 1))) | self;
+  pos[tok] = ok ? L + __builtin_popcountl(word) - 1 : 0;
+  if (t != 0) return;
+  const int g0 = ok ? L / KT : 0, g1 = ok ? (L + K - 1) / KT : 0;
+  const int ns = ok ? min(((L + K + KT - 1) / KT + kt - 1) / kt, splits) : 0;
+  reinterpret_cast<v4i*>(tab)[i] = v4i{ok ? b : -1, ok ? K : 0, i * K, 0};
+  reinterpret_cast<v4i*>(tiles)[i] = v4i{ok ? i : -1, g0, ok && g1 != g0 ? i : -1, g1 != g0 ? g1 : 0};
+  reinterpret_cast<v4i*>(seq_rec)[2 * i] = v4i{ok ? b : -1, i * K, K, ns};
+  reinterpret_cast<v4i*>(seq_rec)[2 * i + 1] = v4i{i * splits * hq * K, 0, 0, K};
+}
+
+// The merge of the step: entry i owns the partial rows [i * splits * Hq * K, (i + 1) * splits * Hq * K), laid out
+// [split][kv head][g * K + t] (the packed step's layout at K queries), so nothing but ns is read from the record
+// and every address lies inside the partials.  mx_merge_row over the entry's ns splits, the arithmetic of
+// mxfp4_varlen_combine_kernel in its order; an entry with ns < 1 (padding) gets O = 0 and lse = -inf in all its
+// K rows.
+template <int D>
+__global__ __launch_bounds__(256) void mxfp4_verify_step_combine_kernel(const float* __restrict__ opart,
+                                                                        const float2* __restrict__ ml,
+                                                                        _Float16* __restrict__ out,
+                                                                        float* __restrict__ lse,
+                                                                        const int* __restrict__ seq_rec, long rows,
+                                                                        int Hq, int G, int K, int splits) {
+  constexpr int TPR = D / 8;
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+  const long row = gid / TPR;
+  if (row >= rows) return;
+  const int c = (int)(gid % TPR);
+  const long token = row / Hq;
+  const int head = (int)(row % Hq);
+  const long i = token / K;
+  const int t = (int)(token % K);
+  const int ns = min(seq_rec[8 * i + 3], splits);
+  if (ns < 1) {
+    *reinterpret_cast<v8h*>(out + row * D + 8 * c) = v8h{};
+    if (c == 0) lse[row] = -INFINITY;
+    return;
+  }
+  const long step = (long)Hq * K;
+  mx_merge_row<D>(opart, ml, i * splits * step + (long)(head / G) * G * K + (long)(head % G) * K + t, step, ns, c,
+                  out + row * D, lse + row);
+}
+}  // namespace qattn
+
+// what the three entries of the verify step hold their sizes to: 1 <= K <= 64 draft tokens per entry and fewer
+// than 2^31 partial rows
+static bool mx_verify_sizes_ok(long n, long draft_tokens, long splits, long kv_heads, long group) {
+  if (n < 0 || draft_tokens < 1 || draft_tokens > 64 || splits < 1 || splits > 65535) return false;
+  if (kv_heads < 1 || group < 1 || kv_heads > 0x7fffffffL / group) return false;
+  return n <= 0x7fffffffL / (splits * kv_heads * group * draft_tokens);
+}
+
+extern "C" int qattn_mxfp4_verify_step_plan(const void* slots, const void* lens, const void* tree, void* seq_tab,
+                                            void* tiles, void* seq_rec, void* pos, long n, long draft_tokens,
+                                            long max_seqs, long capacity, long kv_heads, long group,
+                                            int keys_per_split, long splits, void* stream) {
+  if (!mx_split_ok(128, keys_per_split) || max_seqs < 1 || max_seqs > 0x7fffffffL) return 1;
+  if (capacity < 64 || capacity % 64 || capacity > (1L << 25)) return 1;
+  if (!mx_verify_sizes_ok(n, draft_tokens, splits, kv_heads, group)) return 1;
+  if (n == 0) return 0;
+  if (!slots || !lens || !tree || !seq_tab || !tiles || !seq_rec || !pos) return 1;
+  const long nthr = n * draft_tokens;
+  hipLaunchKernelGGL(mx_verify_plan_kernel<64>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, (const int*)slots, (const int*)lens, (const unsigned long*)tree,
+                     (int*)seq_tab, (int*)tiles, (int*)seq_rec, (int*)pos, (int)n, (int)draft_tokens, (int)max_seqs,
+                     (int)capacity, keys_per_split / 64, (int)splits, (int)(kv_heads * group));
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// The attention of the step over its fixed grid (kernel: mxfp4_attn_split_kernel STEP with TREE): n entries x
+// ceil(group * K / 128) row blocks x splits work records x kv_heads workgroups.  seq_rec is
+// mx_verify_plan_kernel's, work i32 [n * row blocks * splits][4] = {i, row block, s, 0} in any order, tree_masks
+// u64 [n * K] the words the plan read; the partials hold n * splits * kv_heads * group * K rows.  It stands behind
+// every older entry, as its kernels are emitted behind theirs.
+extern "C" int qattn_mxfp4_attn_fwd_verify_step(
+    const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt, const void* vscale,
+    void* opart, void* ml, const void* lens, const void* block_table, const void* seq_rec, const void* work,
+    const void* tree_masks, long n, long draft_tokens, long splits, long max_seqs, long kv_heads, long group,
+    long num_pages, long page_tokens, long max_pages_per_seq, int keys_per_split, int head_dim, float qks,
+    void* stream) {
+  if (!mx_verify_sizes_ok(n, draft_tokens, splits, kv_heads, group)) return 1;
+  if (n > 0 && (!q4 || !qscale || !k4 || !kscale || !vt || !vscale || !opart || !ml || !tree_masks)) return 1;
+  const long nrb = (group * draft_tokens + MxCfg<128>::QROWS - 1) / MxCfg<128>::QROWS;
+  if (n > 0x7fffffffL / (nrb * splits * kv_heads)) return 1;
+  MxSplitCall c;
+  const int rc = mx_varlen_call(c, q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work,
+                                n, n * nrb * splits, n * draft_tokens,
+                                n * splits * kv_heads * group * draft_tokens, max_seqs, kv_heads, group, num_pages,
+                                page_tokens, max_pages_per_seq, 2, keys_per_split, head_dim, qks, 0, 0, tree_masks);
+  if (rc >= 0) return rc;
+  return mx_split_launch<true, true, true, true, false, false, true, true>(c, stream);
+}
+
+extern "C" int qattn_mxfp4_verify_step_combine(const void* opart, const void* ml, void* out, void* lse,
+                                               const void* seq_rec, long n, long draft_tokens, long splits,
+                                               long q_heads, long kv_heads, int head_dim, void* stream) {
+  if (head_dim != 128 || kv_heads < 1 || q_heads < 1 || q_heads % kv_heads != 0) return 1;
+  if (!mx_verify_sizes_ok(n, draft_tokens, splits, kv_heads, q_heads / kv_heads)) return 1;
+  if (n == 0) return 0;
+  if (!opart || !ml || !out || !lse || !seq_rec) return 1;
+  const long rows = n * draft_tokens * q_heads, nthr = rows * (128 / 8);
+  if ((nthr + 255) / 256 > 0x7fffffffL) return 1;
+  hipLaunchKernelGGL(mxfp4_verify_step_combine_kernel<128>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)opart, (const float2*)ml, (_Float16*)out, (float*)lse,
+                     (const int*)seq_rec, rows, (int)q_heads, (int)(q_heads / kv_heads), (int)draft_tokens,
+                     (int)splits);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }

@@ -47,6 +47,10 @@
 //       -> (seq_tab, tiles, pos, seq_rec): kv_cache_mxfp4.DecodeStep's tables, derived on the device
 //   mxfp4_decode_step(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, splits, keys_per_split, window,
 //       sinks) -> (O, lse): kv_cache_mxfp4.DecodeStep.attend over its fixed grid
+//   mxfp4_verify_step_plan(slots, lens, tree, draft_tokens, capacity, kv_heads, group, keys_per_split, splits)
+//       -> (seq_tab, tiles, pos, seq_rec): kv_cache_mxfp4.VerifyStep's tables, derived on the device
+//   mxfp4_verify_step(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, tree, draft_tokens, splits,
+//       keys_per_split) -> (O, lse): kv_cache_mxfp4.VerifyStep.attend over its fixed grid
 // Workspaces, head chunks and key splits are planned by the library (csrc/plan.hip), as in the drop-ins.
 // Errors: TORCH_CHECK (c10::Error, RuntimeError in Python) with the drop-ins' messages; int8_quant's
 // argument checks raise ValueError (TORCH_CHECK_VALUE) as its Python predecessor did.
@@ -841,6 +845,89 @@ std::tuple<Tensor, Tensor> mxfp4_decode_step(const Tensor& q_in, const Tensor& k
   return {out, lse};
 }
 
+// kv_cache_mxfp4.VerifyStep's plan as an operator: from slots i32 [n], the pool's lens i32 [B] (the lengths BEFORE
+// the step's append) and the ancestor words tree i64 [n * K] the four device tables of
+// qattn_mxfp4_verify_step_plan, seq_tab i32 [n, 4], tiles i32 [2 n, 2], pos i32 [n * K] and seq_rec i32 [n, 8].
+// Nothing is read back.
+std::tuple<Tensor, Tensor, Tensor, Tensor> mxfp4_verify_step_plan(const Tensor& slots, const Tensor& lens,
+                                                                  const Tensor& tree, int64_t draft_tokens,
+                                                                  int64_t capacity, int64_t kv_heads,
+                                                                  int64_t group, int64_t keys_per_split,
+                                                                  int64_t splits) {
+  require_gpu({&slots, &lens, &tree});
+  TORCH_CHECK(slots.scalar_type() == at::kInt && slots.is_contiguous() && slots.dim() == 1 && slots.size(0) >= 1,
+              "qattn mxfp4 verify step: slots must be contiguous int32 [n >= 1]");
+  TORCH_CHECK(lens.scalar_type() == at::kInt && lens.is_contiguous() && lens.dim() == 1 && lens.size(0) >= 1,
+              "qattn mxfp4 verify step: lens must be contiguous int32 [max_seqs]");
+  TORCH_CHECK(draft_tokens >= 1 && draft_tokens <= 64, "qattn mxfp4 verify step: draft_tokens must be in [1, 64]");
+  const int64_t n = slots.size(0), K = draft_tokens;
+  TORCH_CHECK(tree.scalar_type() == at::kLong && tree.is_contiguous() && tree.dim() == 1 && tree.size(0) == n * K,
+              "qattn mxfp4 verify step: tree must be contiguous int64 [n * draft_tokens]");
+  TORCH_CHECK(keys_per_split >= 64 && keys_per_split % 64 == 0,
+              "qattn mxfp4 verify step: keys_per_split must be a multiple of 64");
+  Ctx c(slots);
+  Tensor seq_tab = empty({n, 4}, at::kInt, slots), tiles = empty({2 * n, 2}, at::kInt, slots);
+  Tensor pos = empty({n * K}, at::kInt, slots), seq_rec = empty({n, 8}, at::kInt, slots);
+  call(qattn_mxfp4_verify_step_plan(P(slots), P(lens), P(tree), P(seq_tab), P(tiles), P(seq_rec), P(pos), n, K,
+                                    lens.size(0), capacity, kv_heads, group, (int)keys_per_split, splits, c.stream),
+       "mxfp4 verify step plan");
+  return {seq_tab, tiles, pos, seq_rec};
+}
+
+// kv_cache_mxfp4.VerifyStep.attend as an operator: q [n * K, Hq, 128], the pool's operands, lens (AFTER the step's
+// append) and block table, seq_rec i32 [n, 8] of the plan above, work i32 [n * nrb * splits, 4] = {i, row block, s,
+// 0} with nrb = ceil(G * K / 128), and the words tree i64 [n * K].
+std::tuple<Tensor, Tensor> mxfp4_verify_step(const Tensor& q_in, const Tensor& k4, const Tensor& ks,
+                                             const Tensor& vt, const Tensor& vs, const Tensor& lens,
+                                             const Tensor& block_table, const Tensor& seq_rec, const Tensor& work,
+                                             const Tensor& tree, int64_t draft_tokens, int64_t splits,
+                                             int64_t keys_per_split) {
+  require_gpu({&q_in, &k4, &ks, &vt, &vs, &lens, &block_table, &seq_rec, &work, &tree});
+  TORCH_CHECK(q_in.dim() == 3 && k4.dim() == 4 && q_in.size(2) == 128 && k4.size(3) == 64,
+              "qattn mxfp4 verify step: q must be [n * draft_tokens, Hq, 128], head_dim 128 in the pool");
+  const int64_t NP = k4.size(0), Hkv = k4.size(1), PT = k4.size(2), D = 128, K = draft_tokens;
+  TORCH_CHECK(PT >= 64 && PT <= 1024 && (PT & (PT - 1)) == 0,
+              "qattn mxfp4 paged cache: page_tokens must be 64 * 2^k in [64, 1024]");
+  TORCH_CHECK(block_table.scalar_type() == at::kInt && block_table.is_contiguous() && block_table.dim() == 2 &&
+                  block_table.size(1) >= 1,
+              "qattn mxfp4 paged cache: block_table must be contiguous int32 [B, max_pages_per_seq]");
+  TORCH_CHECK(K >= 1 && K <= 64 && q_in.size(0) >= K && q_in.size(0) % K == 0,
+              "qattn mxfp4 verify step: draft_tokens in [1, 64] and q rows a multiple of it expected");
+  const int64_t B = block_table.size(0), mpp = block_table.size(1);
+  const int64_t n = q_in.size(0) / K, Hq = q_in.size(1);
+  TORCH_CHECK(Hkv > 0 && NP > 0 && Hq > 0 && Hq % Hkv == 0 && n <= B,
+              "qattn mxfp4 verify step: q must have G * Hkv heads for the pool's Hkv and at most B entries");
+  check_fp4_operands(k4, ks, vt, vs, &lens, B, true);
+  TORCH_CHECK(splits >= 1 && splits <= 65535 && n * splits * Hq * K < (int64_t(1) << 31),
+              "qattn mxfp4 verify step: splits in [1, 65535] and fewer than 2^31 partial rows expected");
+  const int64_t nrb = (Hq / Hkv * K + 127) / 128;
+  TORCH_CHECK(seq_rec.scalar_type() == at::kInt && seq_rec.is_contiguous() && seq_rec.dim() == 2 &&
+                  seq_rec.size(1) == 8 && seq_rec.size(0) == n,
+              "qattn mxfp4 verify step: seq_rec must be contiguous int32 [n, 8]");
+  TORCH_CHECK(work.scalar_type() == at::kInt && work.is_contiguous() && work.dim() == 2 && work.size(1) == 4 &&
+                  work.size(0) == n * nrb * splits,
+              "qattn mxfp4 verify step: work must be contiguous int32 [n * row blocks * splits, 4]");
+  TORCH_CHECK(tree.scalar_type() == at::kLong && tree.is_contiguous() && tree.dim() == 1 && tree.size(0) == n * K,
+              "qattn mxfp4 verify step: tree must be contiguous int64 [n * draft_tokens]");
+  TORCH_CHECK(keys_per_split >= 64 && keys_per_split % 64 == 0,
+              "qattn mxfp4 verify step: keys_per_split must be a multiple of 64");
+  Ctx c(q_in);
+  const Tensor q = kin(q_in, at::kHalf);
+  const int64_t T = n * K;
+  Tensor q4 = empty({T * Hq, D / 2}, at::kByte, q), qs = empty({T * Hq, D / 32}, at::kByte, q);
+  Tensor out = empty({T, Hq, D}, at::kHalf, q), lse = empty({T, Hq}, at::kFloat, q);
+  Tensor opart = empty({n * splits * Hq * K, D}, at::kFloat, q), ml = empty({n * splits * Hq * K, 2}, at::kFloat, q);
+  call(qattn_mxfp4_quant_rows(P(q), nullptr, P(q4), P(qs), T * Hq, Hq, (int)D, c.stream), "quantise q");
+  call(qattn_mxfp4_attn_fwd_verify_step(P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens),
+                                        P(block_table), P(seq_rec), P(work), P(tree), n, K, splits, B, Hkv,
+                                        Hq / Hkv, NP, PT, mpp, (int)keys_per_split, (int)D, qk_scale(D), c.stream),
+       "mxfp4 verify step forward");
+  call(qattn_mxfp4_verify_step_combine(P(opart), P(ml), P(out), P(lse), P(seq_rec), n, K, splits, Hq, Hkv, (int)D,
+                                       c.stream),
+       "mxfp4 verify step merge");
+  return {out, lse};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(qattn, m) {
@@ -880,6 +967,11 @@ TORCH_LIBRARY(qattn, m) {
         "int keys_per_split, int splits, int window, int sinks) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("mxfp4_decode_step(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, Tensor block_table, "
         "Tensor seq_rec, Tensor work, int splits, int keys_per_split, int window, int sinks) -> (Tensor, Tensor)");
+  m.def("mxfp4_verify_step_plan(Tensor slots, Tensor lens, Tensor tree, int draft_tokens, int capacity, "
+        "int kv_heads, int group, int keys_per_split, int splits) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("mxfp4_verify_step(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, Tensor block_table, "
+        "Tensor seq_rec, Tensor work, Tensor tree, int draft_tokens, int splits, int keys_per_split) "
+        "-> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
@@ -902,4 +994,6 @@ TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
   m.impl("mxfp4_varlen_paged_rope", &mxfp4_varlen_paged_rope);
   m.impl("mxfp4_decode_step_plan", &mxfp4_decode_step_plan);
   m.impl("mxfp4_decode_step", &mxfp4_decode_step);
+  m.impl("mxfp4_verify_step_plan", &mxfp4_verify_step_plan);
+  m.impl("mxfp4_verify_step", &mxfp4_verify_step);
 }

@@ -163,7 +163,17 @@ restates it), the attention runs ``splits`` (:func:`decode_step_splits`) work re
 lengths are, and a workgroup whose split its sequence does not have exits at once.  The host keeps what only it
 can do, in ``prepare``: the checks, the page reservation, the table upload when a page was added and the upload
 of ``slots``.  Results are the host-planned pair's bit for bit at the same keys per split.  ``share_prefix``,
-trees, ``trim``, prefill chunks and more than one new token per sequence stay on the host-planned path.
+``trim`` and prefill chunks stay on the host-planned path.
+
+The device-planned verify step (:class:`VerifyStep`) is the same for speculative decoding: every listed sequence
+appends K draft tokens (1 <= K <= 64, a chain or a tree, K fixed when the step is made) and attends to them under
+the tree mask.  ``qattn_mxfp4_verify_step_plan`` derives the append record, the at most two V tiles, the K rotary
+positions (depth behind the cached keys) and ``seq_rec`` from ``slots``, ``lens`` and the uploaded ancestor words
+(:func:`plan_verify_step` restates it); the attention is the tree instantiation over a fixed grid of N *
+ceil(G K / 128) * ``splits`` work records.  ``prepare`` uploads ``slots`` and the words of all N * K tokens every
+time, so another tree costs no new capture.  A round is ``checkpoint`` BEFORE ``prepare`` (prepare moves the
+mirror lengths), then ``append`` / ``attend`` or their replay, then ``rollback`` or ``accept`` as on the
+host-planned path.  No window, no ``share_prefix``, one K for every entry of a step.
 
 Wire format (little-endian), the container of kv_cache.py with a magic of its own::
 
@@ -203,7 +213,7 @@ __all__ = ["QuantizedKVFP4", "quantize_kv_fp4", "attention_mxfp4_cached", "Preal
            "attention_mxfp4_decode", "PageAllocator", "PagedKVFP4", "attention_mxfp4_decode_paged",
            "plan_varlen", "plan_varlen_shared", "attention_mxfp4_varlen_paged", "tree_ancestor_masks",
            "tree_path", "Checkpoint", "Rope", "rope_table", "rope_positions", "DecodeStep",
-           "decode_step_splits", "plan_decode_step"]
+           "decode_step_splits", "plan_decode_step", "VerifyStep", "verify_step_splits", "plan_verify_step"]
 
 
 @dataclass
@@ -2010,4 +2020,280 @@ class DecodeStep:
                   a.max_pages_per_seq, self.kps, D, _qk_scale(D), self.window or 0, self.sinks, st)
         _lib.call("qattn_mxfp4_decode_step_combine", _lib.ptr(self.opart), _lib.ptr(self.ml), _lib.ptr(self.O),
                   _lib.ptr(self.lse), _lib.ptr(self.seq_rec), N, self.splits, Hq, H, D, st)
+        return self.O, self.lse
+
+
+# ------------------------------------------------------------------------------ device-planned verify step
+_WORD = (1 << 64) - 1
+
+
+def _signed64(x: int) -> int:
+    return x - (1 << 64) if x >> 63 else x
+
+
+def verify_step_splits(max_keys: int, kps: int) -> int:
+    """The largest number of key splits a sequence of at most ``max_keys`` keys (the K draft tokens included) needs
+    at ``kps`` keys per split: the ``splits`` of a :class:`VerifyStep`, ceil(ceil64(max_keys) / kps).  Pure Python."""
+    max_keys, kps = int(max_keys), int(kps)
+    if max_keys < 1 or kps < BLOCK or kps % BLOCK:
+        raise _lib.QAttnError("qattn mxfp4 verify step: max_keys >= 1 and keys_per_split a multiple of 64 expected")
+    return -(-_ceil64(max_keys) // kps)
+
+
+def plan_verify_step(lengths_before, slots, K: int, words, kps: int, splits: int, kv_heads: int, group: int,
+                     capacity: Optional[int] = None):
+    """The tables of one device-planned verify step -> (seq_tab, tiles, pos, seq_rec, work) as lists: the pure-
+    Python statement of what ``qattn_mxfp4_verify_step_plan`` writes (and of ``work``, which a :class:`VerifyStep`
+    writes once when it is made).  No device.  ``lengths_before`` holds one length per slot BEFORE the step's
+    append, ``slots`` one slot per entry of the step, any value outside [0, len(lengths_before)) marking padding,
+    and ``words`` the len(slots) * K ancestor words (:func:`tree_ancestor_masks`, entry by entry; as unsigned or
+    as int64 values), each cleaned as the kernels clean it: ``(word & (self | (self - 1))) | self`` with ``self = 1
+    << t``.  For entry i with b = slots[i] and L = lengths_before[b]:
+
+        seq_tab[i]       = [b, K, i * K, 0]         the record of ``append_packed``
+        tiles[2 i]       = [i, L // 64]             the V tiles the K tokens touch: at most two, as K <= 64;
+        tiles[2 i + 1]   = [i, (L + K - 1) // 64]   when that is another tile, else [-1, 0], which the append skips
+        pos[i * K + t]   = L + popcount(cleaned word) - 1, the node's depth behind the cached keys
+        seq_rec[i]       = [b, i * K, K, ns, i * splits * kv_heads * group * K, 0, 0, K]
+
+    with ns = min(ceil(ceil64(L + K) / kps), splits): :func:`plan_varlen`'s record for a sequence of L + K keys and
+    K queries that are all tree nodes, but for the partial base, a fixed stride.  A padding entry -- b out of range,
+    or L + K > ``capacity`` -- is seq_tab [-1, 0, i * K, 0], both tiles [-1, 0], pos 0 and seq_rec [-1, i * K, K, 0,
+    base, 0, 0, K].  ``work`` = [i, row block, s, 0] for every entry, every row block < ceil(group * K / 128) and
+    every s < ``splits``, split by split."""
+    lengths = [int(x) for x in lengths_before]
+    slots = [int(b) for b in slots]
+    K, kps, splits, hq, group = int(K), int(kps), int(splits), int(kv_heads) * int(group), int(group)
+    if not 1 <= K <= TREE_NODES or kps < BLOCK or kps % BLOCK or splits < 1 or hq < 1:
+        raise _lib.QAttnError(f"qattn mxfp4 verify step: draft_tokens in [1, {TREE_NODES}], keys_per_split a "
+                              "multiple of 64, splits, kv_heads and group >= 1 expected")
+    words = [int(w) & _WORD for w in words]
+    if len(words) != len(slots) * K:
+        raise _lib.QAttnError(f"qattn mxfp4 verify step: {len(slots) * K} ancestor words expected, got {len(words)}")
+    seq_tab, tiles, pos, seq_rec = [], [], [], []
+    for i, b in enumerate(slots):
+        L = lengths[b] if 0 <= b < len(lengths) else -1
+        base = i * splits * hq * K
+        if L < 0 or (capacity is not None and L + K > capacity):
+            seq_tab.append([-1, 0, i * K, 0])
+            tiles += [[-1, 0], [-1, 0]]
+            pos += [0] * K
+            seq_rec.append([-1, i * K, K, 0, base, 0, 0, K])
+            continue
+        g0, g1 = L // BLOCK, (L + K - 1) // BLOCK
+        seq_tab.append([b, K, i * K, 0])
+        tiles += [[i, g0], [i, g1] if g1 != g0 else [-1, 0]]
+        for t in range(K):
+            w = (words[i * K + t] & ((2 << t) - 1)) | 1 << t
+            pos.append(L + bin(w).count("1") - 1)
+        seq_rec.append([b, i * K, K, min(-(-_ceil64(L + K) // kps), splits), base, 0, 0, K])
+    nrb = -(-group * K // QROWS)
+    work = [[i, rb, s, 0] for s in range(splits) for rb in range(nrb) for i in range(len(slots))]
+    return seq_tab, tiles, pos, seq_rec, work
+
+
+class VerifyStep:
+    """One verify step of speculative decoding -- ``draft_tokens`` = K new tokens (1 <= K <= 64), a chain or a
+    draft tree, for each of up to ``max_batch`` running sequences of a :class:`PagedKVFP4` -- planned on the device
+    like :class:`DecodeStep`, so ``append`` and ``attend`` can be captured in a graph once and replayed while the
+    sequences grow, are rolled back, leave and join, and while the trees change.
+
+    Everything is allocated here, once: ``slots`` i32 [N] and ``tree`` int64 [N * K] (the ancestor words; one
+    buffer, one upload per ``prepare``), the append table ``seq_tab`` i32 [N, 4] and tile list ``tiles`` i32 [2 N,
+    2], ``seq_rec`` i32 [N, 8], ``pos`` i32 [N * K], ``work`` i32 [N * nrb * splits, 4] with nrb = ceil(G K / 128)
+    (written here and never again), the quantised queries ``q4`` / ``qs``, the partials ``opart`` f32 [N * splits *
+    Hq * K, 128] / ``ml``, and the results ``O`` f16 [N * K, Hq, 128] / ``lse`` f32 [N * K, Hq], which ``attend``
+    returns and the next ``attend`` overwrites.  ``parents`` (None: a chain of K nodes) is the default topology, a
+    ``parents`` list of exactly K nodes (:func:`tree_ancestor_masks`).  ``kps`` is fixed here: ``keys_per_split``,
+    or ``qattn_split_keys(kv_heads * N * nrb, 1, ceil64(max_keys), 64)``; ``splits`` = :func:`verify_step_splits`,
+    so the attention grid is N * nrb * splits * kv_heads workgroups whatever the lengths are.  ``max_keys`` bounds
+    a sequence's length AFTER the K tokens.
+
+    A round: ``ckpt = cache.checkpoint(ids)`` BEFORE ``prepare`` (``prepare`` moves the mirror lengths to L + K,
+    and a checkpoint notes the mirror), then ``prepare``, then ``append`` and ``attend`` or the replay of their
+    graph, then ``cache.rollback(ckpt)`` or ``cache.accept(ckpt, k[:n * K], v[:n * K], ids, [K] * n, accepted)`` as
+    on the host-planned path.  Every listed entry gets, bit for bit, what ``append_packed(k, v, ids, [K] * n[,
+    rope=rope, tree=trees])`` followed by ``attention_mxfp4_varlen_paged(q, cache, ids, [K] * n, causal=True,
+    keys_per_split=step.kps, tree=trees[, rope=rope])`` gives, and the pool holds that pair's bytes.  No window
+    and no ``share_prefix`` (a tree excludes both), one K for every entry; page reservation stays on the host."""
+
+    def __init__(self, max_batch: int, max_keys: int, q_heads: int, kv_heads: int, device, draft_tokens: int,
+                 parents=None, keys_per_split: Optional[int] = None):
+        N, max_keys, Hq, Hkv, K, D = int(max_batch), int(max_keys), int(q_heads), int(kv_heads), int(draft_tokens), 128
+        if N < 1 or Hkv < 1 or Hq < 1 or Hq % Hkv or not 1 <= max_keys <= 1 << 25:
+            raise _lib.QAttnError("qattn mxfp4 verify step: max_batch >= 1, q_heads = G * kv_heads and max_keys in "
+                                  "[1, 2^25] expected")
+        if not 1 <= K <= TREE_NODES:
+            raise _lib.QAttnError(f"qattn mxfp4 verify step: draft_tokens must be in [1, {TREE_NODES}] (one bit of "
+                                  f"the ancestor word each), got {K}")
+        self.K = K
+        self.words, self.depth = self._tree(list(range(-1, K - 1)) if parents is None else parents)
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.QAttnError(f"qattn kernels run on the GPU only; got device {dev} "
+                                  "(no CPU fallback by design)")
+        self.nrb = -(-(Hq // Hkv) * K // QROWS)
+        if keys_per_split is None:
+            kps = _lib.load().qattn_split_keys(Hkv * N * self.nrb, 1, _ceil64(max_keys), BLOCK)
+        else:
+            kps = int(keys_per_split)
+        if kps < BLOCK or kps % BLOCK:
+            raise _lib.QAttnError("qattn mxfp4 verify step: keys_per_split must be a multiple of 64")
+        self.N, self.max_keys, self.q_heads, self.kv_heads, self.kps = N, max_keys, Hq, Hkv, kps
+        self.splits = verify_step_splits(max_keys, kps)
+        if self.splits > 65535 or N * self.splits * Hq * K >= 1 << 31:
+            raise _lib.QAttnError("qattn mxfp4 verify step: more than 65535 splits or 2^31 partial rows; raise "
+                                  "keys_per_split")
+        z = lambda *shape, dt=torch.int32: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        # one buffer for what prepare uploads: the words first, then, at a multiple of 16 bytes, the slots
+        self._gap = -(2 * N * K) % 4
+        self.args = z(2 * N * K + self._gap + N)
+        self.tree, self.slots = self.args[:2 * N * K].view(torch.int64), self.args[2 * N * K + self._gap:]
+        self.slots.fill_(-1)
+        self.seq_tab, self.tiles, self.seq_rec, self.pos = z(N, 4), z(2 * N, 2), z(N, 8), z(N * K)
+        self.work = torch.tensor([[i, rb, s, 0] for s in range(self.splits) for rb in range(self.nrb)
+                                  for i in range(N)], dtype=torch.int32).to(dev)
+        rows = N * self.splits * Hq * K
+        self.opart, self.ml = z(rows, D, dt=torch.float32), z(rows, 2, dt=torch.float32)
+        self.q4, self.qs = z(N * K * Hq, D // 2, dt=torch.uint8), z(N * K * Hq, D // 32, dt=torch.uint8)
+        self.O, self.lse = z(N * K, Hq, D, dt=torch.float16), z(N * K, Hq, dt=torch.float32)
+        self.listed = []    # the slots of the last prepare
+        self.top = 0        # the highest rotary position of the last prepare
+
+    def _tree(self, parents):
+        """(int64 words, depth of the deepest node) of a ``parents`` list of exactly K nodes."""
+        anc = tree_ancestor_masks(parents)
+        if len(anc) != self.K:
+            raise _lib.QAttnError(f"qattn mxfp4 verify step: a tree of {len(anc)} nodes on a step of {self.K} draft "
+                                  "tokens (every entry's tree has exactly draft_tokens nodes)")
+        return [_signed64(x) for x in anc], max(bin(x).count("1") for x in anc) - 1
+
+    def _pool(self, cache: "PagedKVFP4") -> None:
+        if not isinstance(cache, PagedKVFP4):
+            raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PagedKVFP4")
+        if cache.shape[1] != self.kv_heads or cache.k4.device != self.slots.device:
+            raise _lib.QAttnError(f"qattn mxfp4 verify step: a pool of {self.kv_heads} key/value heads on "
+                                  f"{self.slots.device} expected")
+        if self.N > cache.alloc.max_seqs:
+            raise _lib.QAttnError(f"qattn mxfp4 verify step: a step of {self.N} entries on a pool of "
+                                  f"{cache.alloc.max_seqs} sequence slots")
+
+    def prepare(self, cache: "PagedKVFP4", seq_ids, trees=None) -> "VerifyStep":
+        """The host's part of a step over the slots ``seq_ids`` of ``cache`` (at most N, distinct, none empty),
+        before ``append`` / ``attend`` or a replay of their graph; not capturable.  ``trees`` (None: the step's
+        default topology for every entry) lists one entry per listed sequence, None or a ``parents`` list of
+        exactly K nodes.  Raises :class:`QAttnError` before anything changes for duplicate or out-of-range slots,
+        more than N of them, a listed slot of length 0, a sequence whose length + K would pass ``max_keys`` or
+        what its table row can hold, a trimmed sequence (there is no window), a ``trees`` list of another length,
+        a tree that does not have K nodes or has a parent outside [-1, t).  Then it reserves the pages the lengths
+        + K need (all or nothing: out of pages raises with nothing changed), uploads the table if it grew, and
+        ``seq_ids``, padded with -1, together with the words of all N * K tokens in one upload, and adds K to the
+        listed ``cache.lengths``.  Stream-ordered, nothing read back."""
+        self._pool(cache)
+        ids = [int(b) for b in (seq_ids.tolist() if isinstance(seq_ids, torch.Tensor) else seq_ids)]
+        a, K = cache.alloc, self.K
+        if len(ids) > self.N or len(set(ids)) != len(ids) or any(not 0 <= b < a.max_seqs for b in ids):
+            raise _lib.QAttnError(f"qattn mxfp4 verify step: seq_ids must be at most {self.N} distinct slots in "
+                                  f"[0, {a.max_seqs}), got {ids}")
+        trees = [None] * len(ids) if trees is None else list(trees)
+        if len(trees) != len(ids):
+            raise _lib.QAttnError(f"qattn mxfp4 verify step: trees must have one entry (None or a parents list) "
+                                  f"per listed sequence, got {len(trees)} for {len(ids)}")
+        seen, per = {}, []   # a batch usually drafts one tree shape: one look-up per sequence
+        for p in trees:
+            w = (self.words, self.depth) if p is None else seen.get(id(p))
+            if w is None:
+                w = seen[id(p)] = self._tree(p)
+            per.append(w)
+        Ls = [cache.lengths[b] for b in ids]
+        if any(L < 1 for L in Ls):
+            raise _lib.QAttnError("qattn mxfp4 verify step: every listed sequence needs at least one cached token "
+                                  f"(slots {ids}, lengths {Ls})")
+        cap = min(self.max_keys, a.max_pages_per_seq * a.page_tokens)
+        if any(L + K > cap for L in Ls):
+            raise _lib.QAttnError(f"qattn mxfp4 verify step: a sequence would pass {cap} keys with its {K} draft "
+                                  f"tokens (the step's max_keys {self.max_keys}, the pool's {a.max_pages_per_seq} "
+                                  f"pages of {a.page_tokens}; slots {ids}, lengths {Ls})")
+        for b in ids:
+            cache._whole(b, "a verify step (it has no window)")
+        grown = a.reserve([(b, L + K) for b, L in zip(ids, Ls)])
+        if grown:
+            cache.block_table.copy_(torch.tensor(a.table, dtype=torch.int32), non_blocking=True)
+        words = list(itertools.chain.from_iterable(w for w, _ in per)) + [0] * (K * (self.N - len(ids)))
+        host = torch.cat([torch.tensor(words, dtype=torch.int64).view(torch.int32),
+                          torch.tensor([0] * self._gap + ids + [-1] * (self.N - len(ids)), dtype=torch.int32)])
+        self.args.copy_(host, non_blocking=True)
+        for b in ids:
+            cache.lengths[b] += K
+        self.listed = ids
+        self.top = max((L + d for L, (_, d) in zip(Ls, per)), default=0)
+        return self
+
+    def _rope(self, rope) -> None:
+        if not isinstance(rope, Rope):
+            raise _lib.QAttnError("qattn mxfp4 rope: rope must be a Rope")
+        if self.top >= rope.max_pos:   # (from the mirror at prepare: a check only, no launch depends on it)
+            raise _lib.QAttnError(f"qattn mxfp4 rope: the step's positions reach {self.top}, outside the table's "
+                                  f"[0, {rope.max_pos})")
+
+    def append(self, cache: "PagedKVFP4", k: torch.Tensor, v: torch.Tensor, rope: Optional[Rope] = None):
+        """Append ``k, v`` fp16 [N * K, Hkv, 128], rows i * K .. i * K + K - 1 the draft tokens of entry i in
+        topological order (rows of padding entries are not read), to the sequences ``slots`` names; capturable.
+        One launch derives the tables from ``cache.lens`` and ``tree`` (``qattn_mxfp4_verify_step_plan``), then
+        ``qattn_mxfp4_paged_append_packed`` (``_rope`` with ``rope``: the keys rotated to ``pos``, the nodes'
+        depths behind the cached keys) runs on them as it is."""
+        self._pool(cache)
+        N, K, H, D = self.N, self.K, self.kv_heads, 128
+        if tuple(k.shape) != (N * K, H, D) or k.shape != v.shape:
+            raise _lib.QAttnError(f"qattn mxfp4 verify step: k, v must be [{N * K}, {H}, 128]")
+        if rope is not None:
+            self._rope(rope)
+        _lib.require_gpu(k, v, cache.k4)
+        k = _lib.kernel_input(k, torch.float16)
+        v = _lib.kernel_input(v, torch.float16)
+        a, st = cache.alloc, _lib.stream_of(k)
+        _lib.call("qattn_mxfp4_verify_step_plan", _lib.ptr(self.slots), _lib.ptr(cache.lens), _lib.ptr(self.tree),
+                  _lib.ptr(self.seq_tab), _lib.ptr(self.tiles), _lib.ptr(self.seq_rec), _lib.ptr(self.pos), N, K,
+                  a.max_seqs, a.max_pages_per_seq * a.page_tokens, H, self.q_heads // H, self.kps, self.splits, st)
+        args = (_lib.ptr(k), _lib.ptr(v), _lib.ptr(cache.k_mean), _lib.ptr(cache.k4), _lib.ptr(cache.ks),
+                _lib.ptr(cache.vt), _lib.ptr(cache.vs), _lib.ptr(cache.vtail), _lib.ptr(cache.lens),
+                _lib.ptr(cache.block_table), _lib.ptr(self.seq_tab), _lib.ptr(self.tiles), N, 2 * N, N * K,
+                a.max_seqs, H, a.num_pages, a.page_tokens, a.max_pages_per_seq, D)
+        if rope is None:
+            _lib.call("qattn_mxfp4_paged_append_packed", *args, st)
+        else:
+            _lib.call("qattn_mxfp4_paged_append_packed_rope", *args, _lib.ptr(rope.table), _lib.ptr(self.pos),
+                      rope.max_pos, int(rope.interleaved), st)
+        return self
+
+    def attend(self, cache: "PagedKVFP4", q: torch.Tensor, rope: Optional[Rope] = None):
+        """Attention of ``q`` fp16 [N * K, Hq, 128], row i * K + t the query of entry i's draft node t, over the
+        sequences after this step's ``append``, node t seeing the cached keys, its ancestors and itself ->
+        (``O`` fp16 [N * K, Hq, 128], ``lse`` fp32 [N * K, Hq] base 2), the step's own buffers; capturable.  ``q``
+        is quantised (rotated to ``pos`` first with ``rope``), one attention launch runs the fixed grid
+        (``qattn_mxfp4_attn_fwd_verify_step``) and one merge follows (``qattn_mxfp4_verify_step_combine``); the
+        rows of padding entries come back as O = 0, lse = -inf."""
+        self._pool(cache)
+        N, K, Hq, H, D = self.N, self.K, self.q_heads, self.kv_heads, 128
+        if tuple(q.shape) != (N * K, Hq, D):
+            raise _lib.QAttnError(f"qattn mxfp4 verify step: q must be [{N * K}, {Hq}, 128]")
+        if rope is not None:
+            self._rope(rope)
+        _lib.require_gpu(q, cache.k4)
+        q = _lib.kernel_input(q, torch.float16)
+        a, st = cache.alloc, _lib.stream_of(q)
+        if rope is None:
+            _lib.call("qattn_mxfp4_quant_rows", _lib.ptr(q), None, _lib.ptr(self.q4), _lib.ptr(self.qs), N * K * Hq,
+                      Hq, D, st)
+        else:
+            _lib.call("qattn_mxfp4_quant_rows_rope", _lib.ptr(q), _lib.ptr(self.q4), _lib.ptr(self.qs),
+                      _lib.ptr(rope.table), _lib.ptr(self.pos), N * K, Hq, rope.max_pos, int(rope.interleaved), D,
+                      st)
+        _lib.call("qattn_mxfp4_attn_fwd_verify_step", _lib.ptr(self.q4), _lib.ptr(self.qs), _lib.ptr(cache.k4),
+                  _lib.ptr(cache.ks), _lib.ptr(cache.vt), _lib.ptr(cache.vs), _lib.ptr(self.opart),
+                  _lib.ptr(self.ml), _lib.ptr(cache.lens), _lib.ptr(cache.block_table), _lib.ptr(self.seq_rec),
+                  _lib.ptr(self.work), _lib.ptr(self.tree), N, K, self.splits, a.max_seqs, H, Hq // H, a.num_pages,
+                  a.page_tokens, a.max_pages_per_seq, self.kps, D, _qk_scale(D), st)
+        _lib.call("qattn_mxfp4_verify_step_combine", _lib.ptr(self.opart), _lib.ptr(self.ml), _lib.ptr(self.O),
+                  _lib.ptr(self.lse), _lib.ptr(self.seq_rec), N, K, self.splits, Hq, H, D, st)
         return self.O, self.lse

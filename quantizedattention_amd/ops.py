@@ -35,6 +35,10 @@ the autograd rules of ``int8_fwd`` and ``bf16_fwd`` (their backward operators).
                                            window, sinks) -> (seq_tab, tiles, pos, seq_rec)
     torch.ops.qattn.mxfp4_decode_step(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, splits,
                                       keys_per_split, window, sinks) -> (O, lse)
+    torch.ops.qattn.mxfp4_verify_step_plan(slots, lens, tree, draft_tokens, capacity, kv_heads, group,
+                                           keys_per_split, splits) -> (seq_tab, tiles, pos, seq_rec)
+    torch.ops.qattn.mxfp4_verify_step(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, tree, draft_tokens,
+                                      splits, keys_per_split) -> (O, lse)
 
 Shapes follow the drop-in functions (attention_int8.py:259-262 for the int8 outputs) except that
 k_i8 is returned row-major [B*Hkv*Sk, D] (the drop-in's k_i8T is its transposed view: an operator
@@ -52,7 +56,8 @@ from . import _lib
 
 __all__ = ["int8_quant", "int8_fwd", "int8_bwd", "bf16_fwd", "bf16_bwd", "jvp_fwd", "mxfp4_fwd",
            "mxfp4_fwd_ex", "mxfp4_cached", "mxfp4_decode", "mxfp4_decode_paged", "mxfp4_varlen_paged",
-           "mxfp4_quant_rows_rope", "mxfp4_decode_step_plan", "mxfp4_decode_step"]
+           "mxfp4_quant_rows_rope", "mxfp4_decode_step_plan", "mxfp4_decode_step",
+           "mxfp4_verify_step_plan", "mxfp4_verify_step"]
 
 _lib.load_ops()
 _ops = torch.ops.qattn
@@ -182,6 +187,19 @@ def _(slots, lens, capacity, kv_heads, group, keys_per_split, splits, window, si
 
 @torch.library.register_fake("qattn::mxfp4_decode_step")
 def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, splits, keys_per_split, window, sinks):
+    T, H, D = q.shape
+    return (q.new_empty((T, H, D), dtype=torch.float16), q.new_empty((T, H), dtype=torch.float32))
+
+
+@torch.library.register_fake("qattn::mxfp4_verify_step_plan")
+def _(slots, lens, tree, draft_tokens, capacity, kv_heads, group, keys_per_split, splits):
+    n = slots.shape[0]
+    e = lambda *s: slots.new_empty(s, dtype=torch.int32)  # noqa: E731
+    return e(n, 4), e(2 * n, 2), e(n * draft_tokens), e(n, 8)
+
+
+@torch.library.register_fake("qattn::mxfp4_verify_step")
+def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, tree, draft_tokens, splits, keys_per_split):
     T, H, D = q.shape
     return (q.new_empty((T, H, D), dtype=torch.float16), q.new_empty((T, H), dtype=torch.float32))
 
@@ -415,3 +433,23 @@ def mxfp4_decode_step(q, step, cache, seq_rec=None):
     return _ops.mxfp4_decode_step(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens, cache.block_table,
                                   step.seq_rec if seq_rec is None else seq_rec, step.work, step.splits, step.kps,
                                   step.window or 0, step.sinks)
+
+
+def mxfp4_verify_step_plan(step, cache):
+    """The tables of ``kv_cache_mxfp4.VerifyStep.append`` as one operator: from ``step.slots`` and ``step.tree``
+    (what ``step.prepare`` uploaded) and ``cache.lens``, the lengths BEFORE the step's append -> new device tensors
+    (seq_tab [N, 4], tiles [2 N, 2], pos [N * K], seq_rec [N, 8]), what ``qattn_mxfp4_verify_step_plan`` writes
+    into the step's own tables."""
+    a = cache.alloc
+    return _ops.mxfp4_verify_step_plan(step.slots, cache.lens, step.tree, step.K,
+                                       a.max_pages_per_seq * a.page_tokens, step.kv_heads,
+                                       step.q_heads // step.kv_heads, step.kps, step.splits)
+
+
+def mxfp4_verify_step(q, step, cache, seq_rec=None):
+    """``kv_cache_mxfp4.VerifyStep.attend`` (without ``rope``) as one operator that allocates its outputs: q [N *
+    K, Hq, 128] against ``cache`` after the step's append, over ``seq_rec`` (default: the step's own, which its
+    ``append`` wrote), the step's ``work`` and ``tree`` -> (O, lse), the Python call's bits."""
+    return _ops.mxfp4_verify_step(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens, cache.block_table,
+                                  step.seq_rec if seq_rec is None else seq_rec, step.work, step.tree, step.K,
+                                  step.splits, step.kps)
