@@ -36,7 +36,7 @@ extern "C" {
  * qattn_source_hash() is the sha256 (hex) of the kernel sources and compile flags the library was
  * built from (quantizedattention_amd/_srchash.py); the Python binding refuses a library whose hash
  * differs from the sources beside it (a stale prebuilt library). */
-#define QATTN_ABI_VERSION 8
+#define QATTN_ABI_VERSION 9
 int qattn_abi_version(void);
 const char* qattn_source_hash(void);
 
@@ -500,7 +500,12 @@ int qattn_mxfp4_paged_append(const void* k, const void* v, const void* k_mean, v
  * that are not listed are never read.  A slot, row or partial row outside the sizes given is clamped or
  * skipped (a wrong table gives a wrong answer, never an address outside the buffers).
  * Preconditions the caller guarantees: 1 <= L_j <= (pages of s_j) * P, causal == 2: n_j <= L_j.
- * Returns 1 for head_dim != 128, a NULL lens / block_table / seq_rec / work, the pool's limits above,
+ * head_dim 64 (ABI 9): this entry, the windowed one below, qattn_mxfp4_varlen_combine(_sink),
+ * qattn_mxfp4_paged_append_packed(_rope) and qattn_mxfp4_quant_rows_rope take head_dim 64 as well: the pool's
+ * operands, q4 / qscale, opart and out are sized by it (K rows of 32 B and 2 scale bytes, V tiles [64][32 B] and
+ * [64][2], opart / out rows of 64), the arithmetic is the same definition at D = 64, and the tiles come through
+ * a ring whose slot holds two consecutive 64-key tiles.  Every other MX-FP4 entry returns 1 for it.
+ * Returns 1 for head_dim other than 128 and 64, a NULL lens / block_table / seq_rec / work, the pool's limits above,
  * keys_per_split < 64 or % 64, causal not 0 or 2, group < 1, max_seqs < 1, nseq > max_seqs or > tokens,
  * tokens * group * kv_heads, part_rows, nwork * kv_heads or max_seqs * kv_heads >= 2^31; 0 without a
  * launch for nseq, nwork or tokens == 0.  Allocates nothing. */
@@ -602,14 +607,26 @@ int qattn_mxfp4_paged_rollback(const void* saved, void* vtail, void* vt, void* v
 
 /* The merge of the packed step: qattn_mxfp4_split_combine's arithmetic in its order, per packed row
  * (token, query head), over the ns_j partial rows of the token's own sequence (found by binary search
- * over seq_rec's first-token column): out f16 [tokens][q_heads][128], lse f32 [tokens][q_heads].
- * Returns 1 for head_dim != 128, seq_rec == NULL, q_heads % kv_heads, nseq > tokens, tokens * q_heads
+ * over seq_rec's first-token column): out f16 [tokens][q_heads][head_dim], lse f32 [tokens][q_heads].
+ * Returns 1 for head_dim other than 128 and 64, seq_rec == NULL, q_heads % kv_heads, nseq > tokens, tokens * q_heads
  * or part_rows >= 2^31; 0 without a launch for nseq or tokens == 0. */
 int qattn_mxfp4_varlen_combine(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
                                long nseq, long tokens, long q_heads, long kv_heads, long part_rows,
                                int head_dim, void* stream);
 
-/* qattn_mxfp4_paged_append for packed tokens: k, v f16 [tokens][kv_heads][128] token-major; seq_tab
+/* The same merge with a learned sink logit per query head: sink_logit f32 [q_heads] on the device, in natural-
+ * log units.  The sink is a key without a value: it joins the denominator here and nowhere else.  With (M, L,
+ * acc) the merged state of a row of query head h: z = sink_logit[h] * log2(e) (one rounded fp32 product), M' =
+ * max(M, ceil(z)), w = 2^(M - M') (exact; 0 for M = -inf), L' = fma(w, L, exp2(z - M')), out = f16((w acc) *
+ * (1 / L')) under the rounding rule of the merge, lse = M' + log2(L'): lse covers the visible keys and the
+ * sink.  A row whose splits saw no key gets out = 0, lse = z.  head_dim 128 or 64; returns 1 for a NULL
+ * sink_logit and as the entry above. */
+int qattn_mxfp4_varlen_combine_sink(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
+                                    const void* sink_logit, long nseq, long tokens, long q_heads, long kv_heads,
+                                    long part_rows, int head_dim, void* stream);
+
+/* qattn_mxfp4_paged_append for packed tokens: k, v f16 [tokens][kv_heads][head_dim] token-major (head_dim 128 or
+ * 64, which that entry does not take); seq_tab
  * i32 [nseq][4] = {slot, count >= 1, first packed token (ascending), 0} and tiles i32 [ntiles][2] = {j,
  * logical 64-key tile}, the tiles [lens/64, (lens + count - 1)/64] of every record j (exactly the V
  * tiles the appends touch), both on the device.  The same quantisers, vtail and lens update; block_table
@@ -625,19 +642,19 @@ int qattn_mxfp4_paged_append_packed(const void* k, const void* v, const void* k_
                                     void* stream);
 
 /* Rotary position embedding fused into the quantisers of the packed step (kv_cache_mxfp4.py Rope).
- * cos_sin f32 [max_pos][128], contiguous: row p holds cos theta(p, i) at column i and sin theta(p, i) at
- * column 64 + i for pair i in [0, 64) (the cos_sin_cache convention; a table scaled by YaRN, llama3 or NTK
- * is passed as it is).  interleaved 0 (NeoX, rotate half) pairs elements (i, i + 64) of a row, 1 (GPT-J)
- * elements (2i, 2i + 1).  With c, s from the row of the token's position, a pair (a, b) of f16 inputs
+ * cos_sin f32 [max_pos][D], D = head_dim (128 or 64), contiguous: row p holds cos theta(p, i) at column i and
+ * sin theta(p, i) at column D/2 + i for pair i in [0, D/2) (the cos_sin_cache convention; a table scaled by
+ * YaRN, llama3 or NTK is passed as it is).  interleaved 0 (NeoX, rotate half) pairs elements (i, i + D/2) of a
+ * row, 1 (GPT-J) elements (2i, 2i + 1).  With c, s from the row of the token's position, a pair (a, b) of f16 inputs
  * becomes first = f16(f32(a c) - f32(b s)), second = f16(f32(b c) + f32(a s)): two rounded fp32 products,
  * one rounded fp32 sum, round-to-nearest-even to f16, no fused multiply-add; the rotated f16 row then
  * goes through the quantiser unchanged (keys: f16(x - k_mean) first, as without).  pos i32 [tokens] on
  * the device holds one position per packed token and is clamped to [0, max_pos - 1]: a wrong position
  * gives a wrong answer, never an address outside the table.
  *
- * qattn_mxfp4_quant_rows_rope: qattn_mxfp4_quant_rows without a mean on x f16 [tokens][heads][128], token-
+ * qattn_mxfp4_quant_rows_rope: qattn_mxfp4_quant_rows without a mean on x f16 [tokens][heads][head_dim], token-
  * major (the packed q of qattn_mxfp4_attn_fwd_varlen_paged), each row rotated first.  Returns 1 for head_dim
- * != 128, a NULL cos_sin or pos, max_pos < 1 or >= 2^31, interleaved outside {0, 1}, tokens * heads >= 2^31;
+ * other than 128 and 64, a NULL cos_sin or pos, max_pos < 1 or >= 2^31, interleaved outside {0, 1}, tokens * heads >= 2^31;
  * 0 without a launch for tokens or heads == 0. */
 int qattn_mxfp4_quant_rows_rope(const void* x, void* q4, void* scale, const void* cos_sin, const void* pos,
                                 long tokens, long heads, long max_pos, int interleaved, int head_dim,

@@ -57,18 +57,19 @@ def mxfp4_quantize_rows(x: torch.Tensor, mean: torch.Tensor | None = None):
     return q4, sc
 
 
-ROPE_DIM = 128   # the head_dim of every rotary entry
+ROPE_DIM = 128   # the head_dim of rope_table's default
+ROPE_DIMS = (64, 128)   # the head dims of the rotary entries
 
 
 @dataclass(frozen=True)
 class Rope:
     """A rotary table for the ``rope=`` arguments of the packed MX-FP4 cache path.
 
-    ``table`` fp32 [max_pos, 128], contiguous, on the GPU: row p holds cos theta(p, i) in column i and
-    sin theta(p, i) in column 64 + i for pair i in [0, 64) (the ``cos_sin_cache`` convention, so a table
-    scaled by YaRN, llama3 or NTK is passed as it is; :func:`rope_table` makes the plain one).
-    ``interleaved=False`` (NeoX, rotate half) pairs elements (i, i + 64) of a head's row, ``True`` (GPT-J)
-    elements (2i, 2i + 1).  The rotation itself is defined bit for bit (include/qattn.h): per pair (a, b),
+    ``table`` fp32 [max_pos, D], D = 128 or 64 (the head_dim of the pool and the queries it is used with),
+    contiguous, on the GPU: row p holds cos theta(p, i) in column i and sin theta(p, i) in column D/2 + i for
+    pair i in [0, D/2) (the ``cos_sin_cache`` convention, so a table scaled by YaRN, llama3 or NTK is passed as
+    it is; :func:`rope_table` makes the plain one).  ``interleaved=False`` (NeoX, rotate half) pairs elements
+    (i, i + D/2) of a head's row, ``True`` (GPT-J) elements (2i, 2i + 1).  The rotation itself is defined bit for bit (include/qattn.h): per pair (a, b),
     ``f16(f32(a c) - f32(b s))`` and ``f16(f32(b c) + f32(a s))``, what ``(a.float() * c - b.float() *
     s).half()`` gives in torch."""
 
@@ -78,9 +79,9 @@ class Rope:
     def __post_init__(self):
         t = self.table
         if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2
-                or t.shape[1] != ROPE_DIM or t.shape[0] < 1 or not t.is_contiguous()):
-            raise _lib.QAttnError("qattn mxfp4 rope: the table must be a contiguous fp32 tensor [max_pos >= 1, 128] "
-                                  "(cos in columns [0, 64), sin in [64, 128))")
+                or t.shape[1] not in ROPE_DIMS or t.shape[0] < 1 or not t.is_contiguous()):
+            raise _lib.QAttnError("qattn mxfp4 rope: the table must be a contiguous fp32 tensor [max_pos >= 1, D], "
+                                  "D = 128 or 64 (cos in columns [0, D/2), sin in [D/2, D))")
         _lib.require_gpu(t)
         if not isinstance(self.interleaved, bool):
             raise _lib.QAttnError(f"qattn mxfp4 rope: interleaved must be a bool, got {self.interleaved!r}")
@@ -89,15 +90,26 @@ class Rope:
     def max_pos(self) -> int:
         return self.table.shape[0]
 
+    @property
+    def head_dim(self) -> int:
+        return self.table.shape[1]
 
-def rope_table(max_pos: int, base: float = 10000.0, device=None) -> torch.Tensor:
-    """The plain rotary table fp32 [max_pos, 128] of :class:`Rope`: the angles ``p * base ** (-2 i / 128)``
-    are computed in float64 on the host, their cos (columns [0, 64)) and sin (columns [64, 128)) rounded
-    once to fp32, then moved to ``device`` (None: left on the host)."""
-    if int(max_pos) < 1 or not base > 0:
-        raise _lib.QAttnError(f"qattn mxfp4 rope: max_pos >= 1 and base > 0 expected, got {max_pos}, {base}")
-    i = torch.arange(ROPE_DIM // 2, dtype=torch.float64)
-    inv_freq = torch.pow(torch.tensor(float(base), dtype=torch.float64), -2.0 * i / ROPE_DIM)
+    def check_head_dim(self, head_dim: int) -> None:
+        """Raise unless the table is as wide as the rows it is to rotate."""
+        if self.head_dim != head_dim:
+            raise _lib.QAttnError(f"qattn mxfp4 rope: a table of width {self.head_dim} for rows of head_dim "
+                                  f"{head_dim}")
+
+
+def rope_table(max_pos: int, base: float = 10000.0, device=None, head_dim: int = ROPE_DIM) -> torch.Tensor:
+    """The plain rotary table fp32 [max_pos, D] of :class:`Rope` (D = ``head_dim``, 128 or 64): the angles
+    ``p * base ** (-2 i / D)`` are computed in float64 on the host, their cos (columns [0, D/2)) and sin
+    (columns [D/2, D)) rounded once to fp32, then moved to ``device`` (None: left on the host)."""
+    if int(max_pos) < 1 or not base > 0 or head_dim not in ROPE_DIMS:
+        raise _lib.QAttnError(f"qattn mxfp4 rope: max_pos >= 1, base > 0 and head_dim 64 or 128 expected, got "
+                              f"{max_pos}, {base}, {head_dim}")
+    i = torch.arange(head_dim // 2, dtype=torch.float64)
+    inv_freq = torch.pow(torch.tensor(float(base), dtype=torch.float64), -2.0 * i / head_dim)
     ang = torch.arange(int(max_pos), dtype=torch.float64)[:, None] * inv_freq[None, :]
     table = torch.cat([ang.cos(), ang.sin()], 1).to(torch.float32).contiguous()
     return table if device is None else table.to(device)
@@ -126,14 +138,15 @@ def _device_positions(positions, tokens: int) -> bool:
 
 
 def mxfp4_quantize_rows_rope(x: torch.Tensor, rope: Rope, positions):
-    """Packed x [T, H, 128] (fp16, token-major), each row rotated by its token's position first (:class:`Rope`)
-    -> (packed uint8 [T*H, 64], scales uint8 [T*H, 4]), bit for bit ``mxfp4_quantize_rows`` of the rotated
+    """Packed x [T, H, D] (fp16, token-major; D = 128 or 64, the table's width), each row rotated by its token's
+    position first (:class:`Rope`) -> (packed uint8 [T*H, D/2], scales uint8 [T*H, D/32]), bit for bit ``mxfp4_quantize_rows`` of the rotated
     fp16 rows.  ``positions``: T ints in [0, rope.max_pos) as a list or a host tensor (checked, uploaded
     without a synchronisation), or a device int32 tensor [T], used as given."""
     if not isinstance(rope, Rope):
         raise _lib.QAttnError("qattn mxfp4 rope: rope must be a Rope")
-    if x.dim() != 3 or x.shape[2] != ROPE_DIM:
-        raise _lib.QAttnError("qattn mxfp4 rope: packed rows must be x [T, H, 128]")
+    if x.dim() != 3 or x.shape[2] not in ROPE_DIMS:
+        raise _lib.QAttnError("qattn mxfp4 rope: packed rows must be x [T, H, 128] or [T, H, 64]")
+    rope.check_head_dim(x.shape[2])
     T, H, D = x.shape
     if T * H >= 1 << 31:
         raise _lib.QAttnError("qattn mxfp4 rope: fewer than 2^31 packed rows expected")

@@ -49,6 +49,10 @@ FILE_FLAGS = {
     # forward (536-544 against 545-559 us); the bf16 backward is slower under it (3.85 against 3.79-3.83
     # ms) and keeps the default (profiles/r05_int8_fwd_sched_ab.log)
     "mxfp4_attn.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
+    # the head_dim 64 kernels share that file's tile body and its scheduler; packed fp32 arithmetic is off (the
+    # rescale of O is the only place it would appear, once per raised row maximum)
+    "mxfp4_attn_d64.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp",
+                           "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

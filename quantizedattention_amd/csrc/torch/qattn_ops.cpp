@@ -32,7 +32,8 @@
 //       the same with a sliding window and sinks (causal only)
 //   mxfp4_varlen_paged(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal,
 //                      keys_per_split) -> (O, lse)
-//       kv_cache_mxfp4.attention_mxfp4_varlen_paged: packed q [T, Hq, 128] and the two plan tables
+//       kv_cache_mxfp4.attention_mxfp4_varlen_paged: packed q [T, Hq, D] (D = 128, or 64 here, in the windowed
+//       and in the rope form) and the two plan tables
 //   mxfp4_varlen_paged_tree(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, tree_masks, part_rows,
 //                           causal, keys_per_split) -> (O, lse)      the same with a tree mask (verify step)
 //   mxfp4_varlen_paged_shared(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, grp_rec, members,
@@ -442,12 +443,12 @@ Tensor mxfp4_fwd(const Tensor& q, const Tensor& k, const Tensor& v) { return mxf
 // What the cache operators check of the four quantised operands (k4 [n0, Hkv, S, 64]; `paged`: a page pool,
 // whose vt / vs keep k4's two leading dimensions) and of lens i32 [B] (null: the operator has none).
 void check_fp4_operands(const Tensor& k4, const Tensor& ks, const Tensor& vt, const Tensor& vs,
-                        const Tensor* lens, int64_t B, bool paged) {
+                        const Tensor* lens, int64_t B, bool paged, int64_t D = 128) {
   const char* what = paged ? "qattn mxfp4 paged cache: " : "qattn mxfp4 kv cache: ";
   for (const Tensor* t : {&k4, &ks, &vt, &vs})
     TORCH_CHECK(t->scalar_type() == at::kByte && t->is_contiguous(), what,
                 "the quantised operands must be contiguous uint8");
-  const int64_t n0 = k4.size(0), H = k4.size(1), S = k4.size(2), D = 128;
+  const int64_t n0 = k4.size(0), H = k4.size(1), S = k4.size(2);
   TORCH_CHECK(ks.sizes() == at::IntArrayRef({n0, H, S, D / 32}) &&
                   (paged ? vt.sizes() == at::IntArrayRef({n0, H, S / 64, D, 32}) &&
                                vs.sizes() == at::IntArrayRef({n0, H, S / 64, D, 2})
@@ -583,11 +584,11 @@ struct RopeArgs {
   const Tensor& pos;
   bool interleaved;
 };
-void check_rope(const RopeArgs& r, int64_t tokens) {
+void check_rope(const RopeArgs& r, int64_t tokens, int64_t D = 128) {
   require_gpu({&r.cos_sin, &r.pos});
   TORCH_CHECK(r.cos_sin.scalar_type() == at::kFloat && r.cos_sin.is_contiguous() && r.cos_sin.dim() == 2 &&
-                  r.cos_sin.size(1) == 128 && r.cos_sin.size(0) >= 1,
-              "qattn mxfp4 rope: the table must be a contiguous fp32 tensor [max_pos >= 1, 128]");
+                  r.cos_sin.size(1) == D && r.cos_sin.size(0) >= 1,
+              "qattn mxfp4 rope: the table must be a contiguous fp32 tensor [max_pos >= 1, head_dim]");
   TORCH_CHECK(r.pos.scalar_type() == at::kInt && r.pos.is_contiguous() && r.pos.dim() == 1 &&
                   r.pos.size(0) == tokens,
               "qattn mxfp4 rope: positions must be a contiguous int32 tensor [T], one per packed token");
@@ -597,10 +598,11 @@ void check_rope(const RopeArgs& r, int64_t tokens) {
 std::tuple<Tensor, Tensor> mxfp4_quant_rows_rope(const Tensor& x_in, const Tensor& cos_sin, const Tensor& pos,
                                                  bool interleaved) {
   require_gpu({&x_in});
-  TORCH_CHECK(x_in.dim() == 3 && x_in.size(2) == 128, "qattn mxfp4 rope: packed rows must be x [T, H, 128]");
-  const int64_t T = x_in.size(0), H = x_in.size(1), D = 128;
+  TORCH_CHECK(x_in.dim() == 3 && (x_in.size(2) == 128 || x_in.size(2) == 64),
+              "qattn mxfp4 rope: packed rows must be x [T, H, 128] or [T, H, 64]");
+  const int64_t T = x_in.size(0), H = x_in.size(1), D = x_in.size(2);
   const RopeArgs rope{cos_sin, pos, interleaved};
-  check_rope(rope, T);
+  check_rope(rope, T, D);
   Ctx c(x_in);
   const Tensor x = kin(x_in, at::kHalf), p = kin(pos);
   Tensor q4 = empty({T * H, D / 2}, at::kByte, x), qs = empty({T * H, D / 32}, at::kByte, x);
@@ -628,7 +630,7 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged_run(const Tensor& q_in, const Tens
                                                   const Tensor* tree = nullptr,
                                                   const RopeArgs* rope = nullptr) {
   require_gpu({&q_in, &k4, &ks, &vt, &vs, &lens, &block_table, &seq_rec, &work});
-  if (rope) check_rope(*rope, q_in.dim() == 3 ? q_in.size(0) : -1);
+  if (rope) check_rope(*rope, q_in.dim() == 3 ? q_in.size(0) : -1, q_in.dim() == 3 ? q_in.size(2) : 128);
   if (tree) {   // the tree entry's ancestor words, one per packed token
     require_gpu({tree});
     TORCH_CHECK(tree->scalar_type() == at::kLong && tree->is_contiguous() && tree->dim() == 1 &&
@@ -646,9 +648,13 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged_run(const Tensor& q_in, const Tens
                 "qattn mxfp4 paged cache: members must be contiguous int32 [nmember, 2], 2 * ngroup <= nmember "
                 "<= nseq");
   }
-  TORCH_CHECK(q_in.dim() == 3 && k4.dim() == 4 && q_in.size(2) == 128 && k4.size(3) == 64,
-              "qattn mxfp4 paged cache: packed queries must be q [T, Hq, 128], head_dim 128 in the pool");
-  const int64_t NP = k4.size(0), Hkv = k4.size(1), PT = k4.size(2), D = 128;
+  TORCH_CHECK(q_in.dim() == 3 && k4.dim() == 4 && (q_in.size(2) == 128 || q_in.size(2) == 64) &&
+                  k4.size(3) * 2 == q_in.size(2),
+              "qattn mxfp4 paged cache: packed queries must be q [T, Hq, D], D = 128 or 64, the pool's head_dim");
+  const int64_t NP = k4.size(0), Hkv = k4.size(1), PT = k4.size(2), D = q_in.size(2);
+  // head_dim 64 is the plain and the windowed packed step's (csrc/mxfp4_attn_d64.hip), with or without rope
+  TORCH_CHECK_VALUE(D == 128 || (!grp_rec && !tree),
+                    "qattn mxfp4 paged cache: shared prefixes and tree masks need head_dim 128, this pool has 64");
   TORCH_CHECK(PT >= 64 && PT <= 1024 && (PT & (PT - 1)) == 0,
               "qattn mxfp4 paged cache: page_tokens must be 64 * 2^k in [64, 1024]");
   TORCH_CHECK(block_table.scalar_type() == at::kInt && block_table.is_contiguous() && block_table.dim() == 2 &&
@@ -659,7 +665,7 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged_run(const Tensor& q_in, const Tens
   TORCH_CHECK(Hkv > 0 && NP > 0 && Hq > 0 && Hq % Hkv == 0,
               "qattn mxfp4 paged cache: q must have G * Hkv heads for the pool's Hkv");
   TORCH_CHECK(causal == 0 || causal == 1, "qattn mxfp4 paged cache: causal must be 0 or 1");
-  check_fp4_operands(k4, ks, vt, vs, &lens, B, true);
+  check_fp4_operands(k4, ks, vt, vs, &lens, B, true, D);
   TORCH_CHECK(seq_rec.scalar_type() == at::kInt && seq_rec.is_contiguous() && seq_rec.dim() == 2 &&
                   seq_rec.size(1) == 8 && seq_rec.size(0) >= 1 && seq_rec.size(0) <= B,
               "qattn mxfp4 paged cache: seq_rec must be contiguous int32 [nseq, 8], 1 <= nseq <= B");

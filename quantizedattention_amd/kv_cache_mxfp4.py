@@ -213,7 +213,8 @@ __all__ = ["QuantizedKVFP4", "quantize_kv_fp4", "attention_mxfp4_cached", "Preal
            "attention_mxfp4_decode", "PageAllocator", "PagedKVFP4", "attention_mxfp4_decode_paged",
            "plan_varlen", "plan_varlen_shared", "attention_mxfp4_varlen_paged", "tree_ancestor_masks",
            "tree_path", "Checkpoint", "Rope", "rope_table", "rope_positions", "DecodeStep",
-           "decode_step_splits", "plan_decode_step", "VerifyStep", "verify_step_splits", "plan_verify_step"]
+           "decode_step_splits", "plan_decode_step", "VerifyStep", "verify_step_splits", "plan_verify_step",
+           "HeadDimError"]
 
 
 @dataclass
@@ -773,6 +774,10 @@ class Checkpoint:
     saved: torch.Tensor
 
 
+class HeadDimError(_lib.QAttnError, ValueError):
+    """A call that a pool of this head_dim does not serve (a ``ValueError`` too)."""
+
+
 class PagedKVFP4:
     """MX-FP4 keys/values of up to ``max_seqs`` sequences x ``kv_heads`` heads in a pool of
     ``num_pages`` pages of ``page_tokens`` tokens; layout and invariant: the module docstring.
@@ -794,9 +799,14 @@ class PagedKVFP4:
 
     @classmethod
     def allocate(cls, num_pages: int, page_tokens: int, max_seqs: int, kv_heads: int, max_pages_per_seq: int,
-                 device, k_mean: Optional[torch.Tensor] = None, free_order=None) -> "PagedKVFP4":
-        """An empty pool (every length 0, every page free), zero-filled."""
-        D = 128
+                 device, k_mean: Optional[torch.Tensor] = None, free_order=None,
+                 head_dim: int = 128) -> "PagedKVFP4":
+        """An empty pool (every length 0, every page free), zero-filled.  ``head_dim`` is 128 or 64; a pool of
+        64 serves the packed path (``append_packed``, :func:`attention_mxfp4_varlen_paged` without
+        ``share_prefix`` and ``tree``) and the host-only operations, and refuses the rest (:meth:`_need128`)."""
+        D = int(head_dim)
+        if D not in (64, 128):
+            raise HeadDimError(f"qattn mxfp4 paged cache: head_dim must be 128 or 64, got {head_dim}")
         alloc = PageAllocator(num_pages, page_tokens, max_seqs, max_pages_per_seq, free_order)
         tpp = page_tokens // BLOCK
         if (kv_heads < 1 or num_pages * kv_heads * tpp >= 1 << 31
@@ -809,7 +819,7 @@ class PagedKVFP4:
                                   "(no CPU fallback by design)")
         if k_mean is not None:
             if tuple(k_mean.shape) != (max_seqs, kv_heads, 1, D):
-                raise _lib.QAttnError("qattn mxfp4 paged cache: k_mean must be [max_seqs, Hkv, 1, 128]")
+                raise _lib.QAttnError(f"qattn mxfp4 paged cache: k_mean must be [max_seqs, Hkv, 1, {D}]")
             k_mean = _lib.kernel_input(k_mean.to(device=dev), torch.float16)
         z = lambda *shape, dt=torch.uint8: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
         return cls(z(num_pages, kv_heads, page_tokens, D // 2), z(num_pages, kv_heads, page_tokens, D // 32),
@@ -820,7 +830,17 @@ class PagedKVFP4:
     @property
     def shape(self):
         """(max_seqs, Hkv, max_pages_per_seq * page_tokens, D): what one table row can hold"""
-        return (self.alloc.max_seqs, self.k4.shape[1], self.alloc.max_pages_per_seq * self.page_tokens, 128)
+        return (self.alloc.max_seqs, self.k4.shape[1], self.alloc.max_pages_per_seq * self.page_tokens,
+                2 * self.k4.shape[3])
+
+    def _need128(self, what: str) -> None:
+        """Raise :class:`HeadDimError` for ``what`` on a pool of head_dim 64, which only the packed step's own
+        kernels serve (csrc/mxfp4_attn_d64.hip); called before anything is reserved, launched or changed."""
+        D = self.shape[3]
+        if D != 128:
+            raise HeadDimError(f"qattn mxfp4 paged cache: {what} needs head_dim 128, this pool has head_dim {D} "
+                               "(served there: append_packed and attention_mxfp4_varlen_paged without "
+                               "share_prefix and tree)")
 
     @property
     def page_tokens(self) -> int:
@@ -861,6 +881,7 @@ class PagedKVFP4:
         ``max_pages_per_seq``, raises before anything is launched or changed), the changed table is
         uploaded in stream order and ``qattn_mxfp4_paged_append`` writes in place.  No host
         synchronisation, nothing is read back; returns ``self``."""
+        self._need128("the padded append")
         B, H, _, D = self.shape
         if (k.dim() != 4 or tuple(k.shape[:2]) != (B, H) or k.shape[3] != D or k.shape != v.shape
                 or k.shape[2] < 1):
@@ -907,7 +928,7 @@ class PagedKVFP4:
             raise _lib.QAttnError("qattn mxfp4 paged cache: packed tokens must be k, v [sum(counts), Hkv, D]")
         if k.shape[0] * H >= 1 << 31:
             raise _lib.QAttnError("qattn mxfp4 paged cache: fewer than 2^31 packed rows expected")
-        pos = _rope_args(rope, positions, tree, k.shape[0], lambda: (self.lengths, ids, cnt, tree))
+        pos = _rope_args(rope, positions, tree, k.shape[0], lambda: (self.lengths, ids, cnt, tree), D)
         _lib.require_gpu(k, v, self.k4)
         grown = self.alloc.reserve([(b, self.lengths[b] + c) for b, c in zip(ids, cnt)])
         k = _lib.kernel_input(k, torch.float16)
@@ -988,6 +1009,7 @@ class PagedKVFP4:
         L0, its logical page count, its hole count and the slot's epoch on the host, and on the device a
         copy of the slots' ``vtail`` rows (rows [0, L0 % 64) are what matters: a later append that crosses
         a tile boundary overwrites them).  Stream-ordered, no synchronisation, nothing read back."""
+        self._need128("checkpoint")
         ids = [self.alloc._seq(b) for b in seq_ids]
         if not ids or len(set(ids)) != len(ids):
             raise _lib.QAttnError(f"qattn mxfp4 paged cache: checkpoint needs distinct slots, got {ids}")
@@ -1034,6 +1056,7 @@ class PagedKVFP4:
         or rolled back through another checkpoint since), "shorter" (its length is below L0 now), "shared"
         (L0 % P != 0 and the page holding position L0 has a reference count above 1).  Stream-ordered, no
         synchronisation; returns ``self``.  Not for :class:`PreallocatedKVFP4`."""
+        self._need128("rollback")
         rows = self._rollback_check(ckpt, seq_ids)
         self._rollback(ckpt, rows)
         return self
@@ -1093,6 +1116,7 @@ class PagedKVFP4:
         sequence j are rotated to L0_j, L0_j + 1, ...: for a :func:`tree_path` exactly where their depths
         put them in the draft step.  ``k`` is then the UNROTATED key of the draft step, the tensor that
         step's ``append_packed(..., rope=)`` was given."""
+        self._need128("accept")
         _, H, _, D = self.shape
         if rope is not None and not isinstance(rope, Rope):
             raise _lib.QAttnError("qattn mxfp4 rope: rope must be a Rope")
@@ -1176,6 +1200,8 @@ def attention_mxfp4_decode_paged(q: torch.Tensor, cache: PagedKVFP4, causal: boo
     tokens gives.  The same contract: every sequence slot needs a length >= 1 (raises otherwise),
     causal needs Sq <= min(lengths); the plan is ``_split_plan_fp4`` at ceil64(max(lengths)), and
     ``keys_per_split`` is any multiple of 64, whatever the page size."""
+    if isinstance(cache, PagedKVFP4):
+        cache._need128("attention_mxfp4_decode_paged")
     bhv, rows, sk_max, kps, nsplit = _decode_plan(q, cache, causal, keys_per_split, PagedKVFP4)
     if any(cache.alloc.nholes):   # this entry has no window: it reads every page
         for b in range(cache.alloc.max_seqs):
@@ -1346,7 +1372,7 @@ def rope_positions(lengths_before, seq_ids, counts, tree=None) -> list:
     return _default_positions(lengths_before, seq_ids, counts, tree)[0].tolist()
 
 
-def _rope_args(rope, positions, tree, tokens: int, default):
+def _rope_args(rope, positions, tree, tokens: int, default, head_dim: int = 128):
     """The rotary arguments of a packed call, checked before anything is reserved or launched -> None
     without ``rope``, else an int32 tensor [tokens]: the device tensor given as ``positions``, or host
     positions inside the table (``positions``, else ``default()``, the arguments of
@@ -1357,6 +1383,7 @@ def _rope_args(rope, positions, tree, tokens: int, default):
         return None
     if not isinstance(rope, Rope):
         raise _lib.QAttnError("qattn mxfp4 rope: rope must be a Rope")
+    rope.check_head_dim(head_dim)
     if positions is None:
         pos, lo, hi = _default_positions(*default())
         if lo < 0 or hi >= rope.max_pos:
@@ -1655,14 +1682,15 @@ def _query_positions(cache: "PagedKVFP4", ids, sq, tree, rope, positions):
         for b, n in zip(ids, sq):
             before[b] -= n
         return before, ids, sq, tree
-    return _rope_args(rope, positions, None, sum(sq), default)
+    return _rope_args(rope, positions, None, sum(sq), default, cache.shape[3])
 
 
 @torch.no_grad()
 def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_lens, causal: bool = False,
                                  keys_per_split: Optional[int] = None, window: Optional[int] = None,
                                  sinks: int = 0, share_prefix: bool = False, tree=None,
-                                 rope: Optional[Rope] = None, positions=None):
+                                 rope: Optional[Rope] = None, positions=None,
+                                 sink_logit: Optional[torch.Tensor] = None):
     """A ragged batch against a paged cache in one attention launch and one merge: packed fp16 queries
     ``q`` [T, Hq, D], token-major, the ``q_lens[0]`` tokens of sequence ``seq_ids[0]`` first, then
     those of ``seq_ids[1]``, ... (nseq >= 1 distinct slots, every q_lens[j] >= 1, T = sum(q_lens)) ->
@@ -1710,15 +1738,36 @@ def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_
     numbers :func:`rope_positions` gives for the ``append_packed`` that preceded this call (the queries
     are the sequence's last q_lens[j] tokens).  Explicit ``positions`` are as in ``append_packed``: a list
     or a host tensor, checked against the table before any launch, or a device int32 tensor [T], used as
-    given.  ``positions`` without ``rope`` raises."""
+    given.  ``positions`` without ``rope`` raises.
+
+    ``sink_logit`` (a device fp32 tensor [Hq], natural-log units, as gpt-oss-style layers store it; None: today's
+    launches and today's bytes) is one learned sink per query head: a key without a value that joins the softmax
+    denominator.  It enters in the merge alone (``qattn_mxfp4_varlen_combine_sink``): with (M, L, acc) the merged
+    state of a row of head h and z = sink_logit[h] * log2(e), M' = max(M, ceil(z)), w = 2^(M - M'), L' = fma(w,
+    L, exp2(z - M')), O = f16(w acc / L') and lse = M' + log2(L'), so ``lse`` covers the visible keys AND the sink.
+    Every mode takes it except ``share_prefix`` and ``tree``, which raise.
+
+    A pool of head_dim 64 (``PagedKVFP4.allocate(head_dim=64)``) takes q [T, Hq, 64] and runs the kernels of
+    csrc/mxfp4_attn_d64.hip: non-causal, causal and windowed calls, ``rope`` (a table of width 64) and
+    ``sink_logit``; ``share_prefix=True`` and ``tree`` raise :class:`HeadDimError` there."""
     if not isinstance(cache, PagedKVFP4):
         raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PagedKVFP4")
     _, Hkv, _, D = cache.shape
     if q.dim() != 3 or q.shape[2] != D:
-        raise _lib.QAttnError("qattn mxfp4 paged cache: packed queries must be q [T, Hq, 128]")
+        raise _lib.QAttnError(f"qattn mxfp4 paged cache: packed queries must be q [T, Hq, {D}]")
     T, Hq = q.shape[0], q.shape[1]
     if Hq == 0 or Hq % Hkv:
         raise _lib.QAttnError("qattn mxfp4 paged cache: q must have G * Hkv heads for the cache's Hkv")
+    if share_prefix or tree is not None:
+        cache._need128("share_prefix=True" if share_prefix else "tree=")
+        if sink_logit is not None:
+            raise _lib.QAttnError("qattn mxfp4 paged cache: sink_logit cannot be combined with share_prefix or "
+                                  "tree")
+    if sink_logit is not None:
+        if (not isinstance(sink_logit, torch.Tensor) or sink_logit.dtype != torch.float32
+                or tuple(sink_logit.shape) != (Hq,) or not sink_logit.is_cuda):
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: sink_logit must be a device fp32 tensor [{Hq}]")
+        sink_logit = _lib.kernel_input(sink_logit)
     ids, sq = _packed_lists(cache.alloc.max_seqs, seq_ids, q_lens, "q_lens")
     if sum(sq) != T:
         raise _lib.QAttnError(f"qattn mxfp4 paged cache: q holds {T} tokens, q_lens sum to {sum(sq)}")
@@ -1767,8 +1816,12 @@ def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_
         _lib.call("qattn_mxfp4_attn_fwd_varlen_paged", *args, st)
     else:   # no sequence holds 2^25 keys or more: a larger window or sink count means the same
         _lib.call("qattn_mxfp4_attn_fwd_varlen_paged_window", *args, min(W, 1 << 26), min(S, 1 << 26), st)
-    _lib.call("qattn_mxfp4_varlen_combine", _lib.ptr(opart), _lib.ptr(ml), _lib.ptr(O), _lib.ptr(lse),
-              _lib.ptr(rec_d), len(ids), T, Hq, Hkv, part_rows, D, st)
+    if sink_logit is None:
+        _lib.call("qattn_mxfp4_varlen_combine", _lib.ptr(opart), _lib.ptr(ml), _lib.ptr(O), _lib.ptr(lse),
+                  _lib.ptr(rec_d), len(ids), T, Hq, Hkv, part_rows, D, st)
+    else:
+        _lib.call("qattn_mxfp4_varlen_combine_sink", _lib.ptr(opart), _lib.ptr(ml), _lib.ptr(O), _lib.ptr(lse),
+                  _lib.ptr(rec_d), _lib.ptr(sink_logit), len(ids), T, Hq, Hkv, part_rows, D, st)
     return O, lse
 
 
@@ -1909,6 +1962,7 @@ class DecodeStep:
     def _pool(self, cache: "PagedKVFP4") -> None:
         if not isinstance(cache, PagedKVFP4):
             raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PagedKVFP4")
+        cache._need128("DecodeStep")
         if cache.shape[1] != self.kv_heads or cache.k4.device != self.slots.device:
             raise _lib.QAttnError(f"qattn mxfp4 decode step: a pool of {self.kv_heads} key/value heads on "
                                   f"{self.slots.device} expected")
@@ -2171,6 +2225,7 @@ class VerifyStep:
     def _pool(self, cache: "PagedKVFP4") -> None:
         if not isinstance(cache, PagedKVFP4):
             raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PagedKVFP4")
+        cache._need128("VerifyStep")
         if cache.shape[1] != self.kv_heads or cache.k4.device != self.slots.device:
             raise _lib.QAttnError(f"qattn mxfp4 verify step: a pool of {self.kv_heads} key/value heads on "
                                   f"{self.slots.device} expected")

@@ -355,13 +355,18 @@ def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=N
     entry per sequence, None or a ``parents`` list) routes to ``torch.ops.qattn.mxfp4_varlen_paged_tree``, the
     tree-masked verify step of the Python call, and to the plain operator when every entry is None.  ``rope``
     (with ``positions``, as the Python call's; without a window, ``share_prefix`` or ``tree``: those
-    combinations are the Python call's alone) routes to ``torch.ops.qattn.mxfp4_varlen_paged_rope``."""
+    combinations are the Python call's alone) routes to ``torch.ops.qattn.mxfp4_varlen_paged_rope``.  A pool of
+    head_dim 64 takes q [T, Hq, 64] in the plain, the windowed and the rope form; ``share_prefix=True`` and
+    ``tree`` raise there as in the Python call.  The learned sink logit (``sink_logit=``) is the Python call's and
+    the C ABI's alone."""
     from .kv_cache_mxfp4 import (PagedKVFP4, _check_trimmed, _packed_lists, _query_positions, _shared_plan,
                                  _tree_args, _window_args, plan_varlen)
     if not isinstance(cache, PagedKVFP4):
         raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PagedKVFP4")
     if q.dim() != 3:
-        raise _lib.QAttnError("qattn mxfp4 paged cache: packed queries must be q [T, Hq, 128]")
+        raise _lib.QAttnError("qattn mxfp4 paged cache: packed queries must be q [T, Hq, D]")
+    if share_prefix or tree is not None:
+        cache._need128("share_prefix=True" if share_prefix else "tree=")
     ids, sq = _packed_lists(cache.alloc.max_seqs, seq_ids, q_lens, "q_lens")
     if sum(sq) != q.shape[0]:
         raise _lib.QAttnError(f"qattn mxfp4 paged cache: q holds {q.shape[0]} tokens, q_lens sum to {sum(sq)}")

@@ -24,6 +24,12 @@ anything is timed (the pools of (b) hold different random tokens).
     with a window of everything (the causal kernel's tiles through the windowed instantiation), and
     free_pages before and after PagedKVFP4.trim of the batch.
 
+(e) with --head-dim 64 (then only (e) runs): gpt-oss-style heads, 64 query / 8 key-value heads of head_dim 64, at
+    three shapes -- 8 decodes at 8192 cached, 64 decodes at 32768 cached under window 128, a 512-token chunk
+    beside 15 decodes.  Per shape, kernel alone (REPS launches): the D = 64 kernel with two tiles per ring slot,
+    with one (QATTN_MX64_TPS), and today's workaround, the same q, k, v zero-padded to 128 on a D = 128 pool;
+    then the whole call with and without ``sink_logit``.
+
 After (a) and (b) the packed call is taken apart: the host plan alone (plan_varlen, a host clock), the
 two table uploads alone (event-timed) and the attention kernel alone (REPS back-to-back launches of the
 C entry on buffers and tables made once, divided by REPS), beside the paged kernel alone in (a).
@@ -233,18 +239,90 @@ def windowed(W, S, rand, passes, iters):
     assert torch.isfinite(O1.float()).all()
 
 
+def pool64(lengths, k, v, Dp):
+    """A pool of head_dim ``Dp`` holding the first ``lengths[j]`` rows of k, v [n, 8, 64] per sequence, zero-
+    padded to ``Dp``."""
+    B, n = len(lengths), max(lengths)
+    cache = PagedKVFP4.allocate(sum(-(-L // P) for L in lengths), P, B, 8, -(-n // P), "cuda", head_dim=Dp)
+    pad = lambda x: torch.nn.functional.pad(x, (0, Dp - 64))  # noqa: E731
+    for t0 in range(0, n, 4096):
+        c = [min(max(L - t0, 0), 4096) for L in lengths]
+        ids = [j for j in range(B) if c[j]]
+        cache.append_packed(torch.cat([pad(k[t0:t0 + c[j]]) for j in ids]), torch.cat([pad(v[t0:t0 + c[j]]) for j in ids]),
+                            ids, [c[j] for j in ids])
+    return cache
+
+
+def kernel64(q, cache, q_lens, W, tps):
+    """REPS launches of the packed attention kernel alone on ``cache`` (either head_dim); tps: tiles per slot."""
+    Dp, ids = cache.shape[3], list(range(len(q_lens)))
+    kps, rec, work, rows = plan_varlen(cache.lengths, ids, q_lens, 64, 8, None, True, W, 0)
+    rec_d, work_d = (torch.tensor(x, dtype=torch.int32).cuda() for x in (rec, work))
+    q4, qs = mxfp4_quantize_rows(q)
+    opart = torch.empty((rows, Dp), dtype=torch.float32, device="cuda")
+    ml = torch.empty((rows, 2), dtype=torch.float32, device="cuda")
+    args = (_lib.ptr(q4), _lib.ptr(qs), *(_lib.ptr(x) for x in cache.kv), _lib.ptr(opart), _lib.ptr(ml),
+            _lib.ptr(cache.lens), _lib.ptr(cache.block_table), _lib.ptr(rec_d), _lib.ptr(work_d), len(rec),
+            len(work), q.shape[0], rows, cache.alloc.max_seqs, 8, 8, cache.num_pages, P,
+            cache.alloc.max_pages_per_seq, 2, kps, Dp, _qk_scale(Dp))
+    name = "qattn_mxfp4_attn_fwd_varlen_paged" + ("_window" if W else "")
+    tail = ((W, 0) if W else ()) + (_lib.stream_of(q),)
+
+    def kernel(keep=(q4, qs, opart, ml, rec_d, work_d)):
+        os.environ["QATTN_MX64_TPS"] = str(tps)
+        for _ in range(REPS):
+            _lib.call(name, *args, *tail)
+    return kernel
+
+
+def d64(rand, passes, iters):
+    os.environ["QATTN_MX64_TPS"] = "2"
+    shapes = [("8 decodes at 8192 cached", [8192] * 8, [1] * 8, None),
+              ("64 decodes at 32768 cached, window 128", [32768] * 64, [1] * 64, 128),
+              ("a 512-token chunk + 15 decodes over 512..8192", [8192] + [512 + 7680 * i // 14 for i in range(15)],
+               [512] + [1] * 15, None)]
+    k, v = rand(32768, 8, 64), rand(32768, 8, 64)
+    for name, lengths, q_lens, W in shapes:
+        c64, c128 = pool64(lengths, k, v, 64), pool64(lengths, k, v, 128)
+        q = rand(sum(q_lens), 64, 64)
+        q128 = torch.nn.functional.pad(q, (0, 64)) * (2.0 ** 0.5)   # qk_scale(128) on the padded rows = qk_scale(64)
+        ids = list(range(len(lengths)))
+        O, _ = attention_mxfp4_varlen_paged(q, c64, ids, q_lens, causal=True, window=W)
+        O128, _ = attention_mxfp4_varlen_paged(q128.half(), c128, ids, q_lens, causal=True, window=W)
+        print(f"(e) {name}: 64/8 heads, P {P}; max |O_64 - O_padded| {(O.float() - O128[..., :64].float()).abs().max():.3e}",
+              flush=True)
+        report(alternate({f"D 64, two tiles per slot x{REPS}": kernel64(q, c64, q_lens, W, 2),
+                          f"D 64, one tile per slot x{REPS}": kernel64(q, c64, q_lens, W, 1),
+                          f"padded to 128 x{REPS}": kernel64(q128.half(), c128, q_lens, W, 2)}, passes, iters))
+        os.environ["QATTN_MX64_TPS"] = "2"
+        sink = rand(64).float()
+        report(alternate({
+            "whole call, D 64": lambda: attention_mxfp4_varlen_paged(q, c64, ids, q_lens, causal=True, window=W),
+            "whole call, D 64, sink_logit": lambda: attention_mxfp4_varlen_paged(q, c64, ids, q_lens, causal=True,
+                                                                                 window=W, sink_logit=sink),
+            "whole call, padded to 128": lambda: attention_mxfp4_varlen_paged(q128.half(), c128, ids, q_lens,
+                                                                              causal=True, window=W)},
+            passes, iters))
+        del c64, c128
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--window", type=int, default=None, help="run only (d), with this window")
     ap.add_argument("--sinks", type=int, default=0)
+    ap.add_argument("--head-dim", type=int, default=128, choices=(64, 128), help="64: run only (e)")
     args = ap.parse_args()
     assert args.passes >= 3
     print(f"device {torch.cuda.get_device_name(0)}; {args.passes} alternating passes x {args.iters} calls, "
           "whole Python call", flush=True)
     g = torch.Generator(device="cuda").manual_seed(0)
     rand = lambda *s: torch.randn(s, device="cuda", generator=g).half()  # noqa: E731
+    if args.head_dim == 64:
+        d64(rand, args.passes, args.iters)
+        return
     if args.window is not None:
         windowed(args.window, args.sinks, rand, args.passes, args.iters)
         return
