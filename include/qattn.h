@@ -36,7 +36,7 @@ extern "C" {
  * qattn_source_hash() is the sha256 (hex) of the kernel sources and compile flags the library was
  * built from (quantizedattention_amd/_srchash.py); the Python binding refuses a library whose hash
  * differs from the sources beside it (a stale prebuilt library). */
-#define QATTN_ABI_VERSION 9
+#define QATTN_ABI_VERSION 10
 int qattn_abi_version(void);
 const char* qattn_source_hash(void);
 
@@ -692,18 +692,26 @@ int qattn_mxfp4_paged_append_packed_rope(const void* k, const void* v, const voi
  * write outside its tables.  Returns 1 for a NULL pointer, a keys_per_split that is no multiple of 64, max_seqs,
  * kv_heads, group or splits < 1, splits > 65535, a capacity that is no multiple of 64 in [64, 2^25], window or
  * sinks < 0, sinks without a window, n * splits * kv_heads * group >= 2^31; 0 without a launch for n == 0.
+ * The entry takes no head_dim: its tables count 64-key tiles, splits and rows, which do not depend on it.
  *
  * qattn_mxfp4_attn_fwd_decode_step is the causal packed forward (with the window's mask for window >= 1) of
  * those n one-token sequences over a grid fixed by n, splits and kv_heads: work i32 [n * splits][4] holds
  * {i, 0, s, 0} for every entry i and split s < splits once, in any order, and a workgroup whose s is >= ns of
  * its entry returns at once without a store.  q4 / qscale: the n * kv_heads * group quantised query rows,
- * token-major; opart f32 [n * splits * kv_heads * group][128] and ml f32 x 2 of as many rows.  Every entry gets,
- * bit for bit, what the first packed entry (or the windowed one) gives it at the same keys_per_split.
+ * token-major; opart f32 [n * splits * kv_heads * group][head_dim] and ml f32 x 2 of as many rows.  Every entry
+ * gets, bit for bit, what the first packed entry (or the windowed one) gives it at the same keys_per_split.
+ * head_dim 128 or 64 (64: the pair ring of the packed entries at that head_dim, with the same early return).
  * Returns 1 as those entries do for their pool, and for the limits of the plan entry.
  *
  * qattn_mxfp4_decode_step_combine merges entry i's ns splits from its rows [i * splits * q_heads, ..) with
- * qattn_mxfp4_varlen_combine's arithmetic into out f16 [n][q_heads][128] and lse f32 [n][q_heads]; a padding
- * entry (ns < 1) gets out = 0 and lse = -inf.  Nothing allocates. */
+ * qattn_mxfp4_varlen_combine's arithmetic into out f16 [n][q_heads][head_dim] and lse f32 [n][q_heads], head_dim
+ * 128 or 64; a padding entry (ns < 1) gets out = 0 and lse = -inf.
+ *
+ * qattn_mxfp4_decode_step_combine_sink is that merge with the learned sink logit of
+ * qattn_mxfp4_varlen_combine_sink (sink_logit f32 [q_heads] on the device, natural-log units, read when the
+ * launch runs): every row of a listed entry gets that entry's bits.  The sink joins listed entries only: a
+ * padding entry still gets out = 0 and lse = -inf.  Returns 1 for a NULL sink_logit and as the entry above.
+ * Nothing allocates. */
 int qattn_mxfp4_decode_step_plan(const void* slots, const void* lens, void* seq_tab, void* tiles, void* seq_rec,
                                  void* pos, long n, long max_seqs, long capacity, long kv_heads, long group,
                                  int keys_per_split, long splits, long window, long sinks, void* stream);
@@ -714,6 +722,9 @@ int qattn_mxfp4_attn_fwd_decode_step(
     long max_pages_per_seq, int keys_per_split, int head_dim, float qks, long window, long sinks, void* stream);
 int qattn_mxfp4_decode_step_combine(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
                                     long n, long splits, long q_heads, long kv_heads, int head_dim, void* stream);
+int qattn_mxfp4_decode_step_combine_sink(const void* opart, const void* ml, void* out, void* lse,
+                                         const void* seq_rec, const void* sink_logit, long n, long splits,
+                                         long q_heads, long kv_heads, int head_dim, void* stream);
 
 /* The device-planned verify step (kv_cache_mxfp4.py VerifyStep): draft_tokens = K new tokens, 1 <= K <= 64, a
  * chain or a draft tree in topological order, for each of up to n listed sequences, appended and then attended

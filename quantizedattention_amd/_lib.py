@@ -109,6 +109,7 @@ SIGNATURES = {
     "qattn_mxfp4_attn_fwd_decode_step": [_vp] * 12 + [_c_long] * 8 + [_c_int, _c_int, _c_float, _c_long, _c_long,
                                                                        _vp],
     "qattn_mxfp4_decode_step_combine": [_vp] * 5 + [_c_long] * 4 + [_c_int, _vp],
+    "qattn_mxfp4_decode_step_combine_sink": [_vp] * 6 + [_c_long] * 4 + [_c_int, _vp],
     "qattn_mxfp4_verify_step_plan": [_vp] * 7 + [_c_long] * 6 + [_c_int, _c_long, _vp],
     "qattn_mxfp4_attn_fwd_verify_step": [_vp] * 13 + [_c_long] * 9 + [_c_int, _c_int, _c_float, _vp],
     "qattn_mxfp4_verify_step_combine": [_vp] * 5 + [_c_long] * 5 + [_c_int, _vp],
@@ -139,7 +140,7 @@ RESTYPES = {"qattn_abi_version": ctypes.c_int, "qattn_source_hash": ctypes.c_cha
             "qattn_int8_bwd_plan": ctypes.c_long, "qattn_bf16_bwd_plan": ctypes.c_long}
 
 # include/qattn.h QATTN_ABI_VERSION: the argument lists SIGNATURES describes
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 _lib = None
 _dev = None

@@ -1285,6 +1285,12 @@ int mx64_varlen_paged(const void* q4, const void* qscale, const void* k4, const 
                       long max_seqs, long kv_heads, long group, long num_pages, long page_tokens,
                       long max_pages_per_seq, int causal, int keys_per_split, float qks, long window, long sinks,
                       void* stream);
+// qattn_mxfp4_attn_fwd_decode_step at head_dim 64, behind that entry's own checks
+int mx64_decode_step(const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
+                     const void* vscale, void* opart, void* ml, const void* lens, const void* block_table,
+                     const void* seq_rec, const void* work, long n, long splits, long max_seqs, long kv_heads,
+                     long group, long num_pages, long page_tokens, long max_pages_per_seq, int keys_per_split,
+                     float qks, long window, long sinks, void* stream);
 int mx64_append_packed(bool rope, const void* k, const void* v, const void* k_mean, void* k4, void* kscale,
                        void* vt, void* vscale, void* vtail, void* lens, const void* block_table,
                        const void* seq_tab, const void* tiles, long nseq, long ntiles, long tokens, long max_seqs,

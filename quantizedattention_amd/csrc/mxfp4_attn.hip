@@ -705,6 +705,8 @@ static bool mx_step_window_ok(long window, long sinks) {
   return window >= 0 && sinks >= 0 && (window > 0 || sinks == 0);
 }
 
+// (No head_dim: the tables count 64-key tiles, splits, packed rows and partial rows, none of which depends on
+// the width of a row, so a step of either head_dim is planned by the same launch.)
 extern "C" int qattn_mxfp4_decode_step_plan(const void* slots, const void* lens, void* seq_tab, void* tiles,
                                             void* seq_rec, void* pos, long n, long max_seqs, long capacity,
                                             long kv_heads, long group, int keys_per_split, long splits,
@@ -736,6 +738,10 @@ extern "C" int qattn_mxfp4_attn_fwd_decode_step(
     return 1;
   if (kv_heads > 0x7fffffffL / group || n > 0x7fffffffL / (splits * kv_heads * group)) return 1;
   if (n > 0 && (!q4 || !qscale || !k4 || !kscale || !vt || !vscale || !opart || !ml)) return 1;
+  if (head_dim == 64)   // mxfp4_attn_varlen64_kernel STEP (mxfp4_attn_d64.hip)
+    return mx64_decode_step(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work, n,
+                            splits, max_seqs, kv_heads, group, num_pages, page_tokens, max_pages_per_seq,
+                            keys_per_split, qks, window, sinks, stream);
   MxSplitCall c;
   const int rc = mx_varlen_call(c, q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work,
                                 n, n * splits, n, n * splits * kv_heads * group, max_seqs, kv_heads, group,
@@ -746,14 +752,29 @@ extern "C" int qattn_mxfp4_attn_fwd_decode_step(
                     : mx_split_launch<true, true, true, true, true, false, false, true>(c, stream);
 }
 
-extern "C" int qattn_mxfp4_decode_step_combine(const void* opart, const void* ml, void* out, void* lse,
-                                               const void* seq_rec, long n, long splits, long q_heads,
-                                               long kv_heads, int head_dim, void* stream) {
-  if (head_dim != 128 || n < 0 || splits < 1 || splits > 65535) return 1;
+// what the two merge entries of the step check: the entry's status when there is nothing to launch, else -1
+static int mx_step_combine_check(const void* opart, const void* ml, const void* out, const void* lse,
+                                 const void* seq_rec, long n, long splits, long q_heads, long kv_heads,
+                                 int head_dim) {
+  if ((head_dim != 128 && head_dim != 64) || n < 0 || splits < 1 || splits > 65535) return 1;
   if (kv_heads < 1 || q_heads < 1 || q_heads % kv_heads != 0 || q_heads > 0x7fffffffL) return 1;
   if (n > 0x7fffffffL / (splits * q_heads)) return 1;
   if (n == 0) return 0;
-  if (!opart || !ml || !out || !lse || !seq_rec) return 1;
+  return !opart || !ml || !out || !lse || !seq_rec ? 1 : -1;
+}
+
+// the merges of the step that came after the first one (head_dim 64, and the sink logit at either head_dim), at
+// the end of this file, as their kernels are emitted behind every older one; sink null: none
+static int mx_step_combine_ext(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
+                               const void* sink, long n, long splits, long q_heads, int head_dim, void* stream);
+
+extern "C" int qattn_mxfp4_decode_step_combine(const void* opart, const void* ml, void* out, void* lse,
+                                               const void* seq_rec, long n, long splits, long q_heads,
+                                               long kv_heads, int head_dim, void* stream) {
+  const int rc = mx_step_combine_check(opart, ml, out, lse, seq_rec, n, splits, q_heads, kv_heads, head_dim);
+  if (rc >= 0) return rc;
+  if (head_dim == 64)
+    return mx_step_combine_ext(opart, ml, out, lse, seq_rec, nullptr, n, splits, q_heads, head_dim, stream);
   const long rows = n * q_heads, nthr = rows * (128 / 8);
   hipLaunchKernelGGL(mxfp4_decode_step_combine_kernel<128>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0,
                      (hipStream_t)stream, (const float*)opart, (const float2*)ml, (_Float16*)out, (float*)lse,
@@ -902,4 +923,66 @@ extern "C" int qattn_mxfp4_verify_step_combine(const void* opart, const void* ml
                      (const int*)seq_rec, rows, (int)q_heads, (int)(q_heads / kv_heads), (int)draft_tokens,
                      (int)splits);
   return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// ------------------------------------------------------- decode step: head_dim 64 and the learned sink logit
+// mxfp4_decode_step_combine_kernel with the learned sink logit of the row's query head (mx_merge_row SINK, the
+// arithmetic of mxfp4_varlen_combine_sink_kernel in its order).  The sink joins the rows of listed entries only:
+// a padding entry (ns < 1) is no sequence, and still gets O = 0 and lse = -inf, not lse = z.
+namespace qattn {
+template <int D>
+__global__ __launch_bounds__(256) void mxfp4_decode_step_combine_sink_kernel(
+    const float* __restrict__ opart, const float2* __restrict__ ml, _Float16* __restrict__ out,
+    float* __restrict__ lse, const int* __restrict__ seq_rec, const float* __restrict__ sink, long rows, int Hq,
+    int splits) {
+  constexpr int TPR = D / 8;
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+  const long row = gid / TPR;
+  if (row >= rows) return;
+  const int c = (int)(gid % TPR);
+  const long token = row / Hq;
+  const int ns = min(seq_rec[8 * token + 3], splits);
+  if (ns < 1) {
+    *reinterpret_cast<v8h*>(out + row * D + 8 * c) = v8h{};
+    if (c == 0) lse[row] = -INFINITY;
+    return;
+  }
+  mx_merge_row<D, true>(opart, ml, token * splits * Hq + row % Hq, Hq, ns, c, out + row * D, lse + row,
+                        sink[row % Hq]);
+}
+}  // namespace qattn
+
+template <int D>
+static void mx_step_combine_launch(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
+                                   const void* sink, long rows, long q_heads, long splits, void* stream) {
+  const dim3 grid((unsigned)((rows * (D / 8) + 255) / 256));
+  if (sink)
+    hipLaunchKernelGGL(mxfp4_decode_step_combine_sink_kernel<D>, grid, dim3(256), 0, (hipStream_t)stream,
+                       (const float*)opart, (const float2*)ml, (_Float16*)out, (float*)lse, (const int*)seq_rec,
+                       (const float*)sink, rows, (int)q_heads, (int)splits);
+  else
+    hipLaunchKernelGGL(mxfp4_decode_step_combine_kernel<D>, grid, dim3(256), 0, (hipStream_t)stream,
+                       (const float*)opart, (const float2*)ml, (_Float16*)out, (float*)lse, (const int*)seq_rec,
+                       rows, (int)q_heads, (int)splits);
+}
+
+static int mx_step_combine_ext(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
+                               const void* sink, long n, long splits, long q_heads, int head_dim, void* stream) {
+  if (head_dim == 64)
+    mx_step_combine_launch<64>(opart, ml, out, lse, seq_rec, sink, n * q_heads, q_heads, splits, stream);
+  else if (sink)   // (without one, head_dim 128 is qattn_mxfp4_decode_step_combine's own launch)
+    mx_step_combine_launch<128>(opart, ml, out, lse, seq_rec, sink, n * q_heads, q_heads, splits, stream);
+  else
+    return 1;
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+extern "C" int qattn_mxfp4_decode_step_combine_sink(const void* opart, const void* ml, void* out, void* lse,
+                                                    const void* seq_rec, const void* sink_logit, long n,
+                                                    long splits, long q_heads, long kv_heads, int head_dim,
+                                                    void* stream) {
+  if (!sink_logit) return 1;
+  const int rc = mx_step_combine_check(opart, ml, out, lse, seq_rec, n, splits, q_heads, kv_heads, head_dim);
+  if (rc >= 0) return rc;
+  return mx_step_combine_ext(opart, ml, out, lse, seq_rec, sink_logit, n, splits, q_heads, head_dim, stream);
 }

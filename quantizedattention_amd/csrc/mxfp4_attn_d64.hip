@@ -21,6 +21,15 @@
 // Both schedules are built; -DQA_MX64_TPS=1 makes one tile per slot the default, and the environment variable
 // QATTN_MX64_TPS (1 or 2, read at every launch) picks one for a process, which is how tools/time_decode_varlen.py
 // --head-dim 64 measures the two side by side.
+//
+// STEP (causal, with or without WINDOW) is the fixed grid of the device-planned decode step (kv_cache_mxfp4.py
+// DecodeStep, mxfp4_attn_split_kernel STEP at D = 128): `splits` work records {i, 0, s, 0} per entry i, the
+// records seq_rec[i] written by mx_decode_plan_kernel from the device lengths.  A workgroup with s >= rec[3] =
+// ns_i -- a padding entry (ns = 0, slot -1) or a sequence that needs fewer splits than the longest could --
+// returns behind the two record reads: no length, no table entry (the ring's constructor reads one, so the exit
+// stands in front of it), no DMA, no barrier, no store.  Every other workgroup is the instantiation without STEP
+// statement for statement, so pair ring, page rebasing, the lone last tile, masks and the compact partials (at
+// the fixed stride the plan writes into rec[4]) are the host-planned call's, and so are the bits.
 #include "mxfp4_attn.h"
 
 #include <cstdlib>
@@ -109,7 +118,7 @@ struct MxRing64 {
 // sequence records, the row mapping, the tile range of a split, the masks, the skipped tiles, the empty state
 // and the compact partials are that kernel's, statement for statement; the ring is MxRing64<TPS>, and one
 // barrier publishes TPS tiles, which the wave runs through mx_tile<64> one after the other.
-template <bool CAUSAL, bool WINDOW, int TPS>
+template <bool CAUSAL, bool WINDOW, int TPS, bool STEP = false>
 __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_varlen64_kernel(
     const uint8_t* __restrict__ q4, const uint8_t* __restrict__ qs, const uint8_t* __restrict__ k4,
     const uint8_t* __restrict__ ks, const uint8_t* __restrict__ vt, const uint8_t* __restrict__ vs,
@@ -120,12 +129,16 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_varlen64_kernel(
   using C = MxCfg<D>;
   using R = MxRing64<TPS>;
   static_assert(CAUSAL || !WINDOW, "a window is causal");
+  static_assert(CAUSAL || !STEP, "the fixed grid is the causal packed step's");
   static_assert(C::WAVES * RowTile<D, float, 2>::BYTES <= C::NSLOT * R::SLOT, "fp32 staging in two passes fits the ring");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef const __attribute__((address_space(4))) int* table_ptr;
   const int hd = (int)(blockIdx.x % (unsigned)hps);
   const table_ptr w = (table_ptr)(unsigned long)(vl.work + 4L * (blockIdx.x / (unsigned)hps));
   const table_ptr rec = (table_ptr)(unsigned long)(vl.seq_rec + 8L * min(max(w[0], 0), vl.nseq - 1));
+  if constexpr (STEP) {   // a surplus workgroup of the fixed grid: nothing fetched, nothing stored
+    if (max(w[2], 0) >= rec[3]) return;
+  }
   const int qt = max(w[1], 0), split = max(w[2], 0);
   const int bh = min(max(rec[0], 0), BHV / hps - 1) * hps + hd;
   const long qbase = rec[1], pbase = rec[4];
@@ -247,12 +260,12 @@ __global__ __launch_bounds__(256) void mxfp4_varlen_combine_sink_kernel(
   mx_merge_row<D, true>(opart, ml, first, step, nsplit, (int)(gid % TPR), out + row * D, lse + row, sink[head]);
 }
 
-template <bool CAUSAL, bool WINDOW, int TPS>
+template <bool CAUSAL, bool WINDOW, int TPS, bool STEP>
 static int mx64_launch_tps(const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
                        const void* vscale, void* opart, void* ml, int bhv, int Sk, int kps, float qks,
                        const void* lens, int hps, const void* btab, int mpp, int lgt, int npool, const MxVarlen& vl,
                        unsigned grid, void* stream) {
-  const auto kernel = mxfp4_attn_varlen64_kernel<CAUSAL, WINDOW, TPS>;
+  const auto kernel = mxfp4_attn_varlen64_kernel<CAUSAL, WINDOW, TPS, STEP>;
   const int lds = MxCfg<64>::NSLOT * MxRing64<TPS>::SLOT;
   { static LdsGrant granted_; if (!lds_grant((const void*)kernel, lds, granted_)) return 1; }
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, (const uint8_t*)q4,
@@ -268,18 +281,21 @@ static int mx64_tps() {
   return e && (e[0] == '1' || e[0] == '2') && !e[1] ? e[0] - '0' : QA_MX64_TPS;
 }
 
-template <bool CAUSAL, bool WINDOW, class... A>
+template <bool CAUSAL, bool WINDOW, bool STEP, class... A>
 static int mx64_launch(A... a) {
-  return mx64_tps() == 2 ? mx64_launch_tps<CAUSAL, WINDOW, 2>(a...) : mx64_launch_tps<CAUSAL, WINDOW, 1>(a...);
+  return mx64_tps() == 2 ? mx64_launch_tps<CAUSAL, WINDOW, 2, STEP>(a...)
+                         : mx64_launch_tps<CAUSAL, WINDOW, 1, STEP>(a...);
 }
 
-// the checks of mx_varlen_call (mxfp4_attn.hip) and the dispatch of mx_varlen_paged, at head_dim 64
-int mx64_varlen_paged(const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
-                      const void* vscale, void* opart, void* ml, const void* lens, const void* block_table,
-                      const void* seq_rec, const void* work, long nseq, long nwork, long tokens, long part_rows,
-                      long max_seqs, long kv_heads, long group, long num_pages, long page_tokens,
-                      long max_pages_per_seq, int causal, int keys_per_split, float qks, long window, long sinks,
-                      void* stream) {
+// the checks of mx_varlen_call (mxfp4_attn.hip) and the dispatch of mx_varlen_paged, at head_dim 64; STEP: the
+// fixed grid of the decode step (causal)
+template <bool STEP>
+static int mx64_packed(const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
+                       const void* vscale, void* opart, void* ml, const void* lens, const void* block_table,
+                       const void* seq_rec, const void* work, long nseq, long nwork, long tokens, long part_rows,
+                       long max_seqs, long kv_heads, long group, long num_pages, long page_tokens,
+                       long max_pages_per_seq, int causal, int keys_per_split, float qks, long window, long sinks,
+                       void* stream) {
   if (keys_per_split < 64 || keys_per_split % 64 != 0) return 1;
   if (nseq < 0 || nwork < 0 || tokens < 0 || part_rows < 0) return 1;
   if (!lens || !block_table || !seq_rec || !work) return 1;
@@ -298,9 +314,35 @@ int mx64_varlen_paged(const void* q4, const void* qscale, const void* k4, const 
   const unsigned grid = (unsigned)(nwork * kv_heads);
 #define QA_MX64_ARGS q4, qscale, k4, kscale, vt, vscale, opart, ml, bhv, Sk, keys_per_split, qks, lens, \
                      (int)kv_heads, block_table, (int)max_pages_per_seq, lgt, (int)num_pages, vl, grid, stream
-  if (window >= 1) return mx64_launch<true, true>(QA_MX64_ARGS);
-  return causal ? mx64_launch<true, false>(QA_MX64_ARGS) : mx64_launch<false, false>(QA_MX64_ARGS);
+  if (window >= 1) return mx64_launch<true, true, STEP>(QA_MX64_ARGS);
+  if constexpr (STEP) return mx64_launch<true, false, true>(QA_MX64_ARGS);
+  else if (causal) return mx64_launch<true, false, false>(QA_MX64_ARGS);
+  else return mx64_launch<false, false, false>(QA_MX64_ARGS);
 #undef QA_MX64_ARGS
+}
+
+int mx64_varlen_paged(const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
+                      const void* vscale, void* opart, void* ml, const void* lens, const void* block_table,
+                      const void* seq_rec, const void* work, long nseq, long nwork, long tokens, long part_rows,
+                      long max_seqs, long kv_heads, long group, long num_pages, long page_tokens,
+                      long max_pages_per_seq, int causal, int keys_per_split, float qks, long window, long sinks,
+                      void* stream) {
+  return mx64_packed<false>(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work, nseq,
+                            nwork, tokens, part_rows, max_seqs, kv_heads, group, num_pages, page_tokens,
+                            max_pages_per_seq, causal, keys_per_split, qks, window, sinks, stream);
+}
+
+// The attention of the decode step at head_dim 64 (qattn_mxfp4_attn_fwd_decode_step, which has checked n, splits
+// and the products below): the packed call at nseq = tokens = n one-token sequences, n * splits work records and
+// n * splits * kv_heads * group partial rows, causal, over the STEP instantiations.
+int mx64_decode_step(const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
+                     const void* vscale, void* opart, void* ml, const void* lens, const void* block_table,
+                     const void* seq_rec, const void* work, long n, long splits, long max_seqs, long kv_heads,
+                     long group, long num_pages, long page_tokens, long max_pages_per_seq, int keys_per_split,
+                     float qks, long window, long sinks, void* stream) {
+  return mx64_packed<true>(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work, n,
+                           n * splits, n, n * splits * kv_heads * group, max_seqs, kv_heads, group, num_pages,
+                           page_tokens, max_pages_per_seq, 2, keys_per_split, qks, window, sinks, stream);
 }
 
 // mx_append_packed (mxfp4_attn.hip) at head_dim 64: the same checks, the same three launches

@@ -47,7 +47,8 @@
 //   mxfp4_decode_step_plan(slots, lens, capacity, kv_heads, group, keys_per_split, splits, window, sinks)
 //       -> (seq_tab, tiles, pos, seq_rec): kv_cache_mxfp4.DecodeStep's tables, derived on the device
 //   mxfp4_decode_step(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, splits, keys_per_split, window,
-//       sinks) -> (O, lse): kv_cache_mxfp4.DecodeStep.attend over its fixed grid
+//       sinks, sink_logit=None) -> (O, lse): kv_cache_mxfp4.DecodeStep.attend over its fixed grid, head_dim 128
+//       or 64 (q's), with the learned sink logit f32 [Hq] when one is given
 //   mxfp4_verify_step_plan(slots, lens, tree, draft_tokens, capacity, kv_heads, group, keys_per_split, splits)
 //       -> (seq_tab, tiles, pos, seq_rec): kv_cache_mxfp4.VerifyStep's tables, derived on the device
 //   mxfp4_verify_step(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, tree, draft_tokens, splits,
@@ -804,17 +805,19 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> mxfp4_decode_step_plan(const Tensor& 
   return {seq_tab, tiles, pos, seq_rec};
 }
 
-// kv_cache_mxfp4.DecodeStep.attend as an operator: q [n, Hq, 128], the pool's operands, lens (AFTER the step's
-// append) and block table, seq_rec i32 [n, 8] of the plan above and work i32 [n * splits, 4] = {i, 0, s, 0}.
+// kv_cache_mxfp4.DecodeStep.attend as an operator: q [n, Hq, D], D = 128 or 64 and the pool's, the pool's
+// operands, lens (AFTER the step's append) and block table, seq_rec i32 [n, 8] of the plan above and work i32 [n
+// * splits, 4] = {i, 0, s, 0}; sink_logit f32 [Hq] on the device (natural-log units) or None.
 std::tuple<Tensor, Tensor> mxfp4_decode_step(const Tensor& q_in, const Tensor& k4, const Tensor& ks,
                                              const Tensor& vt, const Tensor& vs, const Tensor& lens,
                                              const Tensor& block_table, const Tensor& seq_rec, const Tensor& work,
                                              int64_t splits, int64_t keys_per_split, int64_t window,
-                                             int64_t sinks) {
+                                             int64_t sinks, const c10::optional<Tensor>& sink_logit) {
   require_gpu({&q_in, &k4, &ks, &vt, &vs, &lens, &block_table, &seq_rec, &work});
-  TORCH_CHECK(q_in.dim() == 3 && k4.dim() == 4 && q_in.size(2) == 128 && k4.size(3) == 64,
-              "qattn mxfp4 decode step: q must be [n, Hq, 128], head_dim 128 in the pool");
-  const int64_t NP = k4.size(0), Hkv = k4.size(1), PT = k4.size(2), D = 128;
+  TORCH_CHECK(q_in.dim() == 3 && k4.dim() == 4 && (q_in.size(2) == 128 || q_in.size(2) == 64) &&
+                  k4.size(3) * 2 == q_in.size(2),
+              "qattn mxfp4 decode step: q must be [n, Hq, D], D = 128 or 64, the pool's head_dim");
+  const int64_t NP = k4.size(0), Hkv = k4.size(1), PT = k4.size(2), D = q_in.size(2);
   TORCH_CHECK(PT >= 64 && PT <= 1024 && (PT & (PT - 1)) == 0,
               "qattn mxfp4 paged cache: page_tokens must be 64 * 2^k in [64, 1024]");
   TORCH_CHECK(block_table.scalar_type() == at::kInt && block_table.is_contiguous() && block_table.dim() == 2 &&
@@ -824,7 +827,14 @@ std::tuple<Tensor, Tensor> mxfp4_decode_step(const Tensor& q_in, const Tensor& k
   const int64_t n = q_in.size(0), Hq = q_in.size(1);
   TORCH_CHECK(Hkv > 0 && NP > 0 && Hq > 0 && Hq % Hkv == 0 && n >= 1 && n <= B,
               "qattn mxfp4 decode step: q must have G * Hkv heads for the pool's Hkv and 1 <= n <= B rows");
-  check_fp4_operands(k4, ks, vt, vs, &lens, B, true);
+  check_fp4_operands(k4, ks, vt, vs, &lens, B, true, D);
+  Tensor sink;
+  if (sink_logit.has_value()) {
+    require_gpu({&*sink_logit});
+    TORCH_CHECK(sink_logit->scalar_type() == at::kFloat && sink_logit->dim() == 1 && sink_logit->size(0) == Hq,
+                "qattn mxfp4 decode step: sink_logit must be a device fp32 tensor [Hq]");
+    sink = kin(*sink_logit);
+  }
   TORCH_CHECK(splits >= 1 && splits <= 65535 && n * splits * Hq < (int64_t(1) << 31),
               "qattn mxfp4 decode step: splits in [1, 65535] and fewer than 2^31 partial rows expected");
   TORCH_CHECK(seq_rec.scalar_type() == at::kInt && seq_rec.is_contiguous() && seq_rec.dim() == 2 &&
@@ -845,9 +855,14 @@ std::tuple<Tensor, Tensor> mxfp4_decode_step(const Tensor& q_in, const Tensor& k
                                         P(block_table), P(seq_rec), P(work), n, splits, B, Hkv, Hq / Hkv, NP, PT,
                                         mpp, (int)keys_per_split, (int)D, qk_scale(D), window, sinks, c.stream),
        "mxfp4 decode step forward");
-  call(qattn_mxfp4_decode_step_combine(P(opart), P(ml), P(out), P(lse), P(seq_rec), n, splits, Hq, Hkv, (int)D,
-                                       c.stream),
-       "mxfp4 decode step merge");
+  if (sink.defined())
+    call(qattn_mxfp4_decode_step_combine_sink(P(opart), P(ml), P(out), P(lse), P(seq_rec), P(sink), n, splits, Hq,
+                                              Hkv, (int)D, c.stream),
+         "mxfp4 decode step merge with a sink logit");
+  else
+    call(qattn_mxfp4_decode_step_combine(P(opart), P(ml), P(out), P(lse), P(seq_rec), n, splits, Hq, Hkv, (int)D,
+                                         c.stream),
+         "mxfp4 decode step merge");
   return {out, lse};
 }
 
@@ -972,7 +987,8 @@ TORCH_LIBRARY(qattn, m) {
   m.def("mxfp4_decode_step_plan(Tensor slots, Tensor lens, int capacity, int kv_heads, int group, "
         "int keys_per_split, int splits, int window, int sinks) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("mxfp4_decode_step(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, Tensor block_table, "
-        "Tensor seq_rec, Tensor work, int splits, int keys_per_split, int window, int sinks) -> (Tensor, Tensor)");
+        "Tensor seq_rec, Tensor work, int splits, int keys_per_split, int window, int sinks, "
+        "Tensor? sink_logit=None) -> (Tensor, Tensor)");
   m.def("mxfp4_verify_step_plan(Tensor slots, Tensor lens, Tensor tree, int draft_tokens, int capacity, "
         "int kv_heads, int group, int keys_per_split, int splits) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("mxfp4_verify_step(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, Tensor block_table, "

@@ -163,7 +163,9 @@ restates it), the attention runs ``splits`` (:func:`decode_step_splits`) work re
 lengths are, and a workgroup whose split its sequence does not have exits at once.  The host keeps what only it
 can do, in ``prepare``: the checks, the page reservation, the table upload when a page was added and the upload
 of ``slots``.  Results are the host-planned pair's bit for bit at the same keys per split.  ``share_prefix``,
-``trim`` and prefill chunks stay on the host-planned path.
+``trim`` and prefill chunks stay on the host-planned path.  A step is made for one head dim, 128 or 64
+(``head_dim=``; at 64 the fixed grid runs the pair ring of csrc/mxfp4_attn_d64.hip), and ``attend`` takes the
+learned ``sink_logit`` of the packed step at either: it enters in the step's merge, for listed entries only.
 
 The device-planned verify step (:class:`VerifyStep`) is the same for speculative decoding: every listed sequence
 appends K draft tokens (1 <= K <= 64, a chain or a tree, K fixed when the step is made) and attends to them under
@@ -803,7 +805,8 @@ class PagedKVFP4:
                  head_dim: int = 128) -> "PagedKVFP4":
         """An empty pool (every length 0, every page free), zero-filled.  ``head_dim`` is 128 or 64; a pool of
         64 serves the packed path (``append_packed``, :func:`attention_mxfp4_varlen_paged` without
-        ``share_prefix`` and ``tree``) and the host-only operations, and refuses the rest (:meth:`_need128`)."""
+        ``share_prefix`` and ``tree``, and a :class:`DecodeStep` made with ``head_dim=64``) and the host-only
+        operations, and refuses the rest (:meth:`_need128`)."""
         D = int(head_dim)
         if D not in (64, 128):
             raise HeadDimError(f"qattn mxfp4 paged cache: head_dim must be 128 or 64, got {head_dim}")
@@ -839,8 +842,8 @@ class PagedKVFP4:
         D = self.shape[3]
         if D != 128:
             raise HeadDimError(f"qattn mxfp4 paged cache: {what} needs head_dim 128, this pool has head_dim {D} "
-                               "(served there: append_packed and attention_mxfp4_varlen_paged without "
-                               "share_prefix and tree)")
+                               "(served there: append_packed, attention_mxfp4_varlen_paged without "
+                               "share_prefix and tree, and DecodeStep(head_dim=64))")
 
     @property
     def page_tokens(self) -> int:
@@ -1910,8 +1913,9 @@ class DecodeStep:
     Everything is allocated here, once, and nothing at call time: ``slots`` i32 [N] (the listed slots, -1 for
     padding), the append table ``seq_tab`` i32 [N, 4] and tile list ``tiles`` i32 [N, 2], ``seq_rec`` i32 [N, 8],
     ``pos`` i32 [N], ``work`` i32 [N * splits, 4] (written here and never again), the quantised queries ``q4`` /
-    ``qs``, the partials ``opart`` f32 [N * splits * Hq, 128] / ``ml``, and the results ``O`` f16 [N, Hq, 128] /
-    ``lse`` f32 [N, Hq], which ``attend`` returns and the next ``attend`` overwrites.  ``kps`` is fixed here:
+    ``qs``, the partials ``opart`` f32 [N * splits * Hq, D] / ``ml``, and the results ``O`` f16 [N, Hq, D] /
+    ``lse`` f32 [N, Hq], which ``attend`` returns and the next ``attend`` overwrites; D = ``head_dim``, 128 or 64
+    (keyword-only; anything else raises :class:`HeadDimError`), the head dim of the pools the step serves.  ``kps`` is fixed here:
     ``keys_per_split``, or ``qattn_split_keys(kv_heads * N, 1, ceil64(max_keys), 64)``; ``splits`` =
     :func:`decode_step_splits`, so the attention grid is N * splits * kv_heads workgroups whatever the lengths
     are.  ``window`` / ``sinks`` as in :func:`attention_mxfp4_varlen_paged`; under a window ``splits`` does not
@@ -1922,13 +1926,21 @@ class DecodeStep:
     ``attend`` quantises ``q`` and runs the fixed grid (``qattn_mxfp4_attn_fwd_decode_step``), whose surplus
     workgroups exit, and the merge (``qattn_mxfp4_decode_step_combine``).  Every listed entry gets, bit for bit,
     what ``append_packed(k, v, ids, [1] * n)`` followed by ``attention_mxfp4_varlen_paged(q, cache, ids, [1] * n,
-    causal=True, keys_per_split=step.kps[, window, sinks][, rope])`` gives.  One step object serves any number of
-    pools, layer after layer, on one stream: each pool's ``append`` rewrites the tables from that pool's own
-    ``lens``."""
+    causal=True, keys_per_split=step.kps[, window, sinks][, rope][, sink_logit])`` gives.  One step object serves
+    any number of pools of its head dim, layer after layer, on one stream: each pool's ``append`` rewrites the
+    tables from that pool's own ``lens``.  At head_dim 64 the attention is the pair ring of
+    csrc/mxfp4_attn_d64.hip over the same fixed grid; a pool of the other head dim raises :class:`HeadDimError`
+    before anything is reserved, uploaded or launched."""
+
+    head_dim = 128   # the default; the constructor sets the instance's
 
     def __init__(self, max_batch: int, max_keys: int, q_heads: int, kv_heads: int, device,
-                 keys_per_split: Optional[int] = None, window: Optional[int] = None, sinks: int = 0):
-        N, max_keys, Hq, Hkv, D = int(max_batch), int(max_keys), int(q_heads), int(kv_heads), 128
+                 keys_per_split: Optional[int] = None, window: Optional[int] = None, sinks: int = 0, *,
+                 head_dim: int = 128):
+        N, max_keys, Hq, Hkv = int(max_batch), int(max_keys), int(q_heads), int(kv_heads)
+        if head_dim not in (64, 128):
+            raise HeadDimError(f"qattn mxfp4 decode step: head_dim must be 128 or 64, got {head_dim}")
+        D = self.head_dim = int(head_dim)
         self.window, self.sinks = _window_args(window, sinks)
         if N < 1 or Hkv < 1 or Hq < 1 or Hq % Hkv or not 1 <= max_keys <= 1 << 25:
             raise _lib.QAttnError("qattn mxfp4 decode step: max_batch >= 1, q_heads = G * kv_heads and max_keys in "
@@ -1962,7 +1974,9 @@ class DecodeStep:
     def _pool(self, cache: "PagedKVFP4") -> None:
         if not isinstance(cache, PagedKVFP4):
             raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PagedKVFP4")
-        cache._need128("DecodeStep")
+        if cache.shape[3] != self.head_dim:
+            raise HeadDimError(f"qattn mxfp4 decode step: a DecodeStep of head_dim {self.head_dim} on a pool of "
+                               f"head_dim {cache.shape[3]} (make the step with head_dim={cache.shape[3]})")
         if cache.shape[1] != self.kv_heads or cache.k4.device != self.slots.device:
             raise _lib.QAttnError(f"qattn mxfp4 decode step: a pool of {self.kv_heads} key/value heads on "
                                   f"{self.slots.device} expected")
@@ -2012,20 +2026,21 @@ class DecodeStep:
     def _rope(self, cache: "PagedKVFP4", rope) -> None:
         if not isinstance(rope, Rope):
             raise _lib.QAttnError("qattn mxfp4 rope: rope must be a Rope")
+        rope.check_head_dim(self.head_dim)
         hi = max((cache.lengths[b] - 1 for b in self.listed), default=0)
         if hi >= rope.max_pos:   # (the mirror after prepare: a check only, no launch depends on it)
             raise _lib.QAttnError(f"qattn mxfp4 rope: the step's positions reach {hi}, outside the table's "
                                   f"[0, {rope.max_pos})")
 
     def append(self, cache: "PagedKVFP4", k: torch.Tensor, v: torch.Tensor, rope: Optional[Rope] = None):
-        """Append ``k, v`` fp16 [N, Hkv, 128], row i the new token of entry i (rows of padding entries are not
+        """Append ``k, v`` fp16 [N, Hkv, D], row i the new token of entry i (rows of padding entries are not
         read), to the sequences ``slots`` names; capturable.  One launch derives the tables from ``cache.lens``
         (``qattn_mxfp4_decode_step_plan``), then ``qattn_mxfp4_paged_append_packed`` (``_rope`` with ``rope``:
         the keys rotated to ``pos``, their lengths before the append) runs on them as it is."""
         self._pool(cache)
-        N, H, D = self.N, self.kv_heads, 128
+        N, H, D = self.N, self.kv_heads, self.head_dim
         if tuple(k.shape) != (N, H, D) or k.shape != v.shape:
-            raise _lib.QAttnError(f"qattn mxfp4 decode step: k, v must be [{N}, {H}, 128]")
+            raise _lib.QAttnError(f"qattn mxfp4 decode step: k, v must be [{N}, {H}, {D}]")
         if rope is not None:
             self._rope(cache, rope)
         _lib.require_gpu(k, v, cache.k4)
@@ -2047,17 +2062,30 @@ class DecodeStep:
                       rope.max_pos, int(rope.interleaved), st)
         return self
 
-    def attend(self, cache: "PagedKVFP4", q: torch.Tensor, rope: Optional[Rope] = None):
-        """Attention of ``q`` fp16 [N, Hq, 128], row i the query of entry i's new token, over the sequences after
-        this step's ``append`` -> (``O`` fp16 [N, Hq, 128], ``lse`` fp32 [N, Hq] base 2), the step's own buffers;
+    def attend(self, cache: "PagedKVFP4", q: torch.Tensor, rope: Optional[Rope] = None,
+               sink_logit: Optional[torch.Tensor] = None):
+        """Attention of ``q`` fp16 [N, Hq, D], row i the query of entry i's new token, over the sequences after
+        this step's ``append`` -> (``O`` fp16 [N, Hq, D], ``lse`` fp32 [N, Hq] base 2), the step's own buffers;
         capturable.  ``q`` is quantised (rotated to ``pos`` first with ``rope``), one attention launch runs the
-        fixed grid and one merge follows; the rows of padding entries come back as O = 0, lse = -inf."""
+        fixed grid and one merge follows; the rows of padding entries come back as O = 0, lse = -inf.
+
+        ``sink_logit`` (a device fp32 tensor [Hq], natural-log units; None: the merge without it) is the learned
+        sink of :func:`attention_mxfp4_varlen_paged`, checked as there, and enters in the merge alone
+        (``qattn_mxfp4_decode_step_combine_sink``).  It joins the rows of listed entries only: padding rows stay
+        O = 0, lse = -inf.  The launch takes the tensor's pointer and the kernel reads the values when it runs, so
+        a captured graph keeps reading that tensor's storage at every replay: keep the tensor alive and update
+        it in place (a non-contiguous ``sink_logit`` is copied, and the graph would read the copy)."""
         self._pool(cache)
-        N, Hq, H, D = self.N, self.q_heads, self.kv_heads, 128
+        N, Hq, H, D = self.N, self.q_heads, self.kv_heads, self.head_dim
         if tuple(q.shape) != (N, Hq, D):
-            raise _lib.QAttnError(f"qattn mxfp4 decode step: q must be [{N}, {Hq}, 128]")
+            raise _lib.QAttnError(f"qattn mxfp4 decode step: q must be [{N}, {Hq}, {D}]")
         if rope is not None:
             self._rope(cache, rope)
+        if sink_logit is not None:
+            if (not isinstance(sink_logit, torch.Tensor) or sink_logit.dtype != torch.float32
+                    or tuple(sink_logit.shape) != (Hq,) or not sink_logit.is_cuda):
+                raise _lib.QAttnError(f"qattn mxfp4 decode step: sink_logit must be a device fp32 tensor [{Hq}]")
+            sink_logit = _lib.kernel_input(sink_logit)
         _lib.require_gpu(q, cache.k4)
         q = _lib.kernel_input(q, torch.float16)
         a, st = cache.alloc, _lib.stream_of(q)
@@ -2072,8 +2100,13 @@ class DecodeStep:
                   _lib.ptr(self.ml), _lib.ptr(cache.lens), _lib.ptr(cache.block_table), _lib.ptr(self.seq_rec),
                   _lib.ptr(self.work), N, self.splits, a.max_seqs, H, Hq // H, a.num_pages, a.page_tokens,
                   a.max_pages_per_seq, self.kps, D, _qk_scale(D), self.window or 0, self.sinks, st)
-        _lib.call("qattn_mxfp4_decode_step_combine", _lib.ptr(self.opart), _lib.ptr(self.ml), _lib.ptr(self.O),
-                  _lib.ptr(self.lse), _lib.ptr(self.seq_rec), N, self.splits, Hq, H, D, st)
+        if sink_logit is None:
+            _lib.call("qattn_mxfp4_decode_step_combine", _lib.ptr(self.opart), _lib.ptr(self.ml), _lib.ptr(self.O),
+                      _lib.ptr(self.lse), _lib.ptr(self.seq_rec), N, self.splits, Hq, H, D, st)
+        else:
+            _lib.call("qattn_mxfp4_decode_step_combine_sink", _lib.ptr(self.opart), _lib.ptr(self.ml),
+                      _lib.ptr(self.O), _lib.ptr(self.lse), _lib.ptr(self.seq_rec), _lib.ptr(sink_logit), N,
+                      self.splits, Hq, H, D, st)
         return self.O, self.lse
 
 

@@ -34,7 +34,7 @@ the autograd rules of ``int8_fwd`` and ``bf16_fwd`` (their backward operators).
     torch.ops.qattn.mxfp4_decode_step_plan(slots, lens, capacity, kv_heads, group, keys_per_split, splits,
                                            window, sinks) -> (seq_tab, tiles, pos, seq_rec)
     torch.ops.qattn.mxfp4_decode_step(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, splits,
-                                      keys_per_split, window, sinks) -> (O, lse)
+                                      keys_per_split, window, sinks, sink_logit=None) -> (O, lse)
     torch.ops.qattn.mxfp4_verify_step_plan(slots, lens, tree, draft_tokens, capacity, kv_heads, group,
                                            keys_per_split, splits) -> (seq_tab, tiles, pos, seq_rec)
     torch.ops.qattn.mxfp4_verify_step(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, tree, draft_tokens,
@@ -186,7 +186,8 @@ def _(slots, lens, capacity, kv_heads, group, keys_per_split, splits, window, si
 
 
 @torch.library.register_fake("qattn::mxfp4_decode_step")
-def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, splits, keys_per_split, window, sinks):
+def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, splits, keys_per_split, window, sinks,
+      sink_logit=None):
     T, H, D = q.shape
     return (q.new_empty((T, H, D), dtype=torch.float16), q.new_empty((T, H), dtype=torch.float32))
 
@@ -431,13 +432,14 @@ def mxfp4_decode_step_plan(step, cache):
                                        step.sinks)
 
 
-def mxfp4_decode_step(q, step, cache, seq_rec=None):
+def mxfp4_decode_step(q, step, cache, seq_rec=None, sink_logit=None):
     """``kv_cache_mxfp4.DecodeStep.attend`` (without ``rope``) as one operator that allocates its outputs: q [N,
-    Hq, 128] against ``cache`` after the step's append, over ``seq_rec`` (default: the step's own, which its
-    ``append`` wrote) and the step's ``work`` -> (O, lse), the Python call's bits."""
+    Hq, D] (D = 128 or 64, the pool's) against ``cache`` after the step's append, over ``seq_rec`` (default: the
+    step's own, which its ``append`` wrote) and the step's ``work``, with the learned ``sink_logit`` f32 [Hq] when
+    one is given -> (O, lse), the Python call's bits."""
     return _ops.mxfp4_decode_step(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens, cache.block_table,
                                   step.seq_rec if seq_rec is None else seq_rec, step.work, step.splits, step.kps,
-                                  step.window or 0, step.sinks)
+                                  step.window or 0, step.sinks, sink_logit)
 
 
 def mxfp4_verify_step_plan(step, cache):

@@ -239,11 +239,12 @@ def windowed(W, S, rand, passes, iters):
     assert torch.isfinite(O1.float()).all()
 
 
-def pool64(lengths, k, v, Dp):
+def pool64(lengths, k, v, Dp, extra=0):
     """A pool of head_dim ``Dp`` holding the first ``lengths[j]`` rows of k, v [n, 8, 64] per sequence, zero-
-    padded to ``Dp``."""
+    padded to ``Dp``, with room for ``extra`` more tokens per sequence."""
     B, n = len(lengths), max(lengths)
-    cache = PagedKVFP4.allocate(sum(-(-L // P) for L in lengths), P, B, 8, -(-n // P), "cuda", head_dim=Dp)
+    cache = PagedKVFP4.allocate(sum(-(-(L + extra) // P) for L in lengths), P, B, 8, -(-(n + extra) // P), "cuda",
+                                head_dim=Dp)
     pad = lambda x: torch.nn.functional.pad(x, (0, Dp - 64))  # noqa: E731
     for t0 in range(0, n, 4096):
         c = [min(max(L - t0, 0), 4096) for L in lengths]
