@@ -36,7 +36,7 @@ extern "C" {
  * qattn_source_hash() is the sha256 (hex) of the kernel sources and compile flags the library was
  * built from (quantizedattention_amd/_srchash.py); the Python binding refuses a library whose hash
  * differs from the sources beside it (a stale prebuilt library). */
-#define QATTN_ABI_VERSION 10
+#define QATTN_ABI_VERSION 11
 int qattn_abi_version(void);
 const char* qattn_source_hash(void);
 
@@ -367,7 +367,7 @@ int qattn_split_bf16(const void* x, void* hi, void* lo, long n, void* stream);
 
 /* Q / K rows: x f16 [rows, head_dim] -> q4 u8 [rows, head_dim/2] (low nibble first), scale u8
  * [rows, head_dim/32].  mean (f16 [rows/seq, head_dim]) or NULL: when given, row r is first
- * smoothed to f16(x - mean[r / seq]) (k_mean from qattn_kmean).  head_dim 64 or 128. */
+ * smoothed to f16(x - mean[r / seq]) (k_mean from qattn_kmean).  head_dim 64, 128 or 256. */
 int qattn_mxfp4_quant_rows(const void* x, const void* mean, void* q4, void* scale, long rows, long seq,
                            int head_dim, void* stream);
 
@@ -505,7 +505,12 @@ int qattn_mxfp4_paged_append(const void* k, const void* v, const void* k_mean, v
  * operands, q4 / qscale, opart and out are sized by it (K rows of 32 B and 2 scale bytes, V tiles [64][32 B] and
  * [64][2], opart / out rows of 64), the arithmetic is the same definition at D = 64, and the tiles come through
  * a ring whose slot holds two consecutive 64-key tiles.  Every other MX-FP4 entry returns 1 for it.
- * Returns 1 for head_dim other than 128 and 64, a NULL lens / block_table / seq_rec / work, the pool's limits above,
+ * head_dim 256 (ABI 11): the same entries, qattn_mxfp4_quant_rows and the three entries of the decode step take
+ * head_dim 256 too (K rows of 128 B and 8 scale bytes, V tiles [256][32 B] and [256][2], 272 B per key and head,
+ * opart / out rows of 256; a rope table f32 [max_pos][256], NeoX pairs (i, i + 128)): the same definition at D =
+ * 256, four k-steps of S per 32 keys accumulated in fp32 in ascending order, through a four-slot ring of 17-KiB
+ * tile images (68 KiB of dynamic LDS).  Every other MX-FP4 entry returns 1 for it.
+ * Returns 1 for head_dim other than 128, 64 and 256, a NULL lens / block_table / seq_rec / work, the pool's limits above,
  * keys_per_split < 64 or % 64, causal not 0 or 2, group < 1, max_seqs < 1, nseq > max_seqs or > tokens,
  * tokens * group * kv_heads, part_rows, nwork * kv_heads or max_seqs * kv_heads >= 2^31; 0 without a
  * launch for nseq, nwork or tokens == 0.  Allocates nothing. */
@@ -619,7 +624,7 @@ int qattn_mxfp4_varlen_combine(const void* opart, const void* ml, void* out, voi
  * acc) the merged state of a row of query head h: z = sink_logit[h] * log2(e) (one rounded fp32 product), M' =
  * max(M, ceil(z)), w = 2^(M - M') (exact; 0 for M = -inf), L' = fma(w, L, exp2(z - M')), out = f16((w acc) *
  * (1 / L')) under the rounding rule of the merge, lse = M' + log2(L'): lse covers the visible keys and the
- * sink.  A row whose splits saw no key gets out = 0, lse = z.  head_dim 128 or 64; returns 1 for a NULL
+ * sink.  A row whose splits saw no key gets out = 0, lse = z.  head_dim 128, 64 or 256; returns 1 for a NULL
  * sink_logit and as the entry above. */
 int qattn_mxfp4_varlen_combine_sink(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
                                     const void* sink_logit, long nseq, long tokens, long q_heads, long kv_heads,
@@ -642,7 +647,7 @@ int qattn_mxfp4_paged_append_packed(const void* k, const void* v, const void* k_
                                     void* stream);
 
 /* Rotary position embedding fused into the quantisers of the packed step (kv_cache_mxfp4.py Rope).
- * cos_sin f32 [max_pos][D], D = head_dim (128 or 64), contiguous: row p holds cos theta(p, i) at column i and
+ * cos_sin f32 [max_pos][D], D = head_dim (128, 64 or 256), contiguous: row p holds cos theta(p, i) at column i and
  * sin theta(p, i) at column D/2 + i for pair i in [0, D/2) (the cos_sin_cache convention; a table scaled by
  * YaRN, llama3 or NTK is passed as it is).  interleaved 0 (NeoX, rotate half) pairs elements (i, i + D/2) of a
  * row, 1 (GPT-J) elements (2i, 2i + 1).  With c, s from the row of the token's position, a pair (a, b) of f16 inputs
@@ -700,12 +705,13 @@ int qattn_mxfp4_paged_append_packed_rope(const void* k, const void* v, const voi
  * its entry returns at once without a store.  q4 / qscale: the n * kv_heads * group quantised query rows,
  * token-major; opart f32 [n * splits * kv_heads * group][head_dim] and ml f32 x 2 of as many rows.  Every entry
  * gets, bit for bit, what the first packed entry (or the windowed one) gives it at the same keys_per_split.
- * head_dim 128 or 64 (64: the pair ring of the packed entries at that head_dim, with the same early return).
+ * head_dim 128, 64 or 256 (64 and 256: the ring of the packed entries at that head_dim, with the same early
+ * return).
  * Returns 1 as those entries do for their pool, and for the limits of the plan entry.
  *
  * qattn_mxfp4_decode_step_combine merges entry i's ns splits from its rows [i * splits * q_heads, ..) with
  * qattn_mxfp4_varlen_combine's arithmetic into out f16 [n][q_heads][head_dim] and lse f32 [n][q_heads], head_dim
- * 128 or 64; a padding entry (ns < 1) gets out = 0 and lse = -inf.
+ * 128, 64 or 256; a padding entry (ns < 1) gets out = 0 and lse = -inf.
  *
  * qattn_mxfp4_decode_step_combine_sink is that merge with the learned sink logit of
  * qattn_mxfp4_varlen_combine_sink (sink_logit f32 [q_heads] on the device, natural-log units, read when the

@@ -140,7 +140,7 @@ RESTYPES = {"qattn_abi_version": ctypes.c_int, "qattn_source_hash": ctypes.c_cha
             "qattn_int8_bwd_plan": ctypes.c_long, "qattn_bf16_bwd_plan": ctypes.c_long}
 
 # include/qattn.h QATTN_ABI_VERSION: the argument lists SIGNATURES describes
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _lib = None
 _dev = None

@@ -41,8 +41,8 @@ def mxfp4_quantize_rows(x: torch.Tensor, mean: torch.Tensor | None = None):
     """
     _lib.require_gpu(x)
     D = x.shape[-1]
-    if D not in (64, 128):
-        raise _lib.QAttnError("qattn mxfp4: head_dim must be 64 or 128")
+    if D not in (64, 128, 256):
+        raise _lib.QAttnError("qattn mxfp4: head_dim must be 64, 128 or 256")
     x = _lib.kernel_input(x, torch.float16)
     rows = x.numel() // D
     seq = x.shape[-2] if x.dim() >= 2 else rows
@@ -58,14 +58,18 @@ def mxfp4_quantize_rows(x: torch.Tensor, mean: torch.Tensor | None = None):
 
 
 ROPE_DIM = 128   # the head_dim of rope_table's default
-ROPE_DIMS = (64, 128)   # the head dims of the rotary entries
+ROPE_DIMS = (64, 128, 256)   # the head dims of the rotary entries
+
+
+class HeadDimError(_lib.QAttnError, ValueError):
+    """A call that a pool, a step or a rotary table of this head_dim does not serve (a ``ValueError`` too)."""
 
 
 @dataclass(frozen=True)
 class Rope:
     """A rotary table for the ``rope=`` arguments of the packed MX-FP4 cache path.
 
-    ``table`` fp32 [max_pos, D], D = 128 or 64 (the head_dim of the pool and the queries it is used with),
+    ``table`` fp32 [max_pos, D], D = 128, 64 or 256 (the head_dim of the pool and the queries it is used with),
     contiguous, on the GPU: row p holds cos theta(p, i) in column i and sin theta(p, i) in column D/2 + i for
     pair i in [0, D/2) (the ``cos_sin_cache`` convention, so a table scaled by YaRN, llama3 or NTK is passed as
     it is; :func:`rope_table` makes the plain one).  ``interleaved=False`` (NeoX, rotate half) pairs elements
@@ -81,7 +85,7 @@ class Rope:
         if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2
                 or t.shape[1] not in ROPE_DIMS or t.shape[0] < 1 or not t.is_contiguous()):
             raise _lib.QAttnError("qattn mxfp4 rope: the table must be a contiguous fp32 tensor [max_pos >= 1, D], "
-                                  "D = 128 or 64 (cos in columns [0, D/2), sin in [D/2, D))")
+                                  "D = 128, 64 or 256 (cos in columns [0, D/2), sin in [D/2, D))")
         _lib.require_gpu(t)
         if not isinstance(self.interleaved, bool):
             raise _lib.QAttnError(f"qattn mxfp4 rope: interleaved must be a bool, got {self.interleaved!r}")
@@ -97,16 +101,16 @@ class Rope:
     def check_head_dim(self, head_dim: int) -> None:
         """Raise unless the table is as wide as the rows it is to rotate."""
         if self.head_dim != head_dim:
-            raise _lib.QAttnError(f"qattn mxfp4 rope: a table of width {self.head_dim} for rows of head_dim "
-                                  f"{head_dim}")
+            raise HeadDimError(f"qattn mxfp4 rope: a table of width {self.head_dim} for rows of head_dim "
+                               f"{head_dim}")
 
 
 def rope_table(max_pos: int, base: float = 10000.0, device=None, head_dim: int = ROPE_DIM) -> torch.Tensor:
-    """The plain rotary table fp32 [max_pos, D] of :class:`Rope` (D = ``head_dim``, 128 or 64): the angles
+    """The plain rotary table fp32 [max_pos, D] of :class:`Rope` (D = ``head_dim``, 128, 64 or 256): the angles
     ``p * base ** (-2 i / D)`` are computed in float64 on the host, their cos (columns [0, D/2)) and sin
     (columns [D/2, D)) rounded once to fp32, then moved to ``device`` (None: left on the host)."""
     if int(max_pos) < 1 or not base > 0 or head_dim not in ROPE_DIMS:
-        raise _lib.QAttnError(f"qattn mxfp4 rope: max_pos >= 1, base > 0 and head_dim 64 or 128 expected, got "
+        raise _lib.QAttnError(f"qattn mxfp4 rope: max_pos >= 1, base > 0 and head_dim 64, 128 or 256 expected, got "
                               f"{max_pos}, {base}, {head_dim}")
     i = torch.arange(head_dim // 2, dtype=torch.float64)
     inv_freq = torch.pow(torch.tensor(float(base), dtype=torch.float64), -2.0 * i / head_dim)
@@ -138,14 +142,14 @@ def _device_positions(positions, tokens: int) -> bool:
 
 
 def mxfp4_quantize_rows_rope(x: torch.Tensor, rope: Rope, positions):
-    """Packed x [T, H, D] (fp16, token-major; D = 128 or 64, the table's width), each row rotated by its token's
+    """Packed x [T, H, D] (fp16, token-major; D = 128, 64 or 256, the table's width), each row rotated by its token's
     position first (:class:`Rope`) -> (packed uint8 [T*H, D/2], scales uint8 [T*H, D/32]), bit for bit ``mxfp4_quantize_rows`` of the rotated
     fp16 rows.  ``positions``: T ints in [0, rope.max_pos) as a list or a host tensor (checked, uploaded
     without a synchronisation), or a device int32 tensor [T], used as given."""
     if not isinstance(rope, Rope):
         raise _lib.QAttnError("qattn mxfp4 rope: rope must be a Rope")
     if x.dim() != 3 or x.shape[2] not in ROPE_DIMS:
-        raise _lib.QAttnError("qattn mxfp4 rope: packed rows must be x [T, H, 128] or [T, H, 64]")
+        raise _lib.QAttnError("qattn mxfp4 rope: packed rows must be x [T, H, D], D = 128, 64 or 256")
     rope.check_head_dim(x.shape[2])
     T, H, D = x.shape
     if T * H >= 1 << 31:

@@ -53,6 +53,9 @@ FILE_FLAGS = {
     # rescale of O is the only place it would appear, once per raised row maximum)
     "mxfp4_attn_d64.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp",
                            "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    # the head_dim 256 kernels: the same tile body, scheduler and fp32 arithmetic
+    "mxfp4_attn_d256.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp",
+                            "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

@@ -1,5 +1,5 @@
 // The device code of the MX-FP4 attention kernels (format, quantisers, rings, tile body, merge, appends) that
-// mxfp4_attn.hip and mxfp4_attn_d64.hip share; the definitions are at the head of mxfp4_attn.hip.
+// mxfp4_attn.hip, mxfp4_attn_d64.hip and mxfp4_attn_d256.hip share; the definitions are at the head of mxfp4_attn.hip.
 #pragma once
 #include "common.h"
 
@@ -251,15 +251,19 @@ struct MxCfg {
   static constexpr int V_BYTES = D * 32;              // [D][32 B]
   static constexpr int KS_BYTES = KT * (D / 32);      // key scales of the tile
   static constexpr int VS_BYTES = D * 2;
-  static constexpr int KOFF = 0, VOFF = K_BYTES, KSOFF = K_BYTES + V_BYTES, VSOFF = KSOFF + 256;
-  static constexpr int SLOT = VSOFF + 256;
+  static constexpr int SC_BLOCK = KS_BYTES > 256 ? KS_BYTES : 256;   // LDS bytes of a scale block: 512 at D = 256
+  static constexpr int KOFF = 0, VOFF = K_BYTES, KSOFF = K_BYTES + V_BYTES, VSOFF = KSOFF + SC_BLOCK;
+  static constexpr int SLOT = VSOFF + SC_BLOCK;       // D = 256: 8 KiB | 8 KiB | 512 B | 512 B = 17 KiB
   static constexpr int P16 = (K_BYTES + V_BYTES) / 1024;   // 1-KiB pieces
   static constexpr int IPW16 = P16 / WAVES;
   static constexpr int IPW = IPW16 + 2;               // + the two 256-B scale blocks
   static constexpr int NKS = D / 64;                  // 32x32x64 k-steps of S
   static constexpr int NDB = D / 32;
   static constexpr float MSLACK = 8.f;                // P <= 2^MSLACK between max raises
-  static_assert(KS_BYTES <= 256 && VS_BYTES <= 256 && P16 % WAVES == 0, "tile layout");
+  // the D / 32 scale bytes of a Q / K row in one word: byte b = the scale of block b
+  using scale_t = std::conditional_t<(D > 128), unsigned long, unsigned>;
+  static_assert(KS_BYTES <= SC_BLOCK && VS_BYTES <= SC_BLOCK && P16 % WAVES == 0 && D / 32 <= (int)sizeof(scale_t),
+                "tile layout");
 };
 
 #ifndef QA_MX_OCC
@@ -394,13 +398,14 @@ struct MxNoRing {
 };
 
 // Query fragments of row r (B operand of S^T): the lane holds Q[r][64s + 32h .. +32] and the row's
-// D / 32 scale bytes packed into one word, which is returned.
+// D / 32 scale bytes packed into one word (64-bit at D = 256), which is returned.
 template <int D>
-QA_DEVICE unsigned mx_load_q(const uint8_t* q4, const uint8_t* qs, long r, int h, v4i (&qf)[MxCfg<D>::NKS]) {
+QA_DEVICE typename MxCfg<D>::scale_t mx_load_q(const uint8_t* q4, const uint8_t* qs, long r, int h,
+                                               v4i (&qf)[MxCfg<D>::NKS]) {
   using C = MxCfg<D>;
 #pragma unroll
   for (int s = 0; s < C::NKS; ++s) qf[s] = *reinterpret_cast<const v4i*>(q4 + r * C::KROWB + 32 * s + 16 * h);
-  unsigned qsw = 0;   // byte b = the scale of block b, in one (unaligned) load
+  typename C::scale_t qsw = 0;   // byte b = the scale of block b, in one (unaligned) load
   __builtin_memcpy(&qsw, qs + r * (D / 32), D / 32);
   return qsw;
 }
@@ -417,7 +422,7 @@ QA_DEVICE unsigned mx_load_q(const uint8_t* q4, const uint8_t* qs, long r, int h
 // already, so e is the constant of the other paths); every test is of a constant bit of one of the two
 // registers and feeds its select at once.
 template <int D, bool CAUSAL, bool WINDOW = false, bool TREE = false>
-QA_DEVICE void mx_tile(const char* sl, const v4i (&qf)[MxCfg<D>::NKS], unsigned qsw,
+QA_DEVICE void mx_tile(const char* sl, const v4i (&qf)[MxCfg<D>::NKS], typename MxCfg<D>::scale_t qsw,
                        v16f (&o)[MxCfg<D>::NDB], float& m, float& l, bool diag, int lim, float qks, int lane,
                        int h, int c32, int lo = 0, int slim = 0, unsigned vis0 = 0, unsigned vis1 = 0) {
   static_assert(CAUSAL || !WINDOW, "a window is causal");
@@ -434,9 +439,9 @@ QA_DEVICE void mx_tile(const char* sl, const v4i (&qf)[MxCfg<D>::NKS], unsigned 
   for (int u = 0; u < 2; ++u) {
     acc[u] = v16f{};
     const int key = 32 * u + c32;
-    unsigned ksw;   // the key row's D / 32 scale bytes, in one aligned load
+    typename C::scale_t ksw;   // the key row's D / 32 scale bytes, in one aligned load
     if constexpr (D == 64) ksw = *reinterpret_cast<const unsigned short*>(sl + C::KSOFF + key * 2);
-    else ksw = *reinterpret_cast<const unsigned*>(sl + C::KSOFF + key * (D / 32));
+    else ksw = *reinterpret_cast<const typename C::scale_t*>(sl + C::KSOFF + key * (D / 32));
 #pragma unroll
     for (int s = 0; s < C::NKS; ++s) {
       const v4i ka = *reinterpret_cast<const v4i*>(sl + C::KOFF + key * C::KROWB + 32 * s + 16 * h);
@@ -1302,9 +1307,36 @@ int mx64_quant_rows_rope(const void* x, void* q4, void* scale, const void* cos_s
 int mx_varlen_combine_ext(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
                           const void* sink_logit, long nseq, long tokens, long q_heads, long kv_heads,
                           long part_rows, int head_dim, void* stream);
+
+// ---- head_dim 256 (mxfp4_attn_d256.hip): the same entries, with the arguments of their mx64_* forms, and the
+// quantiser and merges of the packed and the decode step at that width (sink_logit / sink null: none)
+int mx256_varlen_paged(const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
+                       const void* vscale, void* opart, void* ml, const void* lens, const void* block_table,
+                       const void* seq_rec, const void* work, long nseq, long nwork, long tokens, long part_rows,
+                       long max_seqs, long kv_heads, long group, long num_pages, long page_tokens,
+                       long max_pages_per_seq, int causal, int keys_per_split, float qks, long window, long sinks,
+                       void* stream);
+int mx256_decode_step(const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
+                      const void* vscale, void* opart, void* ml, const void* lens, const void* block_table,
+                      const void* seq_rec, const void* work, long n, long splits, long max_seqs, long kv_heads,
+                      long group, long num_pages, long page_tokens, long max_pages_per_seq, int keys_per_split,
+                      float qks, long window, long sinks, void* stream);
+int mx256_append_packed(bool rope, const void* k, const void* v, const void* k_mean, void* k4, void* kscale,
+                        void* vt, void* vscale, void* vtail, void* lens, const void* block_table,
+                        const void* seq_tab, const void* tiles, long nseq, long ntiles, long tokens, long max_seqs,
+                        long kv_heads, long num_pages, long page_tokens, long max_pages_per_seq,
+                        const void* cos_sin, const void* pos, long max_pos, int interleaved, void* stream);
+int mx256_quant_rows(const void* x, const void* mean, void* q4, void* scale, long nblk, long seq, void* stream);
+int mx256_quant_rows_rope(const void* x, void* q4, void* scale, const void* cos_sin, const void* pos, long tokens,
+                          long heads, long max_pos, int interleaved, void* stream);
+int mx256_varlen_combine(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
+                         const void* sink_logit, long nseq, long tokens, long q_heads, long kv_heads,
+                         long part_rows, void* stream);
+int mx256_step_combine(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
+                       const void* sink, long n, long splits, long q_heads, void* stream);
 }  // namespace qattn
 
-// ---- host checks the C entries of both files share
+// ---- host checks the C entries of the three files share
 // log2(page_tokens / 64) of a page size 64 * 2^k in [64, 1024], else -1
 static int mx_page_lgt(long page_tokens) {
   for (int k = 0; k <= 4; ++k)

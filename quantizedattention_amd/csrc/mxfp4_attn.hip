@@ -55,10 +55,11 @@ using namespace qattn;
 
 extern "C" int qattn_mxfp4_quant_rows(const void* x, const void* mean, void* q4, void* scale, long rows,
                                       long seq, int head_dim, void* stream) {
-  if (head_dim != 64 && head_dim != 128) return 1;
+  if (head_dim != 64 && head_dim != 128 && head_dim != 256) return 1;
   if (mean && (seq <= 0 || rows % seq != 0)) return 1;
   const long nblk = rows * head_dim / 32;
   if (nblk == 0) return 0;
+  if (head_dim == 256) return mx256_quant_rows(x, mean, q4, scale, nblk, seq, stream);
   dim3 grid((unsigned)((nblk + 255) / 256)), block(256);
   if (head_dim == 128)
     hipLaunchKernelGGL((mx_quant_rows_kernel<128>), grid, block, 0, (hipStream_t)stream,
@@ -334,6 +335,10 @@ static int mx_varlen_paged(const void* q4, const void* qscale, const void* k4, c
     return mx64_varlen_paged(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work,
                              nseq, nwork, tokens, part_rows, max_seqs, kv_heads, group, num_pages, page_tokens,
                              max_pages_per_seq, causal, keys_per_split, qks, window, sinks, stream);
+  if (head_dim == 256)   // the kernels of mxfp4_attn_d256.hip
+    return mx256_varlen_paged(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work,
+                              nseq, nwork, tokens, part_rows, max_seqs, kv_heads, group, num_pages, page_tokens,
+                              max_pages_per_seq, causal, keys_per_split, qks, window, sinks, stream);
   MxSplitCall c;
   const int rc = mx_varlen_call(c, q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec,
                                 work, nseq, nwork, tokens, part_rows, max_seqs, kv_heads, group, num_pages,
@@ -385,6 +390,9 @@ extern "C" int qattn_mxfp4_varlen_combine(const void* opart, const void* ml, voi
   if (head_dim == 64)
     return mx_varlen_combine_ext(opart, ml, out, lse, seq_rec, nullptr, nseq, tokens, q_heads, kv_heads,
                                  part_rows, 64, stream);
+  if (head_dim == 256)
+    return mx256_varlen_combine(opart, ml, out, lse, seq_rec, nullptr, nseq, tokens, q_heads, kv_heads, part_rows,
+                                stream);
   if (head_dim != 128 || nseq < 0 || tokens < 0 || part_rows < 0 || !seq_rec) return 1;
   if (kv_heads < 1 || q_heads < 1 || q_heads % kv_heads != 0 || q_heads > 0x7fffffffL) return 1;
   if (nseq == 0 || tokens == 0) return 0;
@@ -412,6 +420,10 @@ static int mx_append_packed(const void* k, const void* v, const void* k_mean, vo
     return mx64_append_packed(ROPE, k, v, k_mean, k4, kscale, vt, vscale, vtail, lens, block_table, seq_tab,
                               tiles, nseq, ntiles, tokens, max_seqs, kv_heads, num_pages, page_tokens,
                               max_pages_per_seq, cos_sin, pos, max_pos, interleaved, stream);
+  if (head_dim == 256)
+    return mx256_append_packed(ROPE, k, v, k_mean, k4, kscale, vt, vscale, vtail, lens, block_table, seq_tab,
+                               tiles, nseq, ntiles, tokens, max_seqs, kv_heads, num_pages, page_tokens,
+                               max_pages_per_seq, cos_sin, pos, max_pos, interleaved, stream);
   if (head_dim != 128 || nseq < 0 || ntiles < 0 || tokens < 0 || max_seqs < 1) return 1;
   if (ROPE && !mx_rope_ok(cos_sin, pos, max_pos, interleaved)) return 1;
   if (!k || !v || !k4 || !kscale || !vt || !vscale || !vtail || !lens || !block_table || !seq_tab || !tiles)
@@ -601,6 +613,8 @@ extern "C" int qattn_mxfp4_quant_rows_rope(const void* x, void* q4, void* scale,
                                            int interleaved, int head_dim, void* stream) {
   if (head_dim == 64)
     return mx64_quant_rows_rope(x, q4, scale, cos_sin, pos, tokens, heads, max_pos, interleaved, stream);
+  if (head_dim == 256)
+    return mx256_quant_rows_rope(x, q4, scale, cos_sin, pos, tokens, heads, max_pos, interleaved, stream);
   if (head_dim != 128 || tokens < 0 || heads < 0 || !mx_rope_ok(cos_sin, pos, max_pos, interleaved)) return 1;
   if (tokens == 0 || heads == 0) return 0;
   if (!x || !q4 || !scale || tokens > 0x7fffffffL / heads) return 1;
@@ -742,6 +756,10 @@ extern "C" int qattn_mxfp4_attn_fwd_decode_step(
     return mx64_decode_step(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work, n,
                             splits, max_seqs, kv_heads, group, num_pages, page_tokens, max_pages_per_seq,
                             keys_per_split, qks, window, sinks, stream);
+  if (head_dim == 256)   // mxfp4_attn_varlen256_kernel STEP (mxfp4_attn_d256.hip)
+    return mx256_decode_step(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work, n,
+                             splits, max_seqs, kv_heads, group, num_pages, page_tokens, max_pages_per_seq,
+                             keys_per_split, qks, window, sinks, stream);
   MxSplitCall c;
   const int rc = mx_varlen_call(c, q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work,
                                 n, n * splits, n, n * splits * kv_heads * group, max_seqs, kv_heads, group,
@@ -756,14 +774,14 @@ extern "C" int qattn_mxfp4_attn_fwd_decode_step(
 static int mx_step_combine_check(const void* opart, const void* ml, const void* out, const void* lse,
                                  const void* seq_rec, long n, long splits, long q_heads, long kv_heads,
                                  int head_dim) {
-  if ((head_dim != 128 && head_dim != 64) || n < 0 || splits < 1 || splits > 65535) return 1;
+  if ((head_dim != 128 && head_dim != 64 && head_dim != 256) || n < 0 || splits < 1 || splits > 65535) return 1;
   if (kv_heads < 1 || q_heads < 1 || q_heads % kv_heads != 0 || q_heads > 0x7fffffffL) return 1;
   if (n > 0x7fffffffL / (splits * q_heads)) return 1;
   if (n == 0) return 0;
   return !opart || !ml || !out || !lse || !seq_rec ? 1 : -1;
 }
 
-// the merges of the step that came after the first one (head_dim 64, and the sink logit at either head_dim), at
+// the merges of the step that came after the first one (head_dim 64 and 256, and the sink logit at any head_dim), at
 // the end of this file, as their kernels are emitted behind every older one; sink null: none
 static int mx_step_combine_ext(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
                                const void* sink, long n, long splits, long q_heads, int head_dim, void* stream);
@@ -773,7 +791,7 @@ extern "C" int qattn_mxfp4_decode_step_combine(const void* opart, const void* ml
                                                long kv_heads, int head_dim, void* stream) {
   const int rc = mx_step_combine_check(opart, ml, out, lse, seq_rec, n, splits, q_heads, kv_heads, head_dim);
   if (rc >= 0) return rc;
-  if (head_dim == 64)
+  if (head_dim != 128)
     return mx_step_combine_ext(opart, ml, out, lse, seq_rec, nullptr, n, splits, q_heads, head_dim, stream);
   const long rows = n * q_heads, nthr = rows * (128 / 8);
   hipLaunchKernelGGL(mxfp4_decode_step_combine_kernel<128>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0,
@@ -968,6 +986,7 @@ static void mx_step_combine_launch(const void* opart, const void* ml, void* out,
 
 static int mx_step_combine_ext(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
                                const void* sink, long n, long splits, long q_heads, int head_dim, void* stream) {
+  if (head_dim == 256) return mx256_step_combine(opart, ml, out, lse, seq_rec, sink, n, splits, q_heads, stream);
   if (head_dim == 64)
     mx_step_combine_launch<64>(opart, ml, out, lse, seq_rec, sink, n * q_heads, q_heads, splits, stream);
   else if (sink)   // (without one, head_dim 128 is qattn_mxfp4_decode_step_combine's own launch)

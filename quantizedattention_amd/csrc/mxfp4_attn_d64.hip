@@ -444,6 +444,9 @@ extern "C" int qattn_mxfp4_varlen_combine_sink(const void* opart, const void* ml
                                                long tokens, long q_heads, long kv_heads, long part_rows,
                                                int head_dim, void* stream) {
   if (!sink_logit) return 1;
+  if (head_dim == 256)   // mxfp4_attn_d256.hip
+    return qattn::mx256_varlen_combine(opart, ml, out, lse, seq_rec, sink_logit, nseq, tokens, q_heads, kv_heads,
+                                       part_rows, stream);
   return qattn::mx_varlen_combine_ext(opart, ml, out, lse, seq_rec, sink_logit, nseq, tokens, q_heads, kv_heads,
                                       part_rows, head_dim, stream);
 }

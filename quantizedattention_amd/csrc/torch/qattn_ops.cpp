@@ -595,12 +595,15 @@ void check_rope(const RopeArgs& r, int64_t tokens, int64_t D = 128) {
               "qattn mxfp4 rope: positions must be a contiguous int32 tensor [T], one per packed token");
 }
 
-// attention_mxfp4.mxfp4_quantize_rows_rope: packed x [T, H, 128], each row rotated by pos[token] first
+// the head dims of the packed step, its quantiser and the decode step
+static bool mx_packed_dim(int64_t D) { return D == 128 || D == 64 || D == 256; }
+
+// attention_mxfp4.mxfp4_quantize_rows_rope: packed x [T, H, D], each row rotated by pos[token] first
 std::tuple<Tensor, Tensor> mxfp4_quant_rows_rope(const Tensor& x_in, const Tensor& cos_sin, const Tensor& pos,
                                                  bool interleaved) {
   require_gpu({&x_in});
-  TORCH_CHECK(x_in.dim() == 3 && (x_in.size(2) == 128 || x_in.size(2) == 64),
-              "qattn mxfp4 rope: packed rows must be x [T, H, 128] or [T, H, 64]");
+  TORCH_CHECK(x_in.dim() == 3 && mx_packed_dim(x_in.size(2)),
+              "qattn mxfp4 rope: packed rows must be x [T, H, D], D = 128, 64 or 256");
   const int64_t T = x_in.size(0), H = x_in.size(1), D = x_in.size(2);
   const RopeArgs rope{cos_sin, pos, interleaved};
   check_rope(rope, T, D);
@@ -649,13 +652,13 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged_run(const Tensor& q_in, const Tens
                 "qattn mxfp4 paged cache: members must be contiguous int32 [nmember, 2], 2 * ngroup <= nmember "
                 "<= nseq");
   }
-  TORCH_CHECK(q_in.dim() == 3 && k4.dim() == 4 && (q_in.size(2) == 128 || q_in.size(2) == 64) &&
-                  k4.size(3) * 2 == q_in.size(2),
-              "qattn mxfp4 paged cache: packed queries must be q [T, Hq, D], D = 128 or 64, the pool's head_dim");
+  TORCH_CHECK(q_in.dim() == 3 && k4.dim() == 4 && mx_packed_dim(q_in.size(2)) && k4.size(3) * 2 == q_in.size(2),
+              "qattn mxfp4 paged cache: packed queries must be q [T, Hq, D], D = 128, 64 or 256, the pool's head_dim");
   const int64_t NP = k4.size(0), Hkv = k4.size(1), PT = k4.size(2), D = q_in.size(2);
-  // head_dim 64 is the plain and the windowed packed step's (csrc/mxfp4_attn_d64.hip), with or without rope
+  // head_dim 64 and 256 are the plain and the windowed packed step's (csrc/mxfp4_attn_d64.hip, _d256.hip), with
+  // or without rope
   TORCH_CHECK_VALUE(D == 128 || (!grp_rec && !tree),
-                    "qattn mxfp4 paged cache: shared prefixes and tree masks need head_dim 128, this pool has 64");
+                    "qattn mxfp4 paged cache: shared prefixes and tree masks need head_dim 128, this pool has ", D);
   TORCH_CHECK(PT >= 64 && PT <= 1024 && (PT & (PT - 1)) == 0,
               "qattn mxfp4 paged cache: page_tokens must be 64 * 2^k in [64, 1024]");
   TORCH_CHECK(block_table.scalar_type() == at::kInt && block_table.is_contiguous() && block_table.dim() == 2 &&
@@ -805,7 +808,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> mxfp4_decode_step_plan(const Tensor& 
   return {seq_tab, tiles, pos, seq_rec};
 }
 
-// kv_cache_mxfp4.DecodeStep.attend as an operator: q [n, Hq, D], D = 128 or 64 and the pool's, the pool's
+// kv_cache_mxfp4.DecodeStep.attend as an operator: q [n, Hq, D], D = 128, 64 or 256 and the pool's, the pool's
 // operands, lens (AFTER the step's append) and block table, seq_rec i32 [n, 8] of the plan above and work i32 [n
 // * splits, 4] = {i, 0, s, 0}; sink_logit f32 [Hq] on the device (natural-log units) or None.
 std::tuple<Tensor, Tensor> mxfp4_decode_step(const Tensor& q_in, const Tensor& k4, const Tensor& ks,
@@ -814,9 +817,8 @@ std::tuple<Tensor, Tensor> mxfp4_decode_step(const Tensor& q_in, const Tensor& k
                                              int64_t splits, int64_t keys_per_split, int64_t window,
                                              int64_t sinks, const c10::optional<Tensor>& sink_logit) {
   require_gpu({&q_in, &k4, &ks, &vt, &vs, &lens, &block_table, &seq_rec, &work});
-  TORCH_CHECK(q_in.dim() == 3 && k4.dim() == 4 && (q_in.size(2) == 128 || q_in.size(2) == 64) &&
-                  k4.size(3) * 2 == q_in.size(2),
-              "qattn mxfp4 decode step: q must be [n, Hq, D], D = 128 or 64, the pool's head_dim");
+  TORCH_CHECK(q_in.dim() == 3 && k4.dim() == 4 && mx_packed_dim(q_in.size(2)) && k4.size(3) * 2 == q_in.size(2),
+              "qattn mxfp4 decode step: q must be [n, Hq, D], D = 128, 64 or 256, the pool's head_dim");
   const int64_t NP = k4.size(0), Hkv = k4.size(1), PT = k4.size(2), D = q_in.size(2);
   TORCH_CHECK(PT >= 64 && PT <= 1024 && (PT & (PT - 1)) == 0,
               "qattn mxfp4 paged cache: page_tokens must be 64 * 2^k in [64, 1024]");

@@ -163,9 +163,9 @@ restates it), the attention runs ``splits`` (:func:`decode_step_splits`) work re
 lengths are, and a workgroup whose split its sequence does not have exits at once.  The host keeps what only it
 can do, in ``prepare``: the checks, the page reservation, the table upload when a page was added and the upload
 of ``slots``.  Results are the host-planned pair's bit for bit at the same keys per split.  ``share_prefix``,
-``trim`` and prefill chunks stay on the host-planned path.  A step is made for one head dim, 128 or 64
-(``head_dim=``; at 64 the fixed grid runs the pair ring of csrc/mxfp4_attn_d64.hip), and ``attend`` takes the
-learned ``sink_logit`` of the packed step at either: it enters in the step's merge, for listed entries only.
+``trim`` and prefill chunks stay on the host-planned path.  A step is made for one head dim, 128, 64 or 256
+(``head_dim=``; at 64 the fixed grid runs the pair ring of csrc/mxfp4_attn_d64.hip, at 256 the ring of
+csrc/mxfp4_attn_d256.hip), and ``attend`` takes the learned ``sink_logit`` of the packed step at each: it enters in the step's merge, for listed entries only.
 
 The device-planned verify step (:class:`VerifyStep`) is the same for speculative decoding: every listed sequence
 appends K draft tokens (1 <= K <= 64, a chain or a tree, K fixed when the step is made) and attends to them under
@@ -203,7 +203,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .attention_mxfp4 import (Rope, _device_positions, _host_positions, _qk_scale, mxfp4_quantize_rows,
+from .attention_mxfp4 import (HeadDimError, Rope, _device_positions, _host_positions, _qk_scale, mxfp4_quantize_rows,
                               mxfp4_quantize_rows_rope, mxfp4_quantize_v, rope_table)
 
 MAGIC = b"QATTNKF4"
@@ -776,10 +776,6 @@ class Checkpoint:
     saved: torch.Tensor
 
 
-class HeadDimError(_lib.QAttnError, ValueError):
-    """A call that a pool of this head_dim does not serve (a ``ValueError`` too)."""
-
-
 class PagedKVFP4:
     """MX-FP4 keys/values of up to ``max_seqs`` sequences x ``kv_heads`` heads in a pool of
     ``num_pages`` pages of ``page_tokens`` tokens; layout and invariant: the module docstring.
@@ -803,13 +799,13 @@ class PagedKVFP4:
     def allocate(cls, num_pages: int, page_tokens: int, max_seqs: int, kv_heads: int, max_pages_per_seq: int,
                  device, k_mean: Optional[torch.Tensor] = None, free_order=None,
                  head_dim: int = 128) -> "PagedKVFP4":
-        """An empty pool (every length 0, every page free), zero-filled.  ``head_dim`` is 128 or 64; a pool of
-        64 serves the packed path (``append_packed``, :func:`attention_mxfp4_varlen_paged` without
-        ``share_prefix`` and ``tree``, and a :class:`DecodeStep` made with ``head_dim=64``) and the host-only
+        """An empty pool (every length 0, every page free), zero-filled.  ``head_dim`` is 128, 64 or 256; a pool
+        of 64 or 256 serves the packed path (``append_packed``, :func:`attention_mxfp4_varlen_paged` without
+        ``share_prefix`` and ``tree``, and a :class:`DecodeStep` made with that ``head_dim``) and the host-only
         operations, and refuses the rest (:meth:`_need128`)."""
         D = int(head_dim)
-        if D not in (64, 128):
-            raise HeadDimError(f"qattn mxfp4 paged cache: head_dim must be 128 or 64, got {head_dim}")
+        if D not in (64, 128, 256):
+            raise HeadDimError(f"qattn mxfp4 paged cache: head_dim must be 128, 64 or 256, got {head_dim}")
         alloc = PageAllocator(num_pages, page_tokens, max_seqs, max_pages_per_seq, free_order)
         tpp = page_tokens // BLOCK
         if (kv_heads < 1 or num_pages * kv_heads * tpp >= 1 << 31
@@ -837,13 +833,15 @@ class PagedKVFP4:
                 2 * self.k4.shape[3])
 
     def _need128(self, what: str) -> None:
-        """Raise :class:`HeadDimError` for ``what`` on a pool of head_dim 64, which only the packed step's own
-        kernels serve (csrc/mxfp4_attn_d64.hip); called before anything is reserved, launched or changed."""
+        """Raise :class:`HeadDimError` for ``what`` on a pool of head_dim 64 or 256, which only the packed step's own
+        kernels serve (csrc/mxfp4_attn_d64.hip, csrc/mxfp4_attn_d256.hip); called before anything is reserved,
+        launched or changed."""
         D = self.shape[3]
         if D != 128:
             raise HeadDimError(f"qattn mxfp4 paged cache: {what} needs head_dim 128, this pool has head_dim {D} "
-                               "(served there: append_packed, attention_mxfp4_varlen_paged without "
-                               "share_prefix and tree, and DecodeStep(head_dim=64))")
+                               "(the widths are 128, 64 and 256; served at 64 and 256: append_packed, "
+                               "attention_mxfp4_varlen_paged without share_prefix and tree, and "
+                               f"DecodeStep(head_dim={D}))")
 
     @property
     def page_tokens(self) -> int:
@@ -1752,7 +1750,9 @@ def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_
 
     A pool of head_dim 64 (``PagedKVFP4.allocate(head_dim=64)``) takes q [T, Hq, 64] and runs the kernels of
     csrc/mxfp4_attn_d64.hip: non-causal, causal and windowed calls, ``rope`` (a table of width 64) and
-    ``sink_logit``; ``share_prefix=True`` and ``tree`` raise :class:`HeadDimError` there."""
+    ``sink_logit``; ``share_prefix=True`` and ``tree`` raise :class:`HeadDimError` there.  A pool of head_dim 256
+    takes q [T, Hq, 256] and serves the same calls through csrc/mxfp4_attn_d256.hip (``rope``: a table of width
+    256, NeoX pairs (i, i + 128))."""
     if not isinstance(cache, PagedKVFP4):
         raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PagedKVFP4")
     _, Hkv, _, D = cache.shape
@@ -1914,7 +1914,7 @@ class DecodeStep:
     padding), the append table ``seq_tab`` i32 [N, 4] and tile list ``tiles`` i32 [N, 2], ``seq_rec`` i32 [N, 8],
     ``pos`` i32 [N], ``work`` i32 [N * splits, 4] (written here and never again), the quantised queries ``q4`` /
     ``qs``, the partials ``opart`` f32 [N * splits * Hq, D] / ``ml``, and the results ``O`` f16 [N, Hq, D] /
-    ``lse`` f32 [N, Hq], which ``attend`` returns and the next ``attend`` overwrites; D = ``head_dim``, 128 or 64
+    ``lse`` f32 [N, Hq], which ``attend`` returns and the next ``attend`` overwrites; D = ``head_dim``, 128, 64 or 256
     (keyword-only; anything else raises :class:`HeadDimError`), the head dim of the pools the step serves.  ``kps`` is fixed here:
     ``keys_per_split``, or ``qattn_split_keys(kv_heads * N, 1, ceil64(max_keys), 64)``; ``splits`` =
     :func:`decode_step_splits`, so the attention grid is N * splits * kv_heads workgroups whatever the lengths
@@ -1929,7 +1929,7 @@ class DecodeStep:
     causal=True, keys_per_split=step.kps[, window, sinks][, rope][, sink_logit])`` gives.  One step object serves
     any number of pools of its head dim, layer after layer, on one stream: each pool's ``append`` rewrites the
     tables from that pool's own ``lens``.  At head_dim 64 the attention is the pair ring of
-    csrc/mxfp4_attn_d64.hip over the same fixed grid; a pool of the other head dim raises :class:`HeadDimError`
+    csrc/mxfp4_attn_d64.hip over the same fixed grid, at 256 the ring of csrc/mxfp4_attn_d256.hip; a pool of another head dim raises :class:`HeadDimError`
     before anything is reserved, uploaded or launched."""
 
     head_dim = 128   # the default; the constructor sets the instance's
@@ -1938,8 +1938,8 @@ class DecodeStep:
                  keys_per_split: Optional[int] = None, window: Optional[int] = None, sinks: int = 0, *,
                  head_dim: int = 128):
         N, max_keys, Hq, Hkv = int(max_batch), int(max_keys), int(q_heads), int(kv_heads)
-        if head_dim not in (64, 128):
-            raise HeadDimError(f"qattn mxfp4 decode step: head_dim must be 128 or 64, got {head_dim}")
+        if head_dim not in (64, 128, 256):
+            raise HeadDimError(f"qattn mxfp4 decode step: head_dim must be 128, 64 or 256, got {head_dim}")
         D = self.head_dim = int(head_dim)
         self.window, self.sinks = _window_args(window, sinks)
         if N < 1 or Hkv < 1 or Hq < 1 or Hq % Hkv or not 1 <= max_keys <= 1 << 25:

@@ -328,14 +328,15 @@ def mxfp4_decode_paged(q, cache, causal=False, keys_per_split=None):
 
 
 def mxfp4_quant_rows_rope(x, rope, positions):
-    """``attention_mxfp4.mxfp4_quantize_rows_rope`` as one operator: packed x [T, H, 128] rotated by its
-    tokens' positions through ``rope`` (a ``Rope``), then quantised -> (q4 u8 [T*H, 64], qs u8 [T*H, 4]).
+    """``attention_mxfp4.mxfp4_quantize_rows_rope`` as one operator: packed x [T, H, D] (D = 128, 64 or
+    256, the table's width) rotated by its tokens' positions through ``rope`` (a ``Rope``), then quantised -> (q4 u8
+    [T*H, D/2], qs u8 [T*H, D/32]).
     Host ``positions`` are checked against the table and uploaded here; a device int32 tensor is passed on."""
     from .attention_mxfp4 import Rope, _device_positions, _host_positions
     if not isinstance(rope, Rope):
         raise _lib.QAttnError("qattn mxfp4 rope: rope must be a Rope")
     if x.dim() != 3:
-        raise _lib.QAttnError("qattn mxfp4 rope: packed rows must be x [T, H, 128]")
+        raise _lib.QAttnError("qattn mxfp4 rope: packed rows must be x [T, H, D]")
     if not _device_positions(positions, x.shape[0]):
         positions = _host_positions(positions, x.shape[0], rope.max_pos).to(x.device, non_blocking=True)
     return _ops.mxfp4_quant_rows_rope(x, rope.table, positions, rope.interleaved)
@@ -357,7 +358,7 @@ def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=N
     tree-masked verify step of the Python call, and to the plain operator when every entry is None.  ``rope``
     (with ``positions``, as the Python call's; without a window, ``share_prefix`` or ``tree``: those
     combinations are the Python call's alone) routes to ``torch.ops.qattn.mxfp4_varlen_paged_rope``.  A pool of
-    head_dim 64 takes q [T, Hq, 64] in the plain, the windowed and the rope form; ``share_prefix=True`` and
+    head_dim 64 or 256 takes q [T, Hq, 64] / [T, Hq, 256] in the plain, the windowed and the rope form; ``share_prefix=True`` and
     ``tree`` raise there as in the Python call.  The learned sink logit (``sink_logit=``) is the Python call's and
     the C ABI's alone."""
     from .kv_cache_mxfp4 import (PagedKVFP4, _check_trimmed, _packed_lists, _query_positions, _shared_plan,
@@ -434,7 +435,7 @@ def mxfp4_decode_step_plan(step, cache):
 
 def mxfp4_decode_step(q, step, cache, seq_rec=None, sink_logit=None):
     """``kv_cache_mxfp4.DecodeStep.attend`` (without ``rope``) as one operator that allocates its outputs: q [N,
-    Hq, D] (D = 128 or 64, the pool's) against ``cache`` after the step's append, over ``seq_rec`` (default: the
+    Hq, D] (D = 128, 64 or 256, the pool's) against ``cache`` after the step's append, over ``seq_rec`` (default: the
     step's own, which its ``append`` wrote) and the step's ``work``, with the learned ``sink_logit`` f32 [Hq] when
     one is given -> (O, lse), the Python call's bits."""
     return _ops.mxfp4_decode_step(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens, cache.block_table,

@@ -20,6 +20,9 @@ and of the fixed grid's entry on the step's, on one pool at the lengths after th
 candidates: the replay of a graph captured with one tile per ring slot (QATTN_MX64_TPS=1 while it is captured),
 and the workaround the step replaces, the replay of a head_dim 128 step on a head_dim 128 pool with q, k, v
 zero-padded to 128.  The kernels alone at this head dim: tools/time_decode_varlen.py --head-dim 64.
+--head-dim 256: the same two shapes with Gemma-style heads, 16 query / 8 key-value heads of head_dim 256
+(DecodeStep(head_dim=256), the ring of csrc/mxfp4_attn_d256.hip over the fixed grid): the three candidates; there is
+no padded workaround at this width.  The kernel alone: tools/time_decode_varlen.py --head-dim 256.
 --sink: every candidate takes a learned sink logit per query head (``sink_logit``).
 
 Results: DESIGN.md section 5.
@@ -100,15 +103,15 @@ def runners(cache, k, v, q, W, S, sink):
 
 
 def case(name, B, L, W, S, rand, passes, iters, Dh=D, use_sink=False):
-    hq = HQ if Dh == D else 64
+    hq = {D: HQ, 64: 64, 256: 16}[Dh]
     k, v, q = rand(B, HKV, Dh), rand(B, HKV, Dh), rand(B, hq, Dh)
     sink = rand(hq).float() if use_sink else None
     if Dh == D:
         cache = pool_of([L] * B, rand, extra=1)
     else:
         os.environ["QATTN_MX64_TPS"] = "2"
-        kk, vv = rand(L, HKV, 64), rand(L, HKV, 64)
-        cache = pool64([L] * B, kk, vv, 64, extra=1)
+        kk, vv = rand(L, HKV, Dh), rand(L, HKV, Dh)
+        cache = pool64([L] * B, kk, vv, Dh, extra=1)
     step, host, eager, capture = runners(cache, k, v, q, W, S, sink)
     RO, Rl = host(step.kps)
     O, lse = eager()
@@ -155,7 +158,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--head-dim", type=int, default=128, choices=(64, 128), help="64: 64 / 8 heads of head_dim 64")
+    ap.add_argument("--head-dim", type=int, default=128, choices=(64, 128, 256),
+                    help="64: 64 / 8 heads of head_dim 64; 256: 16 / 8 heads of head_dim 256")
     ap.add_argument("--sink", action="store_true", help="with a learned sink logit per query head")
     args = ap.parse_args()
     assert args.passes >= 3

@@ -30,6 +30,11 @@ anything is timed (the pools of (b) hold different random tokens).
     with one (QATTN_MX64_TPS), and today's workaround, the same q, k, v zero-padded to 128 on a D = 128 pool;
     then the whole call with and without ``sink_logit``.
 
+(f) with --head-dim 256 (then only (f) runs): Gemma-style heads, 16 query / 8 key-value heads of head_dim 256, at
+    the two decode shapes of (e) with a window of 4096.  Per shape, the kernel alone (REPS launches) with the bytes
+    it must read (the visited 64-key tiles at 272 B per key and key/value head) and the fraction of the HBM peak
+    (8 TB/s) that makes, then the whole call.
+
 After (a) and (b) the packed call is taken apart: the host plan alone (plan_varlen, a host clock), the
 two table uploads alone (event-timed) and the attention kernel alone (REPS back-to-back launches of the
 C entry on buffers and tables made once, divided by REPS), beside the paged kernel alone in (a).
@@ -240,12 +245,12 @@ def windowed(W, S, rand, passes, iters):
 
 
 def pool64(lengths, k, v, Dp, extra=0):
-    """A pool of head_dim ``Dp`` holding the first ``lengths[j]`` rows of k, v [n, 8, 64] per sequence, zero-
+    """A pool of head_dim ``Dp`` holding the first ``lengths[j]`` rows of k, v [n, 8, D <= Dp] per sequence, zero-
     padded to ``Dp``, with room for ``extra`` more tokens per sequence."""
     B, n = len(lengths), max(lengths)
     cache = PagedKVFP4.allocate(sum(-(-(L + extra) // P) for L in lengths), P, B, 8, -(-(n + extra) // P), "cuda",
                                 head_dim=Dp)
-    pad = lambda x: torch.nn.functional.pad(x, (0, Dp - 64))  # noqa: E731
+    pad = lambda x: torch.nn.functional.pad(x, (0, Dp - k.shape[2]))  # noqa: E731
     for t0 in range(0, n, 4096):
         c = [min(max(L - t0, 0), 4096) for L in lengths]
         ids = [j for j in range(B) if c[j]]
@@ -257,14 +262,14 @@ def pool64(lengths, k, v, Dp, extra=0):
 def kernel64(q, cache, q_lens, W, tps):
     """REPS launches of the packed attention kernel alone on ``cache`` (either head_dim); tps: tiles per slot."""
     Dp, ids = cache.shape[3], list(range(len(q_lens)))
-    kps, rec, work, rows = plan_varlen(cache.lengths, ids, q_lens, 64, 8, None, True, W, 0)
+    kps, rec, work, rows = plan_varlen(cache.lengths, ids, q_lens, q.shape[1], 8, None, True, W, 0)
     rec_d, work_d = (torch.tensor(x, dtype=torch.int32).cuda() for x in (rec, work))
     q4, qs = mxfp4_quantize_rows(q)
     opart = torch.empty((rows, Dp), dtype=torch.float32, device="cuda")
     ml = torch.empty((rows, 2), dtype=torch.float32, device="cuda")
     args = (_lib.ptr(q4), _lib.ptr(qs), *(_lib.ptr(x) for x in cache.kv), _lib.ptr(opart), _lib.ptr(ml),
             _lib.ptr(cache.lens), _lib.ptr(cache.block_table), _lib.ptr(rec_d), _lib.ptr(work_d), len(rec),
-            len(work), q.shape[0], rows, cache.alloc.max_seqs, 8, 8, cache.num_pages, P,
+            len(work), q.shape[0], rows, cache.alloc.max_seqs, 8, q.shape[1] // 8, cache.num_pages, P,
             cache.alloc.max_pages_per_seq, 2, kps, Dp, _qk_scale(Dp))
     name = "qattn_mxfp4_attn_fwd_varlen_paged" + ("_window" if W else "")
     tail = ((W, 0) if W else ()) + (_lib.stream_of(q),)
@@ -308,13 +313,39 @@ def d64(rand, passes, iters):
         torch.cuda.empty_cache()
 
 
+HBM_PEAK = 8.0e12   # bytes / s
+
+
+def d256(rand, passes, iters):
+    shapes = [("8 decodes at 8192 cached", [8192] * 8, None),
+              ("64 decodes at 32768 cached, window 4096", [32768] * 64, 4096)]
+    k, v = rand(32768, 8, 256), rand(32768, 8, 256)
+    for name, lengths, W in shapes:
+        cache, q_lens, ids = pool64(lengths, k, v, 256), [1] * len(lengths), list(range(len(lengths)))
+        q = rand(len(lengths), 16, 256)
+        # the 64-key tiles a decode query's workgroups visit: all of them, or from the window's first tile on
+        tiles = sum(-(-L // 64) - (max(0, L - W) // 64 if W else 0) for L in lengths)
+        nbytes = tiles * 64 * 8 * 272
+        print(f"(f) {name}: 16/8 heads of head_dim 256, P {P}; {nbytes / 1e6:.1f} MB to read", flush=True)
+        res = alternate({f"D 256 kernel x{REPS}": kernel64(q, cache, q_lens, W, 2)}, passes, iters)
+        report(res)
+        med, pm = next(iter(res.values()))
+        print(f"  kernel {med / REPS:.1f} us: {nbytes / (med / REPS * 1e-6) / 1e12:.2f} TB/s, "
+              f"{nbytes / (med / REPS * 1e-6) / HBM_PEAK:.1%} of the HBM peak", flush=True)
+        report(alternate({"whole call, D 256": lambda: attention_mxfp4_varlen_paged(q, cache, ids, q_lens, causal=True,
+                                                                                   window=W)}, passes, iters))
+        del cache
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--window", type=int, default=None, help="run only (d), with this window")
     ap.add_argument("--sinks", type=int, default=0)
-    ap.add_argument("--head-dim", type=int, default=128, choices=(64, 128), help="64: run only (e)")
+    ap.add_argument("--head-dim", type=int, default=128, choices=(64, 128, 256),
+                    help="64: run only (e); 256: run only (f)")
     args = ap.parse_args()
     assert args.passes >= 3
     print(f"device {torch.cuda.get_device_name(0)}; {args.passes} alternating passes x {args.iters} calls, "
@@ -323,6 +354,9 @@ def main():
     rand = lambda *s: torch.randn(s, device="cuda", generator=g).half()  # noqa: E731
     if args.head_dim == 64:
         d64(rand, args.passes, args.iters)
+        return
+    if args.head_dim == 256:
+        d256(rand, args.passes, args.iters)
         return
     if args.window is not None:
         windowed(args.window, args.sinks, rand, args.passes, args.iters)
