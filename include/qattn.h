@@ -36,7 +36,7 @@ extern "C" {
  * qattn_source_hash() is the sha256 (hex) of the kernel sources and compile flags the library was
  * built from (quantizedattention_amd/_srchash.py); the Python binding refuses a library whose hash
  * differs from the sources beside it (a stale prebuilt library). */
-#define QATTN_ABI_VERSION 11
+#define QATTN_ABI_VERSION 12
 int qattn_abi_version(void);
 const char* qattn_source_hash(void);
 
@@ -731,6 +731,36 @@ int qattn_mxfp4_decode_step_combine(const void* opart, const void* ml, void* out
 int qattn_mxfp4_decode_step_combine_sink(const void* opart, const void* ml, void* out, void* lse,
                                          const void* seq_rec, const void* sink_logit, long n, long splits,
                                          long q_heads, long kv_heads, int head_dim, void* stream);
+
+/* Logit soft-capping (Gemma-2, Grok-1; kv_cache_mxfp4.py attention_mxfp4_varlen_paged(softcap=) and
+ * DecodeStep(softcap=)): with s = deq(q) . deq(k), the fp32 result of the block-scaled product, and qks = scale *
+ * log2(e) as everywhere (any softmax scale > 0, not only 1 / sqrt(head_dim)), the logit of a visible key in
+ * natural-log units is softcap * tanh(scale * s / softcap) in place of scale * s.  The kernels compute, in log2
+ * units, C * t with t = 1 - 2 / (1 + 2^(s * c1)), c1 = 2 * qks / softcap and C = softcap * log2(e) (the two
+ * constants rounded to fp32 once, from doubles, by these entries) on the hardware exp2 and reciprocal, which is
+ * exact at both saturations (+-C, no NaN); P = 2^(C t - m) with the integer running max m of the uncapped
+ * kernels.  A masked key keeps P = 0 exactly and takes no part in the row max.  lse (base 2) is over the capped
+ * logits of the visible keys, and of the sink logit when the merge is given one.
+ *
+ * qattn_mxfp4_attn_fwd_varlen_paged_softcap is the packed step: qattn_mxfp4_attn_fwd_varlen_paged for window ==
+ * 0 (then sinks == 0; causal 0 or 2) and qattn_mxfp4_attn_fwd_varlen_paged_window for window >= 1 (causal == 2),
+ * with the tables, partial rows, limits and merges of those entries; head_dim 128, 64 or 256.
+ * qattn_mxfp4_attn_fwd_decode_step_softcap is qattn_mxfp4_attn_fwd_decode_step in the same way: the tables of
+ * qattn_mxfp4_decode_step_plan, the fixed grid, the merges of the step.  The cap changes no split, so every entry
+ * of the step gets, bit for bit, what the capped packed entry gives it at the same keys_per_split.
+ * Both return 1 without a launch unless qks and softcap are finite and > 0, and as the entries they follow. */
+int qattn_mxfp4_attn_fwd_varlen_paged_softcap(
+    const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt, const void* vscale,
+    void* opart, void* ml, const void* lens, const void* block_table, const void* seq_rec, const void* work,
+    long nseq, long nwork, long tokens, long part_rows, long max_seqs, long kv_heads, long group,
+    long num_pages, long page_tokens, long max_pages_per_seq, int causal, int keys_per_split, int head_dim,
+    float qks, long window, long sinks, float softcap, void* stream);
+int qattn_mxfp4_attn_fwd_decode_step_softcap(
+    const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt, const void* vscale,
+    void* opart, void* ml, const void* lens, const void* block_table, const void* seq_rec, const void* work, long n,
+    long splits, long max_seqs, long kv_heads, long group, long num_pages, long page_tokens,
+    long max_pages_per_seq, int keys_per_split, int head_dim, float qks, long window, long sinks, float softcap,
+    void* stream);
 
 /* The device-planned verify step (kv_cache_mxfp4.py VerifyStep): draft_tokens = K new tokens, 1 <= K <= 64, a
  * chain or a draft tree in topological order, for each of up to n listed sequences, appended and then attended

@@ -108,6 +108,10 @@ SIGNATURES = {
     "qattn_mxfp4_decode_step_plan": [_vp] * 6 + [_c_long] * 5 + [_c_int] + [_c_long] * 3 + [_vp],
     "qattn_mxfp4_attn_fwd_decode_step": [_vp] * 12 + [_c_long] * 8 + [_c_int, _c_int, _c_float, _c_long, _c_long,
                                                                        _vp],
+    "qattn_mxfp4_attn_fwd_varlen_paged_softcap": [_vp] * 12 + [_c_long] * 10 + [_c_int, _c_int, _c_int, _c_float,
+                                                                                _c_long, _c_long, _c_float, _vp],
+    "qattn_mxfp4_attn_fwd_decode_step_softcap": [_vp] * 12 + [_c_long] * 8 + [_c_int, _c_int, _c_float, _c_long,
+                                                                               _c_long, _c_float, _vp],
     "qattn_mxfp4_decode_step_combine": [_vp] * 5 + [_c_long] * 4 + [_c_int, _vp],
     "qattn_mxfp4_decode_step_combine_sink": [_vp] * 6 + [_c_long] * 4 + [_c_int, _vp],
     "qattn_mxfp4_verify_step_plan": [_vp] * 7 + [_c_long] * 6 + [_c_int, _c_long, _vp],
@@ -140,7 +144,7 @@ RESTYPES = {"qattn_abi_version": ctypes.c_int, "qattn_source_hash": ctypes.c_cha
             "qattn_int8_bwd_plan": ctypes.c_long, "qattn_bf16_bwd_plan": ctypes.c_long}
 
 # include/qattn.h QATTN_ABI_VERSION: the argument lists SIGNATURES describes
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 _lib = None
 _dev = None
@@ -287,9 +291,11 @@ def call(name: str, *args) -> None:
         raise QAttnError(f"{name}: kernel launch failed (status {rc})")
 
 
-def qk_scale(head_dim: int) -> float:
-    """qks of include/qattn.h: 1/sqrt(D) * log2(e), the double rounded once to fp32."""
-    return float(torch.tensor(1.0 / math.sqrt(head_dim) * 1.44269504, dtype=torch.float32))
+def qk_scale(head_dim: int, scale: float | None = None) -> float:
+    """qks of include/qattn.h: ``scale`` (None: 1/sqrt(D)) * log2(e), the double rounded once to fp32."""
+    if scale is None:
+        return float(torch.tensor(1.0 / math.sqrt(head_dim) * 1.44269504, dtype=torch.float32))
+    return ctypes.c_float(float(scale) * 1.44269504).value   # (no tensor: callers check arguments with it)
 
 
 def sm_scale(head_dim: int) -> float:

@@ -56,6 +56,10 @@ FILE_FLAGS = {
     # the head_dim 256 kernels: the same tile body, scheduler and fp32 arithmetic
     "mxfp4_attn_d256.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp",
                             "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    # the head_dim 128 kernels with logit soft-capping: a file of their own so that they too are compiled without
+    # packed fp32 arithmetic (the tanh of a lane's 32 scores would be paired) while mxfp4_attn.hip keeps its flags
+    "mxfp4_attn_softcap.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp",
+                               "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

@@ -421,10 +421,21 @@ QA_DEVICE typename MxCfg<D>::scale_t mx_load_q(const uint8_t* q4, const uint8_t*
 // tile's visibility word, bit e of (vis1:vis0) set iff it sees element e (the word is shifted down by 4h
 // already, so e is the constant of the other paths); every test is of a constant bit of one of the two
 // registers and feeds its select at once.
-template <int D, bool CAUSAL, bool WINDOW = false, bool TREE = false>
+// SOFTCAP (logit soft-capping, Gemma-2 / Grok-1): the logit of a visible key is cap * tanh(scale * s / cap) in
+// place of scale * s.  In log2 units that is C * t with C = cap * log2(e) and t = tanh(scale * s / cap) = 1 - 2 /
+// (1 + 2^(s * c1)), c1 = 2 * log2(e) * scale / cap; both constants are wave-uniform and qks is not used.  mx_softcap_tanh is t; the cap
+// stands between the S accumulator and the online softmax, and the masks act after it as they do without it (a
+// select on P, and a lane's max over its visible scores alone), so tanh(-inf) = -1 never reaches a sum.
+QA_DEVICE float mx_softcap_tanh(float s, float c1) {
+  // 1 - 2 / (1 + 2^(s c1)) on the hardware exp2 and rcp (1 ulp each): 2^x = inf gives 1 and 2^x = 0 gives -1,
+  // exactly and without a NaN, so a score far past the cap needs no clamp
+  return __builtin_fmaf(-2.f, __builtin_amdgcn_rcpf(1.f + exp2_f32(s * c1)), 1.f);
+}
+template <int D, bool CAUSAL, bool WINDOW = false, bool TREE = false, bool SOFTCAP = false>
 QA_DEVICE void mx_tile(const char* sl, const v4i (&qf)[MxCfg<D>::NKS], typename MxCfg<D>::scale_t qsw,
                        v16f (&o)[MxCfg<D>::NDB], float& m, float& l, bool diag, int lim, float qks, int lane,
-                       int h, int c32, int lo = 0, int slim = 0, unsigned vis0 = 0, unsigned vis1 = 0) {
+                       int h, int c32, int lo = 0, int slim = 0, unsigned vis0 = 0, unsigned vis1 = 0,
+                       float c1 = 0.f, float capc = 0.f) {
   static_assert(CAUSAL || !WINDOW, "a window is causal");
   static_assert(!TREE || (CAUSAL && !WINDOW), "a tree mask is causal, without a window");
   // WINDOW, TREE: element e of the lane is visible
@@ -477,7 +488,16 @@ QA_DEVICE void mx_tile(const char* sl, const v4i (&qf)[MxCfg<D>::NKS], typename 
 #pragma unroll
       for (int r = (u == 0 ? 1 : 0); r < 16; ++r) amx = fmaxf(amx, acc[u][r]);
   }
-  const float lmx = amx * qks;                                  // this lane's max of S * qks
+  // SOFTCAP: tanh is monotonic, so the lane's largest capped score is the cap of its largest score: one tanh,
+  // not a second pass over 32 capped values.  A lane without a visible key keeps -inf (tanh would make it -1, a
+  // finite logit -C that raises m from -inf).  m stays the integer running max with its slack, though every
+  // logit lies in [-C, C]: with m fixed at ceil(C) a row whose visible logits all sit near -C would hold P =
+  // 2^(-2C), 2^-145 at cap 50, below the fp32 normals, which the hardware exp2 does not return, so the row's
+  // sum and its O would be lost; following the row max keeps the largest P of a row in [2^-1, 2^MSLACK] as without
+  // a cap.
+  [[maybe_unused]] float tmx = 0.f;
+  if constexpr (SOFTCAP) tmx = amx == -INFINITY ? amx : mx_softcap_tanh(amx, c1);
+  const float lmx = SOFTCAP ? tmx * capc : amx * qks;           // this lane's max of the logits (log2 units)
   const float mx = fmaxf(lmx, xor32_swap(lmx, lane));
   if (__ballot(mx > m + C::MSLACK)) {
     const float nm = mx > m + C::MSLACK ? ceilf(mx) : m;
@@ -494,7 +514,9 @@ QA_DEVICE void mx_tile(const char* sl, const v4i (&qf)[MxCfg<D>::NKS], typename 
 #pragma unroll
   for (int u = 0; u < 2; ++u)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) x[16 * u + r] = exp2_f32(__builtin_fmaf(acc[u][r], qks, nm));
+    for (int r = 0; r < 16; ++r)
+      x[16 * u + r] = exp2_f32(SOFTCAP ? __builtin_fmaf(capc, mx_softcap_tanh(acc[u][r], c1), nm)
+                                       : __builtin_fmaf(acc[u][r], qks, nm));
   if ((WINDOW || TREE) && diag) {
 #pragma unroll
     for (int u = 0; u < 2; ++u)
@@ -512,7 +534,8 @@ QA_DEVICE void mx_tile(const char* sl, const v4i (&qf)[MxCfg<D>::NKS], typename 
   // key of the lane masked amx = -inf and pmax = 0.  In a row still at m = -inf (a key split none of
   // whose keys the row sees) the argument is then -inf + inf = NaN, which e8m0_of maps to scale byte
   // 0 like pmax = 0 (its P is all zero)
-  const float pmax = exp2_f32(__builtin_fmaf(amx, qks, nm));
+  // (SOFTCAP: the same of the lane's capped max, tmx = -inf for a lane without a visible key)
+  const float pmax = exp2_f32(SOFTCAP ? __builtin_fmaf(capc, tmx, nm) : __builtin_fmaf(amx, qks, nm));
   // P block of this lane half: its 32 values, nibble j = 16u + r
   const unsigned pe = e8m0_of(pmax);
   const v4i pk = pack_fp4x32(x, e8m0_value(pe));
@@ -670,6 +693,9 @@ __global__ __launch_bounds__(256, CAUSAL ? QA_MX_OCC_CAUSAL : QA_MX_OCC) void mx
 // the end of this file) is the same exit in front of the TREE instantiation: mx_verify_plan_kernel writes the
 // records, rec[7] = K draft nodes of K queries, and the work records {i, row block, s, 0} cover ceil(G * K /
 // 128) row blocks per entry.
+// SOFTCAP (with VARLEN, without SHARED or TREE; attention_mxfp4_varlen_paged(softcap=) and DecodeStep(softcap=)):
+// the tile body is mx_tile SOFTCAP with the two constants of vl; every other statement is the instantiation's
+// without it, so tiles, splits, masks, skips, partials and the merge do not change.
 struct MxVarlen {
   const int* work;      // i32 [nwork][4]
   const int* seq_rec;   // i32 [nseq][8]
@@ -684,6 +710,8 @@ struct MxVarlen {
   // TREE (after them, for the same reason)
   const unsigned long* tree;   // u64 [tokens]: the ancestor word of every packed token, 0 outside a tree
   long tokens;
+  // SOFTCAP (after them, for the same reason): mx_tile's c1 = 2 * log2(e) * scale / cap and C = cap * log2(e)
+  float cap_c1, cap_c;
 };
 
 // SHARED (with VARLEN; the shared-prefix step of kv_cache_mxfp4.py): one workgroup of a group record {g,
@@ -779,7 +807,7 @@ QA_DEVICE void mx_group_split(const uint8_t* __restrict__ q4, const uint8_t* __r
 constexpr int MX_GROUP_LDS = MxCfg<128>::WAVES * 32 * (int)sizeof(int);   // rowidx, behind the ring
 
 template <int D, bool CAUSAL, bool LEN = false, bool PAGED = false, bool VARLEN = false, bool WINDOW = false,
-          bool SHARED = false, bool TREE = false, bool STEP = false>
+          bool SHARED = false, bool TREE = false, bool STEP = false, bool SOFTCAP = false>
 __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
     const uint8_t* __restrict__ q4, const uint8_t* __restrict__ qs, const uint8_t* __restrict__ k4,
     const uint8_t* __restrict__ ks, const uint8_t* __restrict__ vt, const uint8_t* __restrict__ vs,
@@ -794,6 +822,7 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
   static_assert(!SHARED || (VARLEN && !WINDOW), "shared prefixes are the packed step's, without a window");
   static_assert(!TREE || (VARLEN && CAUSAL && !WINDOW && !SHARED), "tree masks are the causal packed step's");
   static_assert(!STEP || (VARLEN && CAUSAL && !SHARED), "the fixed grid is the causal packed step's");
+  static_assert(!SOFTCAP || (VARLEN && !SHARED && !TREE), "the cap is the packed step's, without groups or trees");
   static_assert(sizeof(float) == 4 && D == 128, "fp32 staging in two passes fills the ring exactly");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int bh, qt, split = (int)blockIdx.y;
@@ -963,12 +992,14 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
       lim = len - 1 - k0 - 4 * h;
     }
     if constexpr (WINDOW)
-      mx_tile<D, MASK, true>(smem + (t & 3) * C::SLOT, qf, qsw, o, m, l, diag, lim, qks, lane, h, c32, lo, slim);
+      mx_tile<D, MASK, true, false, SOFTCAP>(smem + (t & 3) * C::SLOT, qf, qsw, o, m, l, diag, lim, qks, lane, h, c32,
+                                             lo, slim, 0, 0, vl.cap_c1, vl.cap_c);
     else if constexpr (TREE)
       mx_tile<D, MASK, false, true>(smem + (t & 3) * C::SLOT, qf, qsw, o, m, l, diag, lim, qks, lane, h, c32, 0, 0,
                                     vis0, vis1);
     else
-      mx_tile<D, MASK>(smem + (t & 3) * C::SLOT, qf, qsw, o, m, l, diag, lim, qks, lane, h, c32);
+      mx_tile<D, MASK, false, false, SOFTCAP>(smem + (t & 3) * C::SLOT, qf, qsw, o, m, l, diag, lim, qks, lane, h,
+                                              c32, 0, 0, 0, 0, vl.cap_c1, vl.cap_c);
   }
   vmcnt_wait_all();
   __syncthreads();
@@ -1334,6 +1365,20 @@ int mx256_varlen_combine(const void* opart, const void* ml, void* out, void* lse
                          long part_rows, void* stream);
 int mx256_step_combine(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
                        const void* sink, long n, long splits, long q_heads, void* stream);
+
+// ---- logit soft-capping at head_dim 64 and 256: what the two entries of mxfp4_attn_softcap.hip hand those widths
+// to.  step false: the packed call, the arguments of mx64_varlen_paged; step true: the decode step, nseq = tokens
+// = n, nwork = n * splits, part_rows = n * splits * kv_heads * group, causal = 2.  cap_c1, cap_c: mx_tile SOFTCAP.
+int mx64_softcap(bool step, const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
+                 const void* vscale, void* opart, void* ml, const void* lens, const void* block_table,
+                 const void* seq_rec, const void* work, long nseq, long nwork, long tokens, long part_rows,
+                 long max_seqs, long kv_heads, long group, long num_pages, long page_tokens, long max_pages_per_seq,
+                 int causal, int keys_per_split, long window, long sinks, float cap_c1, float cap_c, void* stream);
+int mx256_softcap(bool step, const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
+                  const void* vscale, void* opart, void* ml, const void* lens, const void* block_table,
+                  const void* seq_rec, const void* work, long nseq, long nwork, long tokens, long part_rows,
+                  long max_seqs, long kv_heads, long group, long num_pages, long page_tokens, long max_pages_per_seq,
+                  int causal, int keys_per_split, long window, long sinks, float cap_c1, float cap_c, void* stream);
 }  // namespace qattn
 
 // ---- host checks the C entries of the three files share
@@ -1355,4 +1400,80 @@ static bool mx_pool_ok(long num_pages, long kv_heads, int lgt, long mpp) {
 // what the rotary entries hold their table to ("rotary positions" above)
 static bool mx_rope_ok(const void* cos_sin, const void* pos, long max_pos, int interleaved) {
   return cos_sin && pos && max_pos >= 1 && max_pos <= 0x7fffffffL && (interleaved == 0 || interleaved == 1);
+}
+
+// ---- the D = 128 key-split launch path, shared by mxfp4_attn.hip and mxfp4_attn_softcap.hip
+// what every key-split entry asks of its head_dim and keys_per_split
+static bool mx_split_ok(int head_dim, int keys_per_split) {
+  return head_dim == 128 && keys_per_split >= 64 && keys_per_split % 64 == 0;
+}
+
+// One call of mxfp4_attn_split_kernel: its arguments as the kernel takes them (Sk: the key stride of a
+// key/value head, which is the key count without lens) and its grid.
+struct MxSplitCall {
+  const void *q4, *qscale, *k4, *kscale, *vt, *vscale;
+  void *opart, *ml;
+  int bhv, rows, sq_head, Sk, kps;
+  float qks;
+  int qoff;
+  const void* lens;
+  int hps;
+  const void* btab;
+  int mpp, lgt, npool;
+  qattn::MxVarlen vl;
+  dim3 grid;
+};
+
+template <bool CAUSAL, bool LEN, bool PAGED, bool VARLEN, bool WINDOW, bool SHARED = false, bool TREE = false,
+          bool STEP = false, bool SOFTCAP = false>
+static int mx_split_launch(const MxSplitCall& c, void* stream) {
+  using C = qattn::MxCfg<128>;
+  const auto kernel = qattn::mxfp4_attn_split_kernel<128, CAUSAL, LEN, PAGED, VARLEN, WINDOW, SHARED, TREE, STEP, SOFTCAP>;
+  const int lds = C::NSLOT * C::SLOT + (SHARED ? qattn::MX_GROUP_LDS : 0);
+  { static qattn::LdsGrant granted_; if (!qattn::lds_grant((const void*)kernel, lds, granted_)) return 1; }
+  hipLaunchKernelGGL(kernel, c.grid, dim3(256), lds, (hipStream_t)stream, (const uint8_t*)c.q4,
+                     (const uint8_t*)c.qscale, (const uint8_t*)c.k4, (const uint8_t*)c.kscale,
+                     (const uint8_t*)c.vt, (const uint8_t*)c.vscale, (float*)c.opart, (float2*)c.ml, c.bhv,
+                     c.rows, c.sq_head, c.Sk, c.kps, c.qks, c.qoff, (const int*)c.lens, c.hps,
+                     (const int*)c.btab, c.mpp, c.lgt, c.npool, c.vl);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// What the packed entries without groups share: their argument checks and the call filled in (nwork work
+// records x kv_heads workgroups in one launch; rows, sq_head and qoff come from the records).  Returns the
+// entry's status when there is nothing to launch, -1 when `c` is to be launched.  tree: the ancestor words
+// of the tree entry, else null.
+static int mx_varlen_call(MxSplitCall& c, const void* q4, const void* qscale, const void* k4,
+                          const void* kscale, const void* vt, const void* vscale, void* opart, void* ml,
+                          const void* lens, const void* block_table, const void* seq_rec, const void* work,
+                          long nseq, long nwork, long tokens, long part_rows, long max_seqs, long kv_heads,
+                          long group, long num_pages, long page_tokens, long max_pages_per_seq, int causal,
+                          int keys_per_split, int head_dim, float qks, long window, long sinks,
+                          const void* tree) {
+  if (!mx_split_ok(head_dim, keys_per_split) || nseq < 0 || nwork < 0 || tokens < 0 || part_rows < 0) return 1;
+  if (!lens || !block_table || !seq_rec || !work) return 1;
+  const int lgt = mx_page_lgt(page_tokens);
+  if (!mx_pool_ok(num_pages, kv_heads, lgt, max_pages_per_seq)) return 1;
+  if (max_seqs < 1 || group < 1 || group > 0x7fffffffL || (causal != 0 && causal != 2)) return 1;
+  if (nseq == 0 || nwork == 0 || tokens == 0) return 0;
+  if (nseq > max_seqs || nseq > tokens || part_rows < 1) return 1;
+  // 32-bit packed rows, partial rows, workgroups and slot heads
+  if (tokens > 0x7fffffffL / (group * kv_heads) || part_rows > 0x7fffffffL) return 1;
+  if (nwork > 0x7fffffffL / kv_heads || max_seqs > 0x7fffffffL / kv_heads) return 1;
+  // a sequence holds at most 2^25 keys (mx_pool_ok): a larger window or sink count means the same, and
+  // the kernel's 32-bit edges cannot overflow
+  const long big = 1L << 26;
+  const qattn::MxVarlen vl{(const int*)work, (const int*)seq_rec, (int)nseq, (int)group, tokens * group * kv_heads,
+                    part_rows, (int)(window < big ? window : big), (int)(sinks < big ? sinks : big),
+                    nullptr, nullptr, 0, 0, (const unsigned long*)tree, tokens};
+  c = MxSplitCall{q4, qscale, k4, kscale, vt, vscale, opart, ml, (int)(max_seqs * kv_heads), 0, 1,
+                  (int)(max_pages_per_seq * page_tokens), keys_per_split, qks, 0, lens, (int)kv_heads,
+                  block_table, (int)max_pages_per_seq, lgt, (int)num_pages, vl,
+                  dim3((unsigned)(nwork * kv_heads))};
+  return -1;
+}
+
+// window 0: none (then sinks must be 0); the kernels' 32-bit edges as in mx_varlen_call
+static bool mx_step_window_ok(long window, long sinks) {
+  return window >= 0 && sinks >= 0 && (window > 0 || sinks == 0);
 }

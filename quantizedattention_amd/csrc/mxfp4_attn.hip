@@ -124,27 +124,8 @@ extern "C" int qattn_mxfp4_attn_fwd(const void* q4, const void* qscale, const vo
                                  head_dim, qks, stream);
 }
 
-// what every key-split entry asks of its head_dim and keys_per_split, and the padded ones of their rows
-static bool mx_split_ok(int head_dim, int keys_per_split) {
-  return head_dim == 128 && keys_per_split >= 64 && keys_per_split % 64 == 0;
-}
+// what the padded key-split entries ask of their rows
 static bool mx_rows_ok(long sq_head, long rows) { return sq_head >= 1 && rows % sq_head == 0; }
-
-// One call of mxfp4_attn_split_kernel: its arguments as the kernel takes them (Sk: the key stride of a
-// key/value head, which is the key count without lens) and its grid.
-struct MxSplitCall {
-  const void *q4, *qscale, *k4, *kscale, *vt, *vscale;
-  void *opart, *ml;
-  int bhv, rows, sq_head, Sk, kps;
-  float qks;
-  int qoff;
-  const void* lens;
-  int hps;
-  const void* btab;
-  int mpp, lgt, npool;
-  MxVarlen vl;
-  dim3 grid;
-};
 
 // the padded layouts' grid: (row blocks x key/value heads, splits of sk keys), false past the launch limits
 static bool mx_split_grid(MxSplitCall& c, long sk) {
@@ -153,21 +134,6 @@ static bool mx_split_grid(MxSplitCall& c, long sk) {
   if (nrb * c.bhv > 0x7fffffffL || nsplit > 65535) return false;
   c.grid = dim3((unsigned)(nrb * c.bhv), (unsigned)nsplit);
   return true;
-}
-
-template <bool CAUSAL, bool LEN, bool PAGED, bool VARLEN, bool WINDOW, bool SHARED = false, bool TREE = false,
-          bool STEP = false>
-static int mx_split_launch(const MxSplitCall& c, void* stream) {
-  using C = MxCfg<128>;
-  const auto kernel = mxfp4_attn_split_kernel<128, CAUSAL, LEN, PAGED, VARLEN, WINDOW, SHARED, TREE, STEP>;
-  const int lds = C::NSLOT * C::SLOT + (SHARED ? MX_GROUP_LDS : 0);
-  { static LdsGrant granted_; if (!lds_grant((const void*)kernel, lds, granted_)) return 1; }
-  hipLaunchKernelGGL(kernel, c.grid, dim3(256), lds, (hipStream_t)stream, (const uint8_t*)c.q4,
-                     (const uint8_t*)c.qscale, (const uint8_t*)c.k4, (const uint8_t*)c.kscale,
-                     (const uint8_t*)c.vt, (const uint8_t*)c.vscale, (float*)c.opart, (float2*)c.ml, c.bhv,
-                     c.rows, c.sq_head, c.Sk, c.kps, c.qks, c.qoff, (const int*)c.lens, c.hps,
-                     (const int*)c.btab, c.mpp, c.lgt, c.npool, c.vl);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
 // the decoding layout: bhv key/value heads, each attended by one virtual head of rows = G * sq_head
@@ -287,40 +253,6 @@ extern "C" int qattn_mxfp4_paged_append(const void* k, const void* v, const void
   return mx_append<true>(k, v, k_mean, k4, kscale, vt, vscale, vtail, lens, counts, block_table, batch,
                          kv_heads, n, max_pages_per_seq * page_tokens, max_pages_per_seq, lgt, num_pages,
                          head_dim, stream);
-}
-
-// What the packed entries without groups share: their argument checks and the call filled in (nwork work
-// records x kv_heads workgroups in one launch; rows, sq_head and qoff come from the records).  Returns the
-// entry's status when there is nothing to launch, -1 when `c` is to be launched.  tree: the ancestor words
-// of the tree entry, else null.
-static int mx_varlen_call(MxSplitCall& c, const void* q4, const void* qscale, const void* k4,
-                          const void* kscale, const void* vt, const void* vscale, void* opart, void* ml,
-                          const void* lens, const void* block_table, const void* seq_rec, const void* work,
-                          long nseq, long nwork, long tokens, long part_rows, long max_seqs, long kv_heads,
-                          long group, long num_pages, long page_tokens, long max_pages_per_seq, int causal,
-                          int keys_per_split, int head_dim, float qks, long window, long sinks,
-                          const void* tree) {
-  if (!mx_split_ok(head_dim, keys_per_split) || nseq < 0 || nwork < 0 || tokens < 0 || part_rows < 0) return 1;
-  if (!lens || !block_table || !seq_rec || !work) return 1;
-  const int lgt = mx_page_lgt(page_tokens);
-  if (!mx_pool_ok(num_pages, kv_heads, lgt, max_pages_per_seq)) return 1;
-  if (max_seqs < 1 || group < 1 || group > 0x7fffffffL || (causal != 0 && causal != 2)) return 1;
-  if (nseq == 0 || nwork == 0 || tokens == 0) return 0;
-  if (nseq > max_seqs || nseq > tokens || part_rows < 1) return 1;
-  // 32-bit packed rows, partial rows, workgroups and slot heads
-  if (tokens > 0x7fffffffL / (group * kv_heads) || part_rows > 0x7fffffffL) return 1;
-  if (nwork > 0x7fffffffL / kv_heads || max_seqs > 0x7fffffffL / kv_heads) return 1;
-  // a sequence holds at most 2^25 keys (mx_pool_ok): a larger window or sink count means the same, and
-  // the kernel's 32-bit edges cannot overflow
-  const long big = 1L << 26;
-  const MxVarlen vl{(const int*)work, (const int*)seq_rec, (int)nseq, (int)group, tokens * group * kv_heads,
-                    part_rows, (int)(window < big ? window : big), (int)(sinks < big ? sinks : big),
-                    nullptr, nullptr, 0, 0, (const unsigned long*)tree, tokens};
-  c = MxSplitCall{q4, qscale, k4, kscale, vt, vscale, opart, ml, (int)(max_seqs * kv_heads), 0, 1,
-                  (int)(max_pages_per_seq * page_tokens), keys_per_split, qks, 0, lens, (int)kv_heads,
-                  block_table, (int)max_pages_per_seq, lgt, (int)num_pages, vl,
-                  dim3((unsigned)(nwork * kv_heads))};
-  return -1;
 }
 
 // The two packed entries below.  window < 1: no window (the plain entry); else causal is 2.
@@ -713,11 +645,6 @@ __global__ __launch_bounds__(256) void mxfp4_decode_step_combine_kernel(const fl
   mx_merge_row<D>(opart, ml, token * splits * Hq + row % Hq, Hq, ns, c, out + row * D, lse + row);
 }
 }  // namespace qattn
-
-// window 0: none (then sinks must be 0); the kernels' 32-bit edges as in mx_varlen_call
-static bool mx_step_window_ok(long window, long sinks) {
-  return window >= 0 && sinks >= 0 && (window > 0 || sinks == 0);
-}
 
 // (No head_dim: the tables count 64-key tiles, splits, packed rows and partial rows, none of which depends on
 // the width of a row, so a step of either head_dim is planned by the same launch.)

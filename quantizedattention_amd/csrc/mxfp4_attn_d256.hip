@@ -90,7 +90,7 @@ struct MxRing256 {
 // mxfp4_attn_varlen64_kernel at D = 256: the work and sequence records, the row mapping, the tile range of a
 // split, the masks, the skipped tiles, the empty state and the compact partials are that kernel's, statement for
 // statement; the ring is MxRing256 and one barrier publishes one tile.
-template <bool CAUSAL, bool WINDOW, bool STEP = false>
+template <bool CAUSAL, bool WINDOW, bool STEP = false, bool SOFTCAP = false>
 __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_varlen256_kernel(
     const uint8_t* __restrict__ q4, const uint8_t* __restrict__ qs, const uint8_t* __restrict__ k4,
     const uint8_t* __restrict__ ks, const uint8_t* __restrict__ vt, const uint8_t* __restrict__ vs,
@@ -193,7 +193,8 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_varlen256_kernel(
       diag = k0 + C::KT > len;
       lim = len - 1 - k0 - 4 * h;
     }
-    mx_tile<D, true, WINDOW>(smem + (t & 3) * C::SLOT, qf, qsw, o, m, l, diag, lim, qks, lane, h, c32, lo, slim);
+    mx_tile<D, true, WINDOW, false, SOFTCAP>(smem + (t & 3) * C::SLOT, qf, qsw, o, m, l, diag, lim, qks, lane, h, c32,
+                                             lo, slim, 0, 0, vl.cap_c1, vl.cap_c);
   }
   vmcnt_wait_all();
   __syncthreads();
@@ -247,12 +248,12 @@ __global__ __launch_bounds__(256) void mxfp4_decode_step_combine256_kernel(
                         SINK ? sink[row % Hq] : 0.f);
 }
 
-template <bool CAUSAL, bool WINDOW, bool STEP>
+template <bool CAUSAL, bool WINDOW, bool STEP, bool SOFTCAP>
 static int mx256_launch(const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
                         const void* vscale, void* opart, void* ml, int bhv, int Sk, int kps, float qks,
                         const void* lens, int hps, const void* btab, int mpp, int lgt, int npool,
                         const MxVarlen& vl, unsigned grid, void* stream) {
-  const auto kernel = mxfp4_attn_varlen256_kernel<CAUSAL, WINDOW, STEP>;
+  const auto kernel = mxfp4_attn_varlen256_kernel<CAUSAL, WINDOW, STEP, SOFTCAP>;
   const int lds = MxCfg<256>::NSLOT * MxCfg<256>::SLOT;
   { static LdsGrant granted_; if (!lds_grant((const void*)kernel, lds, granted_)) return 1; }
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, (const uint8_t*)q4,
@@ -263,14 +264,14 @@ static int mx256_launch(const void* q4, const void* qscale, const void* k4, cons
 }
 
 // the checks of mx64_packed (mxfp4_attn_d64.hip) and its dispatch, at head_dim 256; STEP: the fixed grid of the
-// decode step (causal)
-template <bool STEP>
+// decode step (causal); SOFTCAP: the capped tile body with its two constants
+template <bool STEP, bool SOFTCAP = false>
 static int mx256_packed(const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
                         const void* vscale, void* opart, void* ml, const void* lens, const void* block_table,
                         const void* seq_rec, const void* work, long nseq, long nwork, long tokens, long part_rows,
                         long max_seqs, long kv_heads, long group, long num_pages, long page_tokens,
                         long max_pages_per_seq, int causal, int keys_per_split, float qks, long window, long sinks,
-                        void* stream) {
+                        void* stream, float cap_c1 = 0.f, float cap_c = 0.f) {
   if (keys_per_split < 64 || keys_per_split % 64 != 0) return 1;
   if (nseq < 0 || nwork < 0 || tokens < 0 || part_rows < 0) return 1;
   if (!lens || !block_table || !seq_rec || !work) return 1;
@@ -284,15 +285,15 @@ static int mx256_packed(const void* q4, const void* qscale, const void* k4, cons
   const long big = 1L << 26;
   const MxVarlen vl{(const int*)work, (const int*)seq_rec, (int)nseq, (int)group, tokens * group * kv_heads,
                     part_rows, (int)(window < big ? window : big), (int)(sinks < big ? sinks : big),
-                    nullptr, nullptr, 0, 0, nullptr, tokens};
+                    nullptr, nullptr, 0, 0, nullptr, tokens, cap_c1, cap_c};
   const int bhv = (int)(max_seqs * kv_heads), Sk = (int)(max_pages_per_seq * page_tokens);
   const unsigned grid = (unsigned)(nwork * kv_heads);
 #define QA_MX256_ARGS q4, qscale, k4, kscale, vt, vscale, opart, ml, bhv, Sk, keys_per_split, qks, lens, \
                       (int)kv_heads, block_table, (int)max_pages_per_seq, lgt, (int)num_pages, vl, grid, stream
-  if (window >= 1) return mx256_launch<true, true, STEP>(QA_MX256_ARGS);
-  if constexpr (STEP) return mx256_launch<true, false, true>(QA_MX256_ARGS);
-  else if (causal) return mx256_launch<true, false, false>(QA_MX256_ARGS);
-  else return mx256_launch<false, false, false>(QA_MX256_ARGS);
+  if (window >= 1) return mx256_launch<true, true, STEP, SOFTCAP>(QA_MX256_ARGS);
+  if constexpr (STEP) return mx256_launch<true, false, true, SOFTCAP>(QA_MX256_ARGS);
+  else if (causal) return mx256_launch<true, false, false, SOFTCAP>(QA_MX256_ARGS);
+  else return mx256_launch<false, false, false, SOFTCAP>(QA_MX256_ARGS);
 #undef QA_MX256_ARGS
 }
 
@@ -415,6 +416,19 @@ int mx256_step_combine(const void* opart, const void* ml, void* out, void* lse, 
                      (const float*)opart, (const float2*)ml, (_Float16*)out, (float*)lse, (const int*)seq_rec,
                      (const float*)sink, rows, (int)q_heads, (int)splits);
   return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// mx64_softcap (mxfp4_attn_d64.hip) at head_dim 256; it stands last, as its kernels are emitted behind every older one
+int mx256_softcap(bool step, const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
+                  const void* vscale, void* opart, void* ml, const void* lens, const void* block_table,
+                  const void* seq_rec, const void* work, long nseq, long nwork, long tokens, long part_rows,
+                  long max_seqs, long kv_heads, long group, long num_pages, long page_tokens, long max_pages_per_seq,
+                  int causal, int keys_per_split, long window, long sinks, float cap_c1, float cap_c, void* stream) {
+#define QA_MX256_CAP q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work, nseq, nwork, \
+                     tokens, part_rows, max_seqs, kv_heads, group, num_pages, page_tokens, max_pages_per_seq,      \
+                     causal, keys_per_split, 0.f, window, sinks, stream, cap_c1, cap_c
+  return step ? mx256_packed<true, true>(QA_MX256_CAP) : mx256_packed<false, true>(QA_MX256_CAP);
+#undef QA_MX256_CAP
 }
 
 }  // namespace qattn

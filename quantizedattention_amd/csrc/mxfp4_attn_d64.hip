@@ -118,7 +118,7 @@ struct MxRing64 {
 // sequence records, the row mapping, the tile range of a split, the masks, the skipped tiles, the empty state
 // and the compact partials are that kernel's, statement for statement; the ring is MxRing64<TPS>, and one
 // barrier publishes TPS tiles, which the wave runs through mx_tile<64> one after the other.
-template <bool CAUSAL, bool WINDOW, int TPS, bool STEP = false>
+template <bool CAUSAL, bool WINDOW, int TPS, bool STEP = false, bool SOFTCAP = false>
 __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_varlen64_kernel(
     const uint8_t* __restrict__ q4, const uint8_t* __restrict__ qs, const uint8_t* __restrict__ k4,
     const uint8_t* __restrict__ ks, const uint8_t* __restrict__ vt, const uint8_t* __restrict__ vs,
@@ -217,7 +217,8 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_varlen64_kernel(
       diag = k0 + C::KT > len;
       lim = len - 1 - k0 - 4 * h;
     }
-    mx_tile<D, true, WINDOW>(sl, qf, qsw, o, m, l, diag, lim, qks, lane, h, c32, lo, slim);
+    mx_tile<D, true, WINDOW, false, SOFTCAP>(sl, qf, qsw, o, m, l, diag, lim, qks, lane, h, c32, lo, slim, 0, 0,
+                                             vl.cap_c1, vl.cap_c);
   };
 
   vmem_drain();
@@ -260,12 +261,12 @@ __global__ __launch_bounds__(256) void mxfp4_varlen_combine_sink_kernel(
   mx_merge_row<D, true>(opart, ml, first, step, nsplit, (int)(gid % TPR), out + row * D, lse + row, sink[head]);
 }
 
-template <bool CAUSAL, bool WINDOW, int TPS, bool STEP>
+template <bool CAUSAL, bool WINDOW, int TPS, bool STEP, bool SOFTCAP>
 static int mx64_launch_tps(const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
                        const void* vscale, void* opart, void* ml, int bhv, int Sk, int kps, float qks,
                        const void* lens, int hps, const void* btab, int mpp, int lgt, int npool, const MxVarlen& vl,
                        unsigned grid, void* stream) {
-  const auto kernel = mxfp4_attn_varlen64_kernel<CAUSAL, WINDOW, TPS, STEP>;
+  const auto kernel = mxfp4_attn_varlen64_kernel<CAUSAL, WINDOW, TPS, STEP, SOFTCAP>;
   const int lds = MxCfg<64>::NSLOT * MxRing64<TPS>::SLOT;
   { static LdsGrant granted_; if (!lds_grant((const void*)kernel, lds, granted_)) return 1; }
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, (const uint8_t*)q4,
@@ -281,21 +282,21 @@ static int mx64_tps() {
   return e && (e[0] == '1' || e[0] == '2') && !e[1] ? e[0] - '0' : QA_MX64_TPS;
 }
 
-template <bool CAUSAL, bool WINDOW, bool STEP, class... A>
+template <bool CAUSAL, bool WINDOW, bool STEP, bool SOFTCAP, class... A>
 static int mx64_launch(A... a) {
-  return mx64_tps() == 2 ? mx64_launch_tps<CAUSAL, WINDOW, 2, STEP>(a...)
-                         : mx64_launch_tps<CAUSAL, WINDOW, 1, STEP>(a...);
+  return mx64_tps() == 2 ? mx64_launch_tps<CAUSAL, WINDOW, 2, STEP, SOFTCAP>(a...)
+                         : mx64_launch_tps<CAUSAL, WINDOW, 1, STEP, SOFTCAP>(a...);
 }
 
 // the checks of mx_varlen_call (mxfp4_attn.hip) and the dispatch of mx_varlen_paged, at head_dim 64; STEP: the
-// fixed grid of the decode step (causal)
-template <bool STEP>
+// fixed grid of the decode step (causal); SOFTCAP: the capped tile body with its two constants
+template <bool STEP, bool SOFTCAP = false>
 static int mx64_packed(const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
                        const void* vscale, void* opart, void* ml, const void* lens, const void* block_table,
                        const void* seq_rec, const void* work, long nseq, long nwork, long tokens, long part_rows,
                        long max_seqs, long kv_heads, long group, long num_pages, long page_tokens,
                        long max_pages_per_seq, int causal, int keys_per_split, float qks, long window, long sinks,
-                       void* stream) {
+                       void* stream, float cap_c1 = 0.f, float cap_c = 0.f) {
   if (keys_per_split < 64 || keys_per_split % 64 != 0) return 1;
   if (nseq < 0 || nwork < 0 || tokens < 0 || part_rows < 0) return 1;
   if (!lens || !block_table || !seq_rec || !work) return 1;
@@ -309,15 +310,15 @@ static int mx64_packed(const void* q4, const void* qscale, const void* k4, const
   const long big = 1L << 26;
   const MxVarlen vl{(const int*)work, (const int*)seq_rec, (int)nseq, (int)group, tokens * group * kv_heads,
                     part_rows, (int)(window < big ? window : big), (int)(sinks < big ? sinks : big),
-                    nullptr, nullptr, 0, 0, nullptr, tokens};
+                    nullptr, nullptr, 0, 0, nullptr, tokens, cap_c1, cap_c};
   const int bhv = (int)(max_seqs * kv_heads), Sk = (int)(max_pages_per_seq * page_tokens);
   const unsigned grid = (unsigned)(nwork * kv_heads);
 #define QA_MX64_ARGS q4, qscale, k4, kscale, vt, vscale, opart, ml, bhv, Sk, keys_per_split, qks, lens, \
                      (int)kv_heads, block_table, (int)max_pages_per_seq, lgt, (int)num_pages, vl, grid, stream
-  if (window >= 1) return mx64_launch<true, true, STEP>(QA_MX64_ARGS);
-  if constexpr (STEP) return mx64_launch<true, false, true>(QA_MX64_ARGS);
-  else if (causal) return mx64_launch<true, false, false>(QA_MX64_ARGS);
-  else return mx64_launch<false, false, false>(QA_MX64_ARGS);
+  if (window >= 1) return mx64_launch<true, true, STEP, SOFTCAP>(QA_MX64_ARGS);
+  if constexpr (STEP) return mx64_launch<true, false, true, SOFTCAP>(QA_MX64_ARGS);
+  else if (causal) return mx64_launch<true, false, false, SOFTCAP>(QA_MX64_ARGS);
+  else return mx64_launch<false, false, false, SOFTCAP>(QA_MX64_ARGS);
 #undef QA_MX64_ARGS
 }
 
@@ -433,6 +434,21 @@ int mx_varlen_combine_ext(const void* opart, const void* ml, void* out, void* ls
     mx_combine_ext_launch<128>(opart, ml, out, lse, seq_rec, sink_logit, nseq, tokens * q_heads, q_heads,
                                kv_heads, part_rows, stream);
   return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// The capped packed call (step false: the arguments of mx64_varlen_paged) and the capped decode step (step true:
+// those that mx64_decode_step hands to mx64_packed) at head_dim 64, for the entries of mxfp4_attn_softcap.hip.  It
+// stands last: its kernels are emitted behind every older one.
+int mx64_softcap(bool step, const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
+                 const void* vscale, void* opart, void* ml, const void* lens, const void* block_table,
+                 const void* seq_rec, const void* work, long nseq, long nwork, long tokens, long part_rows,
+                 long max_seqs, long kv_heads, long group, long num_pages, long page_tokens, long max_pages_per_seq,
+                 int causal, int keys_per_split, long window, long sinks, float cap_c1, float cap_c, void* stream) {
+#define QA_MX64_CAP q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work, nseq, nwork, \
+                    tokens, part_rows, max_seqs, kv_heads, group, num_pages, page_tokens, max_pages_per_seq,      \
+                    causal, keys_per_split, 0.f, window, sinks, stream, cap_c1, cap_c
+  return step ? mx64_packed<true, true>(QA_MX64_CAP) : mx64_packed<false, true>(QA_MX64_CAP);
+#undef QA_MX64_CAP
 }
 
 }  // namespace qattn

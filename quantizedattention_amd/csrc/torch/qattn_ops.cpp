@@ -47,8 +47,11 @@
 //   mxfp4_decode_step_plan(slots, lens, capacity, kv_heads, group, keys_per_split, splits, window, sinks)
 //       -> (seq_tab, tiles, pos, seq_rec): kv_cache_mxfp4.DecodeStep's tables, derived on the device
 //   mxfp4_decode_step(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, splits, keys_per_split, window,
-//       sinks, sink_logit=None) -> (O, lse): kv_cache_mxfp4.DecodeStep.attend over its fixed grid, head_dim 128
-//       or 64 (q's), with the learned sink logit f32 [Hq] when one is given
+//       sinks, sink_logit=None, softcap=0, qks=0) -> (O, lse): kv_cache_mxfp4.DecodeStep.attend over its fixed
+//       grid, head_dim 128 or 64 (q's), with the learned sink logit f32 [Hq] when one is given; softcap > 0: the
+//       logit cap of DecodeStep(softcap=), qks > 0: scale * log2(e) of DecodeStep(scale=)
+//   mxfp4_varlen_paged_softcap(.. the arguments of mxfp4_varlen_paged_window, window 0: none .., softcap, qks)
+//       -> (O, lse): attention_mxfp4_varlen_paged(softcap=, scale=), the tanh cap inside the kernel
 //   mxfp4_verify_step_plan(slots, lens, tree, draft_tokens, capacity, kv_heads, group, keys_per_split, splits)
 //       -> (seq_tab, tiles, pos, seq_rec): kv_cache_mxfp4.VerifyStep's tables, derived on the device
 //   mxfp4_verify_step(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, tree, draft_tokens, splits,
@@ -632,7 +635,8 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged_run(const Tensor& q_in, const Tens
                                                   int64_t sinks, const Tensor* grp_rec = nullptr,
                                                   const Tensor* members = nullptr,
                                                   const Tensor* tree = nullptr,
-                                                  const RopeArgs* rope = nullptr) {
+                                                  const RopeArgs* rope = nullptr, double softcap = 0.,
+                                                  double qks_in = 0.) {
   require_gpu({&q_in, &k4, &ks, &vt, &vs, &lens, &block_table, &seq_rec, &work});
   if (rope) check_rope(*rope, q_in.dim() == 3 ? q_in.size(0) : -1, q_in.dim() == 3 ? q_in.size(2) : 128);
   if (tree) {   // the tree entry's ancestor words, one per packed token
@@ -692,30 +696,38 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged_run(const Tensor& q_in, const Tens
     call(qattn_mxfp4_quant_rows(P(q), nullptr, P(q4), P(qs), T * Hq, Hq, (int)D, c.stream), "quantise q");
   }
   Tensor opart = empty({part_rows, D}, at::kFloat, q), ml = empty({part_rows, 2}, at::kFloat, q);
-  if (grp_rec)
+  const float qks = qks_in > 0. ? (float)qks_in : qk_scale(D);
+  if (softcap > 0.)
+    call(qattn_mxfp4_attn_fwd_varlen_paged_softcap(
+             P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens), P(block_table), P(seq_rec),
+             P(work), seq_rec.size(0), work.size(0), T, part_rows, B, Hkv, Hq / Hkv, NP, PT, mpp, causal ? 2 : 0,
+             (int)keys_per_split, (int)D, qks, windowed ? (long)window : 0L, windowed ? (long)sinks : 0L,
+             (float)softcap, c.stream),
+         "mxfp4 soft-capped varlen forward");
+  else if (grp_rec)
     call(qattn_mxfp4_attn_fwd_varlen_paged_shared(
              P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens), P(block_table), P(seq_rec),
              P(work), seq_rec.size(0), work.size(0), T, part_rows, B, Hkv, Hq / Hkv, NP, PT, mpp, causal ? 2 : 0,
-             (int)keys_per_split, (int)D, qk_scale(D), P(*grp_rec), P(*members), grp_rec->size(0),
+             (int)keys_per_split, (int)D, qks, P(*grp_rec), P(*members), grp_rec->size(0),
              members->size(0), c.stream),
          "mxfp4 shared-prefix varlen forward");
   else if (tree)
     call(qattn_mxfp4_attn_fwd_varlen_paged_tree(
              P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens), P(block_table), P(seq_rec),
              P(work), seq_rec.size(0), work.size(0), T, part_rows, B, Hkv, Hq / Hkv, NP, PT, mpp, causal ? 2 : 0,
-             (int)keys_per_split, (int)D, qk_scale(D), P(*tree), c.stream),
+             (int)keys_per_split, (int)D, qks, P(*tree), c.stream),
          "mxfp4 tree-masked varlen forward");
   else if (windowed)
     call(qattn_mxfp4_attn_fwd_varlen_paged_window(
              P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens), P(block_table), P(seq_rec),
              P(work), seq_rec.size(0), work.size(0), T, part_rows, B, Hkv, Hq / Hkv, NP, PT, mpp, causal ? 2 : 0,
-             (int)keys_per_split, (int)D, qk_scale(D), (long)window, (long)sinks, c.stream),
+             (int)keys_per_split, (int)D, qks, (long)window, (long)sinks, c.stream),
          "mxfp4 windowed varlen forward");
   else
     call(qattn_mxfp4_attn_fwd_varlen_paged(P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens),
                                            P(block_table), P(seq_rec), P(work), seq_rec.size(0), work.size(0),
                                            T, part_rows, B, Hkv, Hq / Hkv, NP, PT, mpp, causal ? 2 : 0,
-                                           (int)keys_per_split, (int)D, qk_scale(D), c.stream),
+                                           (int)keys_per_split, (int)D, qks, c.stream),
          "mxfp4 varlen forward");
   call(qattn_mxfp4_varlen_combine(P(opart), P(ml), P(out), P(lse), P(seq_rec), seq_rec.size(0), T, Hq, Hkv,
                                   part_rows, (int)D, c.stream),
@@ -783,6 +795,25 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged_tree(const Tensor& q, const Tensor
                                 keys_per_split, false, 0, 0, nullptr, nullptr, &tree_masks);
 }
 
+// the plain (window 0) or the windowed call with a softmax scale and a logit cap (kv_cache_mxfp4.
+// attention_mxfp4_varlen_paged(softcap=, scale=)): qks = scale * log2(e) as the Python call rounds it to fp32 (0:
+// 1 / sqrt(D)), softcap in natural-log units (0: none, the uncapped entries at that qks)
+std::tuple<Tensor, Tensor> mxfp4_varlen_paged_softcap(const Tensor& q, const Tensor& k4, const Tensor& ks,
+                                                      const Tensor& vt, const Tensor& vs, const Tensor& lens,
+                                                      const Tensor& block_table, const Tensor& seq_rec,
+                                                      const Tensor& work, int64_t part_rows, int64_t causal,
+                                                      int64_t keys_per_split, int64_t window, int64_t sinks,
+                                                      double softcap, double qks) {
+  TORCH_CHECK(window >= 0 && sinks >= 0 && (window > 0 || sinks == 0) && (window == 0 || causal == 1),
+              "qattn mxfp4 paged cache: window >= 0 (0: none), sinks >= 0 only with a window, a window only with "
+              "causal 1");
+  TORCH_CHECK(std::isfinite(softcap) && softcap >= 0. && std::isfinite(qks) && qks >= 0.,
+              "qattn mxfp4 paged cache: softcap and qks must be finite and >= 0 (0: no cap, the default scale)");
+  return mxfp4_varlen_paged_run(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal,
+                                keys_per_split, window > 0, window, sinks, nullptr, nullptr, nullptr, nullptr,
+                                softcap, qks);
+}
+
 // kv_cache_mxfp4.DecodeStep's plan as an operator: from slots i32 [n] and the pool's lens i32 [B] (the lengths
 // BEFORE the step's append) the four device tables of qattn_mxfp4_decode_step_plan, seq_tab i32 [n, 4], tiles
 // i32 [n, 2], pos i32 [n] and seq_rec i32 [n, 8].  Nothing is read back; window 0: none.
@@ -815,7 +846,8 @@ std::tuple<Tensor, Tensor> mxfp4_decode_step(const Tensor& q_in, const Tensor& k
                                              const Tensor& vt, const Tensor& vs, const Tensor& lens,
                                              const Tensor& block_table, const Tensor& seq_rec, const Tensor& work,
                                              int64_t splits, int64_t keys_per_split, int64_t window,
-                                             int64_t sinks, const c10::optional<Tensor>& sink_logit) {
+                                             int64_t sinks, const c10::optional<Tensor>& sink_logit,
+                                             double softcap, double qks_in) {
   require_gpu({&q_in, &k4, &ks, &vt, &vs, &lens, &block_table, &seq_rec, &work});
   TORCH_CHECK(q_in.dim() == 3 && k4.dim() == 4 && mx_packed_dim(q_in.size(2)) && k4.size(3) * 2 == q_in.size(2),
               "qattn mxfp4 decode step: q must be [n, Hq, D], D = 128, 64 or 256, the pool's head_dim");
@@ -853,10 +885,20 @@ std::tuple<Tensor, Tensor> mxfp4_decode_step(const Tensor& q_in, const Tensor& k
   Tensor out = empty({n, Hq, D}, at::kHalf, q), lse = empty({n, Hq}, at::kFloat, q);
   Tensor opart = empty({n * splits * Hq, D}, at::kFloat, q), ml = empty({n * splits * Hq, 2}, at::kFloat, q);
   call(qattn_mxfp4_quant_rows(P(q), nullptr, P(q4), P(qs), n * Hq, Hq, (int)D, c.stream), "quantise q");
-  call(qattn_mxfp4_attn_fwd_decode_step(P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens),
-                                        P(block_table), P(seq_rec), P(work), n, splits, B, Hkv, Hq / Hkv, NP, PT,
-                                        mpp, (int)keys_per_split, (int)D, qk_scale(D), window, sinks, c.stream),
-       "mxfp4 decode step forward");
+  TORCH_CHECK(std::isfinite(softcap) && softcap >= 0. && std::isfinite(qks_in) && qks_in >= 0.,
+              "qattn mxfp4 decode step: softcap and qks must be finite and >= 0 (0: no cap, the default scale)");
+  const float qks = qks_in > 0. ? (float)qks_in : qk_scale(D);
+  if (softcap > 0.)
+    call(qattn_mxfp4_attn_fwd_decode_step_softcap(P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens),
+                                                  P(block_table), P(seq_rec), P(work), n, splits, B, Hkv, Hq / Hkv,
+                                                  NP, PT, mpp, (int)keys_per_split, (int)D, qks, window, sinks,
+                                                  (float)softcap, c.stream),
+         "mxfp4 soft-capped decode step forward");
+  else
+    call(qattn_mxfp4_attn_fwd_decode_step(P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens),
+                                          P(block_table), P(seq_rec), P(work), n, splits, B, Hkv, Hq / Hkv, NP, PT,
+                                          mpp, (int)keys_per_split, (int)D, qks, window, sinks, c.stream),
+         "mxfp4 decode step forward");
   if (sink.defined())
     call(qattn_mxfp4_decode_step_combine_sink(P(opart), P(ml), P(out), P(lse), P(seq_rec), P(sink), n, splits, Hq,
                                               Hkv, (int)D, c.stream),
@@ -990,7 +1032,10 @@ TORCH_LIBRARY(qattn, m) {
         "int keys_per_split, int splits, int window, int sinks) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("mxfp4_decode_step(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, Tensor block_table, "
         "Tensor seq_rec, Tensor work, int splits, int keys_per_split, int window, int sinks, "
-        "Tensor? sink_logit=None) -> (Tensor, Tensor)");
+        "Tensor? sink_logit=None, float softcap=0., float qks=0.) -> (Tensor, Tensor)");
+  m.def("mxfp4_varlen_paged_softcap(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, "
+        "Tensor block_table, Tensor seq_rec, Tensor work, int part_rows, int causal, int keys_per_split, "
+        "int window, int sinks, float softcap, float qks) -> (Tensor, Tensor)");
   m.def("mxfp4_verify_step_plan(Tensor slots, Tensor lens, Tensor tree, int draft_tokens, int capacity, "
         "int kv_heads, int group, int keys_per_split, int splits) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("mxfp4_verify_step(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, Tensor block_table, "
@@ -1016,6 +1061,7 @@ TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
   m.impl("mxfp4_varlen_paged_tree", &mxfp4_varlen_paged_tree);
   m.impl("mxfp4_quant_rows_rope", &mxfp4_quant_rows_rope);
   m.impl("mxfp4_varlen_paged_rope", &mxfp4_varlen_paged_rope);
+  m.impl("mxfp4_varlen_paged_softcap", &mxfp4_varlen_paged_softcap);
   m.impl("mxfp4_decode_step_plan", &mxfp4_decode_step_plan);
   m.impl("mxfp4_decode_step", &mxfp4_decode_step);
   m.impl("mxfp4_verify_step_plan", &mxfp4_verify_step_plan);

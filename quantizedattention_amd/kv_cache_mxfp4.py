@@ -195,8 +195,10 @@ keeps the keys <= Sk - Sq + i), Sq <= Sk.
 """
 from __future__ import annotations
 
+import ctypes
 import itertools
 import json
+import math
 from dataclasses import dataclass
 from typing import Optional
 
@@ -1643,6 +1645,28 @@ def _check_trimmed(cache: "PagedKVFP4", ids, sq, W, S) -> None:
                                   "window or fewer sinks)")
 
 
+_QKS = {D: _qk_scale(D) for D in (64, 128, 256)}   # the default qks of every pool width, made at import
+
+
+def _softcap_args(softcap, scale, head_dim: int, grouped: bool = False):
+    """``softcap`` and ``scale`` of a call, checked -> (the cap as a float or None, qks = scale * log2(e) in fp32,
+    ``scale`` None: 1 / sqrt(head_dim)).  Each must be a finite number > 0, in fp32 too; ``grouped``: the call has
+    ``tree=`` or ``share_prefix=True``, whose kernels have no capped form.  Every refusal names its argument."""
+    for name, x in (("softcap", softcap), ("scale", scale)):
+        if x is None:
+            continue
+        ok = isinstance(x, (int, float)) and not isinstance(x, bool) and math.isfinite(x) and x > 0
+        if not ok or not 0.0 < ctypes.c_float(float(x)).value < math.inf:
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: {name} must be a finite float > 0, got {x!r}")
+    if softcap is not None and grouped:
+        raise _lib.QAttnError("qattn mxfp4 paged cache: softcap cannot be combined with tree or share_prefix "
+                              "(their kernels have no capped form; scale= alone works there)")
+    qks = _QKS[head_dim] if scale is None else _qk_scale(head_dim, scale)
+    if not 0.0 < qks < math.inf:
+        raise _lib.QAttnError(f"qattn mxfp4 paged cache: scale must be a finite float > 0, got {scale!r}")
+    return (None if softcap is None else float(softcap)), qks
+
+
 def _tree_args(tree, sq, causal: bool, window, share_prefix: bool):
     """``tree`` of a packed call over sequences of ``sq`` queries, checked -> (tree lengths, the int64
     ancestor word of every packed token as a host int32 tensor [2 T], low half first), or None when no
@@ -1691,7 +1715,8 @@ def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_
                                  keys_per_split: Optional[int] = None, window: Optional[int] = None,
                                  sinks: int = 0, share_prefix: bool = False, tree=None,
                                  rope: Optional[Rope] = None, positions=None,
-                                 sink_logit: Optional[torch.Tensor] = None):
+                                 sink_logit: Optional[torch.Tensor] = None, softcap: Optional[float] = None,
+                                 scale: Optional[float] = None):
     """A ragged batch against a paged cache in one attention launch and one merge: packed fp16 queries
     ``q`` [T, Hq, D], token-major, the ``q_lens[0]`` tokens of sequence ``seq_ids[0]`` first, then
     those of ``seq_ids[1]``, ... (nseq >= 1 distinct slots, every q_lens[j] >= 1, T = sum(q_lens)) ->
@@ -1752,7 +1777,18 @@ def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_
     csrc/mxfp4_attn_d64.hip: non-causal, causal and windowed calls, ``rope`` (a table of width 64) and
     ``sink_logit``; ``share_prefix=True`` and ``tree`` raise :class:`HeadDimError` there.  A pool of head_dim 256
     takes q [T, Hq, 256] and serves the same calls through csrc/mxfp4_attn_d256.hip (``rope``: a table of width
-    256, NeoX pairs (i, i + 128))."""
+    256, NeoX pairs (i, i + 128)).
+
+    ``scale`` (a finite float > 0; None: 1 / sqrt(D), today's launches and bytes) is the softmax scale: the logit
+    of a visible key is ``scale * s``, s = deq(q) . deq(k).  It is the kernels' runtime ``qks`` and works in every
+    mode.  ``softcap`` (a finite float > 0; None: none) caps the logit to ``softcap * tanh(scale * s / softcap)``,
+    as Gemma-2 (50, at head_dim 256 and, with ``scale = 1 / sqrt(144)``, at 128) and Grok-1 layers do.  The tanh
+    stands inside the kernel, between Q.K^T and the online softmax (``qattn_mxfp4_attn_fwd_varlen_paged_softcap``,
+    mx_tile SOFTCAP); masked keys keep P = 0 exactly, ``lse`` is over the capped logits (and the sink's), and plan,
+    splits and merge do not change.  It works in non-causal, causal and ``window=`` / ``sinks=`` calls at head_dim
+    64, 128 and 256, with ``rope=``, ``keys_per_split=`` and ``sink_logit=``; with ``tree=`` or
+    ``share_prefix=True`` it raises.  A bad ``softcap`` or ``scale`` raises :class:`QAttnError` naming the
+    argument before any tensor is made."""
     if not isinstance(cache, PagedKVFP4):
         raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PagedKVFP4")
     _, Hkv, _, D = cache.shape
@@ -1761,6 +1797,7 @@ def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_
     T, Hq = q.shape[0], q.shape[1]
     if Hq == 0 or Hq % Hkv:
         raise _lib.QAttnError("qattn mxfp4 paged cache: q must have G * Hkv heads for the cache's Hkv")
+    cap, qks = _softcap_args(softcap, scale, D, share_prefix or tree is not None)
     if share_prefix or tree is not None:
         cache._need128("share_prefix=True" if share_prefix else "tree=")
         if sink_logit is not None:
@@ -1809,8 +1846,11 @@ def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_
             _lib.ptr(cache.ks), _lib.ptr(cache.vt), _lib.ptr(cache.vs), _lib.ptr(opart), _lib.ptr(ml),
             _lib.ptr(cache.lens), _lib.ptr(cache.block_table), _lib.ptr(rec_d), _lib.ptr(work_d), len(ids),
             len(work), T, part_rows, cache.alloc.max_seqs, Hkv, Hq // Hkv, cache.num_pages,
-            cache.page_tokens, cache.alloc.max_pages_per_seq, 2 if causal else 0, kps, D, _qk_scale(D))
-    if shared is not None:
+            cache.page_tokens, cache.alloc.max_pages_per_seq, 2 if causal else 0, kps, D, qks)
+    if cap is not None:   # (no sequence holds 2^25 keys or more: a larger window or sink count means the same)
+        _lib.call("qattn_mxfp4_attn_fwd_varlen_paged_softcap", *args, min(W or 0, 1 << 26), min(S, 1 << 26), cap,
+                  st)
+    elif shared is not None:
         _lib.call("qattn_mxfp4_attn_fwd_varlen_paged_shared", *args, _lib.ptr(grp_d),
                   _lib.ptr(grp_d[4 * len(grp_rec):]), len(grp_rec), len(members), st)
     elif trees is not None:
@@ -1919,14 +1959,16 @@ class DecodeStep:
     ``keys_per_split``, or ``qattn_split_keys(kv_heads * N, 1, ceil64(max_keys), 64)``; ``splits`` =
     :func:`decode_step_splits`, so the attention grid is N * splits * kv_heads workgroups whatever the lengths
     are.  ``window`` / ``sinks`` as in :func:`attention_mxfp4_varlen_paged`; under a window ``splits`` does not
-    grow with ``max_keys``.
+    grow with ``max_keys``.  ``softcap`` / ``scale`` (keyword-only) as there too: both are fixed here, so a
+    captured graph stays valid, and ``attend`` then runs ``qattn_mxfp4_attn_fwd_decode_step_softcap`` (``scale``
+    alone: the uncapped entry with its ``qks``); ``kps`` and ``splits`` do not depend on them.
 
     ``prepare`` is the host's part, before every step or replay: the checks, the pages, ``slots``.  ``append``
     derives the step's tables from the device lengths (``qattn_mxfp4_decode_step_plan``) and appends;
     ``attend`` quantises ``q`` and runs the fixed grid (``qattn_mxfp4_attn_fwd_decode_step``), whose surplus
     workgroups exit, and the merge (``qattn_mxfp4_decode_step_combine``).  Every listed entry gets, bit for bit,
     what ``append_packed(k, v, ids, [1] * n)`` followed by ``attention_mxfp4_varlen_paged(q, cache, ids, [1] * n,
-    causal=True, keys_per_split=step.kps[, window, sinks][, rope][, sink_logit])`` gives.  One step object serves
+    causal=True, keys_per_split=step.kps[, window, sinks][, rope][, sink_logit][, softcap, scale])`` gives.  One step object serves
     any number of pools of its head dim, layer after layer, on one stream: each pool's ``append`` rewrites the
     tables from that pool's own ``lens``.  At head_dim 64 the attention is the pair ring of
     csrc/mxfp4_attn_d64.hip over the same fixed grid, at 256 the ring of csrc/mxfp4_attn_d256.hip; a pool of another head dim raises :class:`HeadDimError`
@@ -1936,11 +1978,12 @@ class DecodeStep:
 
     def __init__(self, max_batch: int, max_keys: int, q_heads: int, kv_heads: int, device,
                  keys_per_split: Optional[int] = None, window: Optional[int] = None, sinks: int = 0, *,
-                 head_dim: int = 128):
+                 head_dim: int = 128, softcap: Optional[float] = None, scale: Optional[float] = None):
         N, max_keys, Hq, Hkv = int(max_batch), int(max_keys), int(q_heads), int(kv_heads)
         if head_dim not in (64, 128, 256):
             raise HeadDimError(f"qattn mxfp4 decode step: head_dim must be 128, 64 or 256, got {head_dim}")
         D = self.head_dim = int(head_dim)
+        self.softcap, self.qks = _softcap_args(softcap, scale, D)
         self.window, self.sinks = _window_args(window, sinks)
         if N < 1 or Hkv < 1 or Hq < 1 or Hq % Hkv or not 1 <= max_keys <= 1 << 25:
             raise _lib.QAttnError("qattn mxfp4 decode step: max_batch >= 1, q_heads = G * kv_heads and max_keys in "
@@ -2095,11 +2138,13 @@ class DecodeStep:
         else:
             _lib.call("qattn_mxfp4_quant_rows_rope", _lib.ptr(q), _lib.ptr(self.q4), _lib.ptr(self.qs),
                       _lib.ptr(rope.table), _lib.ptr(self.pos), N, Hq, rope.max_pos, int(rope.interleaved), D, st)
-        _lib.call("qattn_mxfp4_attn_fwd_decode_step", _lib.ptr(self.q4), _lib.ptr(self.qs), _lib.ptr(cache.k4),
+        entry = "qattn_mxfp4_attn_fwd_decode_step" + ("" if self.softcap is None else "_softcap")
+        _lib.call(entry, _lib.ptr(self.q4), _lib.ptr(self.qs), _lib.ptr(cache.k4),
                   _lib.ptr(cache.ks), _lib.ptr(cache.vt), _lib.ptr(cache.vs), _lib.ptr(self.opart),
                   _lib.ptr(self.ml), _lib.ptr(cache.lens), _lib.ptr(cache.block_table), _lib.ptr(self.seq_rec),
                   _lib.ptr(self.work), N, self.splits, a.max_seqs, H, Hq // H, a.num_pages, a.page_tokens,
-                  a.max_pages_per_seq, self.kps, D, _qk_scale(D), self.window or 0, self.sinks, st)
+                  a.max_pages_per_seq, self.kps, D, self.qks, self.window or 0, self.sinks,
+                  *(() if self.softcap is None else (self.softcap,)), st)
         if sink_logit is None:
             _lib.call("qattn_mxfp4_decode_step_combine", _lib.ptr(self.opart), _lib.ptr(self.ml), _lib.ptr(self.O),
                       _lib.ptr(self.lse), _lib.ptr(self.seq_rec), N, self.splits, Hq, H, D, st)

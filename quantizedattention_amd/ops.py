@@ -34,7 +34,10 @@ the autograd rules of ``int8_fwd`` and ``bf16_fwd`` (their backward operators).
     torch.ops.qattn.mxfp4_decode_step_plan(slots, lens, capacity, kv_heads, group, keys_per_split, splits,
                                            window, sinks) -> (seq_tab, tiles, pos, seq_rec)
     torch.ops.qattn.mxfp4_decode_step(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, splits,
-                                      keys_per_split, window, sinks, sink_logit=None) -> (O, lse)
+                                      keys_per_split, window, sinks, sink_logit=None, softcap=0., qks=0.)
+                                      -> (O, lse)
+    torch.ops.qattn.mxfp4_varlen_paged_softcap(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows,
+                                               causal, keys_per_split, window, sinks, softcap, qks) -> (O, lse)
     torch.ops.qattn.mxfp4_verify_step_plan(slots, lens, tree, draft_tokens, capacity, kv_heads, group,
                                            keys_per_split, splits) -> (seq_tab, tiles, pos, seq_rec)
     torch.ops.qattn.mxfp4_verify_step(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, tree, draft_tokens,
@@ -187,7 +190,14 @@ def _(slots, lens, capacity, kv_heads, group, keys_per_split, splits, window, si
 
 @torch.library.register_fake("qattn::mxfp4_decode_step")
 def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, splits, keys_per_split, window, sinks,
-      sink_logit=None):
+      sink_logit=None, softcap=0., qks=0.):
+    T, H, D = q.shape
+    return (q.new_empty((T, H, D), dtype=torch.float16), q.new_empty((T, H), dtype=torch.float32))
+
+
+@torch.library.register_fake("qattn::mxfp4_varlen_paged_softcap")
+def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal, keys_per_split, window, sinks,
+      softcap, qks):
     T, H, D = q.shape
     return (q.new_empty((T, H, D), dtype=torch.float16), q.new_empty((T, H), dtype=torch.float32))
 
@@ -343,7 +353,7 @@ def mxfp4_quant_rows_rope(x, rope, positions):
 
 
 def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=None, window=None, sinks=0,
-                       share_prefix=False, tree=None, rope=None, positions=None):
+                       share_prefix=False, tree=None, rope=None, positions=None, softcap=None, scale=None):
     """``kv_cache_mxfp4.attention_mxfp4_varlen_paged`` as one operator: packed q [T, Hq, 128] against
     a ``PagedKVFP4``, the ``q_lens[j]`` tokens of slot ``seq_ids[j]`` over that sequence's own length
     and pages -> (O fp16 [T, Hq, 128], lse fp32 [T, Hq]).  The plan (``plan_varlen``) is made and checked
@@ -360,13 +370,21 @@ def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=N
     combinations are the Python call's alone) routes to ``torch.ops.qattn.mxfp4_varlen_paged_rope``.  A pool of
     head_dim 64 or 256 takes q [T, Hq, 64] / [T, Hq, 256] in the plain, the windowed and the rope form; ``share_prefix=True`` and
     ``tree`` raise there as in the Python call.  The learned sink logit (``sink_logit=``) is the Python call's and
-    the C ABI's alone."""
+    the C ABI's alone.  ``softcap`` and / or ``scale`` (checked as the Python call checks them; the plain and the
+    windowed form, every head_dim) route to ``torch.ops.qattn.mxfp4_varlen_paged_softcap``, the Python call's
+    bits; with ``rope``, ``share_prefix`` or ``tree`` they are the Python call's alone."""
     from .kv_cache_mxfp4 import (PagedKVFP4, _check_trimmed, _packed_lists, _query_positions, _shared_plan,
-                                 _tree_args, _window_args, plan_varlen)
+                                 _softcap_args, _tree_args, _window_args, plan_varlen)
     if not isinstance(cache, PagedKVFP4):
         raise _lib.QAttnError("qattn mxfp4 kv cache: cache must be a PagedKVFP4")
     if q.dim() != 3:
         raise _lib.QAttnError("qattn mxfp4 paged cache: packed queries must be q [T, Hq, D]")
+    capped = softcap is not None or scale is not None
+    cap, qks = _softcap_args(softcap, scale, q.shape[2], share_prefix or tree is not None)
+    if capped and (share_prefix or tree is not None or rope is not None or positions is not None):
+        raise _lib.QAttnError("qattn mxfp4 paged cache: the softcap operator takes no rope, share_prefix or tree; "
+                              "kv_cache_mxfp4.attention_mxfp4_varlen_paged serves those with scale= (and rope "
+                              "with softcap=)")
     if share_prefix or tree is not None:
         cache._need128("share_prefix=True" if share_prefix else "tree=")
     ids, sq = _packed_lists(cache.alloc.max_seqs, seq_ids, q_lens, "q_lens")
@@ -410,6 +428,10 @@ def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=N
     _lib.require_gpu(q, cache.k4)
     rec_d = torch.tensor(seq_rec, dtype=torch.int32).to(q.device, non_blocking=True)
     work_d = torch.tensor(work, dtype=torch.int32).to(q.device, non_blocking=True)
+    if capped:
+        return _ops.mxfp4_varlen_paged_softcap(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens,
+                                               cache.block_table, rec_d, work_d, part_rows, int(bool(causal)), kps,
+                                               min(W or 0, 1 << 26), min(S, 1 << 26), cap or 0., qks)
     if rope is not None:
         return _ops.mxfp4_varlen_paged_rope(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens,
                                             cache.block_table, rec_d, work_d, part_rows, int(bool(causal)), kps,
@@ -437,10 +459,10 @@ def mxfp4_decode_step(q, step, cache, seq_rec=None, sink_logit=None):
     """``kv_cache_mxfp4.DecodeStep.attend`` (without ``rope``) as one operator that allocates its outputs: q [N,
     Hq, D] (D = 128, 64 or 256, the pool's) against ``cache`` after the step's append, over ``seq_rec`` (default: the
     step's own, which its ``append`` wrote) and the step's ``work``, with the learned ``sink_logit`` f32 [Hq] when
-    one is given -> (O, lse), the Python call's bits."""
+    one is given and the step's ``softcap`` and scale -> (O, lse), the Python call's bits."""
     return _ops.mxfp4_decode_step(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens, cache.block_table,
                                   step.seq_rec if seq_rec is None else seq_rec, step.work, step.splits, step.kps,
-                                  step.window or 0, step.sinks, sink_logit)
+                                  step.window or 0, step.sinks, sink_logit, step.softcap or 0., step.qks)
 
 
 def mxfp4_verify_step_plan(step, cache):

@@ -35,6 +35,10 @@ anything is timed (the pools of (b) hold different random tokens).
     it must read (the visited 64-key tiles at 272 B per key and key/value head) and the fraction of the HBM peak
     (8 TB/s) that makes, then the whole call.
 
+(g) with --softcap C (then only (g) runs): the attention kernel alone (REPS launches) with the logit cap C
+    (qattn_mxfp4_attn_fwd_varlen_paged_softcap) beside the uncapped kernel of the same build, alternating, at the two
+    decode shapes of (f) and at one 512-token prefill chunk over 8192 cached keys at head_dim 128, 32 / 8 heads.
+
 After (a) and (b) the packed call is taken apart: the host plan alone (plan_varlen, a host clock), the
 two table uploads alone (event-timed) and the attention kernel alone (REPS back-to-back launches of the
 C entry on buffers and tables made once, divided by REPS), beside the paged kernel alone in (a).
@@ -259,8 +263,9 @@ def pool64(lengths, k, v, Dp, extra=0):
     return cache
 
 
-def kernel64(q, cache, q_lens, W, tps):
-    """REPS launches of the packed attention kernel alone on ``cache`` (either head_dim); tps: tiles per slot."""
+def kernel64(q, cache, q_lens, W, tps, softcap=None):
+    """REPS launches of the packed attention kernel alone on ``cache`` (any head_dim); tps: tiles per slot; softcap:
+    the capped entry."""
     Dp, ids = cache.shape[3], list(range(len(q_lens)))
     kps, rec, work, rows = plan_varlen(cache.lengths, ids, q_lens, q.shape[1], 8, None, True, W, 0)
     rec_d, work_d = (torch.tensor(x, dtype=torch.int32).cuda() for x in (rec, work))
@@ -271,8 +276,8 @@ def kernel64(q, cache, q_lens, W, tps):
             _lib.ptr(cache.lens), _lib.ptr(cache.block_table), _lib.ptr(rec_d), _lib.ptr(work_d), len(rec),
             len(work), q.shape[0], rows, cache.alloc.max_seqs, 8, q.shape[1] // 8, cache.num_pages, P,
             cache.alloc.max_pages_per_seq, 2, kps, Dp, _qk_scale(Dp))
-    name = "qattn_mxfp4_attn_fwd_varlen_paged" + ("_window" if W else "")
-    tail = ((W, 0) if W else ()) + (_lib.stream_of(q),)
+    name = "qattn_mxfp4_attn_fwd_varlen_paged" + ("_softcap" if softcap else "_window" if W else "")
+    tail = ((W or 0, 0, softcap) if softcap else (W, 0) if W else ()) + (_lib.stream_of(q),)
 
     def kernel(keep=(q4, qs, opart, ml, rec_d, work_d)):
         os.environ["QATTN_MX64_TPS"] = str(tps)
@@ -338,6 +343,20 @@ def d256(rand, passes, iters):
         torch.cuda.empty_cache()
 
 
+def softcapped(cap, rand, passes, iters):
+    shapes = [("8 decodes at 8192 cached", 256, 16, [8192] * 8, [1] * 8, None),
+              ("64 decodes at 32768 cached, window 4096", 256, 16, [32768] * 64, [1] * 64, 4096),
+              ("a 512-token chunk at 8192 cached", 128, 32, [8192], [512], None)]
+    for name, Dp, hq, lengths, q_lens, W in shapes:
+        cache = pool64(lengths, rand(max(lengths), 8, Dp), rand(max(lengths), 8, Dp), Dp)
+        q = rand(sum(q_lens), hq, Dp)
+        print(f"(g) {name}: {hq}/8 heads of head_dim {Dp}, P {P}", flush=True)
+        report(alternate({f"uncapped kernel x{REPS}": kernel64(q, cache, q_lens, W, 2),
+                          f"softcap {cap:g} kernel x{REPS}": kernel64(q, cache, q_lens, W, 2, cap)}, passes, iters))
+        del cache
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--passes", type=int, default=3)
@@ -346,12 +365,16 @@ def main():
     ap.add_argument("--sinks", type=int, default=0)
     ap.add_argument("--head-dim", type=int, default=128, choices=(64, 128, 256),
                     help="64: run only (e); 256: run only (f)")
+    ap.add_argument("--softcap", type=float, default=None, help="run only (g), with this logit cap")
     args = ap.parse_args()
     assert args.passes >= 3
     print(f"device {torch.cuda.get_device_name(0)}; {args.passes} alternating passes x {args.iters} calls, "
           "whole Python call", flush=True)
     g = torch.Generator(device="cuda").manual_seed(0)
     rand = lambda *s: torch.randn(s, device="cuda", generator=g).half()  # noqa: E731
+    if args.softcap is not None:
+        softcapped(args.softcap, rand, args.passes, args.iters)
+        return
     if args.head_dim == 64:
         d64(rand, args.passes, args.iters)
         return
