@@ -1,5 +1,7 @@
-// The device code of the MX-FP4 attention kernels (format, quantisers, rings, tile body, merge, appends) that
-// mxfp4_attn.hip, mxfp4_attn_d64.hip and mxfp4_attn_d256.hip share; the definitions are at the head of mxfp4_attn.hip.
+// The device code of the MX-FP4 attention kernels (format, quantisers, rings, tile body, the packed-step kernel of
+// head_dim 64 and 256, merges, appends) and the host paths that exist once for every head_dim, which mxfp4_attn.hip,
+// mxfp4_attn_softcap.hip, mxfp4_attn_d64.hip and mxfp4_attn_d256.hip share; the definitions of the format are at
+// the head of mxfp4_attn.hip.
 #pragma once
 #include "common.h"
 
@@ -240,8 +242,9 @@ static __global__ __launch_bounds__(256) void mx_append_len_kernel(int* __restri
 }
 
 // ------------------------------------------------------------------------------ attention
-template <int D>
+template <int D_>
 struct MxCfg {
+  static constexpr int D = D_;
   static constexpr int WAVES = 4;
   static constexpr int QROWS = 32 * WAVES;
   static constexpr int KT = 64;                       // keys per tile / ring slot
@@ -1012,6 +1015,158 @@ __global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_split_kernel(
                                        lane, 0.f, nr);
 }
 
+// The packed step over the paged pool at the head dims whose tile schedule is not the D = 128 ring's: head_dim 64
+// (Ring = MxRing64<TPS>, mxfp4_attn_d64.hip) and 256 (MxRing256, mxfp4_attn_d256.hip).  It is the VARLEN + PAGED
+// branch of mxfp4_attn_split_kernel, which stays its one sibling (that kernel carries the LEN, PAGED, SHARED and
+// TREE paths at D = 128 and is compiled under other flags): the work and sequence records, the row mapping, the
+// tile range of a split, the empty state, the causal and window masks, the skipped tiles and the compact partials
+// are that branch's, statement for statement, so a change to one of the two belongs in the other.
+// The ring supplies C = MxCfg<D>, SLOT (the LDS bytes of a slot), IPW (VMEM ops of a wave per slot), TPS (64-key
+// tiles per slot), TILE_IN_LOOP (the form of the tile loop, below), issue and prologue.  One barrier publishes a slot; the wave runs its TPS tiles through mx_tile
+// one after the other, and a run of an odd tile count leaves the last slot of a pair ring with one live tile.
+// STEP is the fixed grid of the device-planned decode step: a workgroup with split >= rec[3] returns behind the
+// two record reads, in front of the ring's constructor (which reads a table entry).
+template <class Ring, bool CAUSAL, bool WINDOW, bool STEP, bool SOFTCAP>
+__global__ __launch_bounds__(256, QA_MX_OCC) void mxfp4_attn_packed_kernel(
+    const uint8_t* __restrict__ q4, const uint8_t* __restrict__ qs, const uint8_t* __restrict__ k4,
+    const uint8_t* __restrict__ ks, const uint8_t* __restrict__ vt, const uint8_t* __restrict__ vs,
+    float* __restrict__ opart, float2* __restrict__ ml, int BHV, int Sk, int kps, float qks,
+    const int* __restrict__ lens, int hps, const int* __restrict__ btab, int mpp, int lgt, int npool,
+    MxVarlen vl) {
+  using R = Ring;
+  using C = typename R::C;
+  constexpr int D = C::D, TPS = R::TPS;
+  static_assert(CAUSAL || !WINDOW, "a window is causal");
+  static_assert(CAUSAL || !STEP, "the fixed grid is the causal packed step's");
+  static_assert(TPS == 1 || TPS == 2, "one tile or a pair of tiles per slot");
+  static_assert(C::WAVES * RowTile<D, float, 2>::BYTES <= C::NSLOT * R::SLOT, "fp32 staging in two passes fits the ring");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  typedef const __attribute__((address_space(4))) int* table_ptr;
+  const int hd = (int)(blockIdx.x % (unsigned)hps);
+  const table_ptr w = (table_ptr)(unsigned long)(vl.work + 4L * (blockIdx.x / (unsigned)hps));
+  const table_ptr rec = (table_ptr)(unsigned long)(vl.seq_rec + 8L * min(max(w[0], 0), vl.nseq - 1));
+  if constexpr (STEP) {   // a surplus workgroup of the fixed grid: nothing fetched, nothing stored
+    if (max(w[2], 0) >= rec[3]) return;
+  }
+  const int qt = max(w[1], 0), split = max(w[2], 0);
+  const int bh = min(max(rec[0], 0), BHV / hps - 1) * hps + hd;
+  const long qbase = rec[1], pbase = rec[4];
+  const int sq_head = max(rec[2], 1);
+  const int rows = vl.group * sq_head;
+  const int wt0 = WINDOW ? max(rec[5], 0) : 0, nsink = WINDOW ? max(rec[6], 0) : 0;
+
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = tid & 63, h = lane >> 5, c32 = lane & 31;
+  const int q0 = qt * C::QROWS + wave * 32;
+  const int qi = min(q0 + c32, rows - 1);
+  const int len = min(__builtin_amdgcn_readfirstlane(lens[bh / hps]), Sk);   // never a tile past the capacity
+  const int qoff = len - sq_head;
+  const int nt = (len + C::KT - 1) / C::KT;
+  const bool sink_run = WINDOW && nsink > 0 && split == 0;
+  const int t0 = !WINDOW ? split * (kps / C::KT)
+                         : sink_run ? 0
+                                    : (int)min((long)wt0 + (long)(split - (nsink > 0)) * (kps / C::KT), (long)nt);
+  const long row0 = pbase + ((long)split * hps + hd) * rows + q0;   // the wave's first row of opart / ml
+  const int nr = min(32, rows - q0);
+  // a wave without rows, or whose rows would pass the partials, stores nothing
+  const bool active = q0 < rows && row0 >= 0 && row0 + nr <= vl.part_rows;
+  if (t0 >= nt) {   // a split past the sequence: the empty state for the workgroup's rows
+    if (!active) return;
+    if (h == 0 && c32 < nr) ml[row0 + c32] = make_float2(-INFINITY, 0.f);
+    v4f* dst = reinterpret_cast<v4f*>(opart + row0 * D);
+#pragma unroll
+    for (int i = 0; i < 32 * (D / 4) / 64; ++i)
+      if (i * 64 + lane < nr * (D / 4)) dst[i * 64 + lane] = v4f{0.f, 0.f, 0.f, 0.f};
+    return;
+  }
+  const int ntw = sink_run ? min(nsink, nt) : min(nt - t0, kps / C::KT);
+  // causal: query positions of the wave's rows (a wave that crosses a head boundary holds both ends)
+  int wmin = 0, wmax = 0, pos = 0;
+  if constexpr (CAUSAL) {
+    const int p0 = q0 % sq_head;
+    const bool wraps = p0 + nr > sq_head;
+    wmin = wraps ? 0 : p0;
+    wmax = wraps ? sq_head - 1 : p0 + nr - 1;
+    pos = qi % sq_head;
+  }
+
+  R ring(k4, ks, vt, vs, btab + (long)(bh / hps) * mpp, (nt + (1 << lgt) - 1) >> lgt, lgt, hps, hd, npool, t0, smem,
+         wave, lane);
+  ring.prologue(ntw);
+
+  v4i qf[C::NKS];
+  const long qrow = min(max((qbase + qi % sq_head) * (vl.group * hps) + hd * vl.group + qi / sq_head, 0L),
+                        vl.qrows - 1);
+  const typename C::scale_t qsw = mx_load_q<D>(q4, qs, qrow, h, qf);
+
+  v16f o[C::NDB];
+#pragma unroll
+  for (int b = 0; b < C::NDB; ++b) o[b] = v16f{};
+  float m = -INFINITY, l = 0.f;
+
+  // Tile t of the run, landed at sl: the masks and the skips of mxfp4_attn_split_kernel, then the tile body.
+  // QA_MX_PACKED_TILE(skip, sl) is that text with `skip` for "this tile changes nothing".  It stands in a macro,
+  // not in a function, because the two rings need it in two forms to keep their instruction streams: MxRing64
+  // (either TPS) as a lambda (skip = return), MxRing256 written into its loop (skip = continue, R::TILE_IN_LOOP).
+  // Through the lambda every head_dim 256 instantiation changes, and without it every head_dim 64 one (DESIGN.md,
+  // "One packed-step kernel").
+#define QA_MX_PACKED_TILE(skip, sl)                                                                               \
+  const int k0 = C::KT * (t0 + t);                                                                                \
+  bool diag;                                                                                                      \
+  int lim, lo = 0, slim = 0;                                                                                      \
+  if constexpr (CAUSAL) {                                                                                         \
+    if (k0 > wmax + qoff) skip; /* no row of the wave sees the tile: m, l, O unchanged */                         \
+    diag = k0 + C::KT - 1 > wmin + qoff;                                                                          \
+    lim = pos + qoff - k0 - 4 * h;                                                                                \
+    if constexpr (WINDOW) {                                                                                       \
+      /* the tile lies below every row's window and holds no sink key: skipped like the one above */             \
+      if (k0 + C::KT - 1 < wmin + qoff - vl.window + 1 && k0 >= vl.sinks) skip;                                   \
+      /* some row's lower edge cuts the tile (the highest edge is the last row's), unless it is all sinks */      \
+      diag = diag || (k0 < wmax + qoff - vl.window + 1 && k0 + C::KT > vl.sinks);                                 \
+      lo = pos + qoff - vl.window + 1 - k0 - 4 * h;                                                               \
+      slim = vl.sinks - 1 - k0 - 4 * h;                                                                           \
+    }                                                                                                             \
+  } else { /* every row sees the keys <= len - 1 */                                                               \
+    diag = k0 + C::KT > len;                                                                                      \
+    lim = len - 1 - k0 - 4 * h;                                                                                   \
+  }                                                                                                               \
+  mx_tile<D, true, WINDOW, false, SOFTCAP>(sl, qf, qsw, o, m, l, diag, lim, qks, lane, h, c32, lo, slim, 0, 0,    \
+                                           vl.cap_c1, vl.cap_c);
+
+  vmem_drain();
+  __syncthreads();
+  if constexpr (R::TILE_IN_LOOP) {
+    static_assert(TPS == 1, "one barrier, one tile");
+    for (int t = 0; t < ntw; ++t) {
+      ring_wait_barrier<2 * R::IPW>();   // tile t landed (t + 1, t + 2 may be in flight); slot (t + 3) & 3 is free
+      ring.issue(t + 3, ntw);
+      if (!active) continue;   // a wave without rows keeps its share of the DMA and the barrier
+      QA_MX_PACKED_TILE(continue, smem + (t & 3) * R::SLOT)
+    }
+  } else {
+    const auto tile = [&](int t, const char* sl) { QA_MX_PACKED_TILE(return, sl) };
+    const int np = (ntw + TPS - 1) / TPS;
+    for (int p = 0; p < np; ++p) {
+      ring_wait_barrier<2 * R::IPW>();   // slot p landed (p + 1, p + 2 may be in flight); slot (p + 3) & 3 is free
+      ring.issue(p + 3, ntw);
+      if (!active) continue;
+      const char* sl = smem + (p & 3) * R::SLOT;
+      tile(TPS * p, sl);
+      if constexpr (TPS == 2) {
+        if (2 * p + 1 < ntw) tile(2 * p + 1, sl + C::SLOT);   // an odd run: the last slot holds one live tile
+      }
+    }
+  }
+#undef QA_MX_PACKED_TILE
+  vmcnt_wait_all();
+  __syncthreads();
+  if (!active) return;
+  if (h == 0 && c32 < nr) ml[row0 + c32] = make_float2(m, l);
+  store_rows<D, float, 2, false, true>(o, 1.0f, smem + wave * RowTile<D, float, 2>::BYTES, opart + row0 * D, lane,
+                                       0.f, nr);
+}
+
 // f16 of the exact product a * b, rounded once (v_fma_mixlo_f16 with fp32 sources)
 QA_DEVICE _Float16 mul_f16_once(float a, float b) {
   unsigned r = 0;
@@ -1106,15 +1261,13 @@ QA_DEVICE int mx_find_seq(const int* tab, int n, int stride, int col, int x) {
 // 8 columns of a packed output row (token, query head).  The thread finds its sequence j by binary search
 // over the first-token column of seq_rec, and merges that sequence's own rec[3] splits, rows first + (s *
 // Hkv + head / group) * group * sq + (head % group) * sq + token - first of opart / ml.  A row whose
-// partial rows would pass part_rows (a wrong table) is not merged.
-template <int D>
-__global__ __launch_bounds__(256) void mxfp4_varlen_combine_kernel(const float* __restrict__ opart,
-                                                                   const float2* __restrict__ ml,
-                                                                   _Float16* __restrict__ out,
-                                                                   float* __restrict__ lse,
-                                                                   const int* __restrict__ seq_rec, int nseq,
-                                                                   long rows, int Hq, int Hkv,
-                                                                   long part_rows) {
+// partial rows would pass part_rows (a wrong table) is not merged.  SINK: the learned sink logit of the row's
+// query head joins the merge (mx_merge_row SINK); `sink` (f32 [Hq]) is read only then.
+template <int D, bool SINK>
+__global__ __launch_bounds__(256) void mxfp4_varlen_combine_kernel(
+    const float* __restrict__ opart, const float2* __restrict__ ml, _Float16* __restrict__ out,
+    float* __restrict__ lse, const int* __restrict__ seq_rec, int nseq, long rows, int Hq, int Hkv, long part_rows,
+    const float* __restrict__ sink) {
   constexpr int TPR = D / 8;
   const long gid = (long)blockIdx.x * 256 + threadIdx.x;
   const long row = gid / TPR;
@@ -1125,7 +1278,36 @@ __global__ __launch_bounds__(256) void mxfp4_varlen_combine_kernel(const float* 
   const long rows_j = (long)G * sq, step = (long)Hkv * rows_j;
   const long first = rec[4] + (head / G) * rows_j + (long)(head % G) * sq + (token - rec[1]);
   if (nsplit < 1 || first < 0 || first + (nsplit - 1) * step >= part_rows) return;
-  mx_merge_row<D>(opart, ml, first, step, nsplit, (int)(gid % TPR), out + row * D, lse + row);
+  float z = 0.f;
+  if constexpr (SINK) z = sink[head];
+  mx_merge_row<D, SINK>(opart, ml, first, step, nsplit, (int)(gid % TPR), out + row * D, lse + row, z);
+}
+
+// The merge of the device-planned decode step (kv_cache_mxfp4.py DecodeStep): entry i owns the partial rows [i *
+// splits * Hq, (i + 1) * splits * Hq), laid out [split][query head] (one query: the virtual head order is the head
+// order), so nothing but ns is read from the record and every address lies inside the partials.  mx_merge_row
+// over the entry's ns splits, the arithmetic of mxfp4_varlen_combine_kernel in its order.  An entry with ns < 1
+// (padding) is no sequence: it gets O = 0 and lse = -inf, with a sink logit too.
+template <int D, bool SINK>
+__global__ __launch_bounds__(256) void mxfp4_decode_step_combine_kernel(
+    const float* __restrict__ opart, const float2* __restrict__ ml, _Float16* __restrict__ out,
+    float* __restrict__ lse, const int* __restrict__ seq_rec, long rows, int Hq, int splits,
+    const float* __restrict__ sink) {
+  constexpr int TPR = D / 8;
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+  const long row = gid / TPR;
+  if (row >= rows) return;
+  const int c = (int)(gid % TPR);
+  const long token = row / Hq;
+  const int ns = min(seq_rec[8 * token + 3], splits);
+  if (ns < 1) {
+    *reinterpret_cast<v8h*>(out + row * D + 8 * c) = v8h{};
+    if (c == 0) lse[row] = -INFINITY;
+    return;
+  }
+  float z = 0.f;
+  if constexpr (SINK) z = sink[row % Hq];
+  mx_merge_row<D, SINK>(opart, ml, token * splits * Hq + row % Hq, Hq, ns, c, out + row * D, lse + row, z);
 }
 
 // ---- packed append into the paged pool (kv_cache_mxfp4.py PagedKVFP4.append_packed)
@@ -1313,72 +1495,9 @@ __global__ __launch_bounds__(256) void mx_append_k_packed_rope_kernel(
 }
 
 
-// ---- head_dim 64 (mxfp4_attn_d64.hip): what the C entries of mxfp4_attn.hip hand a head_dim of 64 to, with
-// the arguments of the entry (or of its shared body) that forwards them
-int mx64_varlen_paged(const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
-                      const void* vscale, void* opart, void* ml, const void* lens, const void* block_table,
-                      const void* seq_rec, const void* work, long nseq, long nwork, long tokens, long part_rows,
-                      long max_seqs, long kv_heads, long group, long num_pages, long page_tokens,
-                      long max_pages_per_seq, int causal, int keys_per_split, float qks, long window, long sinks,
-                      void* stream);
-// qattn_mxfp4_attn_fwd_decode_step at head_dim 64, behind that entry's own checks
-int mx64_decode_step(const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
-                     const void* vscale, void* opart, void* ml, const void* lens, const void* block_table,
-                     const void* seq_rec, const void* work, long n, long splits, long max_seqs, long kv_heads,
-                     long group, long num_pages, long page_tokens, long max_pages_per_seq, int keys_per_split,
-                     float qks, long window, long sinks, void* stream);
-int mx64_append_packed(bool rope, const void* k, const void* v, const void* k_mean, void* k4, void* kscale,
-                       void* vt, void* vscale, void* vtail, void* lens, const void* block_table,
-                       const void* seq_tab, const void* tiles, long nseq, long ntiles, long tokens, long max_seqs,
-                       long kv_heads, long num_pages, long page_tokens, long max_pages_per_seq,
-                       const void* cos_sin, const void* pos, long max_pos, int interleaved, void* stream);
-int mx64_quant_rows_rope(const void* x, void* q4, void* scale, const void* cos_sin, const void* pos, long tokens,
-                         long heads, long max_pos, int interleaved, void* stream);
-// the packed step's merge at either head_dim, `sink_logit` f32 [q_heads] or null (null: head_dim 64 only)
-int mx_varlen_combine_ext(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
-                          const void* sink_logit, long nseq, long tokens, long q_heads, long kv_heads,
-                          long part_rows, int head_dim, void* stream);
-
-// ---- head_dim 256 (mxfp4_attn_d256.hip): the same entries, with the arguments of their mx64_* forms, and the
-// quantiser and merges of the packed and the decode step at that width (sink_logit / sink null: none)
-int mx256_varlen_paged(const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
-                       const void* vscale, void* opart, void* ml, const void* lens, const void* block_table,
-                       const void* seq_rec, const void* work, long nseq, long nwork, long tokens, long part_rows,
-                       long max_seqs, long kv_heads, long group, long num_pages, long page_tokens,
-                       long max_pages_per_seq, int causal, int keys_per_split, float qks, long window, long sinks,
-                       void* stream);
-int mx256_decode_step(const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
-                      const void* vscale, void* opart, void* ml, const void* lens, const void* block_table,
-                      const void* seq_rec, const void* work, long n, long splits, long max_seqs, long kv_heads,
-                      long group, long num_pages, long page_tokens, long max_pages_per_seq, int keys_per_split,
-                      float qks, long window, long sinks, void* stream);
-int mx256_append_packed(bool rope, const void* k, const void* v, const void* k_mean, void* k4, void* kscale,
-                        void* vt, void* vscale, void* vtail, void* lens, const void* block_table,
-                        const void* seq_tab, const void* tiles, long nseq, long ntiles, long tokens, long max_seqs,
-                        long kv_heads, long num_pages, long page_tokens, long max_pages_per_seq,
-                        const void* cos_sin, const void* pos, long max_pos, int interleaved, void* stream);
+// qattn_mxfp4_quant_rows at head_dim 256, behind that entry's checks of mean and seq; nblk = rows * 8 >= 1.  The
+// kernel is instantiated in mxfp4_attn_d256.hip, under that file's flags.
 int mx256_quant_rows(const void* x, const void* mean, void* q4, void* scale, long nblk, long seq, void* stream);
-int mx256_quant_rows_rope(const void* x, void* q4, void* scale, const void* cos_sin, const void* pos, long tokens,
-                          long heads, long max_pos, int interleaved, void* stream);
-int mx256_varlen_combine(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
-                         const void* sink_logit, long nseq, long tokens, long q_heads, long kv_heads,
-                         long part_rows, void* stream);
-int mx256_step_combine(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
-                       const void* sink, long n, long splits, long q_heads, void* stream);
-
-// ---- logit soft-capping at head_dim 64 and 256: what the two entries of mxfp4_attn_softcap.hip hand those widths
-// to.  step false: the packed call, the arguments of mx64_varlen_paged; step true: the decode step, nseq = tokens
-// = n, nwork = n * splits, part_rows = n * splits * kv_heads * group, causal = 2.  cap_c1, cap_c: mx_tile SOFTCAP.
-int mx64_softcap(bool step, const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
-                 const void* vscale, void* opart, void* ml, const void* lens, const void* block_table,
-                 const void* seq_rec, const void* work, long nseq, long nwork, long tokens, long part_rows,
-                 long max_seqs, long kv_heads, long group, long num_pages, long page_tokens, long max_pages_per_seq,
-                 int causal, int keys_per_split, long window, long sinks, float cap_c1, float cap_c, void* stream);
-int mx256_softcap(bool step, const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt,
-                  const void* vscale, void* opart, void* ml, const void* lens, const void* block_table,
-                  const void* seq_rec, const void* work, long nseq, long nwork, long tokens, long part_rows,
-                  long max_seqs, long kv_heads, long group, long num_pages, long page_tokens, long max_pages_per_seq,
-                  int causal, int keys_per_split, long window, long sinks, float cap_c1, float cap_c, void* stream);
 }  // namespace qattn
 
 // ---- host checks the C entries of the three files share
@@ -1439,18 +1558,20 @@ static int mx_split_launch(const MxSplitCall& c, void* stream) {
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
-// What the packed entries without groups share: their argument checks and the call filled in (nwork work
-// records x kv_heads workgroups in one launch; rows, sq_head and qoff come from the records).  Returns the
-// entry's status when there is nothing to launch, -1 when `c` is to be launched.  tree: the ancestor words
-// of the tree entry, else null.
-static int mx_varlen_call(MxSplitCall& c, const void* q4, const void* qscale, const void* k4,
+// What the packed entries without groups share at head_dim 64, 128 and 256: their argument checks and the call
+// filled in (nwork work records x kv_heads workgroups in one launch; rows, sq_head and qoff come from the
+// records, so the packed kernels of head_dim 64 and 256 take the call without them).  Returns the entry's status
+// when there is nothing to launch, -1 when `c` is to be launched.  tree: the ancestor words of the tree entry, else
+// null; cap_c1, cap_c: mx_tile SOFTCAP's constants, else 0.
+static int mx_packed_call(MxSplitCall& c, const void* q4, const void* qscale, const void* k4,
                           const void* kscale, const void* vt, const void* vscale, void* opart, void* ml,
                           const void* lens, const void* block_table, const void* seq_rec, const void* work,
                           long nseq, long nwork, long tokens, long part_rows, long max_seqs, long kv_heads,
                           long group, long num_pages, long page_tokens, long max_pages_per_seq, int causal,
                           int keys_per_split, int head_dim, float qks, long window, long sinks,
-                          const void* tree) {
-  if (!mx_split_ok(head_dim, keys_per_split) || nseq < 0 || nwork < 0 || tokens < 0 || part_rows < 0) return 1;
+                          const void* tree, float cap_c1 = 0.f, float cap_c = 0.f) {
+  if (head_dim != 64 && head_dim != 128 && head_dim != 256) return 1;
+  if (!mx_split_ok(128, keys_per_split) || nseq < 0 || nwork < 0 || tokens < 0 || part_rows < 0) return 1;
   if (!lens || !block_table || !seq_rec || !work) return 1;
   const int lgt = mx_page_lgt(page_tokens);
   if (!mx_pool_ok(num_pages, kv_heads, lgt, max_pages_per_seq)) return 1;
@@ -1465,7 +1586,7 @@ static int mx_varlen_call(MxSplitCall& c, const void* q4, const void* qscale, co
   const long big = 1L << 26;
   const qattn::MxVarlen vl{(const int*)work, (const int*)seq_rec, (int)nseq, (int)group, tokens * group * kv_heads,
                     part_rows, (int)(window < big ? window : big), (int)(sinks < big ? sinks : big),
-                    nullptr, nullptr, 0, 0, (const unsigned long*)tree, tokens};
+                    nullptr, nullptr, 0, 0, (const unsigned long*)tree, tokens, cap_c1, cap_c};
   c = MxSplitCall{q4, qscale, k4, kscale, vt, vscale, opart, ml, (int)(max_seqs * kv_heads), 0, 1,
                   (int)(max_pages_per_seq * page_tokens), keys_per_split, qks, 0, lens, (int)kv_heads,
                   block_table, (int)max_pages_per_seq, lgt, (int)num_pages, vl,
@@ -1473,7 +1594,179 @@ static int mx_varlen_call(MxSplitCall& c, const void* q4, const void* qscale, co
   return -1;
 }
 
+// mx_packed_call for the entries that exist at head_dim 128 alone (the tree and the verify step)
+static int mx_varlen_call(MxSplitCall& c, const void* q4, const void* qscale, const void* k4,
+                          const void* kscale, const void* vt, const void* vscale, void* opart, void* ml,
+                          const void* lens, const void* block_table, const void* seq_rec, const void* work,
+                          long nseq, long nwork, long tokens, long part_rows, long max_seqs, long kv_heads,
+                          long group, long num_pages, long page_tokens, long max_pages_per_seq, int causal,
+                          int keys_per_split, int head_dim, float qks, long window, long sinks,
+                          const void* tree) {
+  if (head_dim != 128) return 1;
+  return mx_packed_call(c, q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work, nseq,
+                        nwork, tokens, part_rows, max_seqs, kv_heads, group, num_pages, page_tokens,
+                        max_pages_per_seq, causal, keys_per_split, head_dim, qks, window, sinks, tree);
+}
+
 // window 0: none (then sinks must be 0); the kernels' 32-bit edges as in mx_varlen_call
 static bool mx_step_window_ok(long window, long sinks) {
   return window >= 0 && sinks >= 0 && (window > 0 || sinks == 0);
 }
+
+// ---- the host paths that exist once for every head_dim
+// Each width's kernels are instantiated in the translation unit whose flags they were measured with (build.py
+// FILE_FLAGS): head_dim 128 in mxfp4_attn.hip, 64 in mxfp4_attn_d64.hip, 256 in mxfp4_attn_d256.hip.  So the
+// templates over D below are defined here, declared `extern template` for the three widths, and explicitly
+// instantiated by the file of each width; a C entry of any file calls the width it was given.
+namespace qattn {
+
+// one launch of the packed kernel over `Ring` (mx_split_launch for mxfp4_attn_packed_kernel)
+template <class Ring, bool CAUSAL, bool WINDOW, bool STEP, bool SOFTCAP>
+static int mx_packed_launch(const MxSplitCall& c, void* stream) {
+  const auto kernel = mxfp4_attn_packed_kernel<Ring, CAUSAL, WINDOW, STEP, SOFTCAP>;
+  const int lds = Ring::C::NSLOT * Ring::SLOT;
+  { static LdsGrant granted_; if (!lds_grant((const void*)kernel, lds, granted_)) return 1; }
+  hipLaunchKernelGGL(kernel, c.grid, dim3(256), lds, (hipStream_t)stream, (const uint8_t*)c.q4,
+                     (const uint8_t*)c.qscale, (const uint8_t*)c.k4, (const uint8_t*)c.kscale,
+                     (const uint8_t*)c.vt, (const uint8_t*)c.vscale, (float*)c.opart, (float2*)c.ml, c.bhv, c.Sk,
+                     c.kps, c.qks, (const int*)c.lens, c.hps, (const int*)c.btab, c.mpp, c.lgt, c.npool, c.vl);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// The dispatch of a checked packed call (mx_packed_call) over `Ring`: the windowed instantiation for window >= 1
+// (then the call is causal), else the causal or the plain one.  STEP: the fixed grid of the decode step, which
+// is causal; SOFTCAP: the capped tile body with the two constants of c.vl.
+template <class Ring, bool STEP, bool SOFTCAP>
+static int mx_packed(const MxSplitCall& c, int causal, long window, void* stream) {
+  if (window >= 1) return mx_packed_launch<Ring, true, true, STEP, SOFTCAP>(c, stream);
+  if constexpr (STEP) return mx_packed_launch<Ring, true, false, true, SOFTCAP>(c, stream);
+  else return causal ? mx_packed_launch<Ring, true, false, false, SOFTCAP>(c, stream)
+                     : mx_packed_launch<Ring, false, false, false, SOFTCAP>(c, stream);
+}
+
+// mx_packed over the ring of head_dim 64 (MxRing64<1> or <2>, by QATTN_MX64_TPS) and of head_dim 256 (MxRing256):
+// each is defined, and instantiated for the four {STEP, SOFTCAP}, in the file that holds its ring
+template <bool STEP, bool SOFTCAP>
+int mx64_packed(const MxSplitCall& c, int causal, long window, void* stream);
+template <bool STEP, bool SOFTCAP>
+int mx256_packed(const MxSplitCall& c, int causal, long window, void* stream);
+
+// a checked packed call of head_dim 64 or 256
+template <bool STEP, bool SOFTCAP>
+static int mx_packed_wide(const MxSplitCall& c, int head_dim, int causal, long window, void* stream) {
+  return head_dim == 64 ? mx64_packed<STEP, SOFTCAP>(c, causal, window, stream)
+                        : mx256_packed<STEP, SOFTCAP>(c, causal, window, stream);
+}
+
+// A packed append into the paged pool ("packed append" above): seq_tab i32 [nseq][4] and tiles i32 [ntiles][2] on
+// the device, the pages the new tokens need in block_table already.  rope: the keys are rotated first
+// (interleaved picks the pairing), V and the lengths as without.
+template <int D>
+int mx_append_packed(bool rope, const void* k, const void* v, const void* k_mean, void* k4, void* kscale, void* vt,
+                     void* vscale, void* vtail, void* lens, const void* block_table, const void* seq_tab,
+                     const void* tiles, long nseq, long ntiles, long tokens, long max_seqs, long kv_heads,
+                     long num_pages, long page_tokens, long max_pages_per_seq, const void* cos_sin,
+                     const void* pos, long max_pos, int interleaved, void* stream) {
+  if (nseq < 0 || ntiles < 0 || tokens < 0 || max_seqs < 1) return 1;
+  if (rope && !mx_rope_ok(cos_sin, pos, max_pos, interleaved)) return 1;
+  if (!k || !v || !k4 || !kscale || !vt || !vscale || !vtail || !lens || !block_table || !seq_tab || !tiles)
+    return 1;
+  const int lgt = mx_page_lgt(page_tokens);
+  if (!mx_pool_ok(num_pages, kv_heads, lgt, max_pages_per_seq)) return 1;
+  if (nseq == 0 || tokens == 0) return 0;
+  if (nseq > max_seqs || nseq > tokens || ntiles < nseq) return 1;
+  if (tokens > 0x7fffffffL / kv_heads || max_seqs > 0x7fffffffL / kv_heads) return 1;
+  const long cap = max_pages_per_seq * page_tokens;
+  // head_dim 256 alone holds the tile list to 2^31 / kv_heads entries; the other two widths came before that
+  // check and accept what they accepted (a list that long passes the thread count below unless the product
+  // overflows)
+  if (D == 256 && ntiles > 0x7fffffffL / kv_heads) return 1;
+  const long nthr = ntiles * kv_heads * D * 2, nblk = tokens * kv_heads * (D / 32);
+  if ((nthr + 255) / 256 > 0x7fffffffL || (nblk + 255) / 256 > 0x7fffffffL) return 1;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(mx_append_vt_packed_kernel<D>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st,
+                     (const _Float16*)v, (const _Float16*)vtail, (uint8_t*)vt, (uint8_t*)vscale,
+                     (const int*)lens, (const int*)seq_tab, (const int*)tiles, nthr, (int)nseq, (int)max_seqs,
+                     (int)kv_heads, tokens, (int)cap, (const int*)block_table, (int)max_pages_per_seq, lgt,
+                     (int)num_pages);
+  const dim3 kgrid((unsigned)((nblk + 255) / 256));
+  if (rope) {
+    auto kern = interleaved ? mx_append_k_packed_rope_kernel<D, true> : mx_append_k_packed_rope_kernel<D, false>;
+    hipLaunchKernelGGL(kern, kgrid, dim3(256), 0, st, (const _Float16*)k, (const _Float16*)v,
+                       (const _Float16*)k_mean, (uint8_t*)k4, (uint8_t*)kscale, (_Float16*)vtail,
+                       (const int*)lens, (const int*)seq_tab, nblk, (int)nseq, (int)max_seqs, (int)kv_heads,
+                       tokens, (int)cap, (const int*)block_table, (int)max_pages_per_seq, lgt, (int)num_pages,
+                       (const float*)cos_sin, (const int*)pos, (int)max_pos);
+  } else {
+    hipLaunchKernelGGL(mx_append_k_packed_kernel<D>, kgrid, dim3(256), 0, st,
+                       (const _Float16*)k, (const _Float16*)v, (const _Float16*)k_mean, (uint8_t*)k4,
+                       (uint8_t*)kscale, (_Float16*)vtail, (const int*)lens, (const int*)seq_tab, nblk,
+                       (int)nseq, (int)max_seqs, (int)kv_heads, tokens, (int)cap, (const int*)block_table,
+                       (int)max_pages_per_seq, lgt, (int)num_pages);
+  }
+  hipLaunchKernelGGL(mx_append_len_packed_kernel, dim3((unsigned)((nseq + 255) / 256)), dim3(256), 0, st,
+                     (int*)lens, (const int*)seq_tab, (int)nseq, (int)max_seqs, tokens, (int)cap);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// ("rotary positions" above) q quantised for the packed step with its rotation; tokens * heads < 2^31 rows, so
+// the grid of D / 32 threads per row is below 2^31 blocks at every width
+template <int D>
+int mx_quant_rows_rope(const void* x, void* q4, void* scale, const void* cos_sin, const void* pos, long tokens,
+                       long heads, long max_pos, int interleaved, void* stream) {
+  if (tokens < 0 || heads < 0 || !mx_rope_ok(cos_sin, pos, max_pos, interleaved)) return 1;
+  if (tokens == 0 || heads == 0) return 0;
+  if (!x || !q4 || !scale || tokens > 0x7fffffffL / heads) return 1;
+  const long nblk = tokens * heads * (D / 32);
+  auto kern = interleaved ? mx_quant_rows_rope_kernel<D, true> : mx_quant_rows_rope_kernel<D, false>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const _Float16*)x, (uint8_t*)q4, (uint8_t*)scale, (const float*)cos_sin, (const int*)pos,
+                     nblk, (int)heads, (int)max_pos);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// the launch of the packed step's merge over rows = tokens * q_heads output rows, behind the entries' checks;
+// sink f32 [q_heads] or null: none
+template <int D>
+int mx_varlen_combine_launch(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
+                             const void* sink, long nseq, long rows, long q_heads, long kv_heads, long part_rows,
+                             void* stream) {
+  const auto kernel = sink ? mxfp4_varlen_combine_kernel<D, true> : mxfp4_varlen_combine_kernel<D, false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((rows * (D / 8) + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const float*)opart, (const float2*)ml, (_Float16*)out, (float*)lse, (const int*)seq_rec,
+                     (int)nseq, rows, (int)q_heads, (int)kv_heads, part_rows, (const float*)sink);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// the launch of the decode step's merge over rows = n * q_heads output rows, behind mx_step_combine_check; sink
+// as above
+template <int D>
+int mx_step_combine_launch(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
+                           const void* sink, long rows, long q_heads, long splits, void* stream) {
+  const auto kernel = sink ? mxfp4_decode_step_combine_kernel<D, true> : mxfp4_decode_step_combine_kernel<D, false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((rows * (D / 8) + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const float*)opart, (const float2*)ml, (_Float16*)out, (float*)lse, (const int*)seq_rec,
+                     rows, (int)q_heads, (int)splits, (const float*)sink);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// their types, for the declarations below and the instantiations in the three files
+typedef int MxAppendPackedFn(bool, const void*, const void*, const void*, void*, void*, void*, void*, void*, void*,
+                             const void*, const void*, const void*, long, long, long, long, long, long, long, long,
+                             const void*, const void*, long, int, void*);
+typedef int MxQuantRowsRopeFn(const void*, void*, void*, const void*, const void*, long, long, long, int, void*);
+typedef int MxVarlenCombineFn(const void*, const void*, void*, void*, const void*, const void*, long, long, long,
+                              long, long, void*);
+typedef int MxStepCombineFn(const void*, const void*, void*, void*, const void*, const void*, long, long, long,
+                            void*);
+// QA_MX_WIDTH(, D) instantiates the four for head_dim D; QA_MX_WIDTH(extern, D) declares that a file does
+#define QA_MX_WIDTH(ext, D)                                      \
+  ext template MxAppendPackedFn mx_append_packed<D>;             \
+  ext template MxQuantRowsRopeFn mx_quant_rows_rope<D>;          \
+  ext template MxVarlenCombineFn mx_varlen_combine_launch<D>;    \
+  ext template MxStepCombineFn mx_step_combine_launch<D>;
+QA_MX_WIDTH(extern, 64)
+QA_MX_WIDTH(extern, 128)
+QA_MX_WIDTH(extern, 256)
+
+}  // namespace qattn

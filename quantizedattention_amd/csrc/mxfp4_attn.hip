@@ -42,13 +42,18 @@
 // tests/mxfp4_split_ref.py merge_bits restates it bit for bit); mx_requant_v_block and mx_append_k_block
 // (the bodies of the padded, paged and packed append kernels, which differ in how a thread finds its
 // sequence, head and source row); and on the host MxSplitCall + mx_split_launch (every key-split entry:
-// its own argument checks, the call filled in, a dispatch on `causal`), mx_varlen_call (the checks and the
-// call of the three packed entries without groups), mx_varlen_paged (the plain and the windowed one),
-// mx_append (the padded and the paged append) and mx_append_packed (the packed append with and without rotary
-// positions; mx_rope_block, the rotation both rope kernels put in front of the one quantiser body, is
-// restated by tests/mxfp4_rope_ref.py and held bit for bit by tests/test_gpu_mxfp4_rope.py).  The two rings, MxRing and MxPagedRing, keep a piece plan each: holding one in common changed the paged kernels' instruction streams.  The C entries
-// stand in the order in which they first use their kernels, which is the order the kernels are emitted
-// in; tools/asm_compare.py compares branch labels too, and those carry the function's number.
+// its own argument checks, the call filled in, a dispatch on `causal`), mx_packed_call (the checks and the call of
+// the packed entries without groups at every head_dim; mx_varlen_call for those of head_dim 128 alone),
+// mx_varlen_paged (the plain and the windowed one), mx_append (the padded and the paged append) and, once for
+// every head_dim in mxfp4_attn.h, mx_append_packed<D> (the packed append with and without rotary positions;
+// mx_rope_block, the rotation both rope kernels put in front of the one quantiser body, is restated by
+// tests/mxfp4_rope_ref.py and held bit for bit by tests/test_gpu_mxfp4_rope.py), mx_quant_rows_rope<D> and the
+// launches of the two merges.  This file instantiates them at head_dim 128; head_dim 64 and 256 go to the
+// instantiations in mxfp4_attn_d64.hip and mxfp4_attn_d256.hip, where mxfp4_attn_packed_kernel, the sibling of
+// mxfp4_attn_split_kernel's VARLEN branch, runs over their rings.  The two rings here, MxRing and MxPagedRing, keep
+// a piece plan each: holding one in common changed the paged kernels' instruction streams.
+// Order: tools/asm_compare.py --labels compares two builds without the emission number a branch label carries, so
+// no entry or kernel of these files has to keep its place for the comparison.
 #include "mxfp4_attn.h"
 
 using namespace qattn;
@@ -263,20 +268,13 @@ static int mx_varlen_paged(const void* q4, const void* qscale, const void* k4, c
                            long num_pages, long page_tokens, long max_pages_per_seq, int causal,
                            int keys_per_split, int head_dim, float qks, long window, long sinks,
                            void* stream) {
-  if (head_dim == 64)   // the kernels of mxfp4_attn_d64.hip
-    return mx64_varlen_paged(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work,
-                             nseq, nwork, tokens, part_rows, max_seqs, kv_heads, group, num_pages, page_tokens,
-                             max_pages_per_seq, causal, keys_per_split, qks, window, sinks, stream);
-  if (head_dim == 256)   // the kernels of mxfp4_attn_d256.hip
-    return mx256_varlen_paged(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work,
-                              nseq, nwork, tokens, part_rows, max_seqs, kv_heads, group, num_pages, page_tokens,
-                              max_pages_per_seq, causal, keys_per_split, qks, window, sinks, stream);
   MxSplitCall c;
-  const int rc = mx_varlen_call(c, q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec,
+  const int rc = mx_packed_call(c, q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec,
                                 work, nseq, nwork, tokens, part_rows, max_seqs, kv_heads, group, num_pages,
                                 page_tokens, max_pages_per_seq, causal, keys_per_split, head_dim, qks, window,
                                 sinks, nullptr);
   if (rc >= 0) return rc;
+  if (head_dim != 128) return mx_packed_wide<false, false>(c, head_dim, causal, window, stream);
   if (window < 1)
     return causal ? mx_split_launch<true, true, true, true, false>(c, stream)
                   : mx_split_launch<false, true, true, true, false>(c, stream);
@@ -315,83 +313,54 @@ extern "C" int qattn_mxfp4_attn_fwd_varlen_paged_window(
                          max_pages_per_seq, causal, keys_per_split, head_dim, qks, window, sinks, stream);
 }
 
-// the merge of the packed step's compact partials into O f16 [tokens][q_heads][head_dim], lse [tokens][q_heads]
-extern "C" int qattn_mxfp4_varlen_combine(const void* opart, const void* ml, void* out, void* lse,
-                                          const void* seq_rec, long nseq, long tokens, long q_heads,
-                                          long kv_heads, long part_rows, int head_dim, void* stream) {
-  if (head_dim == 64)
-    return mx_varlen_combine_ext(opart, ml, out, lse, seq_rec, nullptr, nseq, tokens, q_heads, kv_heads,
-                                 part_rows, 64, stream);
-  if (head_dim == 256)
-    return mx256_varlen_combine(opart, ml, out, lse, seq_rec, nullptr, nseq, tokens, q_heads, kv_heads, part_rows,
-                                stream);
-  if (head_dim != 128 || nseq < 0 || tokens < 0 || part_rows < 0 || !seq_rec) return 1;
+// the merge of the packed step's compact partials into O f16 [tokens][q_heads][head_dim], lse [tokens][q_heads];
+// sink_logit f32 [q_heads] on the device, natural-log units (mx_merge_row SINK: lse then covers the visible keys
+// and the sink), or null: none
+static int mx_varlen_combine(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
+                             const void* sink_logit, long nseq, long tokens, long q_heads, long kv_heads,
+                             long part_rows, int head_dim, void* stream) {
+  if (head_dim != 64 && head_dim != 128 && head_dim != 256) return 1;
+  if (nseq < 0 || tokens < 0 || part_rows < 0 || !seq_rec) return 1;
   if (kv_heads < 1 || q_heads < 1 || q_heads % kv_heads != 0 || q_heads > 0x7fffffffL) return 1;
   if (nseq == 0 || tokens == 0) return 0;
   if (nseq > tokens || part_rows < 1) return 1;
   if (tokens > 0x7fffffffL / q_heads || part_rows > 0x7fffffffL) return 1;
-  const long rows = tokens * q_heads, nthr = rows * (128 / 8);
-  hipLaunchKernelGGL(mxfp4_varlen_combine_kernel<128>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, (const float*)opart, (const float2*)ml, (_Float16*)out,
-                     (float*)lse, (const int*)seq_rec, (int)nseq, rows, (int)q_heads, (int)kv_heads,
-                     part_rows);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+  const auto launch = head_dim == 64    ? mx_varlen_combine_launch<64>
+                      : head_dim == 128 ? mx_varlen_combine_launch<128>
+                                        : mx_varlen_combine_launch<256>;
+  return launch(opart, ml, out, lse, seq_rec, sink_logit, nseq, tokens * q_heads, q_heads, kv_heads, part_rows,
+                stream);
 }
 
-// a packed append into the paged pool ("packed append" above): seq_tab i32 [nseq][4] and tiles i32
-// [ntiles][2] on the device, the pages the new tokens need in block_table already.  ROPE: the keys are
-// rotated first (interleaved picks the pairing), V and the lengths as without.
-template <bool ROPE>
-static int mx_append_packed(const void* k, const void* v, const void* k_mean, void* k4, void* kscale, void* vt,
-                            void* vscale, void* vtail, void* lens, const void* block_table,
-                            const void* seq_tab, const void* tiles, long nseq, long ntiles, long tokens,
-                            long max_seqs, long kv_heads, long num_pages, long page_tokens,
-                            long max_pages_per_seq, int head_dim, const void* cos_sin, const void* pos,
-                            long max_pos, int interleaved, void* stream) {
-  if (head_dim == 64)
-    return mx64_append_packed(ROPE, k, v, k_mean, k4, kscale, vt, vscale, vtail, lens, block_table, seq_tab,
-                              tiles, nseq, ntiles, tokens, max_seqs, kv_heads, num_pages, page_tokens,
-                              max_pages_per_seq, cos_sin, pos, max_pos, interleaved, stream);
-  if (head_dim == 256)
-    return mx256_append_packed(ROPE, k, v, k_mean, k4, kscale, vt, vscale, vtail, lens, block_table, seq_tab,
-                               tiles, nseq, ntiles, tokens, max_seqs, kv_heads, num_pages, page_tokens,
-                               max_pages_per_seq, cos_sin, pos, max_pos, interleaved, stream);
-  if (head_dim != 128 || nseq < 0 || ntiles < 0 || tokens < 0 || max_seqs < 1) return 1;
-  if (ROPE && !mx_rope_ok(cos_sin, pos, max_pos, interleaved)) return 1;
-  if (!k || !v || !k4 || !kscale || !vt || !vscale || !vtail || !lens || !block_table || !seq_tab || !tiles)
-    return 1;
-  const int lgt = mx_page_lgt(page_tokens);
-  if (!mx_pool_ok(num_pages, kv_heads, lgt, max_pages_per_seq)) return 1;
-  if (nseq == 0 || tokens == 0) return 0;
-  if (nseq > max_seqs || nseq > tokens || ntiles < nseq) return 1;
-  if (tokens > 0x7fffffffL / kv_heads || max_seqs > 0x7fffffffL / kv_heads) return 1;
-  const long cap = max_pages_per_seq * page_tokens;
-  const long nthr = ntiles * kv_heads * 128 * 2, nblk = tokens * kv_heads * (128 / 32);
-  if ((nthr + 255) / 256 > 0x7fffffffL || (nblk + 255) / 256 > 0x7fffffffL) return 1;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(mx_append_vt_packed_kernel<128>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st,
-                     (const _Float16*)v, (const _Float16*)vtail, (uint8_t*)vt, (uint8_t*)vscale,
-                     (const int*)lens, (const int*)seq_tab, (const int*)tiles, nthr, (int)nseq, (int)max_seqs,
-                     (int)kv_heads, tokens, (int)cap, (const int*)block_table, (int)max_pages_per_seq, lgt,
-                     (int)num_pages);
-  const dim3 kgrid((unsigned)((nblk + 255) / 256));
-  if constexpr (ROPE) {
-    auto kern = interleaved ? mx_append_k_packed_rope_kernel<128, true> : mx_append_k_packed_rope_kernel<128, false>;
-    hipLaunchKernelGGL(kern, kgrid, dim3(256), 0, st, (const _Float16*)k, (const _Float16*)v,
-                       (const _Float16*)k_mean, (uint8_t*)k4, (uint8_t*)kscale, (_Float16*)vtail,
-                       (const int*)lens, (const int*)seq_tab, nblk, (int)nseq, (int)max_seqs, (int)kv_heads,
-                       tokens, (int)cap, (const int*)block_table, (int)max_pages_per_seq, lgt, (int)num_pages,
-                       (const float*)cos_sin, (const int*)pos, (int)max_pos);
-  } else {
-    hipLaunchKernelGGL(mx_append_k_packed_kernel<128>, kgrid, dim3(256), 0, st,
-                       (const _Float16*)k, (const _Float16*)v, (const _Float16*)k_mean, (uint8_t*)k4,
-                       (uint8_t*)kscale, (_Float16*)vtail, (const int*)lens, (const int*)seq_tab, nblk,
-                       (int)nseq, (int)max_seqs, (int)kv_heads, tokens, (int)cap, (const int*)block_table,
-                       (int)max_pages_per_seq, lgt, (int)num_pages);
-  }
-  hipLaunchKernelGGL(mx_append_len_packed_kernel, dim3((unsigned)((nseq + 255) / 256)), dim3(256), 0, st,
-                     (int*)lens, (const int*)seq_tab, (int)nseq, (int)max_seqs, tokens, (int)cap);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+extern "C" int qattn_mxfp4_varlen_combine(const void* opart, const void* ml, void* out, void* lse,
+                                          const void* seq_rec, long nseq, long tokens, long q_heads,
+                                          long kv_heads, long part_rows, int head_dim, void* stream) {
+  return mx_varlen_combine(opart, ml, out, lse, seq_rec, nullptr, nseq, tokens, q_heads, kv_heads, part_rows,
+                           head_dim, stream);
+}
+
+extern "C" int qattn_mxfp4_varlen_combine_sink(const void* opart, const void* ml, void* out, void* lse,
+                                               const void* seq_rec, const void* sink_logit, long nseq,
+                                               long tokens, long q_heads, long kv_heads, long part_rows,
+                                               int head_dim, void* stream) {
+  if (!sink_logit) return 1;
+  return mx_varlen_combine(opart, ml, out, lse, seq_rec, sink_logit, nseq, tokens, q_heads, kv_heads, part_rows,
+                           head_dim, stream);
+}
+
+// the packed append (mx_append_packed<D>, mxfp4_attn.h) at the entry's head_dim
+static int mx_append_packed_any(bool rope, const void* k, const void* v, const void* k_mean, void* k4, void* kscale,
+                                void* vt, void* vscale, void* vtail, void* lens, const void* block_table,
+                                const void* seq_tab, const void* tiles, long nseq, long ntiles, long tokens,
+                                long max_seqs, long kv_heads, long num_pages, long page_tokens,
+                                long max_pages_per_seq, int head_dim, const void* cos_sin, const void* pos,
+                                long max_pos, int interleaved, void* stream) {
+  if (head_dim != 64 && head_dim != 128 && head_dim != 256) return 1;
+  const auto append = head_dim == 64 ? mx_append_packed<64> : head_dim == 128 ? mx_append_packed<128>
+                                                                              : mx_append_packed<256>;
+  return append(rope, k, v, k_mean, k4, kscale, vt, vscale, vtail, lens, block_table, seq_tab, tiles, nseq, ntiles,
+                tokens, max_seqs, kv_heads, num_pages, page_tokens, max_pages_per_seq, cos_sin, pos, max_pos,
+                interleaved, stream);
 }
 
 extern "C" int qattn_mxfp4_paged_append_packed(const void* k, const void* v, const void* k_mean, void* k4,
@@ -401,9 +370,9 @@ extern "C" int qattn_mxfp4_paged_append_packed(const void* k, const void* v, con
                                                long max_seqs, long kv_heads, long num_pages,
                                                long page_tokens, long max_pages_per_seq, int head_dim,
                                                void* stream) {
-  return mx_append_packed<false>(k, v, k_mean, k4, kscale, vt, vscale, vtail, lens, block_table, seq_tab, tiles,
-                                 nseq, ntiles, tokens, max_seqs, kv_heads, num_pages, page_tokens,
-                                 max_pages_per_seq, head_dim, nullptr, nullptr, 0, 0, stream);
+  return mx_append_packed_any(false, k, v, k_mean, k4, kscale, vt, vscale, vtail, lens, block_table, seq_tab, tiles,
+                              nseq, ntiles, tokens, max_seqs, kv_heads, num_pages, page_tokens, max_pages_per_seq,
+                              head_dim, nullptr, nullptr, 0, 0, stream);
 }
 
 extern "C" int qattn_mxfp4_split_combine(const void* opart, const void* ml, void* out, void* lse,
@@ -422,8 +391,7 @@ extern "C" int qattn_mxfp4_split_combine(const void* opart, const void* ml, void
 // plan of kv_cache_mxfp4.plan_varlen_shared): qattn_mxfp4_attn_fwd_varlen_paged with work records of two
 // kinds, [j, row block, split, 0] as there and [g, row block of group g's stacked rows, split, 1], which
 // one workgroup runs once for every member of the group (grp_rec i32 [ngroup][4], members i32
-// [nmember][2] on the device).  Partials and merge are the plain entry's.  It stands last: its kernels
-// are emitted after every other one of this file.
+// [nmember][2] on the device).  Partials and merge are the plain entry's.
 extern "C" int qattn_mxfp4_attn_fwd_varlen_paged_shared(
     const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt, const void* vscale,
     void* opart, void* ml, const void* lens, const void* block_table, const void* seq_rec, const void* work,
@@ -456,8 +424,7 @@ extern "C" int qattn_mxfp4_attn_fwd_varlen_paged_shared(
 // The packed step with a tree mask on every sequence's last queries (kernel: mxfp4_attn_split_kernel TREE;
 // kv_cache_mxfp4.attention_mxfp4_varlen_paged(tree=)): qattn_mxfp4_attn_fwd_varlen_paged at causal == 2
 // with seq_rec[j][7] = nd_j tree nodes and tree_masks u64 [tokens] on the device, the ancestor word of
-// every packed token (0 outside a tree).  Partials and merge are the plain entry's.  It stands behind
-// every older entry, as its kernel is emitted behind theirs.
+// every packed token (0 outside a tree).  Partials and merge are the plain entry's.
 extern "C" int qattn_mxfp4_attn_fwd_varlen_paged_tree(
     const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt, const void* vscale,
     void* opart, void* ml, const void* lens, const void* block_table, const void* seq_rec, const void* work,
@@ -543,19 +510,10 @@ extern "C" int qattn_mxfp4_paged_rollback(const void* saved, void* vtail, void* 
 extern "C" int qattn_mxfp4_quant_rows_rope(const void* x, void* q4, void* scale, const void* cos_sin,
                                            const void* pos, long tokens, long heads, long max_pos,
                                            int interleaved, int head_dim, void* stream) {
-  if (head_dim == 64)
-    return mx64_quant_rows_rope(x, q4, scale, cos_sin, pos, tokens, heads, max_pos, interleaved, stream);
-  if (head_dim == 256)
-    return mx256_quant_rows_rope(x, q4, scale, cos_sin, pos, tokens, heads, max_pos, interleaved, stream);
-  if (head_dim != 128 || tokens < 0 || heads < 0 || !mx_rope_ok(cos_sin, pos, max_pos, interleaved)) return 1;
-  if (tokens == 0 || heads == 0) return 0;
-  if (!x || !q4 || !scale || tokens > 0x7fffffffL / heads) return 1;
-  const long nblk = tokens * heads * (128 / 32);
-  auto kern = interleaved ? mx_quant_rows_rope_kernel<128, true> : mx_quant_rows_rope_kernel<128, false>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const _Float16*)x, (uint8_t*)q4, (uint8_t*)scale, (const float*)cos_sin, (const int*)pos,
-                     nblk, (int)heads, (int)max_pos);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+  if (head_dim != 64 && head_dim != 128 && head_dim != 256) return 1;
+  const auto quant = head_dim == 64 ? mx_quant_rows_rope<64> : head_dim == 128 ? mx_quant_rows_rope<128>
+                                                                               : mx_quant_rows_rope<256>;
+  return quant(x, q4, scale, cos_sin, pos, tokens, heads, max_pos, interleaved, stream);
 }
 
 extern "C" int qattn_mxfp4_paged_append_packed_rope(
@@ -564,9 +522,9 @@ extern "C" int qattn_mxfp4_paged_append_packed_rope(
     long ntiles, long tokens, long max_seqs, long kv_heads, long num_pages, long page_tokens,
     long max_pages_per_seq, int head_dim, const void* cos_sin, const void* pos, long max_pos, int interleaved,
     void* stream) {
-  return mx_append_packed<true>(k, v, k_mean, k4, kscale, vt, vscale, vtail, lens, block_table, seq_tab, tiles,
-                                nseq, ntiles, tokens, max_seqs, kv_heads, num_pages, page_tokens,
-                                max_pages_per_seq, head_dim, cos_sin, pos, max_pos, interleaved, stream);
+  return mx_append_packed_any(true, k, v, k_mean, k4, kscale, vt, vscale, vtail, lens, block_table, seq_tab, tiles,
+                              nseq, ntiles, tokens, max_seqs, kv_heads, num_pages, page_tokens, max_pages_per_seq,
+                              head_dim, cos_sin, pos, max_pos, interleaved, stream);
 }
 
 // ------------------------------------------------------------------------------ device-planned decode step
@@ -585,7 +543,6 @@ extern "C" int qattn_mxfp4_paged_append_packed_rope(
 // An entry whose b lies outside [0, B) or whose L lies outside [0, cap) is padding: tab {-1, 0, i, 0}, which
 // the append kernels skip, tiles {-1, 0}, pos 0 and ns = 0, so no workgroup runs for it and the merge writes
 // O = 0, lse = -inf.  lens is read only at a checked b; every store goes to row i < n of a table of n rows.
-// (A template over the tile's keys, so that it is emitted where it is first used, behind every older kernel.)
 namespace qattn {
 template <int KT>
 __global__ __launch_bounds__(256) void mx_decode_plan_kernel(const int* __restrict__ slots,
@@ -617,33 +574,6 @@ __global__ __launch_bounds__(256) void mx_decode_plan_kernel(const int* __restri
   reinterpret_cast<v4i*>(seq_rec)[2 * i] = v4i{ok ? b : -1, i, 1, ns};
   reinterpret_cast<v4i*>(seq_rec)[2 * i + 1] = v4i{i * splits * hq, wt0, nst, 0};
 }
-
-// The merge of the step: entry i owns the partial rows [i * splits * Hq, (i + 1) * splits * Hq), laid out
-// [split][query head] (one query: the virtual head order is the head order), so nothing but ns is read from
-// the record and every address lies inside the partials.  mx_merge_row over the entry's ns splits, the
-// arithmetic of mxfp4_varlen_combine_kernel in its order; an entry with ns < 1 (padding) gets O = 0 and lse =
-// -inf.
-template <int D>
-__global__ __launch_bounds__(256) void mxfp4_decode_step_combine_kernel(const float* __restrict__ opart,
-                                                                        const float2* __restrict__ ml,
-                                                                        _Float16* __restrict__ out,
-                                                                        float* __restrict__ lse,
-                                                                        const int* __restrict__ seq_rec, long rows,
-                                                                        int Hq, int splits) {
-  constexpr int TPR = D / 8;
-  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-  const long row = gid / TPR;
-  if (row >= rows) return;
-  const int c = (int)(gid % TPR);
-  const long token = row / Hq;
-  const int ns = min(seq_rec[8 * token + 3], splits);
-  if (ns < 1) {
-    *reinterpret_cast<v8h*>(out + row * D + 8 * c) = v8h{};
-    if (c == 0) lse[row] = -INFINITY;
-    return;
-  }
-  mx_merge_row<D>(opart, ml, token * splits * Hq + row % Hq, Hq, ns, c, out + row * D, lse + row);
-}
 }  // namespace qattn
 
 // (No head_dim: the tables count 64-key tiles, splits, packed rows and partial rows, none of which depends on
@@ -666,10 +596,11 @@ extern "C" int qattn_mxfp4_decode_step_plan(const void* slots, const void* lens,
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
-// The attention of the step over its fixed grid (kernel: mxfp4_attn_split_kernel STEP): n entries x splits
+// The attention of the step over its fixed grid (kernel: mxfp4_attn_split_kernel STEP; head_dim 64 and 256:
+// mxfp4_attn_packed_kernel STEP): n entries x splits
 // work records x kv_heads workgroups, causal, with the window's instantiation for window >= 1.  seq_rec is
 // mx_decode_plan_kernel's, work i32 [n * splits][4] = {i, 0, s, 0} in any order; the partials hold n * splits
-// * kv_heads * group rows.  It stands behind every older entry, as its kernels are emitted behind theirs.
+// * kv_heads * group rows.
 extern "C" int qattn_mxfp4_attn_fwd_decode_step(
     const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt, const void* vscale,
     void* opart, void* ml, const void* lens, const void* block_table, const void* seq_rec, const void* work, long n,
@@ -679,20 +610,13 @@ extern "C" int qattn_mxfp4_attn_fwd_decode_step(
     return 1;
   if (kv_heads > 0x7fffffffL / group || n > 0x7fffffffL / (splits * kv_heads * group)) return 1;
   if (n > 0 && (!q4 || !qscale || !k4 || !kscale || !vt || !vscale || !opart || !ml)) return 1;
-  if (head_dim == 64)   // mxfp4_attn_varlen64_kernel STEP (mxfp4_attn_d64.hip)
-    return mx64_decode_step(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work, n,
-                            splits, max_seqs, kv_heads, group, num_pages, page_tokens, max_pages_per_seq,
-                            keys_per_split, qks, window, sinks, stream);
-  if (head_dim == 256)   // mxfp4_attn_varlen256_kernel STEP (mxfp4_attn_d256.hip)
-    return mx256_decode_step(q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work, n,
-                             splits, max_seqs, kv_heads, group, num_pages, page_tokens, max_pages_per_seq,
-                             keys_per_split, qks, window, sinks, stream);
   MxSplitCall c;
-  const int rc = mx_varlen_call(c, q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work,
+  const int rc = mx_packed_call(c, q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work,
                                 n, n * splits, n, n * splits * kv_heads * group, max_seqs, kv_heads, group,
                                 num_pages, page_tokens, max_pages_per_seq, 2, keys_per_split, head_dim, qks,
                                 window, sinks, nullptr);
   if (rc >= 0) return rc;
+  if (head_dim != 128) return mx_packed_wide<true, false>(c, head_dim, 2, window, stream);   // mxfp4_attn_packed_kernel STEP
   return window < 1 ? mx_split_launch<true, true, true, true, false, false, false, true>(c, stream)
                     : mx_split_launch<true, true, true, true, true, false, false, true>(c, stream);
 }
@@ -708,23 +632,32 @@ static int mx_step_combine_check(const void* opart, const void* ml, const void* 
   return !opart || !ml || !out || !lse || !seq_rec ? 1 : -1;
 }
 
-// the merges of the step that came after the first one (head_dim 64 and 256, and the sink logit at any head_dim), at
-// the end of this file, as their kernels are emitted behind every older one; sink null: none
-static int mx_step_combine_ext(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
-                               const void* sink, long n, long splits, long q_heads, int head_dim, void* stream);
+// the merge of the step (mxfp4_decode_step_combine_kernel); sink f32 [q_heads] on the device or null: none
+static int mx_step_combine(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
+                           const void* sink, long n, long splits, long q_heads, long kv_heads, int head_dim,
+                           void* stream) {
+  const int rc = mx_step_combine_check(opart, ml, out, lse, seq_rec, n, splits, q_heads, kv_heads, head_dim);
+  if (rc >= 0) return rc;
+  const auto launch = head_dim == 64    ? mx_step_combine_launch<64>
+                      : head_dim == 128 ? mx_step_combine_launch<128>
+                                        : mx_step_combine_launch<256>;
+  return launch(opart, ml, out, lse, seq_rec, sink, n * q_heads, q_heads, splits, stream);
+}
 
 extern "C" int qattn_mxfp4_decode_step_combine(const void* opart, const void* ml, void* out, void* lse,
                                                const void* seq_rec, long n, long splits, long q_heads,
                                                long kv_heads, int head_dim, void* stream) {
-  const int rc = mx_step_combine_check(opart, ml, out, lse, seq_rec, n, splits, q_heads, kv_heads, head_dim);
-  if (rc >= 0) return rc;
-  if (head_dim != 128)
-    return mx_step_combine_ext(opart, ml, out, lse, seq_rec, nullptr, n, splits, q_heads, head_dim, stream);
-  const long rows = n * q_heads, nthr = rows * (128 / 8);
-  hipLaunchKernelGGL(mxfp4_decode_step_combine_kernel<128>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, (const float*)opart, (const float2*)ml, (_Float16*)out, (float*)lse,
-                     (const int*)seq_rec, rows, (int)q_heads, (int)splits);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+  return mx_step_combine(opart, ml, out, lse, seq_rec, nullptr, n, splits, q_heads, kv_heads, head_dim, stream);
+}
+
+// with a learned sink logit per query head, which joins the rows of listed entries only: a padding entry gets O =
+// 0 and lse = -inf, not lse = z
+extern "C" int qattn_mxfp4_decode_step_combine_sink(const void* opart, const void* ml, void* out, void* lse,
+                                                    const void* seq_rec, const void* sink_logit, long n,
+                                                    long splits, long q_heads, long kv_heads, int head_dim,
+                                                    void* stream) {
+  if (!sink_logit) return 1;
+  return mx_step_combine(opart, ml, out, lse, seq_rec, sink_logit, n, splits, q_heads, kv_heads, head_dim, stream);
 }
 
 // ------------------------------------------------------------------------------ device-planned verify step
@@ -833,8 +766,7 @@ extern "C" int qattn_mxfp4_verify_step_plan(const void* slots, const void* lens,
 // The attention of the step over its fixed grid (kernel: mxfp4_attn_split_kernel STEP with TREE): n entries x
 // ceil(group * K / 128) row blocks x splits work records x kv_heads workgroups.  seq_rec is
 // mx_verify_plan_kernel's, work i32 [n * row blocks * splits][4] = {i, row block, s, 0} in any order, tree_masks
-// u64 [n * K] the words the plan read; the partials hold n * splits * kv_heads * group * K rows.  It stands behind
-// every older entry, as its kernels are emitted behind theirs.
+// u64 [n * K] the words the plan read; the partials hold n * splits * kv_heads * group * K rows.
 extern "C" int qattn_mxfp4_attn_fwd_verify_step(
     const void* q4, const void* qscale, const void* k4, const void* kscale, const void* vt, const void* vscale,
     void* opart, void* ml, const void* lens, const void* block_table, const void* seq_rec, const void* work,
@@ -870,65 +802,7 @@ extern "C" int qattn_mxfp4_verify_step_combine(const void* opart, const void* ml
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
-// ------------------------------------------------------- decode step: head_dim 64 and the learned sink logit
-// mxfp4_decode_step_combine_kernel with the learned sink logit of the row's query head (mx_merge_row SINK, the
-// arithmetic of mxfp4_varlen_combine_sink_kernel in its order).  The sink joins the rows of listed entries only:
-// a padding entry (ns < 1) is no sequence, and still gets O = 0 and lse = -inf, not lse = z.
+// the packed append, the rope quantiser and the two merges at head_dim 128
 namespace qattn {
-template <int D>
-__global__ __launch_bounds__(256) void mxfp4_decode_step_combine_sink_kernel(
-    const float* __restrict__ opart, const float2* __restrict__ ml, _Float16* __restrict__ out,
-    float* __restrict__ lse, const int* __restrict__ seq_rec, const float* __restrict__ sink, long rows, int Hq,
-    int splits) {
-  constexpr int TPR = D / 8;
-  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-  const long row = gid / TPR;
-  if (row >= rows) return;
-  const int c = (int)(gid % TPR);
-  const long token = row / Hq;
-  const int ns = min(seq_rec[8 * token + 3], splits);
-  if (ns < 1) {
-    *reinterpret_cast<v8h*>(out + row * D + 8 * c) = v8h{};
-    if (c == 0) lse[row] = -INFINITY;
-    return;
-  }
-  mx_merge_row<D, true>(opart, ml, token * splits * Hq + row % Hq, Hq, ns, c, out + row * D, lse + row,
-                        sink[row % Hq]);
-}
-}  // namespace qattn
-
-template <int D>
-static void mx_step_combine_launch(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
-                                   const void* sink, long rows, long q_heads, long splits, void* stream) {
-  const dim3 grid((unsigned)((rows * (D / 8) + 255) / 256));
-  if (sink)
-    hipLaunchKernelGGL(mxfp4_decode_step_combine_sink_kernel<D>, grid, dim3(256), 0, (hipStream_t)stream,
-                       (const float*)opart, (const float2*)ml, (_Float16*)out, (float*)lse, (const int*)seq_rec,
-                       (const float*)sink, rows, (int)q_heads, (int)splits);
-  else
-    hipLaunchKernelGGL(mxfp4_decode_step_combine_kernel<D>, grid, dim3(256), 0, (hipStream_t)stream,
-                       (const float*)opart, (const float2*)ml, (_Float16*)out, (float*)lse, (const int*)seq_rec,
-                       rows, (int)q_heads, (int)splits);
-}
-
-static int mx_step_combine_ext(const void* opart, const void* ml, void* out, void* lse, const void* seq_rec,
-                               const void* sink, long n, long splits, long q_heads, int head_dim, void* stream) {
-  if (head_dim == 256) return mx256_step_combine(opart, ml, out, lse, seq_rec, sink, n, splits, q_heads, stream);
-  if (head_dim == 64)
-    mx_step_combine_launch<64>(opart, ml, out, lse, seq_rec, sink, n * q_heads, q_heads, splits, stream);
-  else if (sink)   // (without one, head_dim 128 is qattn_mxfp4_decode_step_combine's own launch)
-    mx_step_combine_launch<128>(opart, ml, out, lse, seq_rec, sink, n * q_heads, q_heads, splits, stream);
-  else
-    return 1;
-  return hipGetLastError() == hipSuccess ? 0 : 2;
-}
-
-extern "C" int qattn_mxfp4_decode_step_combine_sink(const void* opart, const void* ml, void* out, void* lse,
-                                                    const void* seq_rec, const void* sink_logit, long n,
-                                                    long splits, long q_heads, long kv_heads, int head_dim,
-                                                    void* stream) {
-  if (!sink_logit) return 1;
-  const int rc = mx_step_combine_check(opart, ml, out, lse, seq_rec, n, splits, q_heads, kv_heads, head_dim);
-  if (rc >= 0) return rc;
-  return mx_step_combine_ext(opart, ml, out, lse, seq_rec, sink_logit, n, splits, q_heads, head_dim, stream);
+QA_MX_WIDTH(, 128)
 }

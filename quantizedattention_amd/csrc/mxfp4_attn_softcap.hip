@@ -10,9 +10,9 @@
 // max: mx_tile says why a fixed m = ceil(C) would not do.
 //
 // This file holds the head_dim 128 instantiations of mxfp4_attn_split_kernel (VARLEN + PAGED non-causal, causal
-// and WINDOW, and the STEP form of the two causal ones) and the two C entries; head_dim 64 and 256 go to
-// mx64_softcap / mx256_softcap in the files of those widths.  The kernels stand in a file of their own because
-// they are compiled without packed fp32 arithmetic, as those two files are: the 32 scores of a lane invite the
+// and WINDOW, and the STEP form of the two causal ones) and the two C entries; head_dim 64 and 256 are the
+// SOFTCAP instantiations of mxfp4_attn_packed_kernel in the files of those widths (mx_packed_wide).  The kernels
+// stand in a file of their own because they are compiled without packed fp32 arithmetic, as those two files are: the 32 scores of a lane invite the
 // vectoriser to pair the multiplies and fmas of the tanh, and mxfp4_attn.hip keeps the flags it was measured with.
 #include "mxfp4_attn.h"
 
@@ -41,22 +41,13 @@ extern "C" int qattn_mxfp4_attn_fwd_varlen_paged_softcap(
   float c1, capc;
   if (!mx_softcap_consts(qks, softcap, c1, capc) || !mx_step_window_ok(window, sinks)) return 1;
   if (window >= 1 && causal != 2) return 1;
-  if (head_dim == 64)
-    return mx64_softcap(false, q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work, nseq,
-                        nwork, tokens, part_rows, max_seqs, kv_heads, group, num_pages, page_tokens,
-                        max_pages_per_seq, causal, keys_per_split, window, sinks, c1, capc, stream);
-  if (head_dim == 256)
-    return mx256_softcap(false, q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work, nseq,
-                         nwork, tokens, part_rows, max_seqs, kv_heads, group, num_pages, page_tokens,
-                         max_pages_per_seq, causal, keys_per_split, window, sinks, c1, capc, stream);
   MxSplitCall c;
-  const int rc = mx_varlen_call(c, q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec,
+  const int rc = mx_packed_call(c, q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec,
                                 work, nseq, nwork, tokens, part_rows, max_seqs, kv_heads, group, num_pages,
                                 page_tokens, max_pages_per_seq, causal, keys_per_split, head_dim, qks, window,
-                                sinks, nullptr);
+                                sinks, nullptr, c1, capc);
   if (rc >= 0) return rc;
-  c.vl.cap_c1 = c1;
-  c.vl.cap_c = capc;
+  if (head_dim != 128) return mx_packed_wide<false, true>(c, head_dim, causal, window, stream);
   if (window >= 1) return mx_split_launch<true, true, true, true, true, false, false, false, true>(c, stream);
   return causal ? mx_split_launch<true, true, true, true, false, false, false, false, true>(c, stream)
                 : mx_split_launch<false, true, true, true, false, false, false, false, true>(c, stream);
@@ -76,22 +67,13 @@ extern "C" int qattn_mxfp4_attn_fwd_decode_step_softcap(
     return 1;
   if (kv_heads > 0x7fffffffL / group || n > 0x7fffffffL / (splits * kv_heads * group)) return 1;
   if (n > 0 && (!q4 || !qscale || !k4 || !kscale || !vt || !vscale || !opart || !ml)) return 1;
-  const long part_rows = n * splits * kv_heads * group;
-  if (head_dim == 64)
-    return mx64_softcap(true, q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work, n,
-                        n * splits, n, part_rows, max_seqs, kv_heads, group, num_pages, page_tokens,
-                        max_pages_per_seq, 2, keys_per_split, window, sinks, c1, capc, stream);
-  if (head_dim == 256)
-    return mx256_softcap(true, q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work, n,
-                         n * splits, n, part_rows, max_seqs, kv_heads, group, num_pages, page_tokens,
-                         max_pages_per_seq, 2, keys_per_split, window, sinks, c1, capc, stream);
   MxSplitCall c;
-  const int rc = mx_varlen_call(c, q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work,
-                                n, n * splits, n, part_rows, max_seqs, kv_heads, group, num_pages, page_tokens,
-                                max_pages_per_seq, 2, keys_per_split, head_dim, qks, window, sinks, nullptr);
+  const int rc = mx_packed_call(c, q4, qscale, k4, kscale, vt, vscale, opart, ml, lens, block_table, seq_rec, work,
+                                n, n * splits, n, n * splits * kv_heads * group, max_seqs, kv_heads, group,
+                                num_pages, page_tokens, max_pages_per_seq, 2, keys_per_split, head_dim, qks, window,
+                                sinks, nullptr, c1, capc);
   if (rc >= 0) return rc;
-  c.vl.cap_c1 = c1;
-  c.vl.cap_c = capc;
+  if (head_dim != 128) return mx_packed_wide<true, true>(c, head_dim, 2, window, stream);
   return window < 1 ? mx_split_launch<true, true, true, true, false, false, false, true, true>(c, stream)
                     : mx_split_launch<true, true, true, true, true, false, false, true, true>(c, stream);
 }
