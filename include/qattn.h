@@ -36,7 +36,7 @@ extern "C" {
  * qattn_source_hash() is the sha256 (hex) of the kernel sources and compile flags the library was
  * built from (quantizedattention_amd/_srchash.py); the Python binding refuses a library whose hash
  * differs from the sources beside it (a stale prebuilt library). */
-#define QATTN_ABI_VERSION 12
+#define QATTN_ABI_VERSION 13
 int qattn_abi_version(void);
 const char* qattn_source_hash(void);
 
@@ -675,6 +675,31 @@ int qattn_mxfp4_paged_append_packed_rope(const void* k, const void* v, const voi
                                          long num_pages, long page_tokens, long max_pages_per_seq,
                                          int head_dim, const void* cos_sin, const void* pos, long max_pos,
                                          int interleaved, void* stream);
+
+/* Hadamard-rotated pools (ABI 13; kv_cache_mxfp4.py PagedKVFP4.allocate(hadamard=True)): the two quantisers of the
+ * packed step with an orthogonal rotation of the head dimension between the f16 row and its block scales.  With H
+ * the unnormalised D x D Walsh-Hadamard matrix (Sylvester order, entries +-1), (H q) . (H k) = D (q . k): a pool
+ * whose keys went through qattn_mxfp4_paged_append_packed_had is attended with queries from
+ * qattn_mxfp4_quant_rows_had and qks / D in place of qks (D is a power of two: the division is exact), through the
+ * attention entries as they are.  An outlier channel is spread over all D elements before the blocks are scaled.
+ * Order inside the quantiser: the rotary rotation as defined above (f16 result), f16(x - k_mean) for keys of a
+ * pool with a mean, the transform in fp32, then the e8m0 scale of the fp32 block and its e2m1 codes, with no
+ * rounding to f16 in between.  The transform, bit for bit: the f16 values converted exactly to fp32; stage s = 0 ..
+ * log2(D) - 1 replaces elements i and i + 2^s (bit s of i clear) by (a + b, a - b), each one rounded fp32
+ * operation, no fused multiply-add, no reassociation.  V, vtail and the lengths are the plain entries'.
+ *
+ * Both take the arguments of their _rope siblings; cos_sin == NULL means no rotary rotation (pos, max_pos and
+ * interleaved are then not read).  head_dim 128, 64 or 256.  They return what those entries return. */
+int qattn_mxfp4_quant_rows_had(const void* x, void* q4, void* scale, const void* cos_sin, const void* pos,
+                               long tokens, long heads, long max_pos, int interleaved, int head_dim,
+                               void* stream);
+int qattn_mxfp4_paged_append_packed_had(const void* k, const void* v, const void* k_mean, void* k4, void* kscale,
+                                        void* vt, void* vscale, void* vtail, void* lens,
+                                        const void* block_table, const void* seq_tab, const void* tiles,
+                                        long nseq, long ntiles, long tokens, long max_seqs, long kv_heads,
+                                        long num_pages, long page_tokens, long max_pages_per_seq, int head_dim,
+                                        const void* cos_sin, const void* pos, long max_pos, int interleaved,
+                                        void* stream);
 
 /* The device-planned decode step (kv_cache_mxfp4.py DecodeStep): one new token for each of up to n listed
  * sequences of the pool, with no argument below that a host computed from the lengths, so the launches can

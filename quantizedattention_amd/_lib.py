@@ -105,6 +105,8 @@ SIGNATURES = {
     "qattn_mxfp4_paged_append_packed": [_vp] * 12 + [_c_long] * 8 + [_c_int, _vp],
     "qattn_mxfp4_quant_rows_rope": [_vp] * 5 + [_c_long] * 3 + [_c_int, _c_int, _vp],
     "qattn_mxfp4_paged_append_packed_rope": [_vp] * 12 + [_c_long] * 8 + [_c_int, _vp, _vp, _c_long, _c_int, _vp],
+    "qattn_mxfp4_quant_rows_had": [_vp] * 5 + [_c_long] * 3 + [_c_int, _c_int, _vp],
+    "qattn_mxfp4_paged_append_packed_had": [_vp] * 12 + [_c_long] * 8 + [_c_int, _vp, _vp, _c_long, _c_int, _vp],
     "qattn_mxfp4_decode_step_plan": [_vp] * 6 + [_c_long] * 5 + [_c_int] + [_c_long] * 3 + [_vp],
     "qattn_mxfp4_attn_fwd_decode_step": [_vp] * 12 + [_c_long] * 8 + [_c_int, _c_int, _c_float, _c_long, _c_long,
                                                                        _vp],
@@ -144,7 +146,7 @@ RESTYPES = {"qattn_abi_version": ctypes.c_int, "qattn_source_hash": ctypes.c_cha
             "qattn_int8_bwd_plan": ctypes.c_long, "qattn_bf16_bwd_plan": ctypes.c_long}
 
 # include/qattn.h QATTN_ABI_VERSION: the argument lists SIGNATURES describes
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 _lib = None
 _dev = None

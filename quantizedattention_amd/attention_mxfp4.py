@@ -28,7 +28,7 @@ import torch
 from . import _lib
 
 __all__ = ["mxfp4_quantize_rows", "mxfp4_quantize_v", "mxfp4_attn_fwd", "mxfp4_attn_fwd_kv",
-           "sage_attention_3_fp4", "Rope", "rope_table", "mxfp4_quantize_rows_rope"]
+           "sage_attention_3_fp4", "Rope", "rope_table", "mxfp4_quantize_rows_rope", "mxfp4_quantize_rows_had"]
 
 
 _qk_scale = _lib.qk_scale
@@ -163,6 +163,39 @@ def mxfp4_quantize_rows_rope(x: torch.Tensor, rope: Rope, positions):
     sc = torch.empty((T * H, D // 32), dtype=torch.uint8, device=x.device)
     _lib.call("qattn_mxfp4_quant_rows_rope", _lib.ptr(x), _lib.ptr(q4), _lib.ptr(sc), _lib.ptr(rope.table),
               _lib.ptr(pos), T, H, rope.max_pos, int(rope.interleaved), D, _lib.stream_of(x))
+    return q4, sc
+
+
+def mxfp4_quantize_rows_had(x: torch.Tensor, rope: Rope | None = None, positions=None):
+    """The query quantiser of a Hadamard-rotated pool (``PagedKVFP4.allocate(hadamard=True)``): packed x [T, H, D]
+    (fp16, token-major; D = 128, 64 or 256) -> (packed uint8 [T*H, D/2], scales uint8 [T*H, D/32]) of H x per
+    row, H the unnormalised D x D Walsh-Hadamard matrix applied in fp32 (include/qattn.h defines it bit for bit);
+    the blocks are scaled and packed from the fp32 values.  With ``rope`` and ``positions`` (as in
+    :func:`mxfp4_quantize_rows_rope`) each row is rotated to its position first.  Scores against keys rotated the
+    same way are D times the plain ones: the attention call passes ``qks / D``."""
+    if x.dim() != 3 or x.shape[2] not in ROPE_DIMS:
+        raise _lib.QAttnError("qattn mxfp4 hadamard: packed rows must be x [T, H, D], D = 128, 64 or 256")
+    T, H, D = x.shape
+    if T * H >= 1 << 31:
+        raise _lib.QAttnError("qattn mxfp4 hadamard: fewer than 2^31 packed rows expected")
+    tail = (None, None, T, H, 0, 0)
+    if rope is not None:
+        if not isinstance(rope, Rope):
+            raise _lib.QAttnError("qattn mxfp4 rope: rope must be a Rope")
+        rope.check_head_dim(D)
+        if not _device_positions(positions, T):
+            positions = _host_positions(positions, T, rope.max_pos)
+        _lib.require_gpu(rope.table)
+    elif positions is not None:
+        raise _lib.QAttnError("qattn mxfp4 rope: positions without rope (they place the rotation)")
+    _lib.require_gpu(x)
+    x = _lib.kernel_input(x, torch.float16)
+    if rope is not None:
+        pos = _lib.kernel_input(positions.to(x.device, non_blocking=True))
+        tail = (_lib.ptr(rope.table), _lib.ptr(pos), T, H, rope.max_pos, int(rope.interleaved))
+    q4 = torch.empty((T * H, D // 2), dtype=torch.uint8, device=x.device)
+    sc = torch.empty((T * H, D // 32), dtype=torch.uint8, device=x.device)
+    _lib.call("qattn_mxfp4_quant_rows_had", _lib.ptr(x), _lib.ptr(q4), _lib.ptr(sc), *tail, D, _lib.stream_of(x))
     return q4, sc
 
 

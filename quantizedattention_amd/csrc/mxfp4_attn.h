@@ -61,6 +61,17 @@ QA_DEVICE void mx_quant_row_block(const v8h* src, const v8h* mu, v4i* q4, uint8_
   *sc = (uint8_t)e;
 }
 
+// The same from 32 fp32 values (the Hadamard-rotated rows below): the scale is of their own max, with no rounding
+// to f16 in between.  |f| is 0 or at least 2^-24, a sum of f16 values, so amax is a normal fp32 or 0 here too.
+QA_DEVICE void mx_quant_row_block_f32(const float (&f)[32], v4i* q4, uint8_t* sc) {
+  float amax = 0.f;
+#pragma unroll
+  for (int j = 0; j < 32; ++j) amax = fmaxf(amax, fabsf(f[j]));
+  const unsigned e = e8m0_of(amax);
+  *q4 = pack_fp4x32(f, e8m0_value(e));
+  *sc = (uint8_t)e;
+}
+
 // Q / K: one thread per 32-element block of a row.  x f16 [rows, D] -> q4 [rows, D/2], sc [rows, D/32].
 // With ``mean`` (f16 [rows/seq, D], SageAttention smoothing) the row is first f16(x - mean[row/seq]).
 template <int D>
@@ -155,16 +166,20 @@ QA_DEVICE void mx_requant_v_block(const _Float16* tail, const _Float16* col, int
 
 // One 32-element block of a new K row at token t: quantised as mx_quant_rows_kernel does (mu: the block of
 // the mean, or null) into block o of k4 / ks; the same 32 elements of v go to vdst, their place in vtail,
-// when the token lies in the new last partial tile (end = L + cnt, the length after the append).
-QA_DEVICE void mx_append_k_block(const _Float16* ksrc, const _Float16* vsrc, const v8h* mu, uint8_t* k4,
-                                 uint8_t* ks, long o, _Float16* vdst, int t, int end) {
-  mx_quant_row_block(reinterpret_cast<const v8h*>(ksrc), mu, reinterpret_cast<v4i*>(k4) + o, ks + o);
+// when the token lies in the new last partial tile (end = L + cnt, the length after the append); mx_vtail_block is
+// that store alone.
+QA_DEVICE void mx_vtail_block(const _Float16* vsrc, _Float16* vdst, int t, int end) {
   if (end % 64 != 0 && t / 64 == end / 64) {
     const v8h* src = reinterpret_cast<const v8h*>(vsrc);
     v8h* dst = reinterpret_cast<v8h*>(vdst);
 #pragma unroll
     for (int c = 0; c < 4; ++c) dst[c] = src[c];
   }
+}
+QA_DEVICE void mx_append_k_block(const _Float16* ksrc, const _Float16* vsrc, const v8h* mu, uint8_t* k4,
+                                 uint8_t* ks, long o, _Float16* vdst, int t, int end) {
+  mx_quant_row_block(reinterpret_cast<const v8h*>(ksrc), mu, reinterpret_cast<v4i*>(k4) + o, ks + o);
+  mx_vtail_block(vsrc, vdst, t, end);
 }
 
 // V: one thread per (head, touched tile j, column d, half h) quantises tile g = L / 64 + j of the touched
@@ -1494,6 +1509,133 @@ __global__ __launch_bounds__(256) void mx_append_k_packed_rope_kernel(
                     vtail + (bh * 64 + t % 64) * D + blk * 32, t, L + cnt);
 }
 
+// ---- Hadamard-rotated Q and K (kv_cache_mxfp4.py PagedKVFP4.allocate(hadamard=True))
+// Before its blocks are scaled, a Q or K row of a rotated pool is multiplied by the unnormalised D x D Walsh-
+// Hadamard matrix H (Sylvester order, entries +-1): (Hq) . (Hk) = D (q . k), so the attention kernels see the same
+// scores times the exact power of two D, which the host takes out of qks, while a channel that runs far above the
+// rest is spread evenly over all D elements, hence over every MX block.  Defined bit for bit: the row is the f16
+// values the plain quantiser would take (after the rotary rotation and f16(x - mean)), converted exactly to fp32;
+// stage s = 0 .. log2(D) - 1 replaces elements i and i + 2^s (bit s of i clear) by (a + b, a - b), each ONE rounded
+// fp32 operation, no fused multiply-add and no reassociation -- what separate fp32 tensor operations give
+// (tests/mxfp4_hadamard_ref.py); then mx_quant_row_block_f32 on the fp32 values.
+// Lane plan: the work split of the plain quantisers, one thread per 32-element block, so stages 0 .. 4 are 5 x 16
+// butterflies on the thread's own registers, and the D / 32 blocks of a row sit in D / 32 adjacent lanes, aligned
+// to D / 32 (every grid starts at a row boundary and 256 is a multiple of D / 32): lane bit b IS block-index bit b.
+// Stage 5 + b therefore exchanges with lane ^ (1 << b): DPP quad_perm for b = 0, 1 and, at D = 256, ds_swizzle in
+// bit mode for b = 2 (the LDS crossbar alone: no LDS is allocated, there is no barrier).  The lane whose block bit
+// is clear keeps own + partner, the other partner - own.
+// What the exchange rests on: a lane reads its partner's register, so both must be executing.  Every early exit of
+// the kernels below (i >= nblk with nblk a multiple of D / 32, a token outside its record) depends on the packed
+// token alone, never on the block, so the D / 32 lanes of a row leave together or not at all.
+template <int M>
+QA_DEVICE float mx_lane_xor(float x) {   // x of lane ^ M, M = 1, 2 or 4
+  const int v = __float_as_int(x);
+  // DPP quad_perm [1, 0, 3, 2] and [2, 3, 0, 1]; ds_swizzle in bit mode: and 0x1f, or 0, xor 4
+  if constexpr (M == 1) return __int_as_float(__builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, true));
+  else if constexpr (M == 2) return __int_as_float(__builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, true));
+  else return __int_as_float(__builtin_amdgcn_ds_swizzle(v, 0x101F));
+}
+
+template <int M>
+QA_DEVICE void mx_hadamard_lanes(float (&f)[32], int blk) {
+#pragma clang fp contract(off)
+  const bool second = (blk & M) != 0;
+#pragma unroll
+  for (int j = 0; j < 32; ++j) {
+    const float p = mx_lane_xor<M>(f[j]);
+    f[j] = second ? p - f[j] : f[j] + p;
+  }
+}
+
+// block blk of H x, x the row whose block blk the lane holds in f
+template <int D>
+QA_DEVICE void mx_hadamard_block(float (&f)[32], int blk) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int s = 0; s < 5; ++s)
+#pragma unroll
+    for (int i = 0; i < 32; ++i)
+      if (((i >> s) & 1) == 0) {
+        const float a = f[i], b = f[i + (1 << s)];
+        f[i] = a + b;
+        f[i + (1 << s)] = a - b;
+      }
+  mx_hadamard_lanes<1>(f, blk);
+  if constexpr (D >= 128) mx_hadamard_lanes<2>(f, blk);
+  if constexpr (D >= 256) mx_hadamard_lanes<4>(f, blk);
+}
+
+// The fp32 values of block blk of a row before the transform: rotated by cs (ROPE; mx_rope_block) or as they are,
+// then f16(x - mu) where there is a mean.
+template <int D, bool ROPE, bool IL>
+QA_DEVICE void mx_had_load(const _Float16* row, const float* cs, int blk, const v8h* mu, float (&f)[32]) {
+  v8h r[4];
+  if constexpr (ROPE) {
+    mx_rope_block<D, IL>(row, cs, blk, r);
+  } else {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) r[c] = reinterpret_cast<const v8h*>(row + blk * 32)[c];
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      f[8 * c + j] = mu ? (float)(_Float16)((float)r[c][j] - (float)mu[c][j]) : (float)r[c][j];
+}
+
+// Q: mx_quant_rows_rope_kernel (ROPE) or mx_quant_rows_kernel without a mean on packed rows x f16 [T][H][D], with
+// the transform between the f16 row and the scales.  IL is false without ROPE.
+template <int D, bool ROPE, bool IL>
+__global__ __launch_bounds__(256) void mx_quant_rows_had_kernel(const _Float16* __restrict__ x,
+                                                                uint8_t* __restrict__ q4, uint8_t* __restrict__ sc,
+                                                                const float* __restrict__ cos_sin,
+                                                                const int* __restrict__ pos, long nblk, int H,
+                                                                int max_pos) {
+  constexpr int NB = D / 32;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nblk) return;   // a whole row's lanes at once: see "what the exchange rests on" above
+  const long row = i / NB;
+  const int blk = (int)(i % NB);
+  const float* cs = nullptr;
+  if constexpr (ROPE) cs = cos_sin + (long)min(max(pos[row / H], 0), max_pos - 1) * D;
+  float f[32];
+  mx_had_load<D, ROPE, IL>(x + row * D, cs, blk, nullptr, f);
+  mx_hadamard_block<D>(f, blk);
+  mx_quant_row_block_f32(f, reinterpret_cast<v4i*>(q4) + i, sc + i);
+}
+
+// K and vtail: mx_append_k_packed_kernel / mx_append_k_packed_rope_kernel with the transform behind f16(x - mean);
+// the paged address and the vtail store of V are theirs.
+template <int D, bool ROPE, bool IL>
+__global__ __launch_bounds__(256) void mx_append_k_packed_had_kernel(
+    const _Float16* __restrict__ k, const _Float16* __restrict__ v, const _Float16* __restrict__ mean,
+    uint8_t* __restrict__ k4, uint8_t* __restrict__ ks, _Float16* __restrict__ vtail,
+    const int* __restrict__ lens, const int* __restrict__ tab, long nblk, int nseq, int B, int Hkv, long T,
+    int cap, const int* __restrict__ btab, int mpp, int lgt, int npool, const float* __restrict__ cos_sin,
+    const int* __restrict__ pos, int max_pos) {
+  constexpr int NB = D / 32;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nblk) return;   // both exits take a whole row's lanes at once: they depend on the token alone
+  const int blk = (int)(i % NB);
+  const int hd = (int)(i / NB % Hkv);
+  const int token = (int)(i / NB / Hkv);
+  int slot, first, L;
+  const int cnt = mx_packed_count(tab, lens, mx_find_seq(tab, nseq, 4, 2, token), B, T, cap, slot, first, L);
+  const int tok = token - first;
+  if (tok < 0 || tok >= cnt) return;   // t < L + cnt <= cap
+  const int t = L + tok;
+  const long bh = (long)slot * Hkv + hd;
+  const v8h* mu = mean ? reinterpret_cast<const v8h*>(mean + bh * D + blk * 32) : nullptr;
+  const long o = (mx_paged_tile(btab, slot, hd, t / 64, Hkv, mpp, lgt, npool) * 64 + t % 64) * NB + blk;
+  const float* cs = nullptr;
+  if constexpr (ROPE) cs = cos_sin + (long)min(max(pos[token], 0), max_pos - 1) * D;
+  float f[32];
+  mx_had_load<D, ROPE, IL>(k + (i / NB) * D, cs, blk, mu, f);
+  mx_hadamard_block<D>(f, blk);
+  mx_quant_row_block_f32(f, reinterpret_cast<v4i*>(k4) + o, ks + o);
+  mx_vtail_block(v + i * 32, vtail + (bh * 64 + t % 64) * D + blk * 32, t, L + cnt);
+}
+
 
 // qattn_mxfp4_quant_rows at head_dim 256, behind that entry's checks of mean and seq; nblk = rows * 8 >= 1.  The
 // kernel is instantiated in mxfp4_attn_d256.hip, under that file's flags.
@@ -1660,10 +1802,11 @@ static int mx_packed_wide(const MxSplitCall& c, int head_dim, int causal, long w
 
 // A packed append into the paged pool ("packed append" above): seq_tab i32 [nseq][4] and tiles i32 [ntiles][2] on
 // the device, the pages the new tokens need in block_table already.  rope: the keys are rotated first
-// (interleaved picks the pairing), V and the lengths as without.
+// (interleaved picks the pairing), V and the lengths as without.  had: the pool is Hadamard-rotated, the K launch is
+// mx_append_k_packed_had_kernel (with or without rope); the V and the length launches are the plain ones.
 template <int D>
-int mx_append_packed(bool rope, const void* k, const void* v, const void* k_mean, void* k4, void* kscale, void* vt,
-                     void* vscale, void* vtail, void* lens, const void* block_table, const void* seq_tab,
+int mx_append_packed(bool rope, bool had, const void* k, const void* v, const void* k_mean, void* k4, void* kscale,
+                     void* vt, void* vscale, void* vtail, void* lens, const void* block_table, const void* seq_tab,
                      const void* tiles, long nseq, long ntiles, long tokens, long max_seqs, long kv_heads,
                      long num_pages, long page_tokens, long max_pages_per_seq, const void* cos_sin,
                      const void* pos, long max_pos, int interleaved, void* stream) {
@@ -1690,7 +1833,16 @@ int mx_append_packed(bool rope, const void* k, const void* v, const void* k_mean
                      (int)kv_heads, tokens, (int)cap, (const int*)block_table, (int)max_pages_per_seq, lgt,
                      (int)num_pages);
   const dim3 kgrid((unsigned)((nblk + 255) / 256));
-  if (rope) {
+  if (had) {
+    auto kern = !rope ? mx_append_k_packed_had_kernel<D, false, false>
+                      : interleaved ? mx_append_k_packed_had_kernel<D, true, true>
+                                    : mx_append_k_packed_had_kernel<D, true, false>;
+    hipLaunchKernelGGL(kern, kgrid, dim3(256), 0, st, (const _Float16*)k, (const _Float16*)v,
+                       (const _Float16*)k_mean, (uint8_t*)k4, (uint8_t*)kscale, (_Float16*)vtail,
+                       (const int*)lens, (const int*)seq_tab, nblk, (int)nseq, (int)max_seqs, (int)kv_heads,
+                       tokens, (int)cap, (const int*)block_table, (int)max_pages_per_seq, lgt, (int)num_pages,
+                       (const float*)cos_sin, (const int*)pos, (int)max_pos);
+  } else if (rope) {
     auto kern = interleaved ? mx_append_k_packed_rope_kernel<D, true> : mx_append_k_packed_rope_kernel<D, false>;
     hipLaunchKernelGGL(kern, kgrid, dim3(256), 0, st, (const _Float16*)k, (const _Float16*)v,
                        (const _Float16*)k_mean, (uint8_t*)k4, (uint8_t*)kscale, (_Float16*)vtail,
@@ -1725,6 +1877,24 @@ int mx_quant_rows_rope(const void* x, void* q4, void* scale, const void* cos_sin
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
+// mx_quant_rows_rope for a Hadamard-rotated pool ("Hadamard-rotated Q and K" above); a null cos_sin: no rope (pos,
+// max_pos and interleaved are then not read)
+template <int D>
+int mx_quant_rows_had(const void* x, void* q4, void* scale, const void* cos_sin, const void* pos, long tokens,
+                      long heads, long max_pos, int interleaved, void* stream) {
+  if (tokens < 0 || heads < 0 || (cos_sin && !mx_rope_ok(cos_sin, pos, max_pos, interleaved))) return 1;
+  if (tokens == 0 || heads == 0) return 0;
+  if (!x || !q4 || !scale || tokens > 0x7fffffffL / heads) return 1;
+  const long nblk = tokens * heads * (D / 32);
+  auto kern = !cos_sin ? mx_quant_rows_had_kernel<D, false, false>
+                       : interleaved ? mx_quant_rows_had_kernel<D, true, true>
+                                     : mx_quant_rows_had_kernel<D, true, false>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const _Float16*)x, (uint8_t*)q4, (uint8_t*)scale, (const float*)cos_sin, (const int*)pos,
+                     nblk, (int)heads, (int)max_pos);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
 // the launch of the packed step's merge over rows = tokens * q_heads output rows, behind the entries' checks;
 // sink f32 [q_heads] or null: none
 template <int D>
@@ -1751,18 +1921,19 @@ int mx_step_combine_launch(const void* opart, const void* ml, void* out, void* l
 }
 
 // their types, for the declarations below and the instantiations in the three files
-typedef int MxAppendPackedFn(bool, const void*, const void*, const void*, void*, void*, void*, void*, void*, void*,
-                             const void*, const void*, const void*, long, long, long, long, long, long, long, long,
-                             const void*, const void*, long, int, void*);
+typedef int MxAppendPackedFn(bool, bool, const void*, const void*, const void*, void*, void*, void*, void*, void*,
+                             void*, const void*, const void*, const void*, long, long, long, long, long, long, long,
+                             long, const void*, const void*, long, int, void*);
 typedef int MxQuantRowsRopeFn(const void*, void*, void*, const void*, const void*, long, long, long, int, void*);
 typedef int MxVarlenCombineFn(const void*, const void*, void*, void*, const void*, const void*, long, long, long,
                               long, long, void*);
 typedef int MxStepCombineFn(const void*, const void*, void*, void*, const void*, const void*, long, long, long,
                             void*);
-// QA_MX_WIDTH(, D) instantiates the four for head_dim D; QA_MX_WIDTH(extern, D) declares that a file does
+// QA_MX_WIDTH(, D) instantiates the five for head_dim D; QA_MX_WIDTH(extern, D) declares that a file does
 #define QA_MX_WIDTH(ext, D)                                      \
   ext template MxAppendPackedFn mx_append_packed<D>;             \
   ext template MxQuantRowsRopeFn mx_quant_rows_rope<D>;          \
+  ext template MxQuantRowsRopeFn mx_quant_rows_had<D>;           \
   ext template MxVarlenCombineFn mx_varlen_combine_launch<D>;    \
   ext template MxStepCombineFn mx_step_combine_launch<D>;
 QA_MX_WIDTH(extern, 64)

@@ -349,8 +349,8 @@ extern "C" int qattn_mxfp4_varlen_combine_sink(const void* opart, const void* ml
 }
 
 // the packed append (mx_append_packed<D>, mxfp4_attn.h) at the entry's head_dim
-static int mx_append_packed_any(bool rope, const void* k, const void* v, const void* k_mean, void* k4, void* kscale,
-                                void* vt, void* vscale, void* vtail, void* lens, const void* block_table,
+static int mx_append_packed_any(bool rope, bool had, const void* k, const void* v, const void* k_mean, void* k4,
+                                void* kscale, void* vt, void* vscale, void* vtail, void* lens, const void* block_table,
                                 const void* seq_tab, const void* tiles, long nseq, long ntiles, long tokens,
                                 long max_seqs, long kv_heads, long num_pages, long page_tokens,
                                 long max_pages_per_seq, int head_dim, const void* cos_sin, const void* pos,
@@ -358,7 +358,7 @@ static int mx_append_packed_any(bool rope, const void* k, const void* v, const v
   if (head_dim != 64 && head_dim != 128 && head_dim != 256) return 1;
   const auto append = head_dim == 64 ? mx_append_packed<64> : head_dim == 128 ? mx_append_packed<128>
                                                                               : mx_append_packed<256>;
-  return append(rope, k, v, k_mean, k4, kscale, vt, vscale, vtail, lens, block_table, seq_tab, tiles, nseq, ntiles,
+  return append(rope, had, k, v, k_mean, k4, kscale, vt, vscale, vtail, lens, block_table, seq_tab, tiles, nseq, ntiles,
                 tokens, max_seqs, kv_heads, num_pages, page_tokens, max_pages_per_seq, cos_sin, pos, max_pos,
                 interleaved, stream);
 }
@@ -370,9 +370,9 @@ extern "C" int qattn_mxfp4_paged_append_packed(const void* k, const void* v, con
                                                long max_seqs, long kv_heads, long num_pages,
                                                long page_tokens, long max_pages_per_seq, int head_dim,
                                                void* stream) {
-  return mx_append_packed_any(false, k, v, k_mean, k4, kscale, vt, vscale, vtail, lens, block_table, seq_tab, tiles,
-                              nseq, ntiles, tokens, max_seqs, kv_heads, num_pages, page_tokens, max_pages_per_seq,
-                              head_dim, nullptr, nullptr, 0, 0, stream);
+  return mx_append_packed_any(false, false, k, v, k_mean, k4, kscale, vt, vscale, vtail, lens, block_table, seq_tab,
+                              tiles, nseq, ntiles, tokens, max_seqs, kv_heads, num_pages, page_tokens,
+                              max_pages_per_seq, head_dim, nullptr, nullptr, 0, 0, stream);
 }
 
 extern "C" int qattn_mxfp4_split_combine(const void* opart, const void* ml, void* out, void* lse,
@@ -522,9 +522,32 @@ extern "C" int qattn_mxfp4_paged_append_packed_rope(
     long ntiles, long tokens, long max_seqs, long kv_heads, long num_pages, long page_tokens,
     long max_pages_per_seq, int head_dim, const void* cos_sin, const void* pos, long max_pos, int interleaved,
     void* stream) {
-  return mx_append_packed_any(true, k, v, k_mean, k4, kscale, vt, vscale, vtail, lens, block_table, seq_tab, tiles,
-                              nseq, ntiles, tokens, max_seqs, kv_heads, num_pages, page_tokens, max_pages_per_seq,
-                              head_dim, cos_sin, pos, max_pos, interleaved, stream);
+  return mx_append_packed_any(true, false, k, v, k_mean, k4, kscale, vt, vscale, vtail, lens, block_table, seq_tab,
+                              tiles, nseq, ntiles, tokens, max_seqs, kv_heads, num_pages, page_tokens,
+                              max_pages_per_seq, head_dim, cos_sin, pos, max_pos, interleaved, stream);
+}
+
+// ------------------------------------------------------------------------------ Hadamard-rotated pools
+// ("Hadamard-rotated Q and K" in mxfp4_attn.h) the two quantiser entries of a pool made with hadamard=True: the rope
+// entries above with the transform between the f16 row and its scales; a null cos_sin: no rope
+extern "C" int qattn_mxfp4_quant_rows_had(const void* x, void* q4, void* scale, const void* cos_sin,
+                                          const void* pos, long tokens, long heads, long max_pos, int interleaved,
+                                          int head_dim, void* stream) {
+  if (head_dim != 64 && head_dim != 128 && head_dim != 256) return 1;
+  const auto quant = head_dim == 64 ? mx_quant_rows_had<64> : head_dim == 128 ? mx_quant_rows_had<128>
+                                                                              : mx_quant_rows_had<256>;
+  return quant(x, q4, scale, cos_sin, pos, tokens, heads, max_pos, interleaved, stream);
+}
+
+extern "C" int qattn_mxfp4_paged_append_packed_had(
+    const void* k, const void* v, const void* k_mean, void* k4, void* kscale, void* vt, void* vscale,
+    void* vtail, void* lens, const void* block_table, const void* seq_tab, const void* tiles, long nseq,
+    long ntiles, long tokens, long max_seqs, long kv_heads, long num_pages, long page_tokens,
+    long max_pages_per_seq, int head_dim, const void* cos_sin, const void* pos, long max_pos, int interleaved,
+    void* stream) {
+  return mx_append_packed_any(cos_sin != nullptr, true, k, v, k_mean, k4, kscale, vt, vscale, vtail, lens,
+                              block_table, seq_tab, tiles, nseq, ntiles, tokens, max_seqs, kv_heads, num_pages,
+                              page_tokens, max_pages_per_seq, head_dim, cos_sin, pos, max_pos, interleaved, stream);
 }
 
 // ------------------------------------------------------------------------------ device-planned decode step
@@ -802,7 +825,7 @@ extern "C" int qattn_mxfp4_verify_step_combine(const void* opart, const void* ml
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
-// the packed append, the rope quantiser and the two merges at head_dim 128
+// the packed append, the two packed quantisers and the two merges at head_dim 128
 namespace qattn {
 QA_MX_WIDTH(, 128)
 }

@@ -99,7 +99,7 @@ template int mx256_packed<true, false>(const MxSplitCall&, int, long, void*);   
 template int mx256_packed<false, true>(const MxSplitCall&, int, long, void*);    // and the two with a cap
 template int mx256_packed<true, true>(const MxSplitCall&, int, long, void*);
 
-// the packed append, the rope quantiser and the two merges at head_dim 256
+// the packed append, the two packed quantisers and the two merges at head_dim 256
 QA_MX_WIDTH(, 256)
 
 // qattn_mxfp4_quant_rows at head_dim 256, behind that entry's checks of mean and seq; nblk = rows * 8 >= 1

@@ -130,7 +130,7 @@ template int mx64_packed<true, false>(const MxSplitCall&, int, long, void*);    
 template int mx64_packed<false, true>(const MxSplitCall&, int, long, void*);    // and the two with a cap
 template int mx64_packed<true, true>(const MxSplitCall&, int, long, void*);
 
-// the packed append, the rope quantiser and the two merges at head_dim 64
+// the packed append, the two packed quantisers and the two merges at head_dim 64
 QA_MX_WIDTH(, 64)
 
 }  // namespace qattn

@@ -56,6 +56,12 @@
 //       -> (seq_tab, tiles, pos, seq_rec): kv_cache_mxfp4.VerifyStep's tables, derived on the device
 //   mxfp4_verify_step(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, tree, draft_tokens, splits,
 //       keys_per_split) -> (O, lse): kv_cache_mxfp4.VerifyStep.attend over its fixed grid
+//   mxfp4_quant_rows_had(x, cos_sin=None, pos=None, interleaved=False) -> (q4, qs)
+//       attention_mxfp4.mxfp4_quantize_rows_had: the query quantiser of a Hadamard-rotated pool, with rope when
+//       cos_sin and pos are given
+//   mxfp4_varlen_paged_had(.. the arguments of mxfp4_varlen_paged_softcap .., cos_sin=None, pos=None,
+//       interleaved=False) -> (O, lse): the plain, windowed, capped or rope call on a Hadamard-rotated pool
+//   (mxfp4_decode_step and mxfp4_verify_step take a trailing hadamard=False for such a pool)
 // Workspaces, head chunks and key splits are planned by the library (csrc/plan.hip), as in the drop-ins.
 // Errors: TORCH_CHECK (c10::Error, RuntimeError in Python) with the drop-ins' messages; int8_quant's
 // argument checks raise ValueError (TORCH_CHECK_VALUE) as its Python predecessor did.
@@ -619,6 +625,32 @@ std::tuple<Tensor, Tensor> mxfp4_quant_rows_rope(const Tensor& x_in, const Tenso
   return {q4, qs};
 }
 
+// attention_mxfp4.mxfp4_quantize_rows_had: packed x [T, H, D] through the query quantiser of a Hadamard-rotated pool
+// (include/qattn.h "Hadamard-rotated pools"), each row rotated by pos[token] first when cos_sin and pos are given
+std::tuple<Tensor, Tensor> mxfp4_quant_rows_had(const Tensor& x_in, const c10::optional<Tensor>& cos_sin,
+                                                const c10::optional<Tensor>& pos, bool interleaved) {
+  require_gpu({&x_in});
+  TORCH_CHECK(x_in.dim() == 3 && mx_packed_dim(x_in.size(2)),
+              "qattn mxfp4 hadamard: packed rows must be x [T, H, D], D = 128, 64 or 256");
+  TORCH_CHECK(cos_sin.has_value() == pos.has_value(), "qattn mxfp4 rope: cos_sin and pos come together");
+  const int64_t T = x_in.size(0), H = x_in.size(1), D = x_in.size(2);
+  Ctx c(x_in);
+  const Tensor x = kin(x_in, at::kHalf);
+  Tensor q4 = empty({T * H, D / 2}, at::kByte, x), qs = empty({T * H, D / 32}, at::kByte, x);
+  if (cos_sin.has_value()) {
+    const RopeArgs rope{*cos_sin, *pos, interleaved};
+    check_rope(rope, T, D);
+    const Tensor p = kin(*pos);
+    call(qattn_mxfp4_quant_rows_had(P(x), P(q4), P(qs), P(*cos_sin), P(p), T, H, cos_sin->size(0), interleaved,
+                                    (int)D, c.stream),
+         "quantise rotated rows (hadamard)");
+  } else {
+    call(qattn_mxfp4_quant_rows_had(P(x), P(q4), P(qs), nullptr, nullptr, T, H, 0, 0, (int)D, c.stream),
+         "quantise rows (hadamard)");
+  }
+  return {q4, qs};
+}
+
 // kv_cache_mxfp4.attention_mxfp4_varlen_paged on a page pool's operands: packed q [T, Hq, 128], lens i32
 // [B] and block_table i32 [B, max_pages_per_seq] on the device, and the two tables of
 // kv_cache_mxfp4.plan_varlen as device tensors, seq_rec i32 [nseq, 8] and work i32 [nwork, 4], with the
@@ -626,7 +658,8 @@ std::tuple<Tensor, Tensor> mxfp4_quant_rows_rope(const Tensor& x_in, const Tenso
 // the caller guarantees that they are a plan of the pool's lengths (the Python wrapper
 // ops.mxfp4_varlen_paged builds them from the cache's host mirror); the kernels keep every address a
 // wrong table names inside the buffers.  With `windowed` the plan is plan_varlen's for (window, sinks) and
-// the forward is qattn_mxfp4_attn_fwd_varlen_paged_window.  With `rope` q is rotated inside its quantiser.
+// the forward is qattn_mxfp4_attn_fwd_varlen_paged_window.  With `rope` q is rotated inside its quantiser.  With
+// `had` the pool is Hadamard-rotated: q goes through qattn_mxfp4_quant_rows_had and qks is divided by D.
 std::tuple<Tensor, Tensor> mxfp4_varlen_paged_run(const Tensor& q_in, const Tensor& k4, const Tensor& ks,
                                                   const Tensor& vt, const Tensor& vs, const Tensor& lens,
                                                   const Tensor& block_table, const Tensor& seq_rec,
@@ -636,7 +669,7 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged_run(const Tensor& q_in, const Tens
                                                   const Tensor* members = nullptr,
                                                   const Tensor* tree = nullptr,
                                                   const RopeArgs* rope = nullptr, double softcap = 0.,
-                                                  double qks_in = 0.) {
+                                                  double qks_in = 0., bool had = false) {
   require_gpu({&q_in, &k4, &ks, &vt, &vs, &lens, &block_table, &seq_rec, &work});
   if (rope) check_rope(*rope, q_in.dim() == 3 ? q_in.size(0) : -1, q_in.dim() == 3 ? q_in.size(2) : 128);
   if (tree) {   // the tree entry's ancestor words, one per packed token
@@ -687,7 +720,13 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged_run(const Tensor& q_in, const Tens
   const Tensor q = kin(q_in, at::kHalf);
   Tensor q4 = empty({T * Hq, D / 2}, at::kByte, q), qs = empty({T * Hq, D / 32}, at::kByte, q);
   Tensor out = empty({T, Hq, D}, at::kHalf, q), lse = empty({T, Hq}, at::kFloat, q);
-  if (rope) {
+  if (had) {
+    const Tensor p = rope ? kin(rope->pos) : Tensor();
+    call(qattn_mxfp4_quant_rows_had(P(q), P(q4), P(qs), rope ? P(rope->cos_sin) : nullptr, rope ? P(p) : nullptr,
+                                    T, Hq, rope ? rope->cos_sin.size(0) : 0, rope && rope->interleaved, (int)D,
+                                    c.stream),
+         "quantise q (hadamard)");
+  } else if (rope) {
     const Tensor p = kin(rope->pos);
     call(qattn_mxfp4_quant_rows_rope(P(q), P(q4), P(qs), P(rope->cos_sin), P(p), T, Hq, rope->cos_sin.size(0),
                                      rope->interleaved, (int)D, c.stream),
@@ -696,7 +735,8 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged_run(const Tensor& q_in, const Tens
     call(qattn_mxfp4_quant_rows(P(q), nullptr, P(q4), P(qs), T * Hq, Hq, (int)D, c.stream), "quantise q");
   }
   Tensor opart = empty({part_rows, D}, at::kFloat, q), ml = empty({part_rows, 2}, at::kFloat, q);
-  const float qks = qks_in > 0. ? (float)qks_in : qk_scale(D);
+  // a rotated pool's scores are D times the plain ones; D is a power of two, so the division is exact
+  const float qks = (qks_in > 0. ? (float)qks_in : qk_scale(D)) / (had ? (float)D : 1.f);
   if (softcap > 0.)
     call(qattn_mxfp4_attn_fwd_varlen_paged_softcap(
              P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens), P(block_table), P(seq_rec),
@@ -814,6 +854,31 @@ std::tuple<Tensor, Tensor> mxfp4_varlen_paged_softcap(const Tensor& q, const Ten
                                 softcap, qks);
 }
 
+// the call above on a Hadamard-rotated pool (kv_cache_mxfp4.PagedKVFP4.allocate(hadamard=True)), with q rotated to
+// pos first when cos_sin and pos are given: qks is the PLAIN scale (0: 1 / sqrt(D)), the operator divides it by D
+std::tuple<Tensor, Tensor> mxfp4_varlen_paged_had(const Tensor& q, const Tensor& k4, const Tensor& ks,
+                                                  const Tensor& vt, const Tensor& vs, const Tensor& lens,
+                                                  const Tensor& block_table, const Tensor& seq_rec,
+                                                  const Tensor& work, int64_t part_rows, int64_t causal,
+                                                  int64_t keys_per_split, int64_t window, int64_t sinks,
+                                                  double softcap, double qks, const c10::optional<Tensor>& cos_sin,
+                                                  const c10::optional<Tensor>& pos, bool interleaved) {
+  TORCH_CHECK(window >= 0 && sinks >= 0 && (window > 0 || sinks == 0) && (window == 0 || causal == 1),
+              "qattn mxfp4 paged cache: window >= 0 (0: none), sinks >= 0 only with a window, a window only with "
+              "causal 1");
+  TORCH_CHECK(std::isfinite(softcap) && softcap >= 0. && std::isfinite(qks) && qks >= 0.,
+              "qattn mxfp4 paged cache: softcap and qks must be finite and >= 0 (0: no cap, the default scale)");
+  TORCH_CHECK(cos_sin.has_value() == pos.has_value(), "qattn mxfp4 rope: cos_sin and pos come together");
+  if (!cos_sin.has_value())
+    return mxfp4_varlen_paged_run(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal,
+                                  keys_per_split, window > 0, window, sinks, nullptr, nullptr, nullptr, nullptr,
+                                  softcap, qks, true);
+  const RopeArgs rope{*cos_sin, *pos, interleaved};
+  return mxfp4_varlen_paged_run(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal,
+                                keys_per_split, window > 0, window, sinks, nullptr, nullptr, nullptr, &rope, softcap,
+                                qks, true);
+}
+
 // kv_cache_mxfp4.DecodeStep's plan as an operator: from slots i32 [n] and the pool's lens i32 [B] (the lengths
 // BEFORE the step's append) the four device tables of qattn_mxfp4_decode_step_plan, seq_tab i32 [n, 4], tiles
 // i32 [n, 2], pos i32 [n] and seq_rec i32 [n, 8].  Nothing is read back; window 0: none.
@@ -841,13 +906,14 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> mxfp4_decode_step_plan(const Tensor& 
 
 // kv_cache_mxfp4.DecodeStep.attend as an operator: q [n, Hq, D], D = 128, 64 or 256 and the pool's, the pool's
 // operands, lens (AFTER the step's append) and block table, seq_rec i32 [n, 8] of the plan above and work i32 [n
-// * splits, 4] = {i, 0, s, 0}; sink_logit f32 [Hq] on the device (natural-log units) or None.
+// * splits, 4] = {i, 0, s, 0}; sink_logit f32 [Hq] on the device (natural-log units) or None.  hadamard: the pool is
+// Hadamard-rotated (q through qattn_mxfp4_quant_rows_had, qks / D).
 std::tuple<Tensor, Tensor> mxfp4_decode_step(const Tensor& q_in, const Tensor& k4, const Tensor& ks,
                                              const Tensor& vt, const Tensor& vs, const Tensor& lens,
                                              const Tensor& block_table, const Tensor& seq_rec, const Tensor& work,
                                              int64_t splits, int64_t keys_per_split, int64_t window,
                                              int64_t sinks, const c10::optional<Tensor>& sink_logit,
-                                             double softcap, double qks_in) {
+                                             double softcap, double qks_in, bool hadamard) {
   require_gpu({&q_in, &k4, &ks, &vt, &vs, &lens, &block_table, &seq_rec, &work});
   TORCH_CHECK(q_in.dim() == 3 && k4.dim() == 4 && mx_packed_dim(q_in.size(2)) && k4.size(3) * 2 == q_in.size(2),
               "qattn mxfp4 decode step: q must be [n, Hq, D], D = 128, 64 or 256, the pool's head_dim");
@@ -884,10 +950,14 @@ std::tuple<Tensor, Tensor> mxfp4_decode_step(const Tensor& q_in, const Tensor& k
   Tensor q4 = empty({n * Hq, D / 2}, at::kByte, q), qs = empty({n * Hq, D / 32}, at::kByte, q);
   Tensor out = empty({n, Hq, D}, at::kHalf, q), lse = empty({n, Hq}, at::kFloat, q);
   Tensor opart = empty({n * splits * Hq, D}, at::kFloat, q), ml = empty({n * splits * Hq, 2}, at::kFloat, q);
-  call(qattn_mxfp4_quant_rows(P(q), nullptr, P(q4), P(qs), n * Hq, Hq, (int)D, c.stream), "quantise q");
+  if (hadamard)
+    call(qattn_mxfp4_quant_rows_had(P(q), P(q4), P(qs), nullptr, nullptr, n, Hq, 0, 0, (int)D, c.stream),
+         "quantise q (hadamard)");
+  else
+    call(qattn_mxfp4_quant_rows(P(q), nullptr, P(q4), P(qs), n * Hq, Hq, (int)D, c.stream), "quantise q");
   TORCH_CHECK(std::isfinite(softcap) && softcap >= 0. && std::isfinite(qks_in) && qks_in >= 0.,
               "qattn mxfp4 decode step: softcap and qks must be finite and >= 0 (0: no cap, the default scale)");
-  const float qks = qks_in > 0. ? (float)qks_in : qk_scale(D);
+  const float qks = (qks_in > 0. ? (float)qks_in : qk_scale(D)) / (hadamard ? (float)D : 1.f);
   if (softcap > 0.)
     call(qattn_mxfp4_attn_fwd_decode_step_softcap(P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens),
                                                   P(block_table), P(seq_rec), P(work), n, splits, B, Hkv, Hq / Hkv,
@@ -946,7 +1016,7 @@ std::tuple<Tensor, Tensor> mxfp4_verify_step(const Tensor& q_in, const Tensor& k
                                              const Tensor& vt, const Tensor& vs, const Tensor& lens,
                                              const Tensor& block_table, const Tensor& seq_rec, const Tensor& work,
                                              const Tensor& tree, int64_t draft_tokens, int64_t splits,
-                                             int64_t keys_per_split) {
+                                             int64_t keys_per_split, bool hadamard) {
   require_gpu({&q_in, &k4, &ks, &vt, &vs, &lens, &block_table, &seq_rec, &work, &tree});
   TORCH_CHECK(q_in.dim() == 3 && k4.dim() == 4 && q_in.size(2) == 128 && k4.size(3) == 64,
               "qattn mxfp4 verify step: q must be [n * draft_tokens, Hq, 128], head_dim 128 in the pool");
@@ -982,10 +1052,15 @@ std::tuple<Tensor, Tensor> mxfp4_verify_step(const Tensor& q_in, const Tensor& k
   Tensor q4 = empty({T * Hq, D / 2}, at::kByte, q), qs = empty({T * Hq, D / 32}, at::kByte, q);
   Tensor out = empty({T, Hq, D}, at::kHalf, q), lse = empty({T, Hq}, at::kFloat, q);
   Tensor opart = empty({n * splits * Hq * K, D}, at::kFloat, q), ml = empty({n * splits * Hq * K, 2}, at::kFloat, q);
-  call(qattn_mxfp4_quant_rows(P(q), nullptr, P(q4), P(qs), T * Hq, Hq, (int)D, c.stream), "quantise q");
+  if (hadamard)   // a Hadamard-rotated pool: q rotated like its keys, the scores D times the plain ones
+    call(qattn_mxfp4_quant_rows_had(P(q), P(q4), P(qs), nullptr, nullptr, T, Hq, 0, 0, (int)D, c.stream),
+         "quantise q (hadamard)");
+  else
+    call(qattn_mxfp4_quant_rows(P(q), nullptr, P(q4), P(qs), T * Hq, Hq, (int)D, c.stream), "quantise q");
   call(qattn_mxfp4_attn_fwd_verify_step(P(q4), P(qs), P(k4), P(ks), P(vt), P(vs), P(opart), P(ml), P(lens),
                                         P(block_table), P(seq_rec), P(work), P(tree), n, K, splits, B, Hkv,
-                                        Hq / Hkv, NP, PT, mpp, (int)keys_per_split, (int)D, qk_scale(D), c.stream),
+                                        Hq / Hkv, NP, PT, mpp, (int)keys_per_split, (int)D,
+                                        qk_scale(D) / (hadamard ? (float)D : 1.f), c.stream),
        "mxfp4 verify step forward");
   call(qattn_mxfp4_verify_step_combine(P(opart), P(ml), P(out), P(lse), P(seq_rec), n, K, splits, Hq, Hkv, (int)D,
                                        c.stream),
@@ -1032,15 +1107,21 @@ TORCH_LIBRARY(qattn, m) {
         "int keys_per_split, int splits, int window, int sinks) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("mxfp4_decode_step(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, Tensor block_table, "
         "Tensor seq_rec, Tensor work, int splits, int keys_per_split, int window, int sinks, "
-        "Tensor? sink_logit=None, float softcap=0., float qks=0.) -> (Tensor, Tensor)");
+        "Tensor? sink_logit=None, float softcap=0., float qks=0., bool hadamard=False) -> (Tensor, Tensor)");
   m.def("mxfp4_varlen_paged_softcap(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, "
         "Tensor block_table, Tensor seq_rec, Tensor work, int part_rows, int causal, int keys_per_split, "
         "int window, int sinks, float softcap, float qks) -> (Tensor, Tensor)");
   m.def("mxfp4_verify_step_plan(Tensor slots, Tensor lens, Tensor tree, int draft_tokens, int capacity, "
         "int kv_heads, int group, int keys_per_split, int splits) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("mxfp4_verify_step(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, Tensor block_table, "
-        "Tensor seq_rec, Tensor work, Tensor tree, int draft_tokens, int splits, int keys_per_split) "
-        "-> (Tensor, Tensor)");
+        "Tensor seq_rec, Tensor work, Tensor tree, int draft_tokens, int splits, int keys_per_split, "
+        "bool hadamard=False) -> (Tensor, Tensor)");
+  m.def("mxfp4_quant_rows_had(Tensor x, Tensor? cos_sin=None, Tensor? pos=None, bool interleaved=False) -> "
+        "(Tensor, Tensor)");
+  m.def("mxfp4_varlen_paged_had(Tensor q, Tensor k4, Tensor ks, Tensor vt, Tensor vs, Tensor lens, "
+        "Tensor block_table, Tensor seq_rec, Tensor work, int part_rows, int causal, int keys_per_split, "
+        "int window, int sinks, float softcap, float qks, Tensor? cos_sin=None, Tensor? pos=None, "
+        "bool interleaved=False) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
@@ -1066,4 +1147,6 @@ TORCH_LIBRARY_IMPL(qattn, CUDA, m) {
   m.impl("mxfp4_decode_step", &mxfp4_decode_step);
   m.impl("mxfp4_verify_step_plan", &mxfp4_verify_step_plan);
   m.impl("mxfp4_verify_step", &mxfp4_verify_step);
+  m.impl("mxfp4_quant_rows_had", &mxfp4_quant_rows_had);
+  m.impl("mxfp4_varlen_paged_had", &mxfp4_varlen_paged_had);
 }

@@ -177,6 +177,19 @@ time, so another tree costs no new capture.  A round is ``checkpoint`` BEFORE ``
 mirror lengths), then ``append`` / ``attend`` or their replay, then ``rollback`` or ``accept`` as on the
 host-planned path.  No window, no ``share_prefix``, one K for every entry of a step.
 
+Hadamard-rotated pools (``PagedKVFP4.allocate(..., hadamard=True)``; head_dim 128, 64 and 256): one e8m0 scale
+serves 32 elements, so a channel that runs 10 to 50 times above the rest (post-rope outlier channels, QK-norm
+gains) leaves the other 31 elements of its block two or three e2m1 codes, and ``k_mean`` removes an offset, not a
+spread of scales, and does nothing for q.  A rotated pool multiplies every key row, and every call that attends
+over it every query row, by the unnormalised D x D Walsh-Hadamard matrix H inside the quantiser
+(``qattn_mxfp4_paged_append_packed_had``, ``qattn_mxfp4_quant_rows_had``): after rope and ``f16(x - k_mean)``, in
+fp32, before the blocks are scaled and packed from the fp32 values.  (Hq) . (Hk) = D (q . k), so the attention
+entries get ``qks / D``, an exact division, and nothing else about them changes; V, ``vtail`` and every host-only
+operation are untouched.  The transform is defined bit for bit (include/qattn.h; tests/mxfp4_hadamard_ref.py
+restates it).  The flag belongs to the pool (``cache.hadamard``): no call takes an argument for it, and a step
+object serves rotated and plain pools alike.  What would mix rotated and plain operands -- the padded ``append``,
+:func:`attention_mxfp4_decode_paged`, ``snapshot`` -- raises :class:`QAttnError` naming "hadamard".
+
 Wire format (little-endian), the container of kv_cache.py with a magic of its own::
 
     offset 0   8 B   magic  b"QATTNKF4"
@@ -206,7 +219,7 @@ import torch
 
 from . import _lib
 from .attention_mxfp4 import (HeadDimError, Rope, _device_positions, _host_positions, _qk_scale, mxfp4_quantize_rows,
-                              mxfp4_quantize_rows_rope, mxfp4_quantize_v, rope_table)
+                              mxfp4_quantize_rows_had, mxfp4_quantize_rows_rope, mxfp4_quantize_v, rope_table)
 
 MAGIC = b"QATTNKF4"
 BLOCK = 64
@@ -791,8 +804,10 @@ class PagedKVFP4:
     written and no copy-on-write is needed.
     """
 
-    def __init__(self, k4, ks, vt, vs, vtail, lens, block_table, alloc: PageAllocator, k_mean=None):
+    def __init__(self, k4, ks, vt, vs, vtail, lens, block_table, alloc: PageAllocator, k_mean=None,
+                 hadamard: bool = False):
         self.k4, self.ks, self.vt, self.vs = k4, ks, vt, vs
+        self.hadamard = bool(hadamard)   # the keys are Hadamard-rotated: a property of the pool (allocate)
         self.vtail, self.lens, self.block_table, self.alloc, self.k_mean = vtail, lens, block_table, alloc, k_mean
         self.lengths = [0] * alloc.max_seqs
         self.epoch = [0] * alloc.max_seqs   # bumped by free, trim and rollback: what a Checkpoint is held to
@@ -800,11 +815,22 @@ class PagedKVFP4:
     @classmethod
     def allocate(cls, num_pages: int, page_tokens: int, max_seqs: int, kv_heads: int, max_pages_per_seq: int,
                  device, k_mean: Optional[torch.Tensor] = None, free_order=None,
-                 head_dim: int = 128) -> "PagedKVFP4":
+                 head_dim: int = 128, *, hadamard: bool = False) -> "PagedKVFP4":
         """An empty pool (every length 0, every page free), zero-filled.  ``head_dim`` is 128, 64 or 256; a pool
         of 64 or 256 serves the packed path (``append_packed``, :func:`attention_mxfp4_varlen_paged` without
         ``share_prefix`` and ``tree``, and a :class:`DecodeStep` made with that ``head_dim``) and the host-only
-        operations, and refuses the rest (:meth:`_need128`)."""
+        operations, and refuses the rest (:meth:`_need128`).
+
+        ``hadamard=True`` (keyword-only; every head_dim) makes a ROTATED pool, ``cache.hadamard``: every key row
+        is multiplied by the unnormalised D x D Walsh-Hadamard matrix H inside its quantiser, after rope and
+        ``k_mean`` and before its MX blocks are scaled (``qattn_mxfp4_paged_append_packed_had``), and every call
+        that attends over the pool rotates its queries the same way (``qattn_mxfp4_quant_rows_had``) and passes
+        ``qks / D``: (Hq) . (Hk) = D (q . k), so the scores are unchanged while an outlier channel of q or k is
+        spread over all D elements instead of flattening the other 31 of its block.  No call takes a new
+        argument: ``append_packed``, ``accept``, :func:`attention_mxfp4_varlen_paged` and the steps ask the pool.
+        V and the host-only operations are untouched.  What would mix rotated and plain operands raises
+        :class:`QAttnError` naming "hadamard" before anything changes: the padded ``append``,
+        :func:`attention_mxfp4_decode_paged` and ``snapshot``."""
         D = int(head_dim)
         if D not in (64, 128, 256):
             raise HeadDimError(f"qattn mxfp4 paged cache: head_dim must be 128, 64 or 256, got {head_dim}")
@@ -826,7 +852,7 @@ class PagedKVFP4:
         return cls(z(num_pages, kv_heads, page_tokens, D // 2), z(num_pages, kv_heads, page_tokens, D // 32),
                    z(num_pages, kv_heads, tpp, D, 32), z(num_pages, kv_heads, tpp, D, 2),
                    z(max_seqs, kv_heads, BLOCK, D, dt=torch.float16), z(max_seqs, dt=torch.int32),
-                   z(max_seqs, max_pages_per_seq, dt=torch.int32), alloc, k_mean)
+                   z(max_seqs, max_pages_per_seq, dt=torch.int32), alloc, k_mean, hadamard)
 
     @property
     def shape(self):
@@ -844,6 +870,14 @@ class PagedKVFP4:
                                "(the widths are 128, 64 and 256; served at 64 and 256: append_packed, "
                                "attention_mxfp4_varlen_paged without share_prefix and tree, and "
                                f"DecodeStep(head_dim={D}))")
+
+    def _plain(self, what: str) -> None:
+        """Raise :class:`QAttnError` for ``what`` on a rotated pool: its kernels quantise q or k without the
+        transform, or its result feeds some that do; called before anything is reserved, launched or changed."""
+        if self.hadamard:
+            raise _lib.QAttnError(f"qattn mxfp4 paged cache: {what} is not served on a hadamard=True pool (it "
+                                  "would mix rotated and plain operands; served there: append_packed, accept, "
+                                  "attention_mxfp4_varlen_paged, DecodeStep and VerifyStep)")
 
     @property
     def page_tokens(self) -> int:
@@ -884,6 +918,7 @@ class PagedKVFP4:
         ``max_pages_per_seq``, raises before anything is launched or changed), the changed table is
         uploaded in stream order and ``qattn_mxfp4_paged_append`` writes in place.  No host
         synchronisation, nothing is read back; returns ``self``."""
+        self._plain("the padded append")
         self._need128("the padded append")
         B, H, _, D = self.shape
         if (k.dim() != 4 or tuple(k.shape[:2]) != (B, H) or k.shape[3] != D or k.shape != v.shape
@@ -956,12 +991,9 @@ class PagedKVFP4:
                 _lib.ptr(self.vtail), _lib.ptr(self.lens), _lib.ptr(self.block_table), _lib.ptr(dev),
                 _lib.ptr(dev[len(tab):]), len(ids), len(tiles) // 2, k.shape[0], self.alloc.max_seqs, H,
                 self.num_pages, self.page_tokens, self.alloc.max_pages_per_seq, D)
-        if rope is None:
-            _lib.call("qattn_mxfp4_paged_append_packed", *args, _lib.stream_of(k))
-        else:
+        if rope is not None:
             pos_d = _lib.kernel_input(pos) if pos.is_cuda else dev[len(dev) - k.shape[0]:]
-            _lib.call("qattn_mxfp4_paged_append_packed_rope", *args, _lib.ptr(rope.table), _lib.ptr(pos_d),
-                      rope.max_pos, int(rope.interleaved), _lib.stream_of(k))
+        _append_packed_call(self, args, rope, None if rope is None else pos_d, _lib.stream_of(k))
         for b, c in zip(ids, cnt):
             self.lengths[b] += c
         return self
@@ -1183,7 +1215,9 @@ class PagedKVFP4:
 
     def snapshot(self, b: int) -> QuantizedKVFP4:
         """A :class:`QuantizedKVFP4` copy (batch 1) of sequence ``b``, whose length must be a
-        multiple of 64 (and not 0)."""
+        multiple of 64 (and not 0).  A rotated pool is refused: the copy feeds :func:`attention_mxfp4_cached`,
+        whose queries are not rotated."""
+        self._plain("snapshot")
         L = self.lengths[self.alloc._seq(b)]
         self._whole(int(b), "snapshot")
         if L == 0 or L % BLOCK:
@@ -1192,6 +1226,38 @@ class PagedKVFP4:
         return QuantizedKVFP4(k4[None, :, :L].contiguous(), ks[None, :, :L].contiguous(),
                               vt[:, :L // BLOCK].contiguous(), vs[:, :L // BLOCK].contiguous(),
                               None if self.k_mean is None else self.k_mean[b:b + 1].clone())
+
+
+def _append_packed_call(cache: "PagedKVFP4", args, rope, pos, st) -> None:
+    """The packed append's launch for ``cache``: ``args`` as ``qattn_mxfp4_paged_append_packed`` takes them up to
+    head_dim, ``rope`` a checked :class:`Rope` with the device positions ``pos``, or None.  A rotated pool takes the
+    entry with the transform, with or without rope; a plain one the entries it always took."""
+    tail = () if rope is None else (_lib.ptr(rope.table), _lib.ptr(pos), rope.max_pos, int(rope.interleaved))
+    if cache.hadamard:
+        _lib.call("qattn_mxfp4_paged_append_packed_had", *args, *(tail or (None, None, 0, 0)), st)
+    elif rope is None:
+        _lib.call("qattn_mxfp4_paged_append_packed", *args, st)
+    else:
+        _lib.call("qattn_mxfp4_paged_append_packed_rope", *args, *tail, st)
+
+
+def _quant_q_call(cache: "PagedKVFP4", q, q4, qs, tokens: int, heads: int, rope, pos, st) -> float:
+    """The query quantiser's launch for ``cache`` on packed ``q`` [tokens, heads, D] into ``q4`` / ``qs`` (``rope``
+    and ``pos`` as in :func:`_append_packed_call`) -> what the attention entry's ``qks`` is to be multiplied by: 1,
+    or 1 / D on a rotated pool, whose scores are D times the plain ones."""
+    D = cache.shape[3]
+    tail = () if rope is None else (_lib.ptr(rope.table), _lib.ptr(pos), tokens, heads, rope.max_pos,
+                                    int(rope.interleaved))
+    if cache.hadamard:
+        _lib.call("qattn_mxfp4_quant_rows_had", _lib.ptr(q), _lib.ptr(q4), _lib.ptr(qs),
+                  *(tail or (None, None, tokens, heads, 0, 0)), D, st)
+        return 1.0 / D
+    if rope is None:
+        _lib.call("qattn_mxfp4_quant_rows", _lib.ptr(q), None, _lib.ptr(q4), _lib.ptr(qs), tokens * heads, heads, D,
+                  st)
+    else:
+        _lib.call("qattn_mxfp4_quant_rows_rope", _lib.ptr(q), _lib.ptr(q4), _lib.ptr(qs), *tail, D, st)
+    return 1.0
 
 
 @torch.no_grad()
@@ -1204,6 +1270,7 @@ def attention_mxfp4_decode_paged(q: torch.Tensor, cache: PagedKVFP4, causal: boo
     causal needs Sq <= min(lengths); the plan is ``_split_plan_fp4`` at ceil64(max(lengths)), and
     ``keys_per_split`` is any multiple of 64, whatever the page size."""
     if isinstance(cache, PagedKVFP4):
+        cache._plain("attention_mxfp4_decode_paged")
         cache._need128("attention_mxfp4_decode_paged")
     bhv, rows, sk_max, kps, nsplit = _decode_plan(q, cache, causal, keys_per_split, PagedKVFP4)
     if any(cache.alloc.nholes):   # this entry has no window: it reads every page
@@ -1837,7 +1904,11 @@ def attention_mxfp4_varlen_paged(q: torch.Tensor, cache: PagedKVFP4, seq_ids, q_
         rec_d = torch.tensor(flat, dtype=torch.int32).to(dev, non_blocking=True)
         work_d = rec_d[8 * len(seq_rec):]
         grp_d = work_d[4 * len(work):]
-    q4, qs = mxfp4_quantize_rows(q) if rope is None else mxfp4_quantize_rows_rope(q, rope, pos)
+    if cache.hadamard:   # rotated like the pool's keys; the scores are D times the plain ones
+        q4, qs = mxfp4_quantize_rows_had(q, rope, pos)
+        qks /= D
+    else:
+        q4, qs = mxfp4_quantize_rows(q) if rope is None else mxfp4_quantize_rows_rope(q, rope, pos)
     O = torch.empty((T, Hq, D), dtype=torch.float16, device=dev)
     lse = torch.empty((T, Hq), dtype=torch.float32, device=dev)
     opart = torch.empty((part_rows, D), dtype=torch.float32, device=dev)
@@ -2098,11 +2169,7 @@ class DecodeStep:
                 _lib.ptr(cache.vt), _lib.ptr(cache.vs), _lib.ptr(cache.vtail), _lib.ptr(cache.lens),
                 _lib.ptr(cache.block_table), _lib.ptr(self.seq_tab), _lib.ptr(self.tiles), N, N, N, a.max_seqs, H,
                 a.num_pages, a.page_tokens, a.max_pages_per_seq, D)
-        if rope is None:
-            _lib.call("qattn_mxfp4_paged_append_packed", *args, st)
-        else:
-            _lib.call("qattn_mxfp4_paged_append_packed_rope", *args, _lib.ptr(rope.table), _lib.ptr(self.pos),
-                      rope.max_pos, int(rope.interleaved), st)
+        _append_packed_call(cache, args, rope, self.pos, st)
         return self
 
     def attend(self, cache: "PagedKVFP4", q: torch.Tensor, rope: Optional[Rope] = None,
@@ -2132,18 +2199,13 @@ class DecodeStep:
         _lib.require_gpu(q, cache.k4)
         q = _lib.kernel_input(q, torch.float16)
         a, st = cache.alloc, _lib.stream_of(q)
-        if rope is None:
-            _lib.call("qattn_mxfp4_quant_rows", _lib.ptr(q), None, _lib.ptr(self.q4), _lib.ptr(self.qs), N * Hq, Hq,
-                      D, st)
-        else:
-            _lib.call("qattn_mxfp4_quant_rows_rope", _lib.ptr(q), _lib.ptr(self.q4), _lib.ptr(self.qs),
-                      _lib.ptr(rope.table), _lib.ptr(self.pos), N, Hq, rope.max_pos, int(rope.interleaved), D, st)
+        qks = self.qks * _quant_q_call(cache, q, self.q4, self.qs, N, Hq, rope, self.pos, st)
         entry = "qattn_mxfp4_attn_fwd_decode_step" + ("" if self.softcap is None else "_softcap")
         _lib.call(entry, _lib.ptr(self.q4), _lib.ptr(self.qs), _lib.ptr(cache.k4),
                   _lib.ptr(cache.ks), _lib.ptr(cache.vt), _lib.ptr(cache.vs), _lib.ptr(self.opart),
                   _lib.ptr(self.ml), _lib.ptr(cache.lens), _lib.ptr(cache.block_table), _lib.ptr(self.seq_rec),
                   _lib.ptr(self.work), N, self.splits, a.max_seqs, H, Hq // H, a.num_pages, a.page_tokens,
-                  a.max_pages_per_seq, self.kps, D, self.qks, self.window or 0, self.sinks,
+                  a.max_pages_per_seq, self.kps, D, qks, self.window or 0, self.sinks,
                   *(() if self.softcap is None else (self.softcap,)), st)
         if sink_logit is None:
             _lib.call("qattn_mxfp4_decode_step_combine", _lib.ptr(self.opart), _lib.ptr(self.ml), _lib.ptr(self.O),
@@ -2392,11 +2454,7 @@ class VerifyStep:
                 _lib.ptr(cache.vt), _lib.ptr(cache.vs), _lib.ptr(cache.vtail), _lib.ptr(cache.lens),
                 _lib.ptr(cache.block_table), _lib.ptr(self.seq_tab), _lib.ptr(self.tiles), N, 2 * N, N * K,
                 a.max_seqs, H, a.num_pages, a.page_tokens, a.max_pages_per_seq, D)
-        if rope is None:
-            _lib.call("qattn_mxfp4_paged_append_packed", *args, st)
-        else:
-            _lib.call("qattn_mxfp4_paged_append_packed_rope", *args, _lib.ptr(rope.table), _lib.ptr(self.pos),
-                      rope.max_pos, int(rope.interleaved), st)
+        _append_packed_call(cache, args, rope, self.pos, st)
         return self
 
     def attend(self, cache: "PagedKVFP4", q: torch.Tensor, rope: Optional[Rope] = None):
@@ -2415,18 +2473,12 @@ class VerifyStep:
         _lib.require_gpu(q, cache.k4)
         q = _lib.kernel_input(q, torch.float16)
         a, st = cache.alloc, _lib.stream_of(q)
-        if rope is None:
-            _lib.call("qattn_mxfp4_quant_rows", _lib.ptr(q), None, _lib.ptr(self.q4), _lib.ptr(self.qs), N * K * Hq,
-                      Hq, D, st)
-        else:
-            _lib.call("qattn_mxfp4_quant_rows_rope", _lib.ptr(q), _lib.ptr(self.q4), _lib.ptr(self.qs),
-                      _lib.ptr(rope.table), _lib.ptr(self.pos), N * K, Hq, rope.max_pos, int(rope.interleaved), D,
-                      st)
+        qks = _qk_scale(D) * _quant_q_call(cache, q, self.q4, self.qs, N * K, Hq, rope, self.pos, st)
         _lib.call("qattn_mxfp4_attn_fwd_verify_step", _lib.ptr(self.q4), _lib.ptr(self.qs), _lib.ptr(cache.k4),
                   _lib.ptr(cache.ks), _lib.ptr(cache.vt), _lib.ptr(cache.vs), _lib.ptr(self.opart),
                   _lib.ptr(self.ml), _lib.ptr(cache.lens), _lib.ptr(cache.block_table), _lib.ptr(self.seq_rec),
                   _lib.ptr(self.work), _lib.ptr(self.tree), N, K, self.splits, a.max_seqs, H, Hq // H, a.num_pages,
-                  a.page_tokens, a.max_pages_per_seq, self.kps, D, _qk_scale(D), st)
+                  a.page_tokens, a.max_pages_per_seq, self.kps, D, qks, st)
         _lib.call("qattn_mxfp4_verify_step_combine", _lib.ptr(self.opart), _lib.ptr(self.ml), _lib.ptr(self.O),
                   _lib.ptr(self.lse), _lib.ptr(self.seq_rec), N, K, self.splits, Hq, H, D, st)
         return self.O, self.lse

@@ -34,14 +34,18 @@ the autograd rules of ``int8_fwd`` and ``bf16_fwd`` (their backward operators).
     torch.ops.qattn.mxfp4_decode_step_plan(slots, lens, capacity, kv_heads, group, keys_per_split, splits,
                                            window, sinks) -> (seq_tab, tiles, pos, seq_rec)
     torch.ops.qattn.mxfp4_decode_step(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, splits,
-                                      keys_per_split, window, sinks, sink_logit=None, softcap=0., qks=0.)
-                                      -> (O, lse)
+                                      keys_per_split, window, sinks, sink_logit=None, softcap=0., qks=0.,
+                                      hadamard=False) -> (O, lse)
     torch.ops.qattn.mxfp4_varlen_paged_softcap(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows,
                                                causal, keys_per_split, window, sinks, softcap, qks) -> (O, lse)
     torch.ops.qattn.mxfp4_verify_step_plan(slots, lens, tree, draft_tokens, capacity, kv_heads, group,
                                            keys_per_split, splits) -> (seq_tab, tiles, pos, seq_rec)
     torch.ops.qattn.mxfp4_verify_step(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, tree, draft_tokens,
-                                      splits, keys_per_split) -> (O, lse)
+                                      splits, keys_per_split, hadamard=False) -> (O, lse)
+    torch.ops.qattn.mxfp4_quant_rows_had(x, cos_sin=None, pos=None, interleaved=False) -> (q4, qs)
+    torch.ops.qattn.mxfp4_varlen_paged_had(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows,
+                                           causal, keys_per_split, window, sinks, softcap, qks, cos_sin=None,
+                                           pos=None, interleaved=False) -> (O, lse)
 
 Shapes follow the drop-in functions (attention_int8.py:259-262 for the int8 outputs) except that
 k_i8 is returned row-major [B*Hkv*Sk, D] (the drop-in's k_i8T is its transposed view: an operator
@@ -60,7 +64,7 @@ from . import _lib
 __all__ = ["int8_quant", "int8_fwd", "int8_bwd", "bf16_fwd", "bf16_bwd", "jvp_fwd", "mxfp4_fwd",
            "mxfp4_fwd_ex", "mxfp4_cached", "mxfp4_decode", "mxfp4_decode_paged", "mxfp4_varlen_paged",
            "mxfp4_quant_rows_rope", "mxfp4_decode_step_plan", "mxfp4_decode_step",
-           "mxfp4_verify_step_plan", "mxfp4_verify_step"]
+           "mxfp4_verify_step_plan", "mxfp4_verify_step", "mxfp4_quant_rows_had"]
 
 _lib.load_ops()
 _ops = torch.ops.qattn
@@ -190,7 +194,7 @@ def _(slots, lens, capacity, kv_heads, group, keys_per_split, splits, window, si
 
 @torch.library.register_fake("qattn::mxfp4_decode_step")
 def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, splits, keys_per_split, window, sinks,
-      sink_logit=None, softcap=0., qks=0.):
+      sink_logit=None, softcap=0., qks=0., hadamard=False):
     T, H, D = q.shape
     return (q.new_empty((T, H, D), dtype=torch.float16), q.new_empty((T, H), dtype=torch.float32))
 
@@ -210,7 +214,21 @@ def _(slots, lens, tree, draft_tokens, capacity, kv_heads, group, keys_per_split
 
 
 @torch.library.register_fake("qattn::mxfp4_verify_step")
-def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, tree, draft_tokens, splits, keys_per_split):
+def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, tree, draft_tokens, splits, keys_per_split,
+      hadamard=False):
+    T, H, D = q.shape
+    return (q.new_empty((T, H, D), dtype=torch.float16), q.new_empty((T, H), dtype=torch.float32))
+
+
+@torch.library.register_fake("qattn::mxfp4_quant_rows_had")
+def _(x, cos_sin=None, pos=None, interleaved=False):
+    T, H, D = x.shape
+    return (x.new_empty((T * H, D // 2), dtype=torch.uint8), x.new_empty((T * H, D // 32), dtype=torch.uint8))
+
+
+@torch.library.register_fake("qattn::mxfp4_varlen_paged_had")
+def _(q, k4, ks, vt, vs, lens, block_table, seq_rec, work, part_rows, causal, keys_per_split, window, sinks,
+      softcap, qks, cos_sin=None, pos=None, interleaved=False):
     T, H, D = q.shape
     return (q.new_empty((T, H, D), dtype=torch.float16), q.new_empty((T, H), dtype=torch.float32))
 
@@ -330,8 +348,11 @@ def mxfp4_decode_paged(q, cache, causal=False, keys_per_split=None):
     """``kv_cache_mxfp4.attention_mxfp4_decode_paged`` as one operator: q [max_seqs, Hq, Sq, 128]
     against a ``PagedKVFP4``, sequence b over its own length and pages -> (O fp16, lse fp32
     [max_seqs*Hq, Sq]).  The lengths are checked here, on the cache's host mirror (the operator reads
-    only ``lens`` and ``block_table`` on the device); ``keys_per_split`` None: the plan."""
+    only ``lens`` and ``block_table`` on the device); ``keys_per_split`` None: the plan.  A ``hadamard=True`` pool
+    is refused as in the Python call."""
     from .kv_cache_mxfp4 import PagedKVFP4, _decode_plan
+    if isinstance(cache, PagedKVFP4):   # the operator's q quantiser is the plain one
+        cache._plain("mxfp4_decode_paged")
     _, _, sk_max, _, _ = _decode_plan(q, cache, causal, keys_per_split, PagedKVFP4)
     return _ops.mxfp4_decode_paged(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens, cache.block_table,
                                    sk_max, int(bool(causal)), 0 if keys_per_split is None else int(keys_per_split))
@@ -350,6 +371,24 @@ def mxfp4_quant_rows_rope(x, rope, positions):
     if not _device_positions(positions, x.shape[0]):
         positions = _host_positions(positions, x.shape[0], rope.max_pos).to(x.device, non_blocking=True)
     return _ops.mxfp4_quant_rows_rope(x, rope.table, positions, rope.interleaved)
+
+
+def mxfp4_quant_rows_had(x, rope=None, positions=None):
+    """``attention_mxfp4.mxfp4_quantize_rows_had`` as one operator: packed x [T, H, D] (D = 128, 64 or 256) through
+    the query quantiser of a Hadamard-rotated pool, rotated by its tokens' positions through ``rope`` first when one
+    is given -> (q4 u8 [T*H, D/2], qs u8 [T*H, D/32]).  Host ``positions`` are checked and uploaded here."""
+    from .attention_mxfp4 import Rope, _device_positions, _host_positions
+    if x.dim() != 3:
+        raise _lib.QAttnError("qattn mxfp4 hadamard: packed rows must be x [T, H, D]")
+    if rope is None:
+        if positions is not None:
+            raise _lib.QAttnError("qattn mxfp4 rope: positions without rope (they place the rotation)")
+        return _ops.mxfp4_quant_rows_had(x)
+    if not isinstance(rope, Rope):
+        raise _lib.QAttnError("qattn mxfp4 rope: rope must be a Rope")
+    if not _device_positions(positions, x.shape[0]):
+        positions = _host_positions(positions, x.shape[0], rope.max_pos).to(x.device, non_blocking=True)
+    return _ops.mxfp4_quant_rows_had(x, rope.table, positions, rope.interleaved)
 
 
 def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=None, window=None, sinks=0,
@@ -372,7 +411,10 @@ def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=N
     ``tree`` raise there as in the Python call.  The learned sink logit (``sink_logit=``) is the Python call's and
     the C ABI's alone.  ``softcap`` and / or ``scale`` (checked as the Python call checks them; the plain and the
     windowed form, every head_dim) route to ``torch.ops.qattn.mxfp4_varlen_paged_softcap``, the Python call's
-    bits; with ``rope``, ``share_prefix`` or ``tree`` they are the Python call's alone."""
+    bits; with ``rope``, ``share_prefix`` or ``tree`` they are the Python call's alone.  On a rotated pool
+    (``cache.hadamard``) the plain, the windowed, the capped and the rope form, and those together, route to
+    ``torch.ops.qattn.mxfp4_varlen_paged_had``, the Python call's bits; ``share_prefix`` and ``tree`` are the Python
+    call's alone there and raise :class:`QAttnError` naming "hadamard"."""
     from .kv_cache_mxfp4 import (PagedKVFP4, _check_trimmed, _packed_lists, _query_positions, _shared_plan,
                                  _softcap_args, _tree_args, _window_args, plan_varlen)
     if not isinstance(cache, PagedKVFP4):
@@ -381,7 +423,11 @@ def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=N
         raise _lib.QAttnError("qattn mxfp4 paged cache: packed queries must be q [T, Hq, D]")
     capped = softcap is not None or scale is not None
     cap, qks = _softcap_args(softcap, scale, q.shape[2], share_prefix or tree is not None)
-    if capped and (share_prefix or tree is not None or rope is not None or positions is not None):
+    had = cache.hadamard
+    if had and (share_prefix or tree is not None):
+        raise _lib.QAttnError("qattn mxfp4 paged cache: the operators of a hadamard=True pool take no share_prefix "
+                              "or tree; kv_cache_mxfp4.attention_mxfp4_varlen_paged serves those")
+    if not had and capped and (share_prefix or tree is not None or rope is not None or positions is not None):
         raise _lib.QAttnError("qattn mxfp4 paged cache: the softcap operator takes no rope, share_prefix or tree; "
                               "kv_cache_mxfp4.attention_mxfp4_varlen_paged serves those with scale= (and rope "
                               "with softcap=)")
@@ -390,7 +436,8 @@ def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=N
     ids, sq = _packed_lists(cache.alloc.max_seqs, seq_ids, q_lens, "q_lens")
     if sum(sq) != q.shape[0]:
         raise _lib.QAttnError(f"qattn mxfp4 paged cache: q holds {q.shape[0]} tokens, q_lens sum to {sum(sq)}")
-    if (rope is not None or positions is not None) and (window is not None or share_prefix or tree is not None):
+    if not had and (rope is not None or positions is not None) and (window is not None or share_prefix
+                                                                    or tree is not None):
         raise _lib.QAttnError("qattn mxfp4 rope: the rope operator takes no window, share_prefix or tree; "
                               "kv_cache_mxfp4.attention_mxfp4_varlen_paged serves those with rope=")
     trees = None if tree is None else _tree_args(tree, sq, causal, window, share_prefix)
@@ -428,6 +475,11 @@ def mxfp4_varlen_paged(q, cache, seq_ids, q_lens, causal=False, keys_per_split=N
     _lib.require_gpu(q, cache.k4)
     rec_d = torch.tensor(seq_rec, dtype=torch.int32).to(q.device, non_blocking=True)
     work_d = torch.tensor(work, dtype=torch.int32).to(q.device, non_blocking=True)
+    if had:   # one operator for every form; qks is the plain scale, the operator divides it by D
+        return _ops.mxfp4_varlen_paged_had(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens, cache.block_table,
+                                           rec_d, work_d, part_rows, int(bool(causal)), kps, min(W or 0, 1 << 26),
+                                           min(S, 1 << 26), cap or 0., qks, *(() if rope is None else (
+                                               rope.table, pos.to(q.device, non_blocking=True), rope.interleaved)))
     if capped:
         return _ops.mxfp4_varlen_paged_softcap(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens,
                                                cache.block_table, rec_d, work_d, part_rows, int(bool(causal)), kps,
@@ -462,7 +514,8 @@ def mxfp4_decode_step(q, step, cache, seq_rec=None, sink_logit=None):
     one is given and the step's ``softcap`` and scale -> (O, lse), the Python call's bits."""
     return _ops.mxfp4_decode_step(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens, cache.block_table,
                                   step.seq_rec if seq_rec is None else seq_rec, step.work, step.splits, step.kps,
-                                  step.window or 0, step.sinks, sink_logit, step.softcap or 0., step.qks)
+                                  step.window or 0, step.sinks, sink_logit, step.softcap or 0., step.qks,
+                                  cache.hadamard)
 
 
 def mxfp4_verify_step_plan(step, cache):
@@ -482,4 +535,4 @@ def mxfp4_verify_step(q, step, cache, seq_rec=None):
     ``append`` wrote), the step's ``work`` and ``tree`` -> (O, lse), the Python call's bits."""
     return _ops.mxfp4_verify_step(q, cache.k4, cache.ks, cache.vt, cache.vs, cache.lens, cache.block_table,
                                   step.seq_rec if seq_rec is None else seq_rec, step.work, step.tree, step.K,
-                                  step.splits, step.kps)
+                                  step.splits, step.kps, cache.hadamard)

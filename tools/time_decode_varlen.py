@@ -39,6 +39,11 @@ anything is timed (the pools of (b) hold different random tokens).
     (qattn_mxfp4_attn_fwd_varlen_paged_softcap) beside the uncapped kernel of the same build, alternating, at the two
     decode shapes of (f) and at one 512-token prefill chunk over 8192 cached keys at head_dim 128, 32 / 8 heads.
 
+(h) with --hadamard (then only (h) runs): the two quantisers of a Hadamard-rotated pool beside the plain ones of
+    the same build, alternating, at the three shapes of (g): the Q quantiser alone (REPS launches) and the packed
+    append's C entry (V, K and length launches; REPS times the entry followed by a copy that puts the lengths back,
+    the same copy for both candidates), on pools that differ only in ``hadamard``.
+
 After (a) and (b) the packed call is taken apart: the host plan alone (plan_varlen, a host clock), the
 two table uploads alone (event-timed) and the attention kernel alone (REPS back-to-back launches of the
 C entry on buffers and tables made once, divided by REPS), beside the paged kernel alone in (a).
@@ -248,12 +253,12 @@ def windowed(W, S, rand, passes, iters):
     assert torch.isfinite(O1.float()).all()
 
 
-def pool64(lengths, k, v, Dp, extra=0):
+def pool64(lengths, k, v, Dp, extra=0, hadamard=False):
     """A pool of head_dim ``Dp`` holding the first ``lengths[j]`` rows of k, v [n, 8, D <= Dp] per sequence, zero-
     padded to ``Dp``, with room for ``extra`` more tokens per sequence."""
     B, n = len(lengths), max(lengths)
     cache = PagedKVFP4.allocate(sum(-(-(L + extra) // P) for L in lengths), P, B, 8, -(-(n + extra) // P), "cuda",
-                                head_dim=Dp)
+                                head_dim=Dp, hadamard=hadamard)
     pad = lambda x: torch.nn.functional.pad(x, (0, Dp - k.shape[2]))  # noqa: E731
     for t0 in range(0, n, 4096):
         c = [min(max(L - t0, 0), 4096) for L in lengths]
@@ -357,6 +362,65 @@ def softcapped(cap, rand, passes, iters):
         torch.cuda.empty_cache()
 
 
+def append_entry(cache, k, v, counts):
+    """REPS times the packed append's C entry on ``cache`` (the plain or the rotated one, by the pool), each followed
+    by the copy that puts the lengths back.  The first, untimed append here reserves the pages."""
+    B, Dp = len(counts), cache.shape[3]
+    lengths, saved = list(cache.lengths), cache.lens.clone()
+    cache.append_packed(k, v, list(range(B)), counts)
+    cache.lengths = list(lengths)
+    cache.lens.copy_(saved)
+    tab, tiles, first = [], [], 0
+    for j, (L, c) in enumerate(zip(lengths, counts)):
+        tab += [j, c, first, 0]
+        tiles += [x for g in range(L // 64, (L + c - 1) // 64 + 1) for x in (j, g)]
+        first += c
+    dev = torch.tensor(tab + tiles, dtype=torch.int32).cuda()
+    a = cache.alloc
+    args = (_lib.ptr(k), _lib.ptr(v), None, *(_lib.ptr(x) for x in cache.kv), _lib.ptr(cache.vtail),
+            _lib.ptr(cache.lens), _lib.ptr(cache.block_table), _lib.ptr(dev), _lib.ptr(dev[len(tab):]), B,
+            len(tiles) // 2, k.shape[0], a.max_seqs, 8, a.num_pages, P, a.max_pages_per_seq, Dp)
+    tail = (None, None, 0, 0) if cache.hadamard else ()
+    entry = "qattn_mxfp4_paged_append_packed" + ("_had" if cache.hadamard else "")
+
+    def run(keep=(dev, saved)):
+        for _ in range(REPS):
+            _lib.call(entry, *args, *tail, _lib.stream_of(k))
+            cache.lens.copy_(saved)
+    return run
+
+
+def hadamard(rand, passes, iters):
+    shapes = [("8 decodes at 8192 cached", 256, 16, [8192] * 8, [1] * 8),
+              ("64 decodes at 32768 cached", 256, 16, [32768] * 64, [1] * 64),
+              ("a 512-token chunk at 8192 cached", 128, 32, [8192], [512])]
+    for name, Dp, hq, lengths, q_lens in shapes:
+        T = sum(q_lens)
+        q, k, v = rand(T, hq, Dp), rand(T, 8, Dp), rand(T, 8, Dp)
+        q4 = torch.empty((T * hq, Dp // 2), dtype=torch.uint8, device="cuda")
+        qs = torch.empty((T * hq, Dp // 32), dtype=torch.uint8, device="cuda")
+        st = _lib.stream_of(q)
+
+        def quant(had, keep=(q, q4, qs)):
+            for _ in range(REPS):
+                if had:
+                    _lib.call("qattn_mxfp4_quant_rows_had", _lib.ptr(q), _lib.ptr(q4), _lib.ptr(qs), None, None, T,
+                              hq, 0, 0, Dp, st)
+                else:
+                    _lib.call("qattn_mxfp4_quant_rows", _lib.ptr(q), None, _lib.ptr(q4), _lib.ptr(qs), T * hq, hq,
+                              Dp, st)
+
+        print(f"(h) {name}: {hq}/8 heads of head_dim {Dp}, P {P}", flush=True)
+        report(alternate({f"plain Q quantiser x{REPS}": lambda: quant(False),
+                          f"rotated Q quantiser x{REPS}": lambda: quant(True)}, passes, iters))
+        fill = rand(max(lengths), 8, Dp)
+        pools = [pool64(lengths, fill, fill, Dp, max(q_lens), h) for h in (False, True)]
+        report(alternate({f"plain append entry x{REPS}": append_entry(pools[0], k, v, q_lens),
+                          f"rotated append entry x{REPS}": append_entry(pools[1], k, v, q_lens)}, passes, iters))
+        del pools
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--passes", type=int, default=3)
@@ -366,12 +430,16 @@ def main():
     ap.add_argument("--head-dim", type=int, default=128, choices=(64, 128, 256),
                     help="64: run only (e); 256: run only (f)")
     ap.add_argument("--softcap", type=float, default=None, help="run only (g), with this logit cap")
+    ap.add_argument("--hadamard", action="store_true", help="run only (h): the rotated quantisers beside the plain")
     args = ap.parse_args()
     assert args.passes >= 3
     print(f"device {torch.cuda.get_device_name(0)}; {args.passes} alternating passes x {args.iters} calls, "
           "whole Python call", flush=True)
     g = torch.Generator(device="cuda").manual_seed(0)
     rand = lambda *s: torch.randn(s, device="cuda", generator=g).half()  # noqa: E731
+    if args.hadamard:
+        hadamard(rand, args.passes, args.iters)
+        return
     if args.softcap is not None:
         softcapped(args.softcap, rand, args.passes, args.iters)
         return
